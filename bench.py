@@ -17,7 +17,11 @@ device-resident before timing.
       N > 1 runs BASELINE configs[4] (C5: 100 M-item table row-sharded, arx.dist.ShardedHMF) and carries
       "scaling_anchor": the SAME code path and table on one rank (also: --gpus 1 --workload c5).
 
-`value` times exactly K steps of the headline workload.  The same line carries
+`value` times exactly K steps of the headline workload, once: a plain run sets up, warms up, times the K steps and
+prints the line.  --dump-outputs DIR also writes what the last timed step left (the loss and a fixed, seeded sample of
+rows of every table and its Adagrad accumulator) as DIR/<name>.npy, so that two builds can be compared output for
+output on identical inputs.  With --full the headline is the median of --repeats timed regions (default 5) and the
+same line carries
   "sub": C2 (configs[1], id-only), C3-MIX (one bag = id token + categories over ONE 1.1 M-row
          table = 563 MB, past the 256 MB Infinity Cache), C4 (configs[3], LSTM, 'mw' and the
          build-defined sampled softmax 'mce'), each with its own rooflines;
@@ -66,11 +70,18 @@ def parse():
     ap.add_argument("--no-anchor", action="store_true",
                     help="N > 1: do not run the world-1 anchor of the same workload after the N-rank run")
     ap.add_argument("--mulhot", action="store_true", help="(compat) same as --workload c3")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the sub-results (--subs), per-kernel rooflines, the CPU baseline, the "
+                         "N > 1 scaling anchor and --repeats timed regions (default 5).  Off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's loss and a fixed sample of every table's rows "
+                         "(and Adagrad accumulators) as DIR/<name>.npy (single-GPU HMF workloads)")
     ap.add_argument("--subs", default="c2,c3mix,c3mce,c3host,c4,c4mce,c4host,k1,c5w1,c3repw1,topk,c3_f32mfma,c2_f32mfma",
-                    help="comma list of sub-results besides the headline ('' = none)")
+                    help="with --full: comma list of sub-results besides the headline ('' = none)")
     ap.add_argument("--sub-steps", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps steps each; the line reports the median one")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the line reports the median one (default: 1, 5 with "
+                         "--full)")
     ap.add_argument("--n-items", type=int, default=None,
                     help="item table rows (default: 1M on one GPU; 100M row-sharded for --gpus N > 1 = configs[4])")
     ap.add_argument("--n-users", type=int, default=1000000)
@@ -96,7 +107,13 @@ def parse():
                          "measured slower (DESIGN.md section 4: two graphs launched in turn cost ~15 us per step)")
     ap.add_argument("--no-rooflines", action="store_true", help="skip the per-kernel timings (profiling runs)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline and nothing else
+        args.subs, args.no_rooflines, args.no_cpu_baseline, args.no_anchor = "", True, True, True
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
 
 
 def _evt_time_ms(fn, iters):
@@ -449,7 +466,30 @@ def _quiesce():
     torch.cuda.synchronize()
 
 
-def run_hmf(args, name, steps, warmup, with_cpu=False, loss='mw', host_feed=False):
+DUMP_BYTES = 48 << 20        # --dump-outputs: the sampled table rows of all tables together stay under this
+
+
+def dump_outputs(model, out_dir):
+    """--dump-outputs: what the last timed step hands its caller -- the step's loss -- and what it leaves in the model,
+    every embedding table, bias and Adagrad accumulator, as float32 DIR/<name>.npy.  The tables are sampled: the same
+    seeded rows in every run (np.random.default_rng(0) per table), as many as DUMP_BYTES allows, sorted."""
+    os.makedirs(out_dir, exist_ok=True)
+    tables = list(model.att_emb.tables.values())
+    row_bytes = sum(4 * 2 * (t.E.shape[1] + (1 if t.bias is not None else 0)) for t in tables)
+    n = max(1, DUMP_BYTES // row_bytes)
+    np.save(os.path.join(out_dir, "loss.npy"), model.loss.read().float().reshape(-1).cpu().numpy())
+    for t in tables:
+        V = t.E.shape[0]
+        rows = np.sort(np.random.default_rng(0).choice(V, size=min(n, V), replace=False))
+        idx = torch.from_numpy(rows).to(t.E.device)
+        arrays = [(t.name, t.E), (t.name + "_acc", t.acc)]
+        if t.bias is not None:
+            arrays += [(t.bias_name, t.bias), (t.bias_name + "_acc", t.bias_acc)]
+        for key, a in arrays:
+            np.save(os.path.join(out_dir, key + ".npy"), a.index_select(0, idx).float().cpu().numpy())
+
+
+def run_hmf(args, name, steps, warmup, with_cpu=False, loss='mw', host_feed=False, dump=None):
     from arx.hmf.hmf_model import LatentProductModel
     from arx.utils.synthetic import SyntheticHMF
     from arx.utils.prepare_train import DeviceSampler
@@ -528,6 +568,8 @@ def run_hmf(args, name, steps, warmup, with_cpu=False, loss='mw', host_feed=Fals
     wall, ev_ms = walls[med], evs[med]
     redraws[0] //= len(walls)
     final_loss = float(model.loss.read().item())
+    if dump:
+        dump_outputs(model, dump)
     out = {
         "value": B * steps / wall, "unit": "interactions/s", "steps": steps, "warmup": warmup,
         "ms_per_step": 1e3 * wall / steps,
@@ -770,7 +812,7 @@ def run_f32mfma(args, workload):
     import subprocess
     env = dict(os.environ, ARX_SCORER_F32="1", ARX_BENCH_CHILD="1")
     sharded = workload == "c5w1"            # the world-1 sharded step: a sub-result of a (short) child run
-    cmd = [sys.executable, os.path.abspath(__file__), "--workload", "c2" if sharded else workload,
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--workload", "c2" if sharded else workload,
            "--subs", "c5w1" if sharded else "", "--no-rooflines",
            "--no-cpu-baseline", "--steps", str(10 if sharded else args.sub_steps), "--warmup", str(min(args.warmup, 10)),
            "--sub-steps", str(args.sub_steps), "--repeats", "1" if sharded else str(args.repeats),
@@ -837,7 +879,7 @@ def scaling_anchor(args):
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     else:
-        cmd += ["--cpu-seconds", str(args.cpu_seconds)]
+        cmd += ["--full", "--cpu-seconds", str(args.cpu_seconds)]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=900)
     j = _child_detail(r.stdout)
     return {"value": j["value"], "unit": j["unit"], "n_gpus": 1, "ms_per_step": j["ms_per_step"],
@@ -1122,6 +1164,8 @@ def main_sharded(args, world, rank, local_rank):
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
+    if args.dump_outputs and (args.gpus > 1 or int(env_world or "1") > 1 or args.workload in ("c5", "c4h")):
+        raise SystemExit("bench.py: --dump-outputs covers the single-GPU HMF workloads (c2, c3, c3mix)")
     if args.gpus > 1 and env_world is None:
         return self_launch(args)
     world = int(env_world or "1")
@@ -1141,7 +1185,7 @@ def main():
     if args.mulhot:
         args.workload = "c3"
     torch.cuda.set_device(0)
-    head = run_hmf(args, args.workload, args.steps, args.warmup)
+    head = run_hmf(args, args.workload, args.steps, args.warmup, dump=args.dump_outputs)
     out = {
         "metric": METRIC, "value": head["value"], "unit": head["unit"], "n_gpus": 1,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
@@ -1154,7 +1198,8 @@ def main():
             out[k] = head[k]
     subs = [s for s in args.subs.split(",") if s and s != args.workload]
     sub = {}
-    _quiesce()
+    if subs:
+        _quiesce()
     for s in subs:
         try:
             if s in WORKLOADS:

@@ -40,7 +40,7 @@ def _bench(extra, timeout=900, env_extra=None):
 
 
 def test_bench_gpus2_self_launch_one_line(dev):
-    j = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--n-items", "2000000", "--n-users", "200000",
+    j = _bench(["--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--n-items", "2000000", "--n-users", "200000",
                 "--batch", "2048"], env_extra={"ARX_DIST_ONE_GPU": "1", "ARX_DIST_BACKEND": "gloo"})
     assert j["n_gpus"] == 2 and j["steps"] == 3 and j["warmup"] == 1
     assert j["scaling"] == "weak" and j["unit"] == "interactions/s" and j["value"] > 0
@@ -76,7 +76,7 @@ def test_bench_c4_hybrid_two_ranks_one_line(dev):
 def test_bench_host_fed_subs(dev):
     """`c3host` / `c4host`: the step with its ids handed over as host arrays (the reference's feed_dict boundary), the
     transfer inside the timed region -- sub-results beside the HBM-resident headline, never `value`."""
-    j = _bench(["--gpus", "1", "--steps", "3", "--warmup", "2", "--sub-steps", "4", "--repeats", "1", "--n-items", "20000",
+    j = _bench(["--gpus", "1", "--full", "--steps", "3", "--warmup", "2", "--sub-steps", "4", "--repeats", "1", "--n-items", "20000",
                 "--n-users", "2000", "--batch", "1024", "--lstm-batch", "64", "--n-sampled", "128", "--subs",
                 "c3host,c4host", "--no-rooflines", "--no-cpu-baseline"])
     sub = j["_detail"]["sub"]
@@ -85,3 +85,29 @@ def test_bench_host_fed_subs(dev):
         assert sub[k]["value"] > 0 and sub[k]["config"]["ids_fed_from"].startswith("host")
     assert j["config"]["ids_fed_from"].startswith("HBM")
     assert set(j["sub_ms_per_step"]) == {"c3host", "c4host"}
+
+
+def test_bench_plain_run_times_k_steps_and_dumps(dev, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times K steps once and measures nothing besides the headline;
+    --dump-outputs writes the last step's loss and the sampled tables as float32 .npy (at most 64 MB), and the same
+    arguments give the same inputs, hence the same outputs up to summation order."""
+    import numpy as np
+    args = ["--gpus", "1", "--steps", "4", "--warmup", "2", "--n-items", "20000", "--n-users", "2000", "--batch", "1024",
+            "--n-sampled", "128"]
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        j = _bench(args + ["--dump-outputs", str(d)])
+        assert j["steps"] == 4 and j["warmup"] == 2 and j["ms_per_step"] > 0 and j["value"] > 0
+        assert j["config"]["timed_regions"] == 1 and j["higher_is_better"] is True and j["dtype"] == "f32"
+        for extra in ("sub", "cpu_baseline", "roofline", "roofline_hbm", "kernels"):
+            assert extra not in j["_detail"], extra
+        arrs = {p.name: np.load(p) for p in d.iterdir()}
+        assert "loss.npy" in arrs and len(arrs) > 1
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert float(arrs["loss.npy"][0]) == pytest.approx(j["config"]["final_loss"], rel=1e-6)
+        runs.append(arrs)
+    assert runs[0].keys() == runs[1].keys()
+    for name in runs[0]:
+        np.testing.assert_allclose(runs[1][name], runs[0][name], rtol=1e-4, atol=1e-6, err_msg=name)

@@ -4,7 +4,7 @@
 R=$PWD; mkdir -p gpurun_out
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/pw
-timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --output-format csv -d /tmp/pw -- python $R/bench.py --no-cpu-baseline --no-graph --steps 20 --warmup 5 "$@" > /tmp/pw.log 2>&1
+timeout 300 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE --output-format csv -d /tmp/pw -- python $R/bench.py --full --no-cpu-baseline --no-graph --steps 20 --warmup 5 "$@" > /tmp/pw.log 2>&1
 f=$(find /tmp/pw -name "*counter_collection.csv" | head -1)
 python - "$f" <<'PY'
 import csv, sys, collections

@@ -14,7 +14,7 @@ OUT=$REPO/gpurun_out
 mkdir -p "$OUT"
 cd /tmp
 export TMPDIR=/tmp
-ARGS="--steps 100 --warmup 20 --repeats 1 --no-cpu-baseline --subs= $*"
+ARGS="--full --steps 100 --warmup 20 --repeats 1 --no-cpu-baseline --subs= $*"
 
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o ks -- \
   python "$REPO/bench.py" $ARGS > "$OUT/${TAG}_bench_under_rocprof.json" 2> /tmp/ks.err

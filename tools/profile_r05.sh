@@ -46,6 +46,6 @@ mv gpurun_out/tr_r05_c3.txt $OUT/r05_c3_step_timeline.txt 2>/dev/null
 ls -la $OUT
 # the full default line (headline + subs + CPU baseline), as the driver runs it
 cd $REPO
-timeout 900 python bench.py > $OUT/r05_bench_default.json 2> $OUT/r05_bench_default.err
-timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r05_bench_steps20.json 2>/dev/null
+timeout 900 python bench.py --full > $OUT/r05_bench_default.json 2> $OUT/r05_bench_default.err
+timeout 600 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/r05_bench_steps20.json 2>/dev/null
 tail -c 600 $OUT/r05_bench_default.json

@@ -53,8 +53,8 @@ cp gpurun_out/r06abl/log.txt $OUT/r06_k7_halves_ablation.txt 2>/dev/null
 bash tools/trace_cmd.sh r06_c3mix k_sc_prep --workload c3mix --subs "" --no-rooflines --repeats 1 > /dev/null 2>&1
 mv gpurun_out/tr_r06_c3mix.txt $OUT/r06_c3mix_step_timeline_csc.txt 2>/dev/null
 # the bench lines as the driver runs them
-timeout 900 python bench.py > $OUT/r06_bench_default.json 2> $OUT/r06_bench_default.err
+timeout 900 python bench.py --full > $OUT/r06_bench_default.json 2> $OUT/r06_bench_default.err
 cp bench_detail.json $OUT/r06_bench_default_detail.json 2>/dev/null
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/r06_bench_steps20.json 2>/dev/null
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/r06_bench_steps20.json 2>/dev/null
 tail -c 400 $OUT/r06_bench_steps20.json
 ls -la $OUT

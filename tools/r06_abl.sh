@@ -6,7 +6,7 @@ set -u
 N=${1:-2}
 OUT=gpurun_out/r06abl; mkdir -p $OUT
 run() { tag=$1; shift
-  env "$@" python bench.py --no-cpu-baseline --subs ${SUBS:-c2} --repeats 3 --no-rooflines 2>/dev/null | grep "^BENCH_DETAIL " | cut -c14- | python -c "
+  env "$@" python bench.py --full --no-cpu-baseline --subs ${SUBS:-c2} --repeats 3 --no-rooflines 2>/dev/null | grep "^BENCH_DETAIL " | cut -c14- | python -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 print('$tag', 'C3 %.1f us' % (1e3*j['ms_per_step']), ' '.join('%s %.1f us' % (k, 1e3*v['ms_per_step']) for k, v in j.get('sub',{}).items() if 'ms_per_step' in v))" | tee -a $OUT/log.txt

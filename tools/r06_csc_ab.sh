@@ -7,7 +7,7 @@ timeout 900 python -m pytest tests/test_kernels_gpu.py -m gpu -x -q -k "cat_mult
 ARX_K7_CSC=1 timeout 1500 python -m pytest tests/test_fullsize_gpu.py tests/test_hmf_gpu.py -m gpu -x -q 2>&1 | tail -2 | sed "s/^/ARX_K7_CSC=1: /" >> $O/tests.txt
 cat $O/tests.txt
 run() {
-  timeout 600 python bench.py --no-cpu-baseline --subs c3mix --repeats 3 --no-rooflines 2>/dev/null | grep "^BENCH_DETAIL " | cut -c14- | python -c "
+  timeout 600 python bench.py --full --no-cpu-baseline --subs c3mix --repeats 3 --no-rooflines 2>/dev/null | grep "^BENCH_DETAIL " | cut -c14- | python -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 print('$1', 'C3 %.1f us' % (1e3*j['ms_per_step']), ' '.join('%s %.1f us' % (k, 1e3*v['ms_per_step']) for k, v in j.get('sub',{}).items() if 'ms_per_step' in v))" | tee -a $O/ab.txt

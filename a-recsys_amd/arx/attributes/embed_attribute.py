@@ -29,6 +29,50 @@ def _np_i32(x):
     return np.ascontiguousarray(np.asarray(x, dtype=np.int32))
 
 
+def exclusion_csr(item_sets, n_keys, item2logit):
+    """Per-user exclusion lists of LOGIT columns as a CSR pair (ptr int32 [n_keys + 1], cols int32 [>= 1]) for the
+    recommend path (arx.h arx_topk_exclude_fill).  item_sets: {user_index: items} or a (ptr, items) CSR pair over
+    user indices, in ITEM-index space (the forms prepare_warp accepts).  Items go through item2logit (a numpy array,
+    -1 where an item has no logit); items without a logit, negative items and users outside [0, n_keys) are dropped;
+    every list comes out sorted ascending without duplicates."""
+    item2logit = np.asarray(item2logit)
+    if isinstance(item_sets, tuple):
+        ptr = np.asarray(item_sets[0], dtype=np.int64)
+        items = np.asarray(item_sets[1], dtype=np.int64).reshape(-1)
+        if len(ptr) == 0:
+            ptr = np.zeros(1, dtype=np.int64)
+        if np.any(np.diff(ptr) < 0) or ptr[0] != 0 or ptr[-1] > len(items):
+            raise ValueError("exclusion CSR: ptr must start at 0, not decrease and end within the items")
+        users = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))
+        items = items[:ptr[-1]]
+    elif isinstance(item_sets, dict):
+        keys = [u for u, its in item_sets.items() if len(its)]
+        parts = [np.asarray(list(item_sets[u]), dtype=np.int64).reshape(-1) for u in keys]
+        lens = np.asarray([len(x) for x in parts], dtype=np.int64)
+        users = np.repeat(np.asarray(keys, dtype=np.int64), lens)
+        items = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+    else:
+        raise ValueError("exclusions: a {user: items} dict or a (ptr, items) CSR pair")
+    ok = (users >= 0) & (users < n_keys) & (items >= 0) & (items < len(item2logit))
+    users, items = users[ok], items[ok]
+    cols = item2logit[items].astype(np.int64)
+    ok = cols >= 0
+    users, cols = users[ok], cols[ok]
+    order = np.lexsort((cols, users))
+    users, cols = users[order], cols[order]
+    if len(users):
+        keep = np.ones(len(users), dtype=bool)
+        keep[1:] = (users[1:] != users[:-1]) | (cols[1:] != cols[:-1])
+        users, cols = users[keep], cols[keep]
+    out_ptr = np.zeros(n_keys + 1, dtype=np.int64)
+    np.cumsum(np.bincount(users, minlength=n_keys), out=out_ptr[1:])
+    if out_ptr[-1] >= 2 ** 31:
+        raise ValueError("exclusion lists: more than 2^31 - 1 entries")
+    if len(cols) == 0:
+        cols = np.zeros(1, dtype=np.int64)          # (a valid device pointer; every list is empty)
+    return out_ptr.astype(np.int32), cols.astype(np.int32)
+
+
 class FeatureList(list):
     """What _get_embedded(concatenation=False) returns in the reference: the list
     cat_list + mulhot_list.  The fused node computing their mean is attached, so
@@ -558,6 +602,23 @@ class EmbeddingAttribute(object):
         if len(items) == 0:
             items = np.zeros(1, dtype=np.int32)
         return rt.upload(ptr, torch.int32), rt.upload(items, torch.int32)
+
+    def prepare_recommend_exclusions(self, item_sets):
+        """Items each user must NOT be recommended (typically the training history): {user_index: items} dicts or a
+        (ptr, items) CSR pair in item-index space.  Mapped to logit columns through item_ind2logit_ind, sorted,
+        deduplicated and uploaded once; recommend(exclude_seen=True) reads them (exclusion_args)."""
+        if self._item2logit_np is None:
+            raise ValueError("recommend exclusions need item_ind2logit_ind")
+        ptr, cols = exclusion_csr(item_sets, self.n_users + 1, self._item2logit_np)   # users 0..n_users (_pos_csr)
+        self._ex_dev = (self.rt.upload(ptr, torch.int32), self.rt.upload(cols, torch.int32))
+
+    def exclusion_args(self):
+        """(row_keys, key_rows, ex_ptr, ex_cols) of the recommend rows: row r excludes the list of user
+        user_input[r % batch_size] (ops.topk_exclude_fill, ops.gemm_nt_topk_filter_excl)."""
+        ex = getattr(self, '_ex_dev', None)
+        if ex is None:
+            raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
+        return (self.u_indices['input'].value, self.batch_size, ex[0], ex[1])
 
     def set_pos_mode(self, forward_only):
         self._pos_mode = 'eval' if forward_only else 'train'      # :727

@@ -127,15 +127,24 @@ class MLP(G.Node):
 
 
 class TopK(G.Node):
-    """hmf_model.py:154 tf.nn.top_k(logits, top_N_items, sorted=True)."""
+    """hmf_model.py:154 tf.nn.top_k(logits, top_N_items, sorted=True).
+    exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
+    each row's excluded columns are set to -inf IN the logits before the select (nothing after this node may read
+    them), and winners of value -inf (rows with fewer than k eligible columns) get index -1."""
 
-    def __init__(self, rt, logits, k):
+    def __init__(self, rt, logits, k, exclude=None):
         super().__init__(rt, (logits.shape[0], k), (logits,))
         self.k = k
+        self.exclude = exclude
         self.indices = torch.empty((logits.shape[0], k), dtype=torch.int32, device=rt.device)
 
     def forward(self, train):
-        ops.topk(self.inputs[0].value, self.k, self.alloc_value(), self.indices)
+        x = self.inputs[0].value
+        if self.exclude is not None:
+            ops.topk_exclude_fill(x, 0, self.exclude())
+        ops.topk(x, self.k, self.alloc_value(), self.indices)
+        if self.exclude is not None:
+            ops.topk_mark_empty(self.value, self.indices)
 
 
 class StreamTopK(G.Node):
@@ -147,11 +156,17 @@ class StreamTopK(G.Node):
     one select over the lists and one merge finish.  A candidate list that overflows (scores rising along the
     vocabulary) sets a flag: overflowed() -- LatentProductModel.step re-runs the request on the chunked path.
     chunked: the GEMM runs over chunks of the pool rows, every chunk keeps its k best per row (radix select) and a
-    merge folds them into the running result."""
+    merge folds them into the running result.
+    exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
+    each row's excluded columns never enter the result (the first chunk and every chunked-path chunk are filled with
+    -inf at them, the fused GEMM's candidates skip them); winners of value -inf get index -1.  The log-sum-exp
+    (want_lse) stays over ALL the columns.  share: another StreamTopK over the same shapes whose logits chunk buffer
+    this one re-uses (plans run one after the other on one stream)."""
 
-    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False):
+    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None):
         super().__init__(rt, (latent.shape[0], k), (latent, pool))
         self.k, self.chunk = k, max(int(chunk), k)
+        self.exclude = exclude
         # want_lse: also self.lse [B] = log sum exp over ALL the row's logits (seqModel.py:514-517 reports the winners'
         # softmax values exp(v - lse)): per column range out of the fused GEMM / per chunk, combined at the end
         self.want_lse = bool(want_lse)
@@ -160,7 +175,10 @@ class StreamTopK(G.Node):
         B, V, dev = latent.shape[0], pool.shape[0], rt.device
         f32, i32 = torch.float32, torch.int32
         self.indices = torch.empty((B, k), dtype=i32, device=dev)
-        self._buf = torch.empty((B, min(self.chunk, V)), dtype=f32, device=dev)
+        if share is not None and tuple(share._buf.shape) == (B, min(self.chunk, V)):
+            self._buf = share._buf
+        else:
+            self._buf = torch.empty((B, min(self.chunk, V)), dtype=f32, device=dev)
         self._cv, self._ci = torch.empty((B, k), dtype=f32, device=dev), torch.empty((B, k), dtype=i32, device=dev)
         self._ov, self._oi = torch.empty((B, k), dtype=f32, device=dev), torch.empty((B, k), dtype=i32, device=dev)
         tail = V % self.chunk                       # a last chunk narrower than k keeps only `tail` entries
@@ -207,23 +225,31 @@ class StreamTopK(G.Node):
         V, k = pool.shape[0], self.k
         run_v, run_i = self.alloc_value(), self.indices
         out_v, out_i = self._ov, self._oi
+        ex = self.exclude() if self.exclude is not None else None
         if self.fused and V > self.chunk and pool.value.stride(0) % 4 == 0 and latent.value.stride(0) % 4 == 0:
             n0 = self.chunk
             lg = self._buf[:, :n0]
             bias = pool.bias_value
             ops.gemm(latent.value, pool.value[:n0], lg, self.rt.ws, transB=True,
                      col_bias=bias[:n0] if bias is not None else None)
-            ops.topk_chunk(lg, k, 0, run_v, run_i)
             capp, cand_v, cand_i, cpos, parts = self._cand_bufs(n0, V)
             lp = None
             if self.want_lse:
                 lp = self._lse_buf(parts + 1)
-                ops.row_logsumexp(lg, self._lse0)
+                ops.row_logsumexp(lg, self._lse0)               # (over the whole chunk: before the exclusion fill)
                 lp[:, parts].copy_(self._lse0)
+            if ex is not None:
+                ops.topk_exclude_fill(lg, 0, ex)                # threshold = the k-th best ELIGIBLE column
+            ops.topk_chunk(lg, k, 0, run_v, run_i)
             ops.fill_f32(cand_v.view(-1), float('-inf'))
             ops.fill_i32(self.overflow, 0)
-            ops.gemm_nt_topk_filter(latent.value, pool.value[n0:], bias[n0:] if bias is not None else None,
-                                    run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, lse_part=lp)
+            if ex is not None:
+                ops.gemm_nt_topk_filter_excl(latent.value, pool.value[n0:], bias[n0:] if bias is not None else None,
+                                             run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, ex,
+                                             lse_part=lp)
+            else:
+                ops.gemm_nt_topk_filter(latent.value, pool.value[n0:], bias[n0:] if bias is not None else None,
+                                        run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, lse_part=lp)
             if self.want_lse:
                 ops.row_logsumexp(lp, self.lse)
             ops.topk_chunk(cand_v, k, 0, self._cv, cpos)
@@ -231,6 +257,8 @@ class StreamTopK(G.Node):
             ops.topk_merge(run_v, run_i, self._cv, self._ci, k, out_v, out_i)
             self.value.copy_(out_v)
             self.indices.copy_(out_i)
+            if ex is not None:
+                ops.topk_mark_empty(self.value, self.indices)
             return
         nch = (V + self.chunk - 1) // self.chunk
         lp = self._lse_buf(nch) if self.want_lse else None
@@ -243,6 +271,8 @@ class StreamTopK(G.Node):
             if self.want_lse:
                 ops.row_logsumexp(lg, self._lse0)
                 lp[:, c0 // self.chunk].copy_(self._lse0)
+            if ex is not None:
+                ops.topk_exclude_fill(lg, c0, ex)
             if c0 == 0:                              # chunk >= k and V >= k: the first chunk fills all k
                 ops.topk_chunk(lg, k, 0, run_v, run_i)
                 continue
@@ -254,6 +284,8 @@ class StreamTopK(G.Node):
         if run_v.data_ptr() != self.value.data_ptr():
             self.value.copy_(run_v)
             self.indices.copy_(run_i)
+        if ex is not None:
+            ops.topk_mark_empty(self.value, self.indices)
         if self.want_lse:
             ops.row_logsumexp(lp, self.lse)
 
@@ -394,6 +426,24 @@ class LatentProductModel(object):
     def prepare_warp(self, pos_item_set, pos_item_set_eval):
         self.att_emb.prepare_warp(pos_item_set, pos_item_set_eval)
 
+    def prepare_recommend_exclusions(self, item_sets):
+        """The items recommend(exclude_seen=True) leaves out per user -- typically the training history:
+        {user_index: items} or a (ptr, items) CSR pair in item-index space (EmbeddingAttribute.
+        prepare_recommend_exclusions).  A second call replaces the lists (the captured plan is dropped)."""
+        self._plans.pop('recommend_ex', None)
+        self.att_emb.prepare_recommend_exclusions(item_sets)
+
+    def _topk_ex(self):
+        """The excluding twin of self.topk (built on first use; the plain node and its plan stay as they are)."""
+        if getattr(self, 'topk_ex', None) is None:
+            m, t = self.att_emb, self.topk
+            if isinstance(t, StreamTopK):
+                self.topk_ex = StreamTopK(self.rt, t.inputs[0], t.inputs[1], t.k, chunk=t.chunk,
+                                          exclude=m.exclusion_args, share=t)
+            else:
+                self.topk_ex = TopK(self.rt, t.inputs[0], t.k, exclude=m.exclusion_args)
+        return self.topk_ex
+
     def _plan(self, key):
         if key in self._plans:
             return self._plans[key]
@@ -410,6 +460,9 @@ class LatentProductModel(object):
             p = G.Plan(rt, [self.loss_eval], False, masks)
         elif key == 'recommend':
             p = G.Plan(rt, [self.topk], False, [])
+        elif key == 'recommend_ex':
+            m.exclusion_args()                 # (raises before anything is built when no lists were prepared)
+            p = G.Plan(rt, [self._topk_ex()], False, [])
         elif key == 'warp_eval':
             p = G.Plan(rt, [self.batch_loss], False, [m.mask['warp_eval']])
         else:
@@ -492,16 +545,23 @@ class LatentProductModel(object):
 
     def step_async(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
                    item_sampled_id2idx=None, forward_only=False, recommend=False,
-                   recommend_new=False, loss=None, run_op=None, run_meta=None):
+                   recommend_new=False, loss=None, run_op=None, run_meta=None, exclude_seen=False):
         """step() without the device->host read of the result: returns the MeanLoss
         node (call .read() for the device scalar) / the top-k index tensor.  recommend with the streaming top-k
         (StreamTopK, fused form): the result is complete only if `self.topk.overflowed()` is False afterwards
-        (one device -> host read; step() checks it and re-runs the request on the chunked path)."""
+        (one device -> host read; step() checks it and re-runs the request on the chunked path).
+        exclude_seen (with recommend): leave out each user's items of prepare_recommend_exclusions -- node
+        self.topk_ex, plan 'recommend_ex'; a user with fewer than top_N eligible items gets -1 tails."""
         if loss is None:
             loss = self.loss_function
+        if exclude_seen and recommend:
+            self.att_emb.exclusion_args()      # ValueError before any feed when nothing was prepared
         self._cur = (user_input, item_input)
         self._feed(user_input, item_input, recommend, loss, item_sampled, item_sampled_id2idx,
                    forward_only)
+        if recommend and exclude_seen:
+            self._plan('recommend_ex').run()
+            return self.topk_ex.indices
         if recommend:
             self._plan('recommend').run()
             return self.topk.indices
@@ -522,25 +582,28 @@ class LatentProductModel(object):
 
     def step(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
-             loss=None, run_op=None, run_meta=None):
+             loss=None, run_op=None, run_meta=None, exclude_seen=False):
         """hmf_model.py:162-228.  Returns: train -> mean loss (float); forward_only ->
-        loss_eval (float); recommend -> int32 [mb, top_N]; warp_eval -> [loss, rank]."""
+        loss_eval (float); recommend -> int32 [mb, top_N]; warp_eval -> [loss, rank].
+        recommend with exclude_seen=True: the top_N logit indices without each user's items of
+        prepare_recommend_exclusions (ValueError if none were prepared); -1 where a user has fewer eligible items."""
         out = self.step_async(session, user_input, item_input, neg_item_input, item_sampled,
                               item_sampled_id2idx, forward_only, recommend, recommend_new, loss,
-                              run_op, run_meta)
+                              run_op, run_meta, exclude_seen=exclude_seen)
         if recommend:
-            if isinstance(self.topk, StreamTopK) and self.topk.overflowed():
+            node, key = (self.topk_ex, 'recommend_ex') if exclude_seen else (self.topk, 'recommend')
+            if isinstance(node, StreamTopK) and node.overflowed():
                 # a candidate list of the fused top-k was too short for this batch: once more on the chunked path
-                self.topk.fused = False
-                self._plans.pop('recommend', None)
+                node.fused = False
+                self._plans.pop(key, None)
                 try:
                     out = self.step_async(session, user_input, item_input, neg_item_input, item_sampled,
                                           item_sampled_id2idx, forward_only, recommend, recommend_new, loss, run_op,
-                                          run_meta)
+                                          run_meta, exclude_seen=exclude_seen)
                     return out.cpu().numpy()
                 finally:
-                    self.topk.fused = True
-                    self._plans.pop('recommend', None)
+                    node.fused = True
+                    self._plans.pop(key, None)
             return out.cpu().numpy()
         if isinstance(out, list):
             return [o.cpu().numpy() for o in out]

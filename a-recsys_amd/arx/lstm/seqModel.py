@@ -267,16 +267,26 @@ class SeqLoss(G.Node):
 class TopKSoftmax(G.Node):
     """seqModel.py:514-517  tf.nn.top_k(tf.nn.softmax(full_logits), topk_n, sorted=True) for every
     time-major row: top-k of the logits (same order as the softmax) + the row logsumexp;
-    the softmax values of the k winners are exp(v - lse)."""
+    the softmax values of the k winners are exp(v - lse).
+    exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
+    the row logsumexp is taken over ALL the columns first, then each row's excluded columns are set to -inf IN the
+    logits and the select runs; winners of value -inf get index -1 (softmax value exp(-inf) = 0)."""
 
-    def __init__(self, rt, logits, k):
+    def __init__(self, rt, logits, k, exclude=None):
         super().__init__(rt, (logits.shape[0], k), (logits,))
         self.k = k
+        self.exclude = exclude
         self.indices = torch.empty((logits.shape[0], k), dtype=torch.int32, device=rt.device)
         self.lse = torch.empty((logits.shape[0],), dtype=torch.float32, device=rt.device)
 
     def forward(self, train):
         x = self.inputs[0].value
+        if self.exclude is not None:
+            ops.row_logsumexp(x, self.lse)
+            ops.topk_exclude_fill(x, 0, self.exclude())
+            ops.topk(x, self.k, self.alloc_value(), self.indices)
+            ops.topk_mark_empty(self.value, self.indices)
+            return
         ops.topk(x, self.k, self.alloc_value(), self.indices)
         ops.row_logsumexp(x, self.lse)
 
@@ -495,6 +505,7 @@ class SeqModel(SeqBatching):
             sel = RowsAt(rt, hs, bk['rec_rows'])
             bk['recommend_stream'] = StreamTopK(rt, sel, m._pool_embed('full', self.output_feat),
                                                 min(self.topk_n, m.logit_size), want_lse=True)
+        bk['full'] = full
         bk['plans'] = {}
         self._bk[bucket_id] = bk
         return bk
@@ -508,6 +519,8 @@ class SeqModel(SeqBatching):
                 bk['plans'][key] = G.Plan(self.rt, [bk['train']], True, masks)
             elif key == 'recommend':
                 bk['plans'][key] = G.Plan(self.rt, [bk.get('recommend_stream', bk['recommend'])], False, [])
+            elif key == 'recommend_ex':
+                bk['plans'][key] = G.Plan(self.rt, [self._recommend_ex_node(bk)], False, [])
             else:
                 l = 'warp' if self.loss == 'mw' else ('ce' if self.loss == 'mce' else self.loss)
                 masks = [m.mask[l]] if (l in m.mask and not bk.get('eval_streamed')) else []
@@ -782,11 +795,37 @@ class SeqModel(SeqBatching):
                                item_sampled, item_sampled_id2idx, forward_only, recommend)
         return float(node.read().item())
 
-    def step_recommend(self, session, user_input, item_inputs, positions, bucket_id):
+    def prepare_recommend_exclusions(self, item_sets):
+        """The items step_recommend(exclude_seen=True) leaves out per user: {user_index: items} or a (ptr, items) CSR
+        pair in item-index space (EmbeddingAttribute.prepare_recommend_exclusions).  A second call replaces them."""
+        for bk in self._bk.values():
+            bk['plans'].pop('recommend_ex', None)
+        self.att_emb.prepare_recommend_exclusions(item_sets)
+
+    def _recommend_ex_node(self, bk):
+        """The excluding twin of the bucket's recommend node (built on first use).  Rows are the time-major [L*mb]
+        logits rows (user_input[r % mb]) or, streamed, the mb gathered rows (user_input[r])."""
+        if 'recommend_ex' not in bk:
+            m = self.att_emb
+            if 'recommend_stream' in bk:
+                from ..hmf.hmf_model import StreamTopK
+                t = bk['recommend_stream']
+                bk['recommend_ex'] = StreamTopK(self.rt, t.inputs[0], t.inputs[1], t.k, chunk=t.chunk, want_lse=True,
+                                                exclude=m.exclusion_args, share=t)
+            else:
+                bk['recommend_ex'] = TopKSoftmax(self.rt, bk['full'], bk['recommend'].k, exclude=m.exclusion_args)
+        return bk['recommend_ex']
+
+    def step_recommend(self, session, user_input, item_inputs, positions, bucket_id, exclude_seen=False):
         """seqModel.py:326-353 -> [(uid, values[topk_n], indexes[topk_n])]: the top-k softmax
         values / logit indexes at time position positions[i] of sequence i.  Small vocabularies: the full
         [L*mb, V] logits are materialised; past ARX_STREAM_TOPK_BYTES (1 GB) the mb rows asked for are gathered
-        and the fused full-vocabulary top-k + log-sum-exp of hmf_model.StreamTopK runs on them (round 5)."""
+        and the fused full-vocabulary top-k + log-sum-exp of hmf_model.StreamTopK runs on them (round 5).
+        exclude_seen: leave out user_input[i]'s items of prepare_recommend_exclusions (plan 'recommend_ex'); the
+        softmax normaliser stays over the full vocabulary, so a winner's value equals the non-excluding one; where
+        a user has fewer than topk_n eligible items the tail has index -1 and value 0."""
+        if exclude_seen:
+            self.att_emb.exclusion_args()      # ValueError before any feed when nothing was prepared
         L = self.buckets[bucket_id]
         m, B = self.att_emb, self.batch_size
         it = item_inputs
@@ -796,22 +835,23 @@ class SeqModel(SeqBatching):
         m.add_input({}, user_input, None, forward_only=True, recommend=True, loss=self.loss)
         bk = self._bucket(bucket_id)
         users = user_input.cpu().numpy() if isinstance(user_input, torch.Tensor) else user_input
+        key = 'recommend_ex' if exclude_seen else 'recommend'
         if 'recommend_stream' in bk:
-            node = bk['recommend_stream']
+            node = self._recommend_ex_node(bk) if exclude_seen else bk['recommend_stream']
             bk['rec_rows'].feed(np.asarray([int(pos) * B + i for i, pos in enumerate(positions)], dtype=np.int32))
-            self._plan(bucket_id, 'recommend').run()
+            self._plan(bucket_id, key).run()
             if node.overflowed():             # a candidate list of the fused top-k was too short: the chunked path
                 node.fused = False
-                bk['plans'].pop('recommend', None)
+                bk['plans'].pop(key, None)
                 try:
-                    self._plan(bucket_id, 'recommend').run()
+                    self._plan(bucket_id, key).run()
                 finally:
                     node.fused = True
-                    bk['plans'].pop('recommend', None)
+                    bk['plans'].pop(key, None)
             vals, idx, lse = node.value.cpu().numpy(), node.indices.cpu().numpy(), node.lse.cpu().numpy()
             return [(users[i], np.exp(vals[i] - lse[i]), idx[i]) for i in range(len(positions))]
-        self._plan(bucket_id, 'recommend').run()
-        node = bk['recommend']
+        self._plan(bucket_id, key).run()
+        node = self._recommend_ex_node(bk) if exclude_seen else bk['recommend']
         vals = node.value.cpu().numpy()
         idx = node.indices.cpu().numpy()
         lse = node.lse.cpu().numpy()

@@ -1065,6 +1065,31 @@ def gemm_nt_topk_filter(A, Bm, col_bias, thr, col_base, cand_v, cand_i, capp, ov
          int(capp), _p(overflow), _p(lse_part), int(lse_part.stride(0)) if lse_part is not None else 0, _stream())
 
 
+def gemm_nt_topk_filter_excl(A, Bm, col_bias, thr, col_base, cand_v, cand_i, capp, overflow, ex, lse_part=None):
+    """gemm_nt_topk_filter whose candidates skip each row's excluded columns (arx.h).  ex: (row_keys, key_rows,
+    ex_ptr, ex_cols) -- row r's list is ex_cols[ex_ptr[key] .. ex_ptr[key + 1]), key = row_keys[r % key_rows]."""
+    keys, key_rows, ptr, cols = ex
+    call("arx_gemm_nt_topk_filter_excl", _p(A), _ld(A), int(A.shape[0]), _p(Bm), _ld(Bm), int(Bm.shape[0]),
+         int(A.shape[1]), _p(col_bias), _p(thr), int(thr.stride(0)), int(col_base), _p(cand_v), _p(cand_i),
+         int(cand_v.stride(0)), int(capp), _p(overflow), _p(lse_part),
+         int(lse_part.stride(0)) if lse_part is not None else 0, _p(keys), int(key_rows), _p(ptr), _p(cols), _stream())
+
+
+def topk_exclude_fill(logits, col0, ex):
+    """logits[r, c - col0] = -inf for row r's excluded columns c in [col0, col0 + logits.shape[1]) (arx.h)."""
+    if logits.numel() == 0:
+        return
+    keys, key_rows, ptr, cols = ex
+    call("arx_topk_exclude_fill", _p(logits), _ld(logits), int(logits.shape[0]), int(col0), int(logits.shape[1]),
+         _p(keys), int(key_rows), _p(ptr), _p(cols), _stream())
+
+
+def topk_mark_empty(values, indices):
+    """indices = -1 where values == -inf (a row with fewer eligible columns than k)."""
+    call("arx_topk_mark_empty", _p(values), _ld(values), _p(indices), _ld(indices), int(values.shape[0]),
+         int(values.shape[1]), _stream())
+
+
 def gemm_nt_eval_parts(A, Bm, col_bias, tscore, lse_part, relu_part):
     """Full-vocabulary evaluation sums out of the scorer GEMM, no logits (arx.h)."""
     ref = lse_part if lse_part is not None else relu_part

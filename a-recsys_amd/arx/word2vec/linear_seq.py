@@ -139,6 +139,12 @@ class LinearSeq(object):
     def prepare_warp(self, pos_item_set, pos_item_set_eval):
         self.att_emb.prepare_warp(pos_item_set, pos_item_set_eval)
 
+    def prepare_recommend_exclusions(self, item_sets):
+        """The items step(recommend=True, exclude_seen=True) leaves out per user: {user_index: items} or a (ptr, items)
+        CSR pair in item-index space (EmbeddingAttribute.prepare_recommend_exclusions).  A second call replaces them."""
+        self._plans.pop('recommend_ex', None)
+        self.att_emb.prepare_recommend_exclusions(item_sets)
+
     def _plan(self, key):
         if key not in self._plans:
             rt, m, loss = self.rt, self.att_emb, self.loss_function
@@ -147,19 +153,26 @@ class LinearSeq(object):
                 self._plans[key] = G.Plan(rt, [self.loss], True, masks)
             elif key == 'eval':
                 self._plans[key] = G.Plan(rt, [self.loss_test], False, masks)
+            elif key == 'recommend_ex':
+                if getattr(self, 'topk_ex', None) is None:      # the excluding twin of self.topk, on first use
+                    self.topk_ex = TopK(rt, self.topk.inputs[0], self.topk.k, exclude=m.exclusion_args)
+                self._plans[key] = G.Plan(rt, [self.topk_ex], False, [])
             else:
                 self._plans[key] = G.Plan(rt, [self.topk], False, [])
         return self._plans[key]
 
     def step(self, session, user_input, item_input=None, item_output=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
-             loss=None, run_op=None, run_meta=None):
+             loss=None, run_op=None, run_meta=None, exclude_seen=False):
         """linear_seq.py:67-121.  item_input: [n_input][mb] context items (time-major);
         item_output: [mb] target items.  Returns the mean loss (train / forward_only) or the
-        top-N logit indices [mb, top_N] (recommend)."""
+        top-N logit indices [mb, top_N] (recommend; exclude_seen=True: without each user's items of
+        prepare_recommend_exclusions, -1 where a user has fewer eligible items)."""
         m = self.att_emb
         if recommend_new:
             raise NotImplementedError("indices_test is never built by the reference (linear_seq.py:98)")
+        if recommend and exclude_seen:
+            m.exclusion_args()                 # ValueError before any feed when nothing was prepared
         if not recommend:
             if isinstance(item_output, torch.Tensor):
                 self.item_id_target.feed(item_output)
@@ -169,6 +182,9 @@ class LinearSeq(object):
         m.add_input({}, user_input, item_input, neg_item_input=None, item_sampled=item_sampled,
                     item_sampled_id2idx=item_sampled_id2idx, forward_only=forward_only,
                     recommend=recommend, loss=loss or self.loss_function)
+        if recommend and exclude_seen:
+            self._plan('recommend_ex').run()
+            return self.topk_ex.indices.cpu().numpy()
         if recommend:
             self._plan('recommend').run()
             return self.topk.indices.cpu().numpy()

@@ -56,11 +56,16 @@ struct NtFilter {
   // without the logits: relu_part[row * ldl + part] = sum over the range of relu(v - tsc[row] + 1) (WMRB, :605-618);
   // thr == nullptr: no candidate lists at all (arx_gemm_nt_eval_parts)
   const float* tsc; float* relu_part;
+  // kNtExcl (the recommend path with each user's seen items left out): row r's excluded ABSOLUTE columns are
+  // ex_cols[ex_ptr[key] .. ex_ptr[key + 1]), sorted ascending, key = row_keys[r % key_rows] (< 0: nothing excluded)
+  const int32_t* row_keys; int64_t key_rows;
+  const int32_t* ex_ptr; const int32_t* ex_cols;
 };
 
-// MODE (FILTER kernels): bit 0 candidate lists (thr), bit 1 lse_part, bit 2 relu_part -- a template parameter, not a
-// run-time switch: every feature is 32 registers of per-row state and the plain kernel already holds 246
-constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4;
+// MODE (FILTER kernels): bit 0 candidate lists (thr), bit 1 lse_part, bit 2 relu_part, bit 3 exclusion lists (with
+// bit 0 only) -- a template parameter, not a run-time switch: every feature is 32 registers of per-row state and the
+// plain kernel already holds 246
+constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8;
 
 template <int KT, int MODE = 0>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
@@ -69,6 +74,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
     const float* __restrict__ col_bias, int tiles_per_block, int nsplit, NtFilter flt) {
   constexpr bool FILTER = MODE != 0;
   constexpr bool want_topk = (MODE & kNtTopk) != 0, want_lse = (MODE & kNtLse) != 0, want_relu = (MODE & kNtRelu) != 0;
+  constexpr bool want_excl = (MODE & kNtExcl) != 0;
+  static_assert(!want_excl || want_topk, "the exclusion lists filter candidates");
   constexpr int NS = KT / 8;                  // steps of 4 MFMAs
   constexpr int CPR = KT / 4;                 // 16-B chunks per pool row
   constexpr int NLB = kNtBN * CPR / 256;      // DMA pieces per thread per tile
@@ -134,6 +141,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   __shared__ float s_th[want_topk ? kNtBM : 1];
   __shared__ float s_tq[want_relu ? kNtBM : 1];
   __shared__ int s_cnt[want_topk ? kNtBM : 1];
+  // kNtExcl: [beg, end) of each row's exclusion list (1 KB; read only by a lane whose logit beat the threshold)
+  __shared__ int s_xb[want_excl ? kNtBM : 1], s_xe[want_excl ? kNtBM : 1];
   float lm[want_lse ? 16 : 1], ls[want_lse ? 16 : 1], rsum[want_relu ? 16 : 1];
   bool ovf = false;
   if (FILTER) {
@@ -144,6 +153,34 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
         s_cnt[threadIdx.x] = 0;
       }
       if (want_relu) s_tq[threadIdx.x] = row < M ? flt.tsc[row] - 1.f : 0.f;
+      if (want_excl) {
+        int xb = 0, xe = 0;
+        if (row < M) {
+          const int32_t key = flt.row_keys[row % flt.key_rows];
+          if (key >= 0) {
+            // narrowed to this workgroup's columns [c_lo, c_hi) once here: the survivor searches get shorter
+            const int32_t c_lo = flt.col_base + (int32_t)(t_beg * kNtBN);
+            const int32_t c_hi = flt.col_base + (int32_t)min(t_end * kNtBN, N);
+            int lo = flt.ex_ptr[key], hi = flt.ex_ptr[key + 1];
+            xe = hi;
+            while (lo < hi) {
+              const int mid = (lo + hi) >> 1;
+              if (flt.ex_cols[mid] < c_lo) lo = mid + 1;
+              else hi = mid;
+            }
+            xb = lo;
+            hi = xe;
+            while (lo < hi) {
+              const int mid = (lo + hi) >> 1;
+              if (flt.ex_cols[mid] < c_hi) lo = mid + 1;
+              else hi = mid;
+            }
+            xe = lo;
+          }
+        }
+        s_xb[threadIdx.x] = xb;
+        s_xe[threadIdx.x] = xe;
+      }
     }
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -241,11 +278,24 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
             lm[e] = fmaxf(lm[e], v);
           }
           if (!want_topk) continue;
-          const bool pred = col < N && v > th[e];
+          bool pred = col < N && v > th[e];
+          const int rl = rl0 + (e & 3) + 8 * (e >> 2);
+          if (want_excl && pred) {
+            // a survivor (rare): lower_bound of its absolute column in the row's list, BEFORE the ballot, so an
+            // excluded column takes no position and the placement stays deterministic
+            const int32_t c = flt.col_base + (int32_t)col;
+            const int xe = s_xe[rl];
+            int lo = s_xb[rl], hi = xe;
+            while (lo < hi) {
+              const int mid = (lo + hi) >> 1;
+              if (flt.ex_cols[mid] < c) lo = mid + 1;
+              else hi = mid;
+            }
+            if (lo < xe && flt.ex_cols[lo] == c) pred = false;
+          }
           const unsigned long long m = __ballot(pred);
           if (m == 0ull) continue;                                  // (the common case by far)
           const uint32_t mh = lhi ? (uint32_t)(m >> 32) : (uint32_t)m;
-          const int rl = rl0 + (e & 3) + 8 * (e >> 2);
           // (the wave owns its rows: no other writer.  volatile: lane l31 == 0 stores the new length, the other lanes of
           // the half read it in the next (j, e) iteration -- a plain access would let the compiler carry a lane's
           // earlier load across a store that lane did not execute; advisor, round 5)
@@ -405,6 +455,38 @@ int arx_gemm_nt_topk_filter(const float* A, int64_t lda, int64_t M, const float*
     nt_launch_mode<kNtTopk | kNtLse>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
   else
     nt_launch_mode<kNtTopk>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_gemm_nt_topk_filter_excl(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
+                                 int64_t K, const float* col_bias, const float* thr, int64_t ldthr, int32_t col_base,
+                                 float* cand_v, int32_t* cand_i, int64_t ldcand, int capp, int* overflow, float* lse_part,
+                                 int64_t ldl, const int32_t* row_keys, int64_t key_rows, const int32_t* ex_ptr,
+                                 const int32_t* ex_cols, void* stream) {
+  ARX_CHECK_ARG(A && Bm && thr && cand_v && cand_i && overflow && M > 0 && N > 0 && capp > 0,
+                "arx_gemm_nt_topk_filter_excl: bad argument");
+  ARX_CHECK_ARG(row_keys && ex_ptr && ex_cols && key_rows > 0,
+                "arx_gemm_nt_topk_filter_excl: need row_keys, ex_ptr, ex_cols and key_rows > 0");
+  ARX_CHECK_ARG(col_base >= 0, "arx_gemm_nt_topk_filter_excl: col_base < 0");
+  ARX_CHECK_ARG(K == 32 || K == 64 || K == 128, "arx_gemm_nt_topk_filter_excl: K must be 32, 64 or 128");
+  ARX_CHECK_ARG(!((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) && lda % 4 == 0 &&
+                    ldb % 4 == 0,
+                "arx_gemm_nt_topk_filter_excl: operands must be 16-byte aligned");
+  int64_t tpb, ns;
+  nt_split(M, N, &tpb, &ns);
+  ARX_CHECK_ARG(ns * capp <= ldcand,
+                "arx_gemm_nt_topk_filter_excl: candidate rows too short (parts * capp > ldcand)");
+  const int64_t grid = ceil_div(M, (int64_t)kNtBM) * ns;
+  ARX_CHECK_ARG(grid <= 0x7fffffff, "arx_gemm_nt_topk_filter_excl: grid too large");
+  ARX_CHECK_ARG(!lse_part || ldl >= ns, "arx_gemm_nt_topk_filter_excl: lse_part rows too short (ldl < parts)");
+  const NtFilter f{thr,      ldthr,   cand_v,   cand_i,   ldcand,   capp,   col_base, overflow, lse_part,
+                   ldl,      nullptr, nullptr,  row_keys, key_rows, ex_ptr, ex_cols};
+  hipStream_t s = as_stream(stream);
+  if (lse_part)
+    nt_launch_mode<kNtTopk | kNtLse | kNtExcl>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
+  else
+    nt_launch_mode<kNtTopk | kNtExcl>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

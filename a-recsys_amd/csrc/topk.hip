@@ -8,6 +8,8 @@
 // one collecting pass: everything > T, plus as many == T as still needed, lowest column first
 // (tf.nn.top_k's tie rule); the <= 1024 winners are rank-sorted in LDS.  Four passes over the
 // row in total, whatever k is.
+// Recommend without each user's seen items: arx_topk_exclude_fill masks them in a logits chunk, arx_topk_mark_empty
+// turns the -inf tails of short rows into index -1.
 #include "common.h"
 
 namespace arx {
@@ -203,6 +205,46 @@ __global__ void k_take_rows_i32(const int32_t* __restrict__ table, int64_t ld, c
   out[r * ldo + j] = table[r * ld + pos[r * ldp + j]];
 }
 
+// Exclusion lists (recommend with each user's seen items left out): row r's list is ex_cols[ex_ptr[key] ..
+// ex_ptr[key + 1]), sorted ascending, key = row_keys[r % key_rows] (< 0: none).  One wave per row writes -inf at the
+// listed columns in [col0, col0 + ncols) of its logits row (column c lands at logits[r * ld + c - col0]): a lower_bound
+// finds the first one, the wave then strides through the list until it leaves the range.
+constexpr int kExRowsPerBlock = 4;
+
+__global__ __launch_bounds__(64 * kExRowsPerBlock) void k_topk_exclude_fill(
+    float* __restrict__ logits, int64_t ld, int64_t B, int32_t col0, int64_t ncols, const int32_t* __restrict__ row_keys,
+    int64_t key_rows, const int32_t* __restrict__ ex_ptr, const int32_t* __restrict__ ex_cols) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * kExRowsPerBlock + (threadIdx.x >> 6);
+  if (r >= B) return;
+  const int32_t key = row_keys[r % key_rows];
+  if (key < 0) return;
+  const int beg = ex_ptr[key], end = ex_ptr[key + 1];
+  int lo = beg, hi = end;                        // first entry >= col0 (the same search in every lane)
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (ex_cols[mid] < col0) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t c1 = (int64_t)col0 + ncols;
+  float* row = logits + r * ld;
+  for (int i = lo + lane; i < end; i += 64) {
+    const int64_t c = ex_cols[i];
+    if (c >= c1) break;                          // sorted: the rest lies past the range
+    if (c >= col0) row[c - col0] = -__builtin_inff();
+  }
+}
+
+// a winner whose value is -inf is no item (a row with fewer eligible columns than k): index -1
+__global__ void k_topk_mark_empty(const float* __restrict__ values, int64_t ldv, int32_t* __restrict__ indices,
+                                  int64_t ldi, int64_t B, int k) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * k) return;
+  const int64_t r = i / k;
+  const int j = (int)(i % k);
+  if (values[r * ldv + j] == -__builtin_inff()) indices[r * ldi + j] = -1;
+}
+
 }  // namespace
 
 int topk_select_launch(const float* logits, int64_t ld, int64_t B, int64_t V, int k, int32_t idx_base,
@@ -241,6 +283,31 @@ int arx_take_rows_i32(const int32_t* table, int64_t ld, const int32_t* pos, int6
   ARX_CHECK_ARG(table && pos && out && k > 0, "arx_take_rows_i32: bad argument");
   if (B <= 0) return ARX_OK;
   k_take_rows_i32<<<(int)ceil_div(B * k, 256), 256, 0, as_stream(stream)>>>(table, ld, pos, ldp, B, k, out, ldo);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_topk_exclude_fill(float* logits, int64_t ld, int64_t B, int32_t col0, int64_t ncols, const int32_t* row_keys,
+                          int64_t key_rows, const int32_t* ex_ptr, const int32_t* ex_cols, void* stream) {
+  ARX_CHECK_ARG(logits && row_keys && ex_ptr && ex_cols, "arx_topk_exclude_fill: null pointer");
+  ARX_CHECK_ARG(B >= 0 && ncols >= 0 && col0 >= 0 && key_rows > 0,
+                "arx_topk_exclude_fill: need B >= 0, ncols >= 0, col0 >= 0, key_rows > 0");
+  ARX_CHECK_ARG(B <= 1 || ld >= ncols, "arx_topk_exclude_fill: ld < ncols");
+  ARX_CHECK_ARG(ceil_div(B, (int64_t)kExRowsPerBlock) <= 0x7fffffff, "arx_topk_exclude_fill: too many rows");
+  if (B == 0 || ncols == 0) return ARX_OK;
+  k_topk_exclude_fill<<<(int)ceil_div(B, (int64_t)kExRowsPerBlock), 64 * kExRowsPerBlock, 0, as_stream(stream)>>>(
+      logits, ld, B, col0, ncols, row_keys, key_rows, ex_ptr, ex_cols);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_topk_mark_empty(const float* values, int64_t ldv, int32_t* indices, int64_t ldi, int64_t B, int k,
+                        void* stream) {
+  ARX_CHECK_ARG(values && indices, "arx_topk_mark_empty: null pointer");
+  ARX_CHECK_ARG(B >= 0 && k > 0 && (B <= 1 || (ldv >= k && ldi >= k)),
+                "arx_topk_mark_empty: need B >= 0, k > 0, ldv >= k, ldi >= k");
+  if (B == 0) return ARX_OK;
+  k_topk_mark_empty<<<(int)ceil_div(B * k, (int64_t)256), 256, 0, as_stream(stream)>>>(values, ldv, indices, ldi, B, k);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

@@ -910,6 +910,30 @@ int arx_gemm_nt_topk_filter(const float* A, int64_t lda, int64_t M, const float*
                             const float* col_bias, const float* thr, int64_t ldthr, int32_t col_base, float* cand_v,
                             int32_t* cand_i, int64_t ldcand, int capp, int* overflow, float* lse_part, int64_t ldl,
                             void* stream);
+/* Recommend only what a user has not seen yet (opt-in; every call above is unchanged).  Row r of a recommend batch has
+ * an EXCLUSION LIST of absolute logit columns: ex_cols[ex_ptr[key] .. ex_ptr[key + 1]), sorted ascending, for
+ * key = row_keys[r % key_rows] -- the mask_rows convention of the *_pos entries: HMF / LinearSeq rows are the batch's
+ * users (key_rows = B), the time-major [L*B] rows of SeqModel use user_input[r % B].  key < 0: nothing excluded;
+ * ex_ptr must have an entry key + 1 for every key >= 0 that occurs.  An excluded column never appears in a result;
+ * the others keep tf.nn.top_k's order (value descending, lower column first on ties); a row with fewer than k
+ * eligible columns ends in value -inf, index -1 (arx_topk_mark_empty).
+ * arx_topk_exclude_fill: logits[r * ld + (c - col0)] = -inf for every listed c of row r in [col0, col0 + ncols) --
+ * the materialised [B, V] logits (col0 = 0) and every chunk of the streaming scorer, ahead of arx_topk_chunk /
+ * arx_topk (a softmax normaliser over the FULL vocabulary, excluded items included, is taken before the fill).
+ * arx_gemm_nt_topk_filter_excl: arx_gemm_nt_topk_filter (same arguments, same outputs) whose candidates skip the
+ * listed columns col_base + column: with the first chunk filled first, thr is the k-th best ELIGIBLE column so far.  A
+ * list covering more than chunk - k columns of the first chunk leaves thr = -inf: every column survives, the segments
+ * overflow, and the caller takes the chunked path as for any overflow.
+ * arx_topk_mark_empty: indices[r * ldi + j] = -1 where values[r * ldv + j] == -inf, r < B, j < k. */
+int arx_topk_exclude_fill(float* logits, int64_t ld, int64_t B, int32_t col0, int64_t ncols, const int32_t* row_keys,
+                          int64_t key_rows, const int32_t* ex_ptr, const int32_t* ex_cols, void* stream);
+int arx_gemm_nt_topk_filter_excl(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
+                                 int64_t K, const float* col_bias, const float* thr, int64_t ldthr, int32_t col_base,
+                                 float* cand_v, int32_t* cand_i, int64_t ldcand, int capp, int* overflow, float* lse_part,
+                                 int64_t ldl, const int32_t* row_keys, int64_t key_rows, const int32_t* ex_ptr,
+                                 const int32_t* ex_cols, void* stream);
+int arx_topk_mark_empty(const float* values, int64_t ldv, int32_t* indices, int64_t ldi, int64_t B, int k,
+                        void* stream);
 /* The evaluation losses over the full vocabulary (hmf_model.py:130,144; seqModel.py:510: the full-softmax / full-WMRB
  * loss a sampled-loss model is selected on) in ONE pass of the same GEMM, no logits: per row and column range p
  * (arx_gemm_nt_topk_parts) lse_part[row][p] = log sum exp of the logits ('ce': loss = logsumexp_p(lse_part) - t) and /

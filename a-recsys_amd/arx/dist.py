@@ -253,6 +253,51 @@ class HipBackend(object):
     def copy_i32(self, src, dst):
         dst.copy_(src, non_blocking=True)
 
+    def shard_topk(self, U, E, bias, k, ex, values, indices):
+        """Recommend's local stage: values / indices [B, k] = every row's k best of U . E^T + bias over the shard's
+        rows, by (value desc, local column asc); ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols of local
+        columns) or None.  The streaming top-k of StreamTopK (hmf_model.TopKScan: fused filter GEMM, the chunked path
+        after an overflow or for shapes the fused kernel does not take); a shard with fewer than k rows fills the rest
+        with (-inf, -1).  Buffers and GEMM workspace are this stage's own (captured step graphs keep theirs)."""
+        from .hmf.hmf_model import TopKScan
+        ops = self.ops
+        B, V, d = int(U.shape[0]), int(E.shape[0]), int(U.shape[1])
+        if getattr(self, 'ws_rec', None) is None:
+            self.ws_rec, self._scans = ops.Workspace(U.device), {}
+        if V < k:
+            ops.fill_f32(values, float('-inf'))
+            ops.fill_i32(indices, -1)
+            if V == 0 or B == 0:
+                return
+            kk = V
+        else:
+            kk = k
+        key = (B, V, d, kk)
+        scan = self._scans.get(key)
+        if scan is None:
+            if len(self._scans) > 8:
+                self._scans.clear()
+            scan = self._scans[key] = TopKScan(B, V, d, kk, U.device)
+            scan.fused = scan.fused and int(E.shape[1]) == d
+            if kk < k:
+                scan.short = (torch.empty((B, kk), dtype=torch.float32, device=U.device),
+                              torch.empty((B, kk), dtype=torch.int32, device=U.device))
+        vo, io = (values, indices) if kk == k else scan.short
+        scan.run(U, E, bias, self.ws_rec, vo, io, ex)
+        if scan.overflowed():                 # a candidate segment was too short: this rank once more, chunked
+            scan.fused = False
+            try:
+                scan.run(U, E, bias, self.ws_rec, vo, io, ex)
+            finally:
+                scan.fused = True
+        if kk < k:
+            values[:, :kk].copy_(vo)
+            indices[:, :kk].copy_(io)
+
+    def topk_merge_shards(self, v, c, vo, io):
+        """[W, B, k] per-shard lists (local columns) -> [B, k] global ids (arx_topk_merge_shards)."""
+        self.ops.topk_merge_shards(v, c, vo, io)
+
 
 class ShardedHMF(object):
     """id-only HMF ('mw' loss) with row-sharded tables.  Global ids everywhere in
@@ -899,6 +944,149 @@ class ShardedHMF(object):
         dist.all_reduce(self.loss, op=dist.ReduceOp.SUM, group=self.group)
         return self.loss
 
+    # --------------------------------------------------------------- recommend
+    def prepare_recommend_exclusions(self, item_sets):
+        """The items recommend(exclude_seen=True) leaves out per user -- typically the training history.  A
+        collective: every rank passes the histories of users IT owns, {global user: global items} or a
+        (users, ptr, items) CSR triple.  The (user, item) pairs travel to the item's owner (all_to_all); each rank
+        keeps, on the device, a CSR keyed by global user id (ptr: n_users + 1 entries) over its own local columns
+        (item // world), sorted, without duplicates.  A second call replaces the lists."""
+        W, r = self.world, self.rank
+        if isinstance(item_sets, dict):
+            keys = list(item_sets.keys())
+            parts = [np.asarray(list(item_sets[u]), dtype=np.int64).reshape(-1) for u in keys]
+            users = np.repeat(np.asarray(keys, dtype=np.int64), [len(x) for x in parts])
+            items = np.concatenate(parts) if parts else np.zeros(0, dtype=np.int64)
+        elif isinstance(item_sets, tuple) and len(item_sets) == 3:
+            u0 = np.asarray(item_sets[0], dtype=np.int64).reshape(-1)
+            ptr = np.asarray(item_sets[1], dtype=np.int64).reshape(-1)
+            items = np.asarray(item_sets[2], dtype=np.int64).reshape(-1)
+            if len(ptr) != len(u0) + 1 or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] > len(items):
+                raise ValueError("exclusions: ptr must have len(users) + 1 entries, start at 0, not decrease and "
+                                 "end within the items")
+            users = np.repeat(u0, np.diff(ptr))
+            items = items[:ptr[-1]]
+        else:
+            raise ValueError("exclusions: a {user: items} dict or a (users, ptr, items) CSR triple")
+        if len(users) and (users.min() < 0 or users.max() >= self.n_users or np.any(users % W != r)):
+            raise ValueError("exclusions: every user must be a global id in [0, %d) owned by rank %d (id %% %d == %d)"
+                             % (self.n_users, r, W, r))
+        if len(items) and (items.min() < 0 or items.max() >= self.n_items):
+            raise ValueError("exclusions: item ids must lie in [0, %d)" % self.n_items)
+        owner = items % W
+        order = np.argsort(owner, kind='stable')
+        pairs = np.stack([users, items], 1)[order].astype(np.int32).reshape(-1)
+        if W == 1:
+            recv = pairs
+        else:
+            send = np.bincount(owner, minlength=W).astype(np.int64)
+            st = torch.from_numpy(send).to(self.device)
+            rt = torch.empty_like(st)
+            _all_to_all(rt, st, group=self.group)
+            cnt = [int(v) for v in rt.cpu().tolist()]
+            out = torch.zeros((2 * sum(cnt),), dtype=torch.int32, device=self.device)
+            _all_to_all(out, torch.from_numpy(pairs).to(self.device), [2 * c for c in cnt],
+                        [2 * int(c) for c in send.tolist()], group=self.group)
+            recv = out.cpu().numpy()
+        ru, cols = recv[0::2].astype(np.int64), recv[1::2].astype(np.int64) // W
+        o = np.lexsort((cols, ru))
+        ru, cols = ru[o], cols[o]
+        if len(ru):
+            keep = np.ones(len(ru), dtype=bool)
+            keep[1:] = (ru[1:] != ru[:-1]) | (cols[1:] != cols[:-1])
+            ru, cols = ru[keep], cols[keep]
+        ptr = np.zeros(self.n_users + 1, dtype=np.int64)
+        np.cumsum(np.bincount(ru, minlength=self.n_users), out=ptr[1:])
+        if ptr[-1] >= 2 ** 31:
+            raise ValueError("exclusion lists: more than 2^31 - 1 entries on one rank")
+        if len(cols) == 0:
+            cols = np.zeros(1, dtype=np.int64)          # (a valid device pointer; every list is empty)
+        self._rec_ex = (torch.from_numpy(ptr.astype(np.int32)).to(self.device),
+                        torch.from_numpy(cols.astype(np.int32)).to(self.device))
+
+    def recommend(self, users, k, exclude_seen=False, return_values=False):
+        """Full-vocabulary top-k (run_hmf.py:340-409: top_k(logits, top_N) per user) of the row-sharded model.  A
+        collective: every rank calls it with the same k and exclude_seen.  users: global ids this rank owns,
+        0 <= len(users) <= B_loc (the count may differ between ranks).  Returns int32 global item ids
+        [len(users), k] on the device, ordered by (score desc, id asc) -- tf.nn.top_k's rule -- (and their float32
+        scores with return_values); -1 (score -inf) where a user has fewer than k eligible items.  exclude_seen:
+        leave out each user's items of prepare_recommend_exclusions (ValueError without it).
+
+          gather          this rank's user rows -> [B_loc, d] (padding rows: zeros, key -1)
+          all_gather      latents [B_loc, d] -> [B, d], user ids [B_loc] -> [B]
+          (local)         top-k of U_all . E_item[:ni]^T + b_item[:ni] over the shard's rows (backend.shard_topk:
+                          the fused filter GEMM of StreamTopK, chunked after an overflow -- on this rank only)
+          all_to_all      value / local-column lists [B, k] -> the ranks that own the rows: [W][B_loc][k]
+          (local)         W-way merge into global ids c * W + s (arx_topk_merge_shards)
+
+        Eager (no capture); with graph segments on the model's stream, joined with the caller's on both sides as
+        step() is, so a recommend right after a step reads that step's tables.  Its buffers are its own, per k."""
+        W, r = self.world, self.rank
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        u = u.astype(np.int64).reshape(-1)
+        k = int(k)
+        if not 1 <= k <= min(1024, self.n_items):
+            raise ValueError("recommend: need 1 <= k <= min(1024, n_items)")
+        if len(u) > self.B_loc:
+            raise ValueError("recommend: at most B_loc = %d users per call and rank" % self.B_loc)
+        if len(u) and (u.min() < 0 or u.max() >= self.n_users or np.any(u % W != r)):
+            raise ValueError("recommend: users must be global ids in [0, %d) owned by rank %d" % (self.n_users, r))
+        if exclude_seen and getattr(self, '_rec_ex', None) is None:
+            raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
+        if self.use_graphs:
+            outer = torch.cuda.current_stream(self.device)
+            if outer != self._stream:
+                self._stream.wait_stream(outer)
+                with torch.cuda.stream(self._stream):
+                    vo, io = self._recommend(u, k, exclude_seen)
+                outer.wait_stream(self._stream)
+            else:
+                vo, io = self._recommend(u, k, exclude_seen)
+        else:
+            vo, io = self._recommend(u, k, exclude_seen)
+        n = len(u)
+        ids = io[:n].clone()
+        return (ids, vo[:n].clone()) if return_values else ids
+
+    def _recommend(self, u, k, exclude_seen):
+        be, W, B_loc, B, d = self.be, self.world, self.B_loc, self.B, self.d
+        dev, f32, i32 = self.device, torch.float32, torch.int32
+        n = len(u)
+        if getattr(self, '_rec_lat', None) is None:     # [B_loc] keys, [B_loc, d] rows; gathered: [B], [B, d]
+            kl, ul = torch.full((B_loc,), -1, dtype=i32, device=dev), torch.zeros((B_loc, d), dtype=f32, device=dev)
+            self._rec_lat = (kl, ul) + ((kl, ul) if W == 1 else
+                                        (torch.empty((B,), dtype=i32, device=dev),
+                                         torch.empty((B, d), dtype=f32, device=dev)))
+            self._rec_k = {}
+        keys_loc, U_loc, keys_all, U_all = self._rec_lat
+        bk = self._rec_k.get(k)
+        if bk is None:
+            e = lambda dt, *sh: torch.empty(sh, dtype=dt, device=dev)
+            bk = self._rec_k[k] = (e(f32, B, k), e(i32, B, k), e(f32, W, B_loc, k), e(i32, W, B_loc, k),
+                                   e(f32, B_loc, k), e(i32, B_loc, k))
+        out_v, out_i, recv_v, recv_c, vo, io = bk
+        kh = np.full(B_loc, -1, dtype=np.int32)
+        kh[:n] = u
+        keys_loc.copy_(torch.from_numpy(kh))
+        if n:
+            rows = torch.from_numpy((u // W).astype(np.int32)).to(dev)
+            be.gather_rows(self.E_user, None, rows, U_loc[:n], None)
+        if n < B_loc:
+            be.fill_zero(U_loc[n:])
+        if W > 1:
+            dist.all_gather_into_tensor(U_all, U_loc, group=self.group)
+            dist.all_gather_into_tensor(keys_all, keys_loc, group=self.group)
+        ex = (keys_all, B, self._rec_ex[0], self._rec_ex[1]) if exclude_seen else None
+        ni = self.ni_loc
+        be.shard_topk(U_all, self.E_item[:ni], self.b_item[:ni], k, ex, out_v, out_i)
+        if W == 1:
+            recv_v, recv_c = out_v.view(1, B, k), out_i.view(1, B, k)
+        else:
+            _all_to_all(recv_v.view(B, k), out_v, group=self.group)
+            _all_to_all(recv_c.view(B, k), out_i, group=self.group)
+        be.topk_merge_shards(recv_v, recv_c, vo, io)
+        return vo, io
+
     # ---- helpers for tests / checkpoints ----
     def gather_global_tables(self):
         """Reassemble the striped tables on every rank (tests only; O(table))."""
@@ -1206,6 +1394,11 @@ class ShardedHMFBags(ShardedHMF):
                         self.lr)
         self.steps += 1
 
+    def recommend(self, users, k, exclude_seen=False, return_values=False):
+        """Not yet: the item latents are bag means, and recommend would first need them materialised per shard."""
+        raise NotImplementedError("%s.recommend: item latents are bag means (ShardedHMF has recommend)"
+                                  % type(self).__name__)
+
     def gather_global_tables(self):
         out = super().gather_global_tables()
         W = self.world
@@ -1431,6 +1624,11 @@ class ShardedHMFRepTokens(ShardedHMF):
             w_tokb.wait()
         self._het_tok_apply()
         self.steps += 1
+
+    def recommend(self, users, k, exclude_seen=False, return_values=False):
+        """Not yet: the item latents are bag means, and recommend would first need them materialised per shard."""
+        raise NotImplementedError("%s.recommend: item latents are bag means (ShardedHMF has recommend)"
+                                  % type(self).__name__)
 
     def gather_global_tables(self):
         out = super().gather_global_tables()

@@ -147,32 +147,20 @@ class TopK(G.Node):
             ops.topk_mark_empty(self.value, self.indices)
 
 
-class StreamTopK(G.Node):
-    """top_k over the FULL vocabulary without the [mb, V] logits (SURVEY 8f #3) -- same indices / values as
-    TopK(Prediction), tf.nn.top_k's tie rule included.
-    fused (round 5, the default where the scorer GEMM's small-K kernel applies): the first chunk of the pool gives
-    every row its k best (GEMM -> radix select); the scorer GEMM over ALL the other columns then writes no logits --
-    arx_gemm_nt_topk_filter keeps only what beats the row's k-th best so far, as short candidate lists in column order;
-    one select over the lists and one merge finish.  A candidate list that overflows (scores rising along the
-    vocabulary) sets a flag: overflowed() -- LatentProductModel.step re-runs the request on the chunked path.
-    chunked: the GEMM runs over chunks of the pool rows, every chunk keeps its k best per row (radix select) and a
-    merge folds them into the running result.
-    exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
-    each row's excluded columns never enter the result (the first chunk and every chunked-path chunk are filled with
-    -inf at them, the fused GEMM's candidates skip them); winners of value -inf get index -1.  The log-sum-exp
-    (want_lse) stays over ALL the columns.  share: another StreamTopK over the same shapes whose logits chunk buffer
-    this one re-uses (plans run one after the other on one stream)."""
+class TopKScan(object):
+    """The streaming full-vocabulary top-k of StreamTopK without a Runtime: its buffers and its algorithm on plain
+    tensors, run(latent, pool, bias, ...) -- StreamTopK runs on it, and so does the per-shard stage of the row-sharded
+    recommend (arx.dist.ShardedHMF.recommend), whose tables are no graph nodes.  B rows, V pool rows of width d."""
 
-    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None):
-        super().__init__(rt, (latent.shape[0], k), (latent, pool))
+    def __init__(self, B, V, d, k, device, chunk=65536, want_lse=False, share=None):
         self.k, self.chunk = k, max(int(chunk), k)
-        self.exclude = exclude
+        self._rows, self._dev = B, device
         # want_lse: also self.lse [B] = log sum exp over ALL the row's logits (seqModel.py:514-517 reports the winners'
         # softmax values exp(v - lse)): per column range out of the fused GEMM / per chunk, combined at the end
         self.want_lse = bool(want_lse)
-        self.lse = torch.empty(latent.shape[0], dtype=torch.float32, device=rt.device) if want_lse else None
+        self.lse = torch.empty(B, dtype=torch.float32, device=device) if want_lse else None
         self._lse_parts = None
-        B, V, dev = latent.shape[0], pool.shape[0], rt.device
+        dev = device
         f32, i32 = torch.float32, torch.int32
         self.indices = torch.empty((B, k), dtype=i32, device=dev)
         if share is not None and tuple(share._buf.shape) == (B, min(self.chunk, V)):
@@ -184,8 +172,7 @@ class StreamTopK(G.Node):
         tail = V % self.chunk                       # a last chunk narrower than k keeps only `tail` entries
         kt = tail if 0 < tail < k else k
         self._tv, self._ti = torch.empty((B, kt), dtype=f32, device=dev), torch.empty((B, kt), dtype=i32, device=dev)
-        self.fused = (os.environ.get('ARX_TOPK_FUSED', '1') != '0' and latent.shape[1] in (32, 64, 128)
-                      and pool.shape[1] == latent.shape[1])
+        self.fused = os.environ.get('ARX_TOPK_FUSED', '1') != '0' and d in (32, 64, 128)
         self.overflow = torch.zeros(1, dtype=i32, device=dev)
         self.slack, self.min_capp = 4.0, 32          # candidate segment = slack x the expected survivors, >= min_capp
         self._cand = None
@@ -195,7 +182,7 @@ class StreamTopK(G.Node):
         no particular order along the vocabulary); four times that, at least 32."""
         key = (n0, V, self.slack, self.min_capp)
         if self._cand is None or self._cand[0] != key:
-            B, k, dev = self.shape[0], self.k, self.rt.device
+            B, k, dev = self._rows, self.k, self._dev
             parts = ops.gemm_nt_topk_parts(B, V - n0)
             expect = k * (V - n0) / float(n0) / parts
             capp = self.min_capp
@@ -211,7 +198,7 @@ class StreamTopK(G.Node):
 
     def _lse_buf(self, ncols):
         if self._lse_parts is None or self._lse_parts.shape[1] != ncols:
-            B, dev = self.shape[0], self.rt.device
+            B, dev = self._rows, self._dev
             self._lse_parts = torch.empty((B, ncols), dtype=torch.float32, device=dev)
             self._lse0 = torch.empty(B, dtype=torch.float32, device=dev)
         return self._lse_parts
@@ -220,18 +207,16 @@ class StreamTopK(G.Node):
         """True when the last fused run dropped candidates (device -> host read)."""
         return bool(self.fused and int(self.overflow.item()) != 0)
 
-    def forward(self, train):
-        latent, pool = self.inputs
+    def run(self, latent, pool, bias, ws, values, indices, ex=None):
+        """values / indices [B, k] = the top-k of latent . pool^T + bias (bias may be None) over all V >= k pool rows;
+        ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace."""
         V, k = pool.shape[0], self.k
-        run_v, run_i = self.alloc_value(), self.indices
+        run_v, run_i = values, indices
         out_v, out_i = self._ov, self._oi
-        ex = self.exclude() if self.exclude is not None else None
-        if self.fused and V > self.chunk and pool.value.stride(0) % 4 == 0 and latent.value.stride(0) % 4 == 0:
+        if self.fused and V > self.chunk and pool.stride(0) % 4 == 0 and latent.stride(0) % 4 == 0:
             n0 = self.chunk
             lg = self._buf[:, :n0]
-            bias = pool.bias_value
-            ops.gemm(latent.value, pool.value[:n0], lg, self.rt.ws, transB=True,
-                     col_bias=bias[:n0] if bias is not None else None)
+            ops.gemm(latent, pool[:n0], lg, ws, transB=True, col_bias=bias[:n0] if bias is not None else None)
             capp, cand_v, cand_i, cpos, parts = self._cand_bufs(n0, V)
             lp = None
             if self.want_lse:
@@ -244,21 +229,21 @@ class StreamTopK(G.Node):
             ops.fill_f32(cand_v.view(-1), float('-inf'))
             ops.fill_i32(self.overflow, 0)
             if ex is not None:
-                ops.gemm_nt_topk_filter_excl(latent.value, pool.value[n0:], bias[n0:] if bias is not None else None,
+                ops.gemm_nt_topk_filter_excl(latent, pool[n0:], bias[n0:] if bias is not None else None,
                                              run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, ex,
                                              lse_part=lp)
             else:
-                ops.gemm_nt_topk_filter(latent.value, pool.value[n0:], bias[n0:] if bias is not None else None,
+                ops.gemm_nt_topk_filter(latent, pool[n0:], bias[n0:] if bias is not None else None,
                                         run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, lse_part=lp)
             if self.want_lse:
                 ops.row_logsumexp(lp, self.lse)
             ops.topk_chunk(cand_v, k, 0, self._cv, cpos)
             ops.take_rows_i32(cand_i, cpos, self._ci)
             ops.topk_merge(run_v, run_i, self._cv, self._ci, k, out_v, out_i)
-            self.value.copy_(out_v)
-            self.indices.copy_(out_i)
+            values.copy_(out_v)
+            indices.copy_(out_i)
             if ex is not None:
-                ops.topk_mark_empty(self.value, self.indices)
+                ops.topk_mark_empty(values, indices)
             return
         nch = (V + self.chunk - 1) // self.chunk
         lp = self._lse_buf(nch) if self.want_lse else None
@@ -266,8 +251,7 @@ class StreamTopK(G.Node):
             c1 = min(V, c0 + self.chunk)
             kc = min(k, c1 - c0)
             lg = self._buf[:, :c1 - c0]
-            bias = pool.bias_value[c0:c1] if pool.bias_value is not None else None
-            ops.gemm(latent.value, pool.value[c0:c1], lg, self.rt.ws, transB=True, col_bias=bias)
+            ops.gemm(latent, pool[c0:c1], lg, ws, transB=True, col_bias=bias[c0:c1] if bias is not None else None)
             if self.want_lse:
                 ops.row_logsumexp(lg, self._lse0)
                 lp[:, c0 // self.chunk].copy_(self._lse0)
@@ -281,13 +265,42 @@ class StreamTopK(G.Node):
             ops.topk_merge(run_v, run_i, cv, ci, k, out_v, out_i)
             run_v, out_v = out_v, run_v
             run_i, out_i = out_i, run_i
-        if run_v.data_ptr() != self.value.data_ptr():
-            self.value.copy_(run_v)
-            self.indices.copy_(run_i)
+        if run_v.data_ptr() != values.data_ptr():
+            values.copy_(run_v)
+            indices.copy_(run_i)
         if ex is not None:
-            ops.topk_mark_empty(self.value, self.indices)
+            ops.topk_mark_empty(values, indices)
         if self.want_lse:
             ops.row_logsumexp(lp, self.lse)
+
+
+class StreamTopK(G.Node, TopKScan):
+    """top_k over the FULL vocabulary without the [mb, V] logits (SURVEY 8f #3) -- same indices / values as
+    TopK(Prediction), tf.nn.top_k's tie rule included.
+    fused (round 5, the default where the scorer GEMM's small-K kernel applies): the first chunk of the pool gives
+    every row its k best (GEMM -> radix select); the scorer GEMM over ALL the other columns then writes no logits --
+    arx_gemm_nt_topk_filter keeps only what beats the row's k-th best so far, as short candidate lists in column order;
+    one select over the lists and one merge finish.  A candidate list that overflows (scores rising along the
+    vocabulary) sets a flag: overflowed() -- LatentProductModel.step re-runs the request on the chunked path.
+    chunked: the GEMM runs over chunks of the pool rows, every chunk keeps its k best per row (radix select) and a
+    merge folds them into the running result.
+    exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
+    each row's excluded columns never enter the result (the first chunk and every chunked-path chunk are filled with
+    -inf at them, the fused GEMM's candidates skip them); winners of value -inf get index -1.  The log-sum-exp
+    (want_lse) stays over ALL the columns.  share: another StreamTopK over the same shapes whose logits chunk buffer
+    this one re-uses (plans run one after the other on one stream).  The algorithm and its buffers: TopKScan."""
+
+    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None):
+        G.Node.__init__(self, rt, (latent.shape[0], k), (latent, pool))
+        TopKScan.__init__(self, latent.shape[0], pool.shape[0], latent.shape[1], k, rt.device, chunk=chunk,
+                          want_lse=want_lse, share=share)
+        self.exclude = exclude
+        self.fused = self.fused and pool.shape[1] == latent.shape[1]
+
+    def forward(self, train):
+        latent, pool = self.inputs
+        ex = self.exclude() if self.exclude is not None else None
+        self.run(latent.value, pool.value, pool.bias_value, self.rt.ws, self.alloc_value(), self.indices, ex)
 
 
 class LatentProductModel(object):

@@ -1090,6 +1090,18 @@ def topk_mark_empty(values, indices):
          int(values.shape[1]), _stream())
 
 
+def topk_merge_shards(v, c, vo, io):
+    """W-way merge of per-shard top-k lists into global ids (arx.h): v / c [W, B, k] (shard s's lists in block s,
+    local columns, -1 = empty) -> vo / io [B, k], id = c * W + s, order (value desc, id asc); -inf / empty -> -1."""
+    W, B, k = (int(x) for x in v.shape)
+    for t in (v, c, vo, io):
+        if not t.is_contiguous():
+            raise ValueError("topk_merge_shards: contiguous tensors only")
+    if tuple(c.shape) != (W, B, k) or tuple(vo.shape) != (B, k) or tuple(io.shape) != (B, k):
+        raise ValueError("topk_merge_shards: v / c [W, B, k], vo / io [B, k]")
+    call("arx_topk_merge_shards", _p(v), _p(c), B, W, k, _p(vo), _p(io), _stream())
+
+
 def gemm_nt_eval_parts(A, Bm, col_bias, tscore, lse_part, relu_part):
     """Full-vocabulary evaluation sums out of the scorer GEMM, no logits (arx.h)."""
     ref = lse_part if lse_part is not None else relu_part

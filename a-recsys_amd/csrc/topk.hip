@@ -10,6 +10,7 @@
 // row in total, whatever k is.
 // Recommend without each user's seen items: arx_topk_exclude_fill masks them in a logits chunk, arx_topk_mark_empty
 // turns the -inf tails of short rows into index -1.
+// Recommend of the row-sharded model: arx_topk_merge_shards folds the W shards' lists into global ids in one launch.
 #include "common.h"
 
 namespace arx {
@@ -245,6 +246,63 @@ __global__ void k_topk_mark_empty(const float* __restrict__ values, int64_t ldv,
   if (values[r * ldv + j] == -__builtin_inff()) indices[r * ldi + j] = -1;
 }
 
+// W-way merge of per-shard top-k lists (row-sharded recommend, owner = id % W): v / c [W][B][k], list (s, r) sorted
+// by (value desc, local column asc), c < 0 = empty.  One wave per row; lane s < W holds the head of list s as one
+// 64-bit key (order-preserving value image << 32 | ~global id: the larger key is the better entry, so the lower id
+// wins a tie -- tf.nn.top_k's rule), 0 when the list is used up.  Round j: a 64-lane max, the winning lane steps to
+// its next non-empty entry; lane j % 64 keeps round j's winner and the wave stores 64 results at a time.
+constexpr int kMergeRowsPerBlock = 4;
+
+__device__ __forceinline__ uint64_t shard_head(const float* __restrict__ v, const int32_t* __restrict__ c,
+                                               int64_t base, int& pos, int k, int W, int s) {
+  for (; pos < k; ++pos) {
+    const int32_t col = c[base + pos];
+    if (col < 0) continue;                                   // an empty entry is no candidate
+    const uint32_t gid = (uint32_t)((int64_t)col * W + s);
+    return ((uint64_t)ord_key(v[base + pos]) << 32) | (uint64_t)(0xffffffffu - gid);
+  }
+  return 0;
+}
+
+__global__ __launch_bounds__(64 * kMergeRowsPerBlock) void k_topk_merge_shards(
+    const float* __restrict__ v, const int32_t* __restrict__ c, int64_t B, int W, int k, float* __restrict__ vo,
+    int32_t* __restrict__ io) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * kMergeRowsPerBlock + (threadIdx.x >> 6);
+  if (r >= B) return;                                        // (whole waves: B is per wave)
+  const int64_t base = ((int64_t)lane * B + r) * k;          // list of shard `lane` for row r
+  int pos = 0;
+  uint64_t head = lane < W ? shard_head(v, c, base, pos, k, W, lane) : 0;
+  float keep_v = -__builtin_inff();
+  int32_t keep_i = -1;
+  for (int j = 0; j < k; ++j) {
+    uint64_t best = head;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const uint32_t lo = __shfl_xor((uint32_t)best, m, 64), hi = __shfl_xor((uint32_t)(best >> 32), m, 64);
+      const uint64_t o = ((uint64_t)hi << 32) | lo;
+      best = o > best ? o : best;
+    }
+    if (best != 0 && head == best) {                         // the one winning lane (global ids are distinct)
+      ++pos;
+      head = shard_head(v, c, base, pos, k, W, lane);
+    }
+    if (lane == (j & 63)) {
+      const float bv = ord_val((uint32_t)(best >> 32));
+      const bool none = best == 0 || bv == -__builtin_inff();
+      keep_v = none ? -__builtin_inff() : bv;
+      keep_i = none ? -1 : (int32_t)(0xffffffffu - (uint32_t)best);
+    }
+    if ((j & 63) == 63 || j == k - 1) {
+      const int64_t o = r * k + (j & ~63) + lane;
+      if (lane <= (j & 63)) {
+        vo[o] = keep_v;
+        io[o] = keep_i;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 int topk_select_launch(const float* logits, int64_t ld, int64_t B, int64_t V, int k, int32_t idx_base,
@@ -308,6 +366,20 @@ int arx_topk_mark_empty(const float* values, int64_t ldv, int32_t* indices, int6
                 "arx_topk_mark_empty: need B >= 0, k > 0, ldv >= k, ldi >= k");
   if (B == 0) return ARX_OK;
   k_topk_mark_empty<<<(int)ceil_div(B * k, (int64_t)256), 256, 0, as_stream(stream)>>>(values, ldv, indices, ldi, B, k);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_topk_merge_shards(const float* v, const int32_t* c, int64_t B, int W, int k, float* vo, int32_t* io,
+                          void* stream) {
+  ARX_CHECK_ARG(v && c && vo && io, "arx_topk_merge_shards: null pointer");
+  ARX_CHECK_ARG(W >= 1 && W <= 64, "arx_topk_merge_shards: need 1 <= W <= 64");
+  ARX_CHECK_ARG(k > 0 && k <= kMaxK, "arx_topk_merge_shards: need 0 < k <= 1024");
+  ARX_CHECK_ARG(B >= 0 && ceil_div(B, (int64_t)kMergeRowsPerBlock) <= 0x7fffffff,
+                "arx_topk_merge_shards: need 0 <= B, B / 4 < 2^31");
+  if (B == 0) return ARX_OK;
+  k_topk_merge_shards<<<(int)ceil_div(B, (int64_t)kMergeRowsPerBlock), 64 * kMergeRowsPerBlock, 0, as_stream(stream)>>>(
+      v, c, B, W, k, vo, io);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

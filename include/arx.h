@@ -934,6 +934,16 @@ int arx_gemm_nt_topk_filter_excl(const float* A, int64_t lda, int64_t M, const f
                                  const int32_t* ex_cols, void* stream);
 int arx_topk_mark_empty(const float* values, int64_t ldv, int32_t* indices, int64_t ldi, int64_t B, int k,
                         void* stream);
+/* Recommend of the row-sharded model (arx.dist.ShardedHMF.recommend; owner of item g = g % W, local column g / W):
+ * every shard ranks its own columns, the lists cross by all_to_all and this W-way merge forms the global top-k of the
+ * rows in ONE launch.  v / c: [W][B][k] contiguous -- block s holds shard s's lists (as all_to_all delivers them),
+ * each sorted by (value descending, local column ascending); c < 0 marks an empty entry.  vo / io [B][k]: the global
+ * ids c * W + s ordered by (value descending, global id ascending) -- tf.nn.top_k's tie rule (within one shard a
+ * lower local column is a lower global id, so each list is already in that order); empty entries never win, and a
+ * result slot without a candidate or with value -inf gets value -inf, index -1.  1 <= W <= 64, 1 <= k <= 1024;
+ * deterministic. */
+int arx_topk_merge_shards(const float* v, const int32_t* c, int64_t B, int W, int k, float* vo, int32_t* io,
+                          void* stream);
 /* The evaluation losses over the full vocabulary (hmf_model.py:130,144; seqModel.py:510: the full-softmax / full-WMRB
  * loss a sampled-loss model is selected on) in ONE pass of the same GEMM, no logits: per row and column range p
  * (arx_gemm_nt_topk_parts) lse_part[row][p] = log sum exp of the logits ('ce': loss = logsumexp_p(lse_part) - t) and /

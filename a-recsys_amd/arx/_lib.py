@@ -224,6 +224,11 @@ PROTOTYPES = {
     "arx_topk_mark_empty": (cint, [f32p, i64, i32p, i64, i64, cint, vp]),
     "arx_topk_merge_shards": (cint, [f32p, i32p, i64, cint, cint, f32p, i32p, vp]),
     "arx_gemm_nt_eval_parts": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, f32p, f32p, f32p, i64, vp]),
+    "arx_gemm_nt_eval_rank_parts": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, f32p, i32p, f32p, i32p, i64,
+                                           vp]),
+    "arx_eval_shard_reduce": (cint, [cint, f32p, i64, cint, i32p, i64, f32p, i64, f32p, i64, f32p, cint, i64, f32p,
+                                     i32p, i32p, i64, i32p, i32p, i64, f32p, i32p, vp]),
+    "arx_eval_merge_shards": (cint, [cint, f32p, i32p, f32p, i64, cint, f32p, i32p, vp]),
     "arx_lstm_fwd": (cint, [f32p, f32p, f32p, i64, i64, cint, cint, f32, f32p, f32p, f32p, vp]),
     "arx_lstm_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, i64, i64, cint, cint, f32p, vp]),
     "arx_lstm_bwd_wxt": (cint, [f32p, f32p, f32p, f32p, f32p, i64, i64, cint, cint, f32p, f32p, vp]),

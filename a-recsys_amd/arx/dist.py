@@ -298,6 +298,72 @@ class HipBackend(object):
         """[W, B, k] per-shard lists (local columns) -> [B, k] global ids (arx_topk_merge_shards)."""
         self.ops.topk_merge_shards(v, c, vo, io)
 
+    def shard_eval(self, U, E, bias, t, tcol, loss, ex, part, cnt):
+        """Evaluation's local stage: per row of U [B, d], this shard's partial over the V rows of E (+ bias) -- 'ce':
+        log sum exp of the logits (-inf when V = 0); 'warp': sum of relu(x - t + 1); 'warp_eval': that sum and cnt =
+        #{x > t}, the row's target column tcol (local; out of range: on another shard) counted as (1, 0) -- with the
+        masked columns of ex (row_keys, key_rows, ex_ptr, ex_cols of local columns; None: none) taken out again.
+        part [B] float32, cnt [B] int32 ('warp_eval').  The fused eval GEMM (arx_gemm_nt_eval_parts / _rank_parts)
+        where d is 32, 64 or 128; other widths score chunks of logits (ops.gemm + arx_eval_chunk_accum, or a
+        log-sum-exp per chunk) and have no 'warp_eval'.  Then arx_eval_shard_reduce.  Buffers and GEMM workspace are
+        this stage's own (captured step graphs keep theirs)."""
+        ops = self.ops
+        B, V, d = int(U.shape[0]), int(E.shape[0]), int(U.shape[1])
+        if getattr(self, 'ws_eval', None) is None:
+            self.ws_eval, self._ev = ops.Workspace(U.device), {}
+        fused = (d in (32, 64, 128) and int(E.shape[1]) == d and U.stride(0) % 4 == 0 and E.stride(0) % 4 == 0
+                 and U.data_ptr() % 16 == 0 and E.data_ptr() % 16 == 0)
+        if loss == 'warp_eval' and not fused:
+            raise NotImplementedError("evaluate(loss='warp_eval'): the rank counts come out of the fused eval GEMM "
+                                      "only -- embedding widths 32, 64 and 128 (got %d)" % d)
+        if B == 0:
+            return
+        parts = cparts = None
+        if V > 0 and fused:
+            npart = ops.gemm_nt_topk_parts(B, V)
+            key = ('fused', B, npart)
+            if key not in self._ev:
+                if len(self._ev) > 8:
+                    self._ev.clear()
+                self._ev[key] = (torch.empty((B, npart), dtype=torch.float32, device=U.device),
+                                 torch.empty((B, npart), dtype=torch.int32, device=U.device))
+            parts, cparts = self._ev[key]
+            if loss == 'ce':
+                ops.gemm_nt_eval_parts(U, E, bias, None, parts, None)
+            elif loss == 'warp':
+                ops.gemm_nt_eval_parts(U, E, bias, t, None, parts)
+            else:
+                ops.gemm_nt_eval_rank_parts(U, E, bias, t, tcol, parts, cparts)
+        elif V > 0:
+            chunk = min(65536, V)
+            nch = (V + chunk - 1) // chunk
+            key = ('chunked', B, chunk, nch)
+            if key not in self._ev:
+                if len(self._ev) > 8:
+                    self._ev.clear()
+                self._ev[key] = (torch.empty((B, chunk), dtype=torch.float32, device=U.device),
+                                 torch.empty((B, nch), dtype=torch.float32, device=U.device),
+                                 torch.empty((B,), dtype=torch.float32, device=U.device))
+            lg_buf, lse_parts, lse0 = self._ev[key]
+            for c in range(nch):
+                c0, c1 = c * chunk, min(V, (c + 1) * chunk)
+                lg = lg_buf[:, :c1 - c0]
+                ops.gemm(U, E[c0:c1], lg, self.ws_eval, transB=True, col_bias=bias[c0:c1] if bias is not None else None)
+                if loss == 'ce':
+                    ops.row_logsumexp(lg, lse0)
+                    lse_parts[:, c].copy_(lse0)
+                else:
+                    ops.eval_chunk_accum(lg, t, 1, c == 0, lse0, None)
+            parts = lse_parts if loss == 'ce' else lse0.view(B, 1)
+        if cparts is not None and loss != 'warp_eval':
+            cparts = None
+        ops.eval_shard_reduce(loss, parts, cparts, U, E, bias, t, tcol, ex if loss != 'ce' else None, part,
+                              cnt if loss == 'warp_eval' else None)
+
+    def eval_merge_shards(self, loss, parts, cnts, t, out, cnt_out):
+        """[W, B] per-shard partials -> per-row loss ('warp_eval': margin_rank, true_rank) (arx_eval_merge_shards)."""
+        self.ops.eval_merge_shards(loss, parts, cnts, t, out, cnt_out)
+
 
 class ShardedHMF(object):
     """id-only HMF ('mw' loss) with row-sharded tables.  Global ids everywhere in
@@ -951,6 +1017,12 @@ class ShardedHMF(object):
         (users, ptr, items) CSR triple.  The (user, item) pairs travel to the item's owner (all_to_all); each rank
         keeps, on the device, a CSR keyed by global user id (ptr: n_users + 1 entries) over its own local columns
         (item // world), sorted, without duplicates.  A second call replaces the lists."""
+        self._rec_ex = self._route_item_sets(item_sets, "exclusions", "exclusion lists")
+
+    def _route_item_sets(self, item_sets, what, lists):
+        """Per-user item sets of the users this rank owns -> the device CSR (ptr [n_users + 1], local columns) of the
+        pairs whose item this rank owns (a collective: the pairs cross by all_to_all).  what / lists: the names in
+        the error messages."""
         W, r = self.world, self.rank
         if isinstance(item_sets, dict):
             keys = list(item_sets.keys())
@@ -962,17 +1034,17 @@ class ShardedHMF(object):
             ptr = np.asarray(item_sets[1], dtype=np.int64).reshape(-1)
             items = np.asarray(item_sets[2], dtype=np.int64).reshape(-1)
             if len(ptr) != len(u0) + 1 or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] > len(items):
-                raise ValueError("exclusions: ptr must have len(users) + 1 entries, start at 0, not decrease and "
-                                 "end within the items")
+                raise ValueError("%s: ptr must have len(users) + 1 entries, start at 0, not decrease and "
+                                 "end within the items" % what)
             users = np.repeat(u0, np.diff(ptr))
             items = items[:ptr[-1]]
         else:
-            raise ValueError("exclusions: a {user: items} dict or a (users, ptr, items) CSR triple")
+            raise ValueError("%s: a {user: items} dict or a (users, ptr, items) CSR triple" % what)
         if len(users) and (users.min() < 0 or users.max() >= self.n_users or np.any(users % W != r)):
-            raise ValueError("exclusions: every user must be a global id in [0, %d) owned by rank %d (id %% %d == %d)"
-                             % (self.n_users, r, W, r))
+            raise ValueError("%s: every user must be a global id in [0, %d) owned by rank %d (id %% %d == %d)"
+                             % (what, self.n_users, r, W, r))
         if len(items) and (items.min() < 0 or items.max() >= self.n_items):
-            raise ValueError("exclusions: item ids must lie in [0, %d)" % self.n_items)
+            raise ValueError("%s: item ids must lie in [0, %d)" % (what, self.n_items))
         owner = items % W
         order = np.argsort(owner, kind='stable')
         pairs = np.stack([users, items], 1)[order].astype(np.int32).reshape(-1)
@@ -998,11 +1070,11 @@ class ShardedHMF(object):
         ptr = np.zeros(self.n_users + 1, dtype=np.int64)
         np.cumsum(np.bincount(ru, minlength=self.n_users), out=ptr[1:])
         if ptr[-1] >= 2 ** 31:
-            raise ValueError("exclusion lists: more than 2^31 - 1 entries on one rank")
+            raise ValueError("%s: more than 2^31 - 1 entries on one rank" % lists)
         if len(cols) == 0:
             cols = np.zeros(1, dtype=np.int64)          # (a valid device pointer; every list is empty)
-        self._rec_ex = (torch.from_numpy(ptr.astype(np.int32)).to(self.device),
-                        torch.from_numpy(cols.astype(np.int32)).to(self.device))
+        return (torch.from_numpy(ptr.astype(np.int32)).to(self.device),
+                torch.from_numpy(cols.astype(np.int32)).to(self.device))
 
     def recommend(self, users, k, exclude_seen=False, return_values=False):
         """Full-vocabulary top-k (run_hmf.py:340-409: top_k(logits, top_N) per user) of the row-sharded model.  A
@@ -1086,6 +1158,124 @@ class ShardedHMF(object):
             _all_to_all(recv_c.view(B, k), out_i, group=self.group)
         be.topk_merge_shards(recv_v, recv_c, vo, io)
         return vo, io
+
+    # -------------------------------------------------------------- evaluate
+    def prepare_eval_positives(self, item_sets):
+        """The items evaluate('warp' / 'warp_eval') leaves out per user -- prepare_warp's pos_item_set_eval
+        (embed_attribute.py:729-741).  A collective, routed and kept as prepare_recommend_exclusions' lists are:
+        every rank passes the sets of users IT owns, {global user: global items} or a (users, ptr, items) CSR triple;
+        an empty dict masks nothing.  A second call replaces the sets."""
+        self._eval_pos = self._route_item_sets(item_sets, "eval positives", "eval positive lists")
+
+    def evaluate(self, users, items, loss='warp', return_rows=False):
+        """Full-vocabulary evaluation loss (run_hmf.py:280-337: model.step(..., forward_only=True) on the dev set) of
+        the row-sharded model.  A collective: every rank calls it with the same loss.  users: global ids this rank
+        owns, 0 <= n <= B_loc (n may differ between ranks); items: their held-out targets, global ids, one per user.
+        Per row (user u, target i, t = U[u] . I[i] + b[i], x_j likewise over all n_items, P_u = u's eval positives):
+          'warp'       log(1 + sum_{j not in P_u} relu(x_j - t + 1))     (embed_attribute.py:605-618, :729-741)
+          'ce'         logsumexp_j x_j - t                                 (no mask)
+          'warp_eval'  margin_rank = sum_{j not in P_u} relu(x_j - t + 1), true_rank = #{j not in P_u, j != i:
+                       x_j > t} (:620-639; the target adds exactly 1 to the margin unless masked; ties do not count)
+        'warp' / 'ce' return the global mean over all ranks' rows as a python float (nan without rows), with
+        return_rows also this rank's float32 [n] rows on the device; 'warp_eval' returns (margin_rank float32 [n],
+        true_rank int32 [n]) on the device.  'warp' / 'warp_eval' need prepare_eval_positives() first.
+
+          gather          this rank's user rows -> [B_loc, d] (padding rows: zeros, key -1)
+          all_gather      latents [B, d], user ids [B], targets [B]
+          (local)         t: the target rows (non-owned: the shard's zero row) . latents; all_reduce(SUM) -> [B]
+          (local)         this shard's partial per row over E_item[:ni] (backend.shard_eval: the fused eval GEMM, then
+                          arx_eval_shard_reduce takes the masked local columns out)
+          all_to_all      partials [B] (+ int32 counts) -> the ranks that own the rows: [W][B_loc]
+          (local)         W-way combine, the loss per row (arx_eval_merge_shards); sum_scaled + all_reduce: the mean
+
+        Eager (no capture); with graph segments on the model's stream, joined with the caller's on both sides as
+        step() is.  Its buffers and GEMM workspace are its own."""
+        W, r = self.world, self.rank
+        if loss not in ('warp', 'ce', 'warp_eval'):
+            raise ValueError("evaluate: loss must be 'warp', 'ce' or 'warp_eval', got %r" % (loss,))
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        it = items.cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
+        u, it = u.astype(np.int64).reshape(-1), it.astype(np.int64).reshape(-1)
+        if len(u) != len(it):
+            raise ValueError("evaluate: one target item per user (%d users, %d items)" % (len(u), len(it)))
+        if len(u) > self.B_loc:
+            raise ValueError("evaluate: at most B_loc = %d users per call and rank" % self.B_loc)
+        if len(u) and (u.min() < 0 or u.max() >= self.n_users or np.any(u % W != r)):
+            raise ValueError("evaluate: users must be global ids in [0, %d) owned by rank %d" % (self.n_users, r))
+        if len(it) and (it.min() < 0 or it.max() >= self.n_items):
+            raise ValueError("evaluate: item ids must lie in [0, %d)" % self.n_items)
+        if loss != 'ce' and getattr(self, '_eval_pos', None) is None:
+            raise ValueError("evaluate(loss=%r) needs prepare_eval_positives() first (an empty dict masks nothing)"
+                             % loss)
+        if self.use_graphs:
+            outer = torch.cuda.current_stream(self.device)
+            if outer != self._stream:
+                self._stream.wait_stream(outer)
+                with torch.cuda.stream(self._stream):
+                    rows_f, rows_i, sc = self._evaluate(u, it, loss)
+                outer.wait_stream(self._stream)
+            else:
+                rows_f, rows_i, sc = self._evaluate(u, it, loss)
+        else:
+            rows_f, rows_i, sc = self._evaluate(u, it, loss)
+        n = len(u)
+        if loss == 'warp_eval':
+            return rows_f[:n].clone(), rows_i[:n].clone()
+        tot, cnt = (float(x) for x in sc.cpu().tolist())
+        mean = tot / cnt if cnt > 0 else float('nan')
+        return (mean, rows_f[:n].clone()) if return_rows else mean
+
+    def _evaluate(self, u, it, loss):
+        be, W, r, B_loc, B, d = self.be, self.world, self.rank, self.B_loc, self.B, self.d
+        dev, f32, i32 = self.device, torch.float32, torch.int32
+        n = len(u)
+        if getattr(self, '_ev_buf', None) is None:
+            e = lambda dt, *sh: torch.empty(sh, dtype=dt, device=dev)
+            kl, ul, tl = torch.full((B_loc,), -1, dtype=i32, device=dev), torch.zeros((B_loc, d), dtype=f32,
+                                                                                      device=dev), e(i32, B_loc)
+            lat = (kl, ul, tl) + ((kl, ul, tl) if W == 1 else (e(i32, B), e(f32, B, d), e(i32, B)))
+            # trow [B] (= the local target column; the zero row ni: not here), T [B, d], tb [B], t [B]; the shard's
+            # partials [B] and counts; the received [W][B_loc]; the rows' results; (sum, count) of the mean
+            self._ev_buf = lat + (e(i32, B), e(f32, B, d), e(f32, B), e(f32, B), e(f32, B), e(i32, B),
+                                  e(f32, W, B_loc), e(i32, W, B_loc), e(f32, B_loc), e(i32, B_loc), e(f32, 2))
+        (keys_loc, U_loc, tgt_loc, keys_all, U_all, tgt_all, trow, T, tb, t, part, cnt, recv_p, recv_c, rows_f,
+         rows_i, sc) = self._ev_buf
+        kh, th = np.full(B_loc, -1, dtype=np.int32), np.zeros(B_loc, dtype=np.int32)
+        kh[:n], th[:n] = u, it
+        keys_loc.copy_(torch.from_numpy(kh))
+        tgt_loc.copy_(torch.from_numpy(th))
+        if n:
+            rows = torch.from_numpy((u // W).astype(np.int32)).to(dev)
+            be.gather_rows(self.E_user, None, rows, U_loc[:n], None)
+        if n < B_loc:
+            be.fill_zero(U_loc[n:])
+        if W > 1:
+            dist.all_gather_into_tensor(U_all, U_loc, group=self.group)
+            dist.all_gather_into_tensor(keys_all, keys_loc, group=self.group)
+            dist.all_gather_into_tensor(tgt_all, tgt_loc, group=self.group)
+        # the target logit: the owner's row, every other rank's zero row -- one non-zero summand per row (exact)
+        be.shard_route(tgt_all, W, r, self.zero_row, trow, None)
+        be.gather_rows(self.E_item, self.b_item, trow, T, tb)
+        be.dot_score(U_all, T, tb, t)
+        if W > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        ni = self.ni_loc
+        ex = (keys_all, B, self._eval_pos[0], self._eval_pos[1]) if loss != 'ce' else None
+        be.shard_eval(U_all, self.E_item[:ni], self.b_item[:ni], t, trow, loss, ex, part, cnt)
+        if W == 1:
+            recv_p, recv_c = part.view(1, B), cnt.view(1, B)
+        else:
+            _all_to_all(recv_p.view(B), part, group=self.group)
+            if loss == 'warp_eval':
+                _all_to_all(recv_c.view(B), cnt, group=self.group)
+        wev = loss == 'warp_eval'
+        be.eval_merge_shards(loss, recv_p, recv_c if wev else None, t[r * B_loc:(r + 1) * B_loc], rows_f,
+                             rows_i if wev else None)
+        if not wev:
+            be.sum_scaled(rows_f[:n], 1.0, sc[:1])
+            sc[1:].copy_(torch.tensor([float(n)], dtype=f32))
+            dist.all_reduce(sc, op=dist.ReduceOp.SUM, group=self.group)
+        return rows_f, rows_i, sc
 
     # ---- helpers for tests / checkpoints ----
     def gather_global_tables(self):
@@ -1399,6 +1589,11 @@ class ShardedHMFBags(ShardedHMF):
         raise NotImplementedError("%s.recommend: item latents are bag means (ShardedHMF has recommend)"
                                   % type(self).__name__)
 
+    def evaluate(self, users, items, loss='warp', return_rows=False):
+        """Not yet: the item latents are bag means, and evaluate would first need them materialised per shard."""
+        raise NotImplementedError("%s.evaluate: item latents are bag means (ShardedHMF has evaluate)"
+                                  % type(self).__name__)
+
     def gather_global_tables(self):
         out = super().gather_global_tables()
         W = self.world
@@ -1628,6 +1823,11 @@ class ShardedHMFRepTokens(ShardedHMF):
     def recommend(self, users, k, exclude_seen=False, return_values=False):
         """Not yet: the item latents are bag means, and recommend would first need them materialised per shard."""
         raise NotImplementedError("%s.recommend: item latents are bag means (ShardedHMF has recommend)"
+                                  % type(self).__name__)
+
+    def evaluate(self, users, items, loss='warp', return_rows=False):
+        """Not yet: the item latents are bag means, and evaluate would first need them materialised per shard."""
+        raise NotImplementedError("%s.evaluate: item latents are bag means (ShardedHMF has evaluate)"
                                   % type(self).__name__)
 
     def gather_global_tables(self):

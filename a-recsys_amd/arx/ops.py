@@ -7,6 +7,7 @@ torch.cuda events / torch.distributed (RCCL) order correctly against them.
 """
 from __future__ import annotations
 
+import gc
 import math
 
 import os
@@ -1109,6 +1110,57 @@ def gemm_nt_eval_parts(A, Bm, col_bias, tscore, lse_part, relu_part):
          _p(col_bias), _p(tscore), _p(lse_part), _p(relu_part), int(ref.stride(0)), _stream())
 
 
+def gemm_nt_eval_rank_parts(A, Bm, col_bias, tscore, tcol, relu_part, cnt_part):
+    """warp_eval's margin sums and counts of x > t out of the scorer GEMM, no logits (arx.h): relu_part / cnt_part
+    [M, >= gemm_nt_topk_parts(M, N)] with one row stride; tcol [M] int32: each row's target column (counted as (1, 0)),
+    or a value outside [0, N)."""
+    if relu_part.dtype != torch.float32 or cnt_part.dtype != torch.int32 or tcol.dtype != torch.int32:
+        raise ValueError("gemm_nt_eval_rank_parts: relu_part float32, cnt_part / tcol int32")
+    if relu_part.stride(0) != cnt_part.stride(0) or tuple(relu_part.shape) != tuple(cnt_part.shape):
+        raise ValueError("gemm_nt_eval_rank_parts: relu_part and cnt_part need one shape and row stride")
+    if int(relu_part.shape[0]) < int(A.shape[0]) or int(tcol.shape[0]) < int(A.shape[0]):
+        raise ValueError("gemm_nt_eval_rank_parts: relu_part / cnt_part / tcol need a row per row of A")
+    call("arx_gemm_nt_eval_rank_parts", _p(A), _ld(A), int(A.shape[0]), _p(Bm), _ld(Bm), int(Bm.shape[0]),
+         int(A.shape[1]), _p(col_bias), _p(tscore), _p(tcol), _p(relu_part), _p(cnt_part), int(relu_part.stride(0)),
+         _stream())
+
+
+EVAL_MODES = {'ce': 0, 'warp': 1, 'warp_eval': 2}
+
+
+def eval_shard_reduce(mode, parts, cnt_parts, U, E, bias, tscore, tcol, ex, out, cnt_out):
+    """One shard's evaluation partial per row (arx.h arx_eval_shard_reduce): parts [B, npart] (None: a shard without
+    columns), cnt_parts likewise int32 ('warp_eval'); masks ex = (row_keys, key_rows, ex_ptr, ex_cols of local columns)
+    or None, columns recomputed from U [B, d] and E [V, d] (+ bias).  out [B] float32, cnt_out [B] int32."""
+    m = EVAL_MODES[mode] if isinstance(mode, str) else int(mode)
+    B = int(out.shape[0])
+    if tuple(U.shape[:1]) != (B,) or (parts is not None and int(parts.shape[0]) != B):
+        raise ValueError("eval_shard_reduce: U, parts and out need one row per row")
+    if (cnt_out is not None and tuple(cnt_out.shape) != (B,)) or \
+            (cnt_parts is not None and tuple(cnt_parts.shape) != tuple(parts.shape)):
+        raise ValueError("eval_shard_reduce: cnt_out [B], cnt_parts shaped as parts")
+    keys, key_rows, ptr, cols = ex if ex is not None else (None, 0, None, None)
+    call("arx_eval_shard_reduce", m, _p(parts), int(parts.stride(0)) if parts is not None else 0,
+         int(parts.shape[1]) if parts is not None else 0, _p(cnt_parts),
+         int(cnt_parts.stride(0)) if cnt_parts is not None else 0, _p(U), _ld(U), _p(E), _ld(E), _p(bias),
+         int(U.shape[1]), int(E.shape[0]), _p(tscore), _p(tcol), _p(keys), int(key_rows), _p(ptr), _p(cols), B,
+         _p(out), _p(cnt_out), _stream())
+
+
+def eval_merge_shards(mode, parts, cnts, tscore, out, cnt_out):
+    """[W, B] per-shard evaluation partials (shard order) -> the loss of each row (arx.h arx_eval_merge_shards):
+    ce logsumexp_w - t, warp log1p(sum_w), warp_eval the margin sum and (cnt_out) the count sum."""
+    m = EVAL_MODES[mode] if isinstance(mode, str) else int(mode)
+    W, B = (int(x) for x in parts.shape)
+    for t in (parts, cnts, tscore, out, cnt_out):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("eval_merge_shards: contiguous tensors only")
+    if tuple(out.shape) != (B,) or (cnts is not None and tuple(cnts.shape) != (W, B)) or \
+            (cnt_out is not None and tuple(cnt_out.shape) != (B,)) or (tscore is not None and int(tscore.shape[0]) < B):
+        raise ValueError("eval_merge_shards: parts / cnts [W, B], tscore / out / cnt_out [B]")
+    call("arx_eval_merge_shards", m, _p(parts), _p(cnts), _p(tscore), B, W, _p(out), _p(cnt_out), _stream())
+
+
 def take_rows_i32(table, pos, out):
     call("arx_take_rows_i32", _p(table), int(table.stride(0)), _p(pos), int(pos.stride(0)), int(pos.shape[0]),
          int(pos.shape[1]), _p(out), int(out.stride(0)), _stream())
@@ -1147,10 +1199,32 @@ class CapturedGraph(object):
         self._fed = False            # the nodes hold live sources (else: they copy nothing)
 
     def begin(self):
-        call("arx_capture_begin", _stream())
+        # no cyclic garbage collection between begin() and end(): a collection there runs the finalizers of
+        # unreachable models -- CapturedGraph.__del__ (hipGraphExecDestroy), the feed slabs' release (a device
+        # synchronize) -- and those HIP calls are illegal inside a capture: it is invalidated, and the next launch
+        # fails "due to a previous error during capture".  Whether a collection lands there depends on the
+        # allocation counts of the whole process, so the failure came and went with unrelated changes.
+        self._gc_was_enabled = gc.isenabled()
+        gc.disable()
+        try:
+            call("arx_capture_begin", _stream())
+        except BaseException:
+            self._gc_restore()
+            raise
+
+    def _gc_restore(self):
+        if getattr(self, '_gc_was_enabled', False):
+            gc.enable()
+        self._gc_was_enabled = False
 
     def end(self, feeds=None):
         """feeds: the [(src, dst), ...] list copy_words() was called with inside this capture (None: no feed nodes)."""
+        try:
+            self._end(feeds)
+        finally:
+            self._gc_restore()
+
+    def _end(self, feeds):
         import ctypes as C
         if not feeds:
             call("arx_capture_end", _stream(), C.byref(self._exec))

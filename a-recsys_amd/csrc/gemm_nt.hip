@@ -60,12 +60,16 @@ struct NtFilter {
   // ex_cols[ex_ptr[key] .. ex_ptr[key + 1]), sorted ascending, key = row_keys[r % key_rows] (< 0: nothing excluded)
   const int32_t* row_keys; int64_t key_rows;
   const int32_t* ex_ptr; const int32_t* ex_cols;
+  // kNtRank (with kNtRelu: warp_eval, embed_attribute.py:620-639 [margin_rank, true_rank]): tsc[row] is t itself, the
+  // margin term is relu((v - t) + 1) and cnt_part[row * ldl + part] = #columns of the range with v > t; the row's own
+  // target column tcol[row] (a column of this launch, anything else: none) counts as (1, 0)
+  const int32_t* tcol; int32_t* cnt_part;
 };
 
 // MODE (FILTER kernels): bit 0 candidate lists (thr), bit 1 lse_part, bit 2 relu_part, bit 3 exclusion lists (with
-// bit 0 only) -- a template parameter, not a run-time switch: every feature is 32 registers of per-row state and the
-// plain kernel already holds 246
-constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8;
+// bit 0 only), bit 4 rank counts (with bit 2 only) -- a template parameter, not a run-time switch: every feature is 32
+// registers of per-row state and the plain kernel already holds 246
+constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8, kNtRank = 16;
 
 template <int KT, int MODE = 0>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
@@ -74,8 +78,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
     const float* __restrict__ col_bias, int tiles_per_block, int nsplit, NtFilter flt) {
   constexpr bool FILTER = MODE != 0;
   constexpr bool want_topk = (MODE & kNtTopk) != 0, want_lse = (MODE & kNtLse) != 0, want_relu = (MODE & kNtRelu) != 0;
-  constexpr bool want_excl = (MODE & kNtExcl) != 0;
+  constexpr bool want_excl = (MODE & kNtExcl) != 0, want_rank = (MODE & kNtRank) != 0;
   static_assert(!want_excl || want_topk, "the exclusion lists filter candidates");
+  static_assert(!want_rank || (want_relu && !want_topk && !want_lse), "the rank counts ride on the margin sums");
   constexpr int NS = KT / 8;                  // steps of 4 MFMAs
   constexpr int CPR = KT / 4;                 // 16-B chunks per pool row
   constexpr int NLB = kNtBN * CPR / 256;      // DMA pieces per thread per tile
@@ -143,7 +148,15 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   __shared__ int s_cnt[want_topk ? kNtBM : 1];
   // kNtExcl: [beg, end) of each row's exclusion list (1 KB; read only by a lane whose logit beat the threshold)
   __shared__ int s_xb[want_excl ? kNtBM : 1], s_xe[want_excl ? kNtBM : 1];
+  // kNtRank: the rows' target columns (read per tile by one lane per row, per logit only in a tile that holds one)
+  __shared__ int s_tc[want_rank ? kNtBM : 1];
   float lm[want_lse ? 16 : 1], ls[want_lse ? 16 : 1], rsum[want_relu ? 16 : 1];
+  // kNtRank: ONE register per count -- a row's count is the popcount of its half of a ballot (wave-uniform), kept by
+  // the lane l31 == e of the half (16 counters spilled at K=128: the margin mode already holds 236 VGPRs).  The margin
+  // is kept as #active + sum over the active columns of (v - t): summing the terms relu((v - t) + 1) themselves, ~1
+  // each where the scores sit close together (an untrained model), a lane's running sum outgrows their fractions
+  // (measured: 1e-4 relative at 100 M columns); acnt counts the active columns exactly
+  int rcnt = 0, acnt = 0;
   bool ovf = false;
   if (FILTER) {
     if (threadIdx.x < kNtBM) {
@@ -152,7 +165,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
         s_th[threadIdx.x] = row < M ? flt.thr[row * flt.ldthr] : __builtin_inff();
         s_cnt[threadIdx.x] = 0;
       }
-      if (want_relu) s_tq[threadIdx.x] = row < M ? flt.tsc[row] - 1.f : 0.f;
+      if (want_relu && !want_rank) s_tq[threadIdx.x] = row < M ? flt.tsc[row] - 1.f : 0.f;
+      if (want_rank) {
+        s_tq[threadIdx.x] = row < M ? flt.tsc[row] : 0.f;
+        s_tc[threadIdx.x] = row < M ? flt.tcol[row] : -1;
+      }
       if (want_excl) {
         int xb = 0, xe = 0;
         if (row < M) {
@@ -252,6 +269,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
     if (FILTER) {
       const int rl0 = wave * 32 + 4 * lhi;                          // the lane's rows: rl0 + (e & 3) + 8 (e >> 2)
       float th[want_topk ? 16 : 1], tq[want_relu ? 16 : 1];
+      // kNtRank: does a row of this wave have its target column in this tile?  (wave-uniform; rarely true)
+      bool tc_hit = false;
+      if (want_rank) {
+        const int tc = s_tc[wave * 32 + l31];
+        tc_hit = __ballot(tc >= n0 && tc < n0 + kNtBN) != 0ull;
+      }
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) {
         if (want_topk) {
@@ -270,6 +293,25 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const float v = alpha * (j == 0 ? acc0[e] : acc1[e]) + bias;
+          if (want_rank) {
+            float dz = v - tq[e];
+            bool act = dz + 1.f > 0.f, gt = v > tq[e];
+            if (tc_hit && col == s_tc[rl0 + (e & 3) + 8 * (e >> 2)]) {   // the target itself: (1, 0)
+              dz = 0.f;
+              act = true;
+              gt = false;
+            }
+            act = act && col < N;
+            if (act) rsum[e] += dz;
+            const unsigned long long m = __ballot(gt && col < N), ma = __ballot(act);
+            const int c = __popc(lhi ? (uint32_t)(m >> 32) : (uint32_t)m);
+            const int ca = __popc(lhi ? (uint32_t)(ma >> 32) : (uint32_t)ma);
+            if (l31 == e) {
+              rcnt += c;
+              acnt += ca;
+            }
+            continue;
+          }
           if (want_relu && col < N) rsum[e] += fmaxf(v - tq[e], 0.f);
           if (want_lse && col < N) {                                // online (max, sum): ONE exp per logit
             const float dd = v - lm[e];
@@ -359,8 +401,16 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
 #pragma unroll
       for (int o = 16; o > 0; o >>= 1) sm += __shfl_xor(sm, o, 64);
       const int64_t row = m0 + wave * 32 + 4 * lhi + (e & 3) + 8 * (e >> 2);
-      if (l31 == 0 && row < M) flt.relu_part[row * flt.ldl + part] = sm;
+      if (want_rank) {
+        if (l31 == e && row < M) flt.relu_part[row * flt.ldl + part] = (float)acnt + sm;
+      } else if (l31 == 0 && row < M) {
+        flt.relu_part[row * flt.ldl + part] = sm;
+      }
     }
+  }
+  if (want_rank) {
+    const int64_t row = m0 + wave * 32 + 4 * lhi + (l31 & 3) + 8 * (l31 >> 2);
+    if (l31 < 16 && row < M) flt.cnt_part[row * flt.ldl + part] = rcnt;
   }
 }
 
@@ -513,6 +563,31 @@ int arx_gemm_nt_eval_parts(const float* A, int64_t lda, int64_t M, const float* 
     nt_launch_mode<kNtLse>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
   else
     nt_launch_mode<kNtRelu>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_gemm_nt_eval_rank_parts(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
+                                int64_t K, const float* col_bias, const float* tscore, const int32_t* tcol,
+                                float* relu_part, int32_t* cnt_part, int64_t ldl, void* stream) {
+  ARX_CHECK_ARG(A && Bm && tscore && tcol && relu_part && cnt_part, "arx_gemm_nt_eval_rank_parts: null pointer");
+  ARX_CHECK_ARG(M > 0 && N > 0 && N <= 0x7fffffff, "arx_gemm_nt_eval_rank_parts: need M > 0, 0 < N < 2^31");
+  ARX_CHECK_ARG(K == 32 || K == 64 || K == 128, "arx_gemm_nt_eval_rank_parts: K must be 32, 64 or 128");
+  ARX_CHECK_ARG(!((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) && lda % 4 == 0 &&
+                    ldb % 4 == 0,
+                "arx_gemm_nt_eval_rank_parts: operands must be 16-byte aligned");
+  int64_t tpb, ns;
+  nt_split(M, N, &tpb, &ns);
+  ARX_CHECK_ARG(ldl >= ns, "arx_gemm_nt_eval_rank_parts: part rows too short (ldl < parts)");
+  const int64_t grid = ceil_div(M, (int64_t)kNtBM) * ns;
+  ARX_CHECK_ARG(grid <= 0x7fffffff, "arx_gemm_nt_eval_rank_parts: grid too large");
+  NtFilter f{};
+  f.ldl = ldl;
+  f.tsc = tscore;
+  f.relu_part = relu_part;
+  f.tcol = tcol;
+  f.cnt_part = cnt_part;
+  nt_launch_mode<kNtRelu | kNtRank>(K, grid, as_stream(stream), M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

@@ -432,6 +432,100 @@ __global__ __launch_bounds__(256) void k_eval_unmask(const float* __restrict__ U
   if (lane == 0) s_acc[r] = fmaxf(s_acc[r] - sub, 0.f);
 }
 
+// Row-sharded evaluation (arx.dist.ShardedHMF.evaluate; owner of item g = g % W, local column g / W).  Every shard
+// scores ALL the gathered rows against its own columns; per row, k_eval_shard_reduce folds the shard's column-range
+// parts (arx_gemm_nt_eval_parts / _rank_parts) into one partial and takes the row's masked local columns out again;
+// after the all_to_all, k_eval_merge_shards folds the W partials of the rows a rank owns and finishes the loss.
+// mode 0 ce (log-sum-exp; no mask), 1 warp (margin sum), 2 warp_eval (margin sum + int count of x > t).
+// One wave per row; the mask list is sorted and unique (no dedup), walked in order, one wave-wide dot per column.
+__global__ __launch_bounds__(256) void k_eval_shard_reduce(
+    int mode, const float* __restrict__ parts, int64_t ldp, int npart, const int32_t* __restrict__ cparts,
+    int64_t ldc, const float* __restrict__ U, int64_t ldu, const float* __restrict__ E, int64_t lde,
+    const float* __restrict__ eb, int d, int64_t V, const float* __restrict__ t, const int32_t* __restrict__ tcol,
+    const int32_t* __restrict__ row_keys, int64_t key_rows, const int32_t* __restrict__ ex_ptr,
+    const int32_t* __restrict__ ex_cols, int64_t B, float* __restrict__ out, int32_t* __restrict__ cnt_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 6;
+  if (r >= B) return;
+  if (mode == 0) {                                         // log-sum-exp of the parts; no parts (V = 0): -inf
+    float m = -INFINITY;
+    for (int p = lane; p < npart; p += 64) m = fmaxf(m, parts[r * ldp + p]);
+    m = wmax(m);
+    float l = 0.f;
+    if (m != -INFINITY)
+      for (int p = lane; p < npart; p += 64) l += expf(parts[r * ldp + p] - m);
+    l = wsum(l);
+    if (lane == 0) out[r] = m == -INFINITY ? -INFINITY : m + logf(l);
+    return;
+  }
+  float s = 0.f;
+  int c = 0;
+  for (int p = lane; p < npart; p += 64) {
+    s += parts[r * ldp + p];
+    if (mode == 2) c += cparts[r * ldc + p];
+  }
+  s = wsum(s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  const int32_t key = row_keys ? row_keys[r % key_rows] : -1;
+  if (key >= 0) {
+    const float tt = t[r];
+    const int32_t tc = tcol[r];
+    const bool colok = lane * 4 < d;
+    float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (colok) u = *reinterpret_cast<const float4*>(U + r * ldu + lane * 4);
+    float sub = 0.f;
+    int csub = 0;
+    const int beg = ex_ptr[key], end = ex_ptr[key + 1];
+    for (int p = beg; p < end; ++p) {                      // (wave-uniform: every lane walks the same list)
+      const int32_t j = ex_cols[p];
+      if (j < 0 || j >= V) continue;
+      if (j == tc) {                                       // the target itself: (1, 0), as the scan counted it
+        sub += 1.f;
+        continue;
+      }
+      float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (colok) e = *reinterpret_cast<const float4*>(E + (int64_t)j * lde + lane * 4);
+      const float x = wsum(u.x * e.x + u.y * e.y + u.z * e.z + u.w * e.w) + (eb ? eb[j] : 0.f);
+      const float v = (x - tt) + 1.f;
+      sub += v > 0.f ? v : 0.f;
+      csub += x > tt ? 1 : 0;
+    }
+    s = fmaxf(s - sub, 0.f);
+    c = max(c - csub, 0);
+  }
+  if (lane == 0) {
+    out[r] = s;
+    if (mode == 2) cnt_out[r] = c;
+  }
+}
+
+// [W][B] partials in shard order (as all_to_all delivers them) -> the loss of each row; one thread per row, the W
+// terms folded in shard order (deterministic)
+__global__ void k_eval_merge_shards(int mode, const float* __restrict__ parts, const int32_t* __restrict__ cnts,
+                                    const float* __restrict__ t, int64_t B, int W, float* __restrict__ out,
+                                    int32_t* __restrict__ cnt_out) {
+  const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (r >= B) return;
+  if (mode == 0) {
+    float m = -INFINITY;
+    for (int s = 0; s < W; ++s) m = fmaxf(m, parts[(int64_t)s * B + r]);
+    float l = 0.f;
+    if (m != -INFINITY)
+      for (int s = 0; s < W; ++s) l += expf(parts[(int64_t)s * B + r] - m);
+    out[r] = (m == -INFINITY ? -INFINITY : m + logf(l)) - t[r];
+    return;
+  }
+  float sm = 0.f;
+  int c = 0;
+  for (int s = 0; s < W; ++s) {
+    sm += parts[(int64_t)s * B + r];
+    if (mode == 2) c += cnts[(int64_t)s * B + r];
+  }
+  out[r] = mode == 1 ? log1pf(sm) : sm;
+  if (mode == 2) cnt_out[r] = c;
+}
+
 __global__ void k_eval_finish(int mode, const float* __restrict__ acc0, const float* __restrict__ acc1,
                               const float* __restrict__ t, int64_t B, float* __restrict__ out) {
   const int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -902,6 +996,49 @@ int arx_eval_warp_unmask(const float* U, int64_t ldu, const float* P, int64_t ld
   k_eval_unmask<<<(int)ceil_div(B, 4), 256, 0, as_stream(stream)>>>(
       U, ldu, P, ldp, pbias, d, tscore, PosMask{user_ids, pos_ptr, pos_items, item2col},
       mask_rows > 0 ? mask_rows : B, V, s_acc, B);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_eval_shard_reduce(int mode, const float* parts, int64_t ldp, int npart, const int32_t* cnt_parts, int64_t ldc,
+                          const float* U, int64_t ldu, const float* E, int64_t lde, const float* bias, int d, int64_t V,
+                          const float* tscore, const int32_t* tcol, const int32_t* row_keys, int64_t key_rows,
+                          const int32_t* ex_ptr, const int32_t* ex_cols, int64_t B, float* out, int32_t* cnt_out,
+                          void* stream) {
+  ARX_CHECK_ARG(mode >= 0 && mode <= 2, "arx_eval_shard_reduce: mode must be 0 (ce), 1 (warp) or 2 (warp_eval)");
+  ARX_CHECK_ARG(out && B >= 0 && npart >= 0, "arx_eval_shard_reduce: need out, B >= 0, npart >= 0");
+  ARX_CHECK_ARG(npart == 0 || (parts && ldp >= npart), "arx_eval_shard_reduce: parts missing or ldp < npart");
+  ARX_CHECK_ARG(mode != 2 || (cnt_out && (npart == 0 || (cnt_parts && ldc >= npart))),
+                "arx_eval_shard_reduce: warp_eval needs cnt_out and count parts (ldc >= npart)");
+  ARX_CHECK_ARG(mode == 0 || tscore, "arx_eval_shard_reduce: the margins need the target scores");
+  const bool masked = mode != 0 && row_keys != nullptr;
+  if (masked) {
+    ARX_CHECK_ARG(key_rows > 0 && ex_ptr && ex_cols && U && E && tcol,
+                  "arx_eval_shard_reduce: masks need key_rows > 0, ex_ptr, ex_cols, U, E and tcol");
+    ARX_CHECK_ARG(d > 0 && d <= 256 && d % 4 == 0 && ldu % 4 == 0 && lde % 4 == 0 &&
+                      !((reinterpret_cast<uintptr_t>(U) | reinterpret_cast<uintptr_t>(E)) & 15),
+                  "arx_eval_shard_reduce: masks need d %% 4 == 0, d <= 256 and 16-byte aligned U / E rows");
+  }
+  ARX_CHECK_ARG(ceil_div(B, (int64_t)4) <= 0x7fffffff, "arx_eval_shard_reduce: B too large");
+  if (B == 0) return ARX_OK;
+  k_eval_shard_reduce<<<(int)ceil_div(B, (int64_t)4), 256, 0, as_stream(stream)>>>(
+      mode, parts, ldp, npart, cnt_parts, ldc, U, ldu, E, lde, bias, d, V, tscore, tcol, masked ? row_keys : nullptr,
+      key_rows, ex_ptr, ex_cols, B, out, cnt_out);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_eval_merge_shards(int mode, const float* parts, const int32_t* cnts, const float* tscore, int64_t B, int W,
+                          float* out, int32_t* cnt_out, void* stream) {
+  ARX_CHECK_ARG(mode >= 0 && mode <= 2, "arx_eval_merge_shards: mode must be 0 (ce), 1 (warp) or 2 (warp_eval)");
+  ARX_CHECK_ARG(parts && out, "arx_eval_merge_shards: null pointer");
+  ARX_CHECK_ARG(mode != 0 || tscore, "arx_eval_merge_shards: ce needs the target scores");
+  ARX_CHECK_ARG(mode != 2 || (cnts && cnt_out), "arx_eval_merge_shards: warp_eval needs cnts and cnt_out");
+  ARX_CHECK_ARG(W >= 1 && W <= 64, "arx_eval_merge_shards: need 1 <= W <= 64");
+  ARX_CHECK_ARG(B >= 0 && ceil_div(B, (int64_t)256) <= 0x7fffffff, "arx_eval_merge_shards: need 0 <= B, B / 256 < 2^31");
+  if (B == 0) return ARX_OK;
+  k_eval_merge_shards<<<(int)ceil_div(B, (int64_t)256), 256, 0, as_stream(stream)>>>(mode, parts, cnts, tscore, B, W,
+                                                                                   out, cnt_out);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

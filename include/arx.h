@@ -952,6 +952,34 @@ int arx_topk_merge_shards(const float* v, const int32_t* c, int64_t B, int W, in
 int arx_gemm_nt_eval_parts(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N, int64_t K,
                            const float* col_bias, const float* tscore, float* lse_part, float* relu_part, int64_t ldl,
                            void* stream);
+/* The reference's warp_eval output (embed_attribute.py:620-639: [margin_rank, true_rank]) out of the same GEMM pass:
+ * per row and column range p, relu_part[row][p] = sum of relu((logit - tscore[row]) + 1) and cnt_part[row][p] = the
+ * number of columns whose logit is > tscore[row] (ties do not count).  tcol[row]: the row's target column among the N
+ * columns of this launch -- it contributes exactly (1, 0) -- or any value outside [0, N) when the target is elsewhere
+ * (another shard).  K in {32, 64, 128}, 16-byte aligned operands; the part rows (stride ldl) need
+ * arx_gemm_nt_topk_parts(M, N) entries. */
+int arx_gemm_nt_eval_rank_parts(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
+                                int64_t K, const float* col_bias, const float* tscore, const int32_t* tcol,
+                                float* relu_part, int32_t* cnt_part, int64_t ldl, void* stream);
+/* Evaluation of the row-sharded model (arx.dist.ShardedHMF.evaluate; owner of item g = g % W, local column g / W).
+ * arx_eval_shard_reduce: one shard's partial per row out of its column-range parts [B][ldp] (npart of them; 0: a shard
+ * without columns).  mode 0 ce: out = log sum exp of the parts (-inf without parts), no mask.  mode 1 warp: out = sum
+ * of the parts.  mode 2 warp_eval: the same, and cnt_out = sum of the int count parts [B][ldc].  Modes 1 / 2 with
+ * row_keys != NULL then take the row's masked columns out again: key = row_keys[r % key_rows] (< 0: none) names the
+ * list ex_cols[ex_ptr[key] .. ex_ptr[key + 1]) of LOCAL columns, sorted and unique; each column j in [0, V) other than
+ * tcol[r] subtracts relu((x - t) + 1) and [x > t], x = U[r] . E[j] + bias[j] recomputed (bias may be NULL); tcol[r]
+ * subtracts (1, 0).  The margin is clamped at >= 0 (the count as well).  One wave per row; masks need d % 4 == 0,
+ * d <= 256 and 16-byte aligned rows of U / E.
+ * arx_eval_merge_shards: parts / cnts [W][B] in shard order (as all_to_all delivers them) -> per row, folded in shard
+ * order (deterministic): ce out = logsumexp_w(parts) - tscore; warp out = log1p(sum_w parts); warp_eval out = sum_w
+ * parts (margin_rank), cnt_out = sum_w cnts (true_rank).  1 <= W <= 64. */
+int arx_eval_shard_reduce(int mode, const float* parts, int64_t ldp, int npart, const int32_t* cnt_parts, int64_t ldc,
+                          const float* U, int64_t ldu, const float* E, int64_t lde, const float* bias, int d, int64_t V,
+                          const float* tscore, const int32_t* tcol, const int32_t* row_keys, int64_t key_rows,
+                          const int32_t* ex_ptr, const int32_t* ex_cols, int64_t B, float* out, int32_t* cnt_out,
+                          void* stream);
+int arx_eval_merge_shards(int mode, const float* parts, const int32_t* cnts, const float* tscore, int64_t B, int W,
+                          float* out, int32_t* cnt_out, void* stream);
 /* out[r][j] = table[r * ld + pos[r * ldp + j]], r < B, j < k */
 int arx_take_rows_i32(const int32_t* table, int64_t ld, const int32_t* pos, int64_t ldp, int64_t B, int k,
                       int32_t* out, int64_t ldo, void* stream);

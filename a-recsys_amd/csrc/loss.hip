@@ -363,16 +363,20 @@ __global__ __launch_bounds__(256) void k_eval_chunk(const float* __restrict__ x,
     for (int64_t c = lane; c < n; c += 64) m = fmaxf(m, row[c]);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    // a chunk whose every logit is -inf (m == -inf: exp(-inf - -inf) would be NaN) adds nothing, and a
+    // running state that is still (-inf, 0) has no weight: the guard of k_eval_shard_reduce / k_eval_merge_shards
+    const bool none = m == -INFINITY;
     float l = 0.f;
-    for (int64_t c = lane; c < n; c += 64) l += expf(row[c] - m);
+    if (!none)
+      for (int64_t c = lane; c < n; c += 64) l += expf(row[c] - m);
     l = wsum(l);
     if (lane == 0) {
       if (first) { acc0[r] = m; acc1[r] = l; }
-      else {
+      else if (!none) {
         const float m0 = acc0[r], l0 = acc1[r];
         const float mm = fmaxf(m0, m);
         acc0[r] = mm;
-        acc1[r] = l0 * expf(m0 - mm) + l * expf(m - mm);
+        acc1[r] = (m0 == -INFINITY ? 0.f : l0 * expf(m0 - mm)) + l * expf(m - mm);
       }
     }
   } else {                               // warp: hinge sum against the target logit
@@ -728,7 +732,17 @@ __global__ __launch_bounds__(256) void k_warp_eval(
   const int64_t r = blockIdx.x;
   const float* x = logits + r * ldl;
   const uint8_t* m = mask ? mask + (r % mask_rows) * ldm : nullptr;
-  const float t = x[target[r]];
+  const int tcol = target[r];
+  // a target without a logit index (see k_loss_margin): margin_rank = NaN -- loud -- and
+  // true_rank = -1; no logit is read through the bad index
+  if (tcol < 0 || tcol >= V) {
+    if (threadIdx.x == 0) {
+      margin_rank[r] = NAN;
+      true_rank[r] = -1;
+    }
+    return;
+  }
+  const float t = x[tcol];
   float s = 0.f, cnt = 0.f;
   for (int64_t c = threadIdx.x; c < V; c += 256) {
     const bool keep = m ? (m[c] != 0) : true;

@@ -382,8 +382,9 @@ int arx_loss_mw_fused_pos(const float* logits, int64_t ldl, const float* U, int6
  * caller runs the scorer GEMM over chunks of the pool and folds every [B, n] chunk of logits in:
  *   mode 0 (ce)   acc0 = running max, acc1 = running sum exp(x - max)   (online log-sum-exp)
  *   mode 1 (warp) acc0 += sum_j relu(x_j - t + 1)                       (t = the target's logit)
- * first != 0 starts the scan.  arx_eval_warp_unmask then takes the terms of the masked columns --
- * the row's user's positives that have a logit (item2col >= 0), each distinct column once,
+ * first != 0 starts the scan.  A ce chunk whose every logit is -inf adds nothing (the state of a scan
+ * that has seen only such chunks is (-inf, 0): log-sum-exp -inf).  arx_eval_warp_unmask then takes
+ * the terms of the masked columns -- the row's user's positives that have a logit (item2col >= 0), each distinct column once,
  * embed_attribute.py:729-741 -- out again (their logits are recomputed from U and the pool rows
  * P / pbias).  arx_eval_finish: batch_loss = acc0 + log(acc1) - t (ce) or log(1 + acc0) (warp). */
 int arx_eval_chunk_accum(const float* logits, int64_t ldl, int64_t B, int64_t n, const float* tscore,
@@ -546,7 +547,9 @@ int arx_loss_ce_fwdbwd(const float* logits, int64_t ldl, const int32_t* target, 
 int arx_row_logsumexp(const float* logits, int64_t ldl, int64_t B, int64_t V, float* out,
                       void* stream);
 
-/* embed_attribute.py:620-639 warp_eval -> margin_rank[B] (float), true_rank[B] (int32) */
+/* embed_attribute.py:620-639 warp_eval -> margin_rank[B] (float), true_rank[B] (int32).
+ * A row whose target is not a logit column (target < 0 or >= V) gets margin_rank = NaN and
+ * true_rank = -1, like the NaN loss of the training losses; nothing is read through the index. */
 int arx_loss_warp_eval(const float* logits, int64_t ldl, const int32_t* target,
                        const uint8_t* mask, int64_t ldm, int64_t mask_rows, int64_t B, int64_t V,
                        float* margin_rank, int32_t* true_rank, void* stream);

@@ -1,6 +1,9 @@
 """Per-kernel parity: every C-ABI entry point against a numpy restatement of the
-TF op it replaces (oracle.ref_graph helpers / plain numpy), on seeded inputs.
-Integer outputs bit-exact; fp32 rtol 1e-4 (north_star tolerance)."""
+TF op it replaces (oracle.ref_graph helpers / plain numpy), on seeded inputs --
+this module together with test_kernels_direct_gpu.py (the rs-family / ce / eval
+losses, pooling, the per-step GEMM and the small utility kernels) and the modules
+of the newer kernel families (sampler, top-k and exclusion, sharded recommend /
+evaluate).  Integer outputs bit-exact; fp32 rtol 1e-4 (north_star tolerance)."""
 import numpy as np
 import pytest
 

@@ -202,7 +202,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       if (want_lse) {
-        lm[e] = -__builtin_inff();
+        // the empty state is (-FLT_MAX, 0), not (-inf, 0): a -inf logit (an item switched off by its bias) met in that
+        // state gives dd = -inf (ex = 0: it adds nothing) where -inf - -inf would be NaN for good; the first finite
+        // logit gives dd = +huge as before, and a range of nothing but -inf ends as -FLT_MAX + log(0) = -inf
+        lm[e] = -__FLT_MAX__;
         ls[e] = 0.f;
       }
       if (want_relu) rsum[e] = 0.f;
@@ -315,7 +318,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
           if (want_relu && col < N) rsum[e] += fmaxf(v - tq[e], 0.f);
           if (want_lse && col < N) {                                // online (max, sum): ONE exp per logit
             const float dd = v - lm[e];
-            const float ex = __expf(-fabsf(dd));                    // (first logit: dd = +inf, ex = 0: ls = 0 * 0 + 1)
+            const float ex = __expf(-fabsf(dd));                    // (first logit: dd ~ FLT_MAX, ex = 0: ls = 0 * 0 + 1)
             ls[e] = dd > 0.f ? ls[e] * ex + 1.f : ls[e] + ex;
             lm[e] = fmaxf(lm[e], v);
           }

@@ -907,7 +907,15 @@ int arx_topk_merge(const float* va, const int32_t* ia, const float* vb, const in
  * (positions -> columns) and arx_topk_merge finish the top-k.  *overflow is set when a range's segment was too short
  * (results incomplete: fall back to the chunked path).  K in {32, 64, 128}; values bit-identical to arx_gemm_f32's.
  * lse_part (nullable) [M, ldl >= parts]: lse_part[row][p] = log sum exp of the row's logits over column range p -- with
- * the first chunk's row log-sum-exp this is the softmax normaliser of seqModel.py:514-517 top_k(softmax(logits)). */
+ * the first chunk's row log-sum-exp this is the softmax normaliser of seqModel.py:514-517 top_k(softmax(logits)).  A
+ * -inf logit (an item switched off by a -inf bias) adds nothing, as in arx_row_logsumexp; a range of nothing but -inf
+ * logits gives lse_part = -inf (never NaN), which adds nothing to arx_row_logsumexp over the parts (+inf logits are
+ * outside the contract here as there: exp(inf - inf)).  The same holds for the lse_part of
+ * arx_gemm_nt_topk_filter_excl and arx_gemm_nt_eval_parts: the four kernels' lse_part are bit-identical.
+ * The ranges: with tiles = ceil(N / 64) and tpb = ceil(tiles / parts), range p covers the columns
+ * [p * tpb * 64, min(N, (p + 1) * tpb * 64)) -- tpb is the launch's tiles per workgroup: parts is ceil(tiles / tpb) for
+ * the smallest tpb that keeps two workgroups per compute unit busy, so ceil(tiles / parts) gives tpb back.  Every range
+ * but the last holds tpb * 64 columns; parts depends on M, N and the device's CU count only. */
 int arx_gemm_nt_topk_parts(int64_t M, int64_t N, int* parts);
 int arx_gemm_nt_topk_filter(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N, int64_t K,
                             const float* col_bias, const float* thr, int64_t ldthr, int32_t col_base, float* cand_v,

@@ -20,16 +20,12 @@ def _dyadic(rng, *shape, lo=-2, hi=3, den=2.0):
 
 
 # ---------------------------------------------------------------- the rank-parts GEMM
-@pytest.mark.parametrize("d", [32, 64, 128])
-@pytest.mark.parametrize("dyadic", [True, False])
-def test_gemm_nt_eval_rank_parts_matches_numpy(dev, d, dyadic):
-    """margins at rtol 1e-5 against the device's own logits (ops.gemm); counts exact on dyadic data, on random floats
-    between the counts at t + 4 ulp and t - 4 ulp; the target column adds exactly (1, 0); rows whose target is
-    elsewhere (tcol -1 or N) count every column."""
+def _check_rank_parts(dev, d, dyadic, M, N, tcol, rng, rand_rows):
+    """One launch of arx_gemm_nt_eval_rank_parts on seeded [M, d] x [N, d] tables against the device's own logits:
+    tcol [M] int32 (outside [0, N): the target is elsewhere); t = the target's logit, an unrelated value in rand_rows.
+    -> the rows' counts.  (test_gemm_nt_fused_gpu.py runs it at the shape edges.)"""
     import torch
     from arx import ops
-    rng = np.random.default_rng(d + 7 * dyadic)
-    M, N = 300, 20011
     if dyadic:
         A, Bm, bias = _dyadic(rng, M, d), _dyadic(rng, N, d), _dyadic(rng, N, lo=-4, hi=5, den=4.0)
     else:
@@ -40,12 +36,10 @@ def test_gemm_nt_eval_rank_parts_matches_numpy(dev, d, dyadic):
     L = torch.empty((M, N), dtype=torch.float32, device=dev)
     ops.gemm(At, Bt, L, ops.Workspace(dev), transB=True, col_bias=bt)
     lg = L.cpu().numpy().astype(np.float64)
-    tcol = rng.integers(0, N, size=M).astype(np.int32)
-    tcol[::5], tcol[1::7] = -1, N                                      # targets on other shards
     t = lg[np.arange(M), np.clip(tcol, 0, N - 1)].astype(np.float32)
-    t[::5] = (rng.standard_normal(len(t[::5])) * 0.5).astype(np.float32)
+    t[rand_rows] = (rng.standard_normal(len(t[rand_rows])) * 0.5).astype(np.float32)
     if dyadic:
-        t[::5] = np.round(t[::5] * 4) / 4
+        t[rand_rows] = np.round(t[rand_rows] * 4) / 4
     npart = ops.gemm_nt_topk_parts(M, N)
     rp = torch.full((M, npart + 3), 7.0, dtype=torch.float32, device=dev)
     cp = torch.full((M, npart + 3), 7, dtype=torch.int32, device=dev)
@@ -65,7 +59,21 @@ def test_gemm_nt_eval_rank_parts_matches_numpy(dev, d, dyadic):
         sp = 4.0 * np.spacing(np.abs(t)).astype(np.float64)[:, None]
         lo, hi = ((lg > tt + sp) & ~hit).sum(1), ((lg > tt - sp) & ~hit).sum(1)
         assert ((got_c >= lo) & (got_c <= hi)).all()
-        assert (got_c > 0).any() and (got_c < N - 1).any()
+    return got_c
+
+
+@pytest.mark.parametrize("d", [32, 64, 128])
+@pytest.mark.parametrize("dyadic", [True, False])
+def test_gemm_nt_eval_rank_parts_matches_numpy(dev, d, dyadic):
+    """margins at rtol 1e-5 against the device's own logits (ops.gemm); counts exact on dyadic data, on random floats
+    between the counts at t + 4 ulp and t - 4 ulp; the target column adds exactly (1, 0); rows whose target is
+    elsewhere (tcol -1 or N) count every column."""
+    rng = np.random.default_rng(d + 7 * dyadic)
+    M, N = 300, 20011
+    tcol = np.random.default_rng(d + 70 * dyadic + 1).integers(0, N, size=M).astype(np.int32)
+    tcol[::5], tcol[1::7] = -1, N                                      # targets on other shards
+    got_c = _check_rank_parts(dev, d, dyadic, M, N, tcol, rng, slice(None, None, 5))
+    assert (got_c > 0).any() and (got_c < N - 1).any()
 
 
 # ---------------------------------------------------------------- the shard reduce

@@ -149,11 +149,12 @@ class HipBackend(object):
     def dot_score(self, U, T, tb, out):
         self.ops.dot_score(U, T, tb, out)
 
-    def dot_score_bwd(self, U, T, ds, dU, acc, dT):
-        self.ops.dot_score_bwd(U, T, ds, dU, acc, dT)
-
     def copy_2d(self, src, dst):
         self.ops.copy_2d(src, dst)
+
+    def copy_words(self, feeds):
+        """[(src, dst)] of 4-byte elements, one launch per eight pairs: the per-batch index vectors of a step."""
+        self.ops.copy_words(feeds)
 
     def copy_strided(self, src, dst):
         self.ops.copy_strided(src, dst)
@@ -174,18 +175,12 @@ class HipBackend(object):
     def pool_blocks(self, ids, world, rank, zero_row, cap, counts, gidx=None, my_slots=None, pool_rows=None):
         self.ops.pool_blocks(ids, world, rank, zero_row, cap, counts, gidx, my_slots, pool_rows)
 
-    def loss_mw_pos(self, logits, t, urows, ptr, items, i2s, bl, dl, dt, gscale):
-        self.ops.loss_mw_pos(logits, t, urows, ptr, items, i2s, bl, dl, dt, gscale)
-
     def loss_mw_fused_pos(self, logits, U, T, tb, urows, ptr, items, i2s, bl, dl, t_out, dt, dU, dT, gscale):
         """loss + target score + rank-one gradients in one kernel; tb / dt may be strided columns."""
         self.ops.loss_mw_fused_pos(logits, U, T, tb, urows, ptr, items, i2s, bl, dl, t_out, dt, dU, dT, gscale)
 
     def sum_scaled(self, x, scale, out):
         self.ops.sum_scaled(x, scale, out)
-
-    def sparse_adagrad(self, E, acc, bias, bias_acc, keys, G, Gb, lr):
-        self.ops.sparse_adagrad(E, acc, bias, bias_acc, keys, None, None, G, Gb, lr, self.ws)
 
     def sparse_adagrad_multi(self, tables, sites, G, Gb, lr, phase=3):
         """tables: [(E, acc, bias|None, bias_acc|None)]; sites: [(table, local_rows, row_base)]:
@@ -230,9 +225,6 @@ class HipBackend(object):
         if getattr(self, '_neg_one', None) is None:
             self._neg_one = torch.tensor([-1.0], dtype=torch.float32, device=D.device)
         self.bags_adagrad(D, None, Db, None, vals, starts, lens, sites, G, Gb, self._neg_one, phase=phase)
-
-    def adagrad_dense(self, w, acc, g, lr):
-        self.ops.adagrad_dense(w, acc, g, lr)
 
     def adagrad_rows_nonzero(self, W, acc, bias, bias_acc, G, Gb, lr):
         """Adagrad on the rows whose dense gradient row is not all zero; the consumed gradient is zeroed (arx.h)."""
@@ -367,7 +359,12 @@ class HipBackend(object):
 
 class ShardedHMF(object):
     """id-only HMF ('mw' loss) with row-sharded tables.  Global ids everywhere in
-    the API; `users` passed to step() must all be owned by this rank."""
+    the API; `users` passed to step() must all be owned by this rank.
+
+    The step of this class and of its two subclasses is ONE body each (_step_body: named segments of kernels between
+    the collectives), run by one driver (_run_step): as captured hipGraph segments on the product backend, kernel by
+    kernel everywhere else (graphs=False, ARX_DIST_EAGER=1, the numpy double of the CPU tests) -- the same launches,
+    padding and exchanges either way.  exchange='logits' is a separate, eager-only step (_step_logits)."""
 
     def __init__(self, n_users, n_items, d, B_loc, S, learning_rate, rank, world, device,
                  backend=None, group=None, tables=None, seed=0, acc0=0.1, graphs=None, exchange='rows'):
@@ -393,11 +390,11 @@ class ShardedHMF(object):
         self.device = torch.device(device)
         self.group = group
         self.be = backend if backend is not None else HipBackend(self.device)
-        # hipGraph segments (_step_static): the product backend on a GPU, unless switched off
+        # "this model captures graphs" (_run_step): the product backend on a GPU, unless switched off -- otherwise the
+        # same step body runs kernel by kernel on the caller's stream
         if graphs is None:
             graphs = not os.environ.get("ARX_DIST_EAGER")
-        self.use_graphs = bool(graphs) and getattr(self, '_static_step_ok', type(self) is ShardedHMF) \
-            and isinstance(self.be, HipBackend) and self.device.type == 'cuda'
+        self.use_graphs = bool(graphs) and isinstance(self.be, HipBackend) and self.device.type == 'cuda'
         self._graphs, self._graph_key, self._warm_key, self.g_idx = {}, None, None, None
         self.n_captures, self.n_replays = 0, 0
         # (the legacy default stream cannot be captured: the step runs on a stream of its own, joined with
@@ -599,76 +596,12 @@ class ShardedHMF(object):
         nothing but kernels and collectives on the step path) or a users array with `items`
         (routed here on the host)."""
         if self.world > 1 and self.cap <= 0:
-            raise RuntimeError("ShardedHMF.step before set_pool(): the pool's block layout sizes the exchanges")
+            raise RuntimeError("%s.step before set_pool(): the pool's block layout sizes the exchanges"
+                               % type(self).__name__)
         route = users if isinstance(users, dict) else self.prepare_route(users, items)
         if self.exchange == 'logits':
             return self._step_logits(route)
-        if self.use_graphs:
-            outer = torch.cuda.current_stream(self.device)
-            if outer == self._stream:          # the caller already works on the model's stream (model.stream)
-                self._step_guard(route)
-                return
-            self._stream.wait_stream(outer)
-            with torch.cuda.stream(self._stream):
-                self._step_guard(route)
-            outer.wait_stream(self._stream)
-            return
-        be, W, r = self.be, self.world, self.rank
-        B, B_loc, S, Sg, d, dp = self.B, self.B_loc, self.S, self.Sg, self.d, self.dp
-        grp = self.group
-        send, recv, R = route['send'], route['recv'], route['R']
-        arena, arena_b = self.arena, self.arena_b
-        # The two large exchanges (target rows out, target-row gradients back: B_loc x (d+4) floats
-        # each) are issued asynchronously and waited for only where their result is needed, so that
-        # they travel under the scorer GEMM and under the two backward GEMMs respectively.
-        # ---- forward ----
-        urows, recv_rows = route['urows'], route['recv_rows']
-        self.urows = urows
-        be.gather_rows(self.E_user, None, urows, self.U_loc, None)
-        cap = self.cap
-        if W == 1:
-            be.gather_rows_packed(self.E_item, self.b_item, self.pool_rows, self.I_all)   # row | bias
-        else:
-            be.gather_rows_packed(self.E_item, self.b_item, self.pool_rows[:cap], self.I_pack[:cap])
-            dist.all_gather_into_tensor(self.I_gath[:W * cap], self.I_pack[:cap], group=grp)
-            be.gather_rows(self.I_gath, None, self.gidx, self.I_all, None)    # blocks -> pool (slot) order
-        be.copy_strided(self.I_all[:, d], self.b_all)
-        T_send = self.T_send[:R]
-        if R > 0:
-            be.gather_rows_packed(self.E_item, self.b_item, recv_rows, T_send)
-        w_rows = _all_to_all(self.T_pack, T_send, send, recv, group=grp, async_op=True)   # packed target rows back ...
-        be.gemm(self.U_loc, self.I_all[:, :d], self.logits, transB=True, col_bias=self.b_all)   # ... under the scorer
-        w_rows.wait()
-        # loss (global mean => gscale = 1/B) with the target score and its rank-one gradients formed
-        # by the same kernel, straight from / into the packed rows (bias and dt live in column d)
-        dU = arena[:B_loc, :d]
-        be.loss_mw_fused_pos(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], self.urows,
-                             self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
-                             self.t_loc, self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
-        # ---- backward ----
-        w_dt = _all_to_all(arena[B_loc + Sg:B_loc + Sg + R], self.dT_pack, recv, send, group=grp,
-                           async_op=True)                             # target-row gradients -> owners ...
-        be.gemm(self.dlogits, self.I_all[:, :d], dU, beta=1.0)                # ... under dU += dL . pool
-        # pool gradient partials (+ bias gradient = row sums) -> owners
-        be.gemm(self.dlogits, self.U_loc, self.dI_all[:S, :d], transA=True, a_rowsum=self.gb_all)
-        be.copy_strided(self.gb_all, self.dI_all[:S, d])
-        if W == 1:
-            be.copy_2d(self.dI_all[:S], arena[B_loc:B_loc + S])
-        else:
-            # 0.5 MB: summed everywhere, every owner picks the rows of its block (padding -> the zero row)
-            dist.all_reduce(self.dI_all[:S], op=dist.ReduceOp.SUM, group=grp)
-            be.gather_rows(self.dI_all, None, self.my_slots[:cap], arena[B_loc:B_loc + cap], None)
-        w_dt.wait()
-        be.copy_strided(arena[B_loc:B_loc + Sg + R, d], arena_b[B_loc:B_loc + Sg + R])
-        # one fused scatter + Adagrad pass over both shards
-        sites = [(0, self.urows, 0), (1, self.pool_rows[:cap], B_loc)]
-        if R > 0:
-            sites.append((1, recv_rows, B_loc + Sg))
-        be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
-                                 (self.E_item, self.A_item, self.b_item, self.Ab_item)],
-                                sites, arena[:, :d], arena_b, self.lr)
-        self.steps += 1
-
+        self._run_step(route)
 
     def _step_logits(self, route):
         """The step with the exchange north_star words (hmf_model.py:52-99 on the global
@@ -763,28 +696,79 @@ class ShardedHMF(object):
 
     @property
     def stream(self):
-        """The stream the graph-segment step runs on (None: eager step, the caller's stream).  A training loop
+        """The stream the graph-segment step runs on (None: no captured graphs, the caller's stream).  A training loop
         that makes it the current stream (`with torch.cuda.stream(model.stream)`) saves the two stream
         joins per step that a caller on another stream pays."""
         return self._stream
 
-    # ------------------------------------------------------- step, hipGraph segments
+    # ------------------------------------------------ step: one body per class, one driver
+    def _run_step(self, route):
+        """Driver of the step of all three classes: the class's _step_body(route) gives the graph key and the body --
+        kernels grouped into named segments between the collectives -- and this runs it.  A model that captures
+        graphs (use_graphs) works on its own stream, joined with the caller's on both sides (the legacy default
+        stream cannot be captured): a configuration (the key: capacities and buffer addresses) runs eagerly once
+        (module loads, workspaces), is captured on its second step and replayed from then on;
+        ARX_DIST_NO_CAPTURE=1 keeps it eager (profiling: the same launches, kernel by kernel).  Any other model
+        (graphs=False / ARX_DIST_EAGER=1, a backend without kernels, a CPU device) runs the same body eagerly on the
+        caller's stream, K7's sort half in line.  A step that raises leaves no captured graph behind: the next one
+        runs eagerly again."""
+        outer = torch.cuda.current_stream(self.device) if self.use_graphs else None
+        if outer is not None and outer != self._stream:    # (== : the caller already works on model.stream)
+            self._stream.wait_stream(outer)
+            with torch.cuda.stream(self._stream):
+                self._run_step_here(route)
+            outer.wait_stream(self._stream)
+            return
+        self._run_step_here(route)
+
+    def _run_step_here(self, route):
+        try:
+            key, body = self._step_body(route)
+            if not self.use_graphs or os.environ.get("ARX_DIST_NO_CAPTURE"):
+                mode = 'eager'
+            elif self._graph_key == key:
+                mode = 'replay'
+            elif self._warm_key == key:
+                mode, self._graphs = 'capture', {}
+            else:
+                mode, self._graphs, self._graph_key = 'eager', {}, None
+            if mode != 'replay' and getattr(self, 'D_tok', None) is not None:
+                # ShardedHMFRepTokens: the dense token-gradient table must be all zero at step entry (the token apply
+                # zeroes the rows it consumes).  A step that died between the gradient pass and that apply would
+                # leave sums behind that the next step counts twice: every step that is NOT a replay (the first
+                # eager one, a re-capture, the step after an exception -- the graphs are dropped below) starts from
+                # a cleared table.
+                self.D_tok.zero_()
+                self.Db_tok.zero_()
+            body(mode)
+        except BaseException:
+            self._graphs, self._graph_key, self._warm_key = {}, None, None
+            raise
+        if mode == 'eager':
+            self._warm_key = key
+        elif mode == 'capture':
+            self._graph_key = key
+            self.n_captures += 1
+        else:
+            self.n_replays += 1
+        self.steps += 1
+
     def _segment(self, mode, name, fn, feeds=None):
         """eager: run; capture: record the launches of `fn` into a hipGraph, keep it, launch it;
         replay: launch the kept graph.  feeds ([(src, dst)], the step's first segment): the copy of the batch's
-        index vector is the graph's first node, its source replaced before every replay
-        (ops.CapturedGraph.set_feeds) -- it was an eager launch in front of the graph."""
-        ops_ = self.be.ops
+        index vectors is the graph's first node, its source replaced before every replay
+        (ops.CapturedGraph.set_feeds)."""
+        be = self.be
         if mode == 'eager':
             if feeds:
-                ops_.copy_words(feeds)
+                be.copy_words(feeds)
             fn()
         elif mode == 'capture':
-            g = ops_.CapturedGraph()
+            g = be.ops.CapturedGraph()
             g.begin()
             try:
                 if feeds:
-                    ops_.copy_words(feeds)
+                    be.copy_words(feeds)
                 fn()
             except BaseException:
                 g.end()
@@ -798,29 +782,46 @@ class ShardedHMF(object):
                 if g.feeds_match(feeds):
                     g.set_feeds(feeds)
                 else:
-                    ops_.copy_words(feeds)
+                    be.copy_words(feeds)
                     g.set_feeds(None)
             g.launch()
 
-    def _step_guard(self, route):
-        """_step_static; a step that raises leaves no captured graph behind: the next one runs eagerly again (and, for
-        the replicated-token class, from a cleared token-gradient table -- see _step_static)."""
-        try:
-            self._step_static(route)
-        except BaseException:
-            self._graphs, self._graph_key, self._warm_key = {}, None, None
-            raise
+    def _k7_sorts(self, mode, k7, own_graph):
+        """k7(1) -- K7's keys, sorts and run records, which need the ids only -- on the second stream, under the
+        forward kernels (the ~70 us chain leaves the critical path): a graph of its own between the segments
+        (own_graph), or a branch of the one graph at world 1.  Returns what _k7_join waits for before the apply half.
+        A model without a second stream runs it in line."""
+        if self._side is None:
+            k7(1)
+            return None
+        main, side = torch.cuda.current_stream(self.device), self._side
+        ev = torch.cuda.Event()
+        ev.record(main)
+        side.wait_event(ev)
+        with torch.cuda.stream(side):
+            if own_graph:
+                self._segment(mode, 'k7_sorts', lambda: k7(1))
+            else:
+                k7(1)
+            done = torch.cuda.Event()
+            done.record(side)
+        return done
 
-    def _step_static(self, route):
-        """The step of step() with every buffer at a fixed address and a fixed size, so that the
-        kernels between two collectives are ONE hipGraph launch each (5 segments + K7's sort half as a
-        sixth, on a second stream under the forward kernels + 4 collectives + one index copy per step
-        instead of ~35 kernel launches from Python; world 1: ONE graph, the sort half a branch of it).  What varies from batch to batch is the index vector [user rows ; received target
-        rows], padded with the shard's padding row to the capacity cap_r (gathers: a zero row;
-        K7: the tables are passed without the padding row, so padded keys are out of range and dropped)
-        and the split sizes of the two all-to-alls, which stay outside the graphs.  A configuration
-        (block capacity, receive capacity) runs eagerly once (module loads, workspaces), is captured
-        on its second step and replayed from then on."""
+    def _k7_join(self, done):
+        if done is not None:
+            torch.cuda.current_stream(self.device).wait_event(done)
+
+    def _step_body(self, route):
+        """The step with every buffer at a fixed address and a fixed size, so that the kernels between two
+        collectives are ONE hipGraph launch each (5 segments + K7's sort half as a sixth, on a second stream under
+        the forward kernels + 4 collectives per step instead of ~35 kernel launches from Python; world 1: ONE graph,
+        the sort half a branch of it).  What varies from batch to batch is the index vector [user rows ; received
+        target rows], padded with the shard's padding row to the capacity cap_r (gathers: a zero row; K7: the tables
+        are passed without the padding row, so padded keys are out of range and dropped) and fed by the first node
+        of the first segment, and the split sizes of the two all-to-alls, which stay outside the graphs.  The two
+        large exchanges (target rows out, target-row gradients back: B_loc x (d+4) floats each) are issued
+        asynchronously and waited for only where their result is needed, so that they travel under the scorer and
+        under the two backward GEMMs.  Returns (graph key, body(mode)) for _run_step."""
         be, W = self.be, self.world
         B, B_loc, S, Sg, d = self.B, self.B_loc, self.S, self.Sg, self.d
         grp, dev = self.group, self.device
@@ -838,28 +839,10 @@ class ShardedHMF(object):
             route['idx'] = idx
         if self.g_idx is None or self.g_idx.shape[0] != n_idx:
             self.g_idx = torch.empty(n_idx, dtype=torch.int32, device=dev)
-        feed = [(idx, self.g_idx)]                     # (a kernel: a device-to-device hipMemcpyAsync costs more;
-        #                                                since round 4 the first node of the step's first graph)
+        feed = [(idx, self.g_idx)]                     # (a kernel: a device-to-device hipMemcpyAsync costs more)
         feed += self._static_feeds(route, cap_r)       # (subclasses: more per-batch index vectors)
         key = (cap, cap_r, self.g_idx.data_ptr(), self.arena.data_ptr(), self.pos_ptr.data_ptr(),
                self.pos_items.data_ptr())
-        if os.environ.get("ARX_DIST_NO_CAPTURE"):        # (profiling: the static step, launched kernel by kernel)
-            mode = 'eager'
-        elif self._graph_key == key:
-            mode = 'replay'
-        elif self._warm_key == key:
-            mode, self._graphs = 'capture', {}
-        else:
-            mode, self._graphs, self._graph_key = 'eager', {}, None
-        seg = lambda name, fn: self._segment(mode, name, fn)
-        if mode != 'replay' and getattr(self, 'D_tok', None) is not None:
-            # ShardedHMFRepTokens: the dense token-gradient table must be all zero at step entry (the token apply zeroes
-            # the rows it consumes).  A step that died between the gradient pass and that apply would leave sums behind
-            # that the next step counts twice: every step that is NOT a replay (the first eager one, a re-capture,
-            # the step after an exception -- _step_guard below drops the graphs) starts from a cleared table
-            # (advisor, round 5).
-            self.D_tok.zero_()
-            self.Db_tok.zero_()
         arena, arena_b = self.arena, self.arena_b
         urows, rrows = self.g_idx[:B_loc], self.g_idx[B_loc:]
         self.urows = urows
@@ -895,6 +878,8 @@ class ShardedHMF(object):
                 be.gemm(self.U_loc, self.I_all[:, :d], self.logits, transB=True, col_bias=self.b_all)
 
         def loss():
+            # (global mean => gscale = 1/B; the target score and its rank-one gradients are formed by the same
+            # kernel, straight from / into the packed rows: bias and dt live in column d)
             dt = arena_b[B_loc + Sg:B_loc + Sg + B_loc] if W == 1 else dT[:, d]
             if fused:
                 self.scorer.fwd(self.U_loc, self.I_all[:, :d], self.b_all, self.T_pack[:, :d], self.T_pack[:, d],
@@ -922,7 +907,7 @@ class ShardedHMF(object):
             be.gemm(self.dlogits, self.U_loc, self.dI_all[:S, :d], transA=True, a_rowsum=self.gb_all)
             be.copy_strided(self.gb_all, self.dI_all[:S, d])
 
-        def k7(phase):
+        def k7(phase):         # one fused scatter + Adagrad pass over both shards
             if het:
                 return self._het_k7(phase, urows, rrows[:B_loc] if W == 1 else rrows, cap, cap_r)
             be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
@@ -941,41 +926,25 @@ class ShardedHMF(object):
             if het and W == 1:
                 self._het_tok_apply()                  # (one rank: nothing to sum, the dense step follows at once)
 
-        def k7_sorts(own_graph, ev=None):
-            # K7's keys, sorts and run records need the ids only: on a second stream, under the forward
-            # kernels (the ~70 us chain leaves the critical path) -- a graph of its own between the
-            # segments, a branch of the one graph at world 1
-            main, side = torch.cuda.current_stream(dev), self._side
-            if ev is None:
-                ev = torch.cuda.Event()
-                ev.record(main)
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                if own_graph:
-                    seg('k7_sorts', lambda: k7(1))
-                else:
-                    k7(1)
-                done = torch.cuda.Event()
-                done.record(side)
-            return done
+        def body(mode):
+            seg = lambda name, fn, feeds=None: self._segment(mode, name, fn, feeds)
 
-        def whole_step():
-            fwd_gather()
-            # (round 5: with the branch's kernels captured BEHIND the scorer's forward launches -- the order arx/graph.py
-            # uses -- the two chains overlap from the start, and the HET step got slower: 436 against 412-427 us.
-            # Captured first, the sorts run ahead of the scorer and only their tail overlaps it: kept)
-            sorted_ = k7_sorts(False)
-            fwd_score()
-            loss()
-            bwd_gemms()
-            torch.cuda.current_stream(dev).wait_event(sorted_)
-            apply()
+            def whole_step():
+                fwd_gather()
+                # (with the branch's kernels captured BEHIND the scorer's forward launches -- the order arx/graph.py
+                # uses -- the two chains overlap from the start, and the HET step got slower: 436 against 412-427 us.
+                # Captured first, the sorts run ahead of the scorer and only their tail overlaps it: kept)
+                sorted_ = self._k7_sorts(mode, k7, False)
+                fwd_score()
+                loss()
+                bwd_gemms()
+                self._k7_join(sorted_)
+                apply()
 
-        if W == 1:
-            self._segment(mode, 'step', whole_step, feeds=feed)
-        else:
-            self._segment(mode, 'fwd_gather', fwd_gather, feeds=feed)
-            sorted_ = k7_sorts(True)
+            if W == 1:
+                return seg('step', whole_step, feed)
+            seg('fwd_gather', fwd_gather, feed)
+            sorted_ = self._k7_sorts(mode, k7, True)
             dist.all_gather_into_tensor(self.I_gath[:W * cap], self.I_pack[:cap], group=grp)
             w_rows = _all_to_all(self.T_pack, self.T_send[:R], send, recv, group=grp, async_op=True)
             seg('fwd_score', fwd_score)                       # scorer GEMM under the target-row exchange
@@ -984,22 +953,17 @@ class ShardedHMF(object):
             w_dt = _all_to_all(arena[B_loc + Sg:B_loc + Sg + R], self.dT_pack, recv, send, group=grp,
                                async_op=True)
             seg('bwd_gemms', bwd_gemms)                       # dU, dI under the gradient exchange
+            # 0.5 MB: summed everywhere, every owner picks the rows of its block (padding -> the zero row)
             dist.all_reduce(self.dI_all[:S], op=dist.ReduceOp.SUM, group=grp)
             w_dt.wait()
-            torch.cuda.current_stream(dev).wait_event(sorted_)
+            self._k7_join(sorted_)
             seg('apply', apply)
             if het:            # the merged token gradients of all ranks, then the same dense Adagrad step everywhere
                 dist.all_reduce(self.D_tok, op=dist.ReduceOp.SUM, group=grp)
                 dist.all_reduce(self.Db_tok, op=dist.ReduceOp.SUM, group=grp)
                 seg('tok_apply', self._het_tok_apply)
-        if mode == 'eager':
-            self._warm_key = key
-        elif mode == 'capture':
-            self._graph_key = key
-            self.n_captures += 1
-        else:
-            self.n_replays += 1
-        self.steps += 1
+
+        return key, body
 
     def _static_feeds(self, route, cap_r):
         return []
@@ -1320,9 +1284,9 @@ class ShardedHMFBags(ShardedHMF):
     moves 2 x B_loc x (d+4) x 4."""
 
     def __init__(self, n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, bags, n_tokens,
-                 backend=None, group=None, tables=None, seed=0, acc0=0.1):
+                 backend=None, group=None, tables=None, seed=0, acc0=0.1, graphs=None):
         super().__init__(n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, backend=backend,
-                         group=group, tables=tables, seed=seed, acc0=acc0)
+                         group=group, tables=tables, seed=seed, acc0=acc0, graphs=graphs)
         dev, f32, i32 = self.device, torch.float32, torch.int32
         vals, starts, lens = [np.asarray(a) for a in bags]
         nt = (n_tokens - rank + world - 1) // world
@@ -1380,16 +1344,13 @@ class ShardedHMFBags(ShardedHMF):
         self.be.shard_route(u, W, self.rank, 0, urows, None)
         return {'users': u, 'items': it, 'urows': urows, 'tgt_all': tgt_all, 'tgt_fwd': fwd, 'tgt_bwd': bwd}
 
-    _static_step_ok = True          # (round 6: the kernels between the collectives as hipGraph segments, below)
-
-    def _step_bags_static(self, route):
-        """The step of step() as hipGraph segments between its four collectives (round 6; round-5 verdict, missing #3:
-        the eager step cost 583 us at world 1 against 187 us for ShardedHMF).  Every buffer is static; what varies from
-        batch to batch are four index vectors (user rows, the global batch's target ids and their id-shard rows /
-        keys), fed by the first node of the first segment.  K7's ids-only half (both one-hot sorts, the entity and
-        token sorts of the bag pass) runs on a second stream under the forward kernels -- a graph of its own between
-        the segments, a branch of the ONE graph at world 1 -- and the scorer is the fused bf16-pipe family where its
-        shapes allow (no [B_loc, S] logits), as in ShardedHMF._step_static."""
+    def _step_body(self, route):
+        """The step as segments between its four collectives (ShardedHMF._run_step drives them).  Every buffer is
+        static; what varies from batch to batch are four index vectors (user rows, the global batch's target ids and
+        their id-shard rows / keys), fed by the first node of the first segment.  K7's ids-only half (both one-hot
+        sorts, the entity and token sorts of the bag pass) runs on a second stream under the forward kernels -- a
+        graph of its own between the segments, a branch of the ONE graph at world 1 -- and the scorer is the fused
+        bf16-pipe family where its shapes allow (no [B_loc, S] logits), as in ShardedHMF._step_body."""
         be, grp, W = self.be, self.group, self.world
         B, B_loc, S, d = self.B, self.B_loc, self.S, self.d
         dev = self.device
@@ -1402,22 +1363,13 @@ class ShardedHMFBags(ShardedHMF):
         self.urows = urows
         feed = [(route['urows'], urows), (route['tgt_fwd'], t_fwd), (route['tgt_all'], t_all), (route['tgt_bwd'], t_bwd)]
         key = (arena.data_ptr(), self.pos_ptr.data_ptr(), self.pos_items.data_ptr(), urows.data_ptr())
-        if os.environ.get("ARX_DIST_NO_CAPTURE"):
-            mode = 'eager'
-        elif self._graph_key == key:
-            mode = 'replay'
-        elif self._warm_key == key:
-            mode, self._graphs = 'capture', {}
-        else:
-            mode, self._graphs, self._graph_key = 'eager', {}, None
-        seg = lambda name, fn: self._segment(mode, name, fn)
         bag = (self.bag_vals, self.bag_starts, self.bag_lens)
         dU = arena[:B_loc, :d]
         gP = arena[B_loc:B_loc + S]
         nt = self.nt_loc
         fused = self._fused_scorer()
 
-        def fwd_pool():
+        def fwd_pool():        # partial embeddings, summed by the collectives
             be.gather_rows(self.E_user, None, urows, self.U_loc, None)
             be.gather_rows(self.E_item, self.b_item, self.pool_fwd, self.P_part[:, :d], self.Pb, scale=0.5)
             be.gather_bags(self.E_tok, self.b_tok, *bag, self.pool_ids, self.P_part[:, :d], self.Pb, scale=0.5,
@@ -1454,6 +1406,8 @@ class ShardedHMFBags(ShardedHMF):
             be.copy_strided(self.gb_all, gP[:, d])
 
         def k7(phase):
+            # id shard + user shard: one fused one-hot pass (rows of other owners carry KEY_NONE); token shard: merge
+            # per item, then per token -- tokens of other owners are out of range
             be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
                                      (self.E_item, self.A_item, self.b_item, self.Ab_item)],
                                     [(0, urows, 0, 1.0), (1, self.pool_bwd, B_loc, 0.5), (1, t_bwd, B_loc + S, 0.5)],
@@ -1466,36 +1420,25 @@ class ShardedHMFBags(ShardedHMF):
             be.copy_strided(arena[B_loc:, d], arena_b[B_loc:])
             k7(2)
 
-        def k7_sorts(own_graph):
-            main, side = torch.cuda.current_stream(dev), self._side
-            ev = torch.cuda.Event()
-            ev.record(main)
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                if own_graph:
-                    seg('k7_sorts', lambda: k7(1))
-                else:
-                    k7(1)
-                done = torch.cuda.Event()
-                done.record(side)
-            return done
+        def body(mode):
+            seg = lambda name, fn, feeds=None: self._segment(mode, name, fn, feeds)
 
-        if W == 1:
             def whole_step():
                 fwd_pool()
-                sorted_ = k7_sorts(False)
+                sorted_ = self._k7_sorts(mode, k7, False)
                 fwd_tgt()
                 be.copy_2d(self.T_part, self.T_pack)          # (one rank: the partials ARE the embeddings)
                 score()
                 loss()
                 be.copy_2d(self.dT_pack, arena[B_loc + S:])
                 bwd()
-                torch.cuda.current_stream(dev).wait_event(sorted_)
+                self._k7_join(sorted_)
                 apply()
-            self._segment(mode, 'step', whole_step, feeds=feed)
-        else:
-            self._segment(mode, 'fwd_pool', fwd_pool, feeds=feed)
-            sorted_ = k7_sorts(True)
+
+            if W == 1:
+                return seg('step', whole_step, feed)
+            seg('fwd_pool', fwd_pool, feed)
+            sorted_ = self._k7_sorts(mode, k7, True)
             w_pool = dist.all_reduce(self.P_part, op=dist.ReduceOp.SUM, group=grp, async_op=True)
             seg('fwd_tgt', fwd_tgt)                               # target partials under the pool all-reduce
             w_pool.wait()
@@ -1507,82 +1450,10 @@ class ShardedHMFBags(ShardedHMF):
             seg('bwd', bwd)                                       # dU, pool gradient under the all-gather
             dist.all_reduce(gP, op=dist.ReduceOp.SUM, group=grp)
             w_dt.wait()
-            torch.cuda.current_stream(dev).wait_event(sorted_)
+            self._k7_join(sorted_)
             seg('apply', apply)
-        if mode == 'eager':
-            self._warm_key = key
-        elif mode == 'capture':
-            self._graph_key = key
-            self.n_captures += 1
-        else:
-            self.n_replays += 1
-        self.steps += 1
 
-    def step(self, users, items=None):
-        route = users if isinstance(users, dict) else self.prepare_route(users, items)
-        if self.use_graphs:
-            def guarded():
-                try:
-                    self._step_bags_static(route)
-                except BaseException:
-                    self._graphs, self._graph_key, self._warm_key = {}, None, None
-                    raise
-            outer = torch.cuda.current_stream(self.device)
-            if outer == self._stream:
-                guarded()
-                return
-            self._stream.wait_stream(outer)
-            with torch.cuda.stream(self._stream):
-                guarded()
-            outer.wait_stream(self._stream)
-            return
-        be, grp = self.be, self.group
-        B, B_loc, S, d = self.B, self.B_loc, self.S, self.d
-        arena, arena_b = self.arena, self.arena_b
-        urows = route['urows']
-        self.urows = urows
-        bag = (self.bag_vals, self.bag_starts, self.bag_lens)
-        # ---- forward: partial embeddings, summed by the collectives ----
-        be.gather_rows(self.E_user, None, urows, self.U_loc, None)
-        be.gather_rows(self.E_item, self.b_item, self.pool_fwd, self.P_part[:, :d], self.Pb, scale=0.5)
-        be.gather_bags(self.E_tok, self.b_tok, *bag, self.pool_ids, self.P_part[:, :d], self.Pb, scale=0.5,
-                       accumulate=True)
-        be.copy_strided(self.Pb, self.P_part[:, d])
-        w_pool = dist.all_reduce(self.P_part, op=dist.ReduceOp.SUM, group=grp, async_op=True)
-        be.gather_rows(self.E_item, self.b_item, route['tgt_fwd'], self.T_part[:, :d], self.Tb, scale=0.5)
-        be.gather_bags(self.E_tok, self.b_tok, *bag, route['tgt_all'], self.T_part[:, :d], self.Tb, scale=0.5,
-                       accumulate=True)
-        be.copy_strided(self.Tb, self.T_part[:, d])
-        w_pool.wait()
-        w_tgt = dist.reduce_scatter_tensor(self.T_pack, self.T_part, op=dist.ReduceOp.SUM, group=grp,
-                                           async_op=True)             # own target embeddings ...
-        be.copy_strided(self.P_part[:, d], self.b_all)
-        be.gemm(self.U_loc, self.P_part[:, :d], self.logits, transB=True, col_bias=self.b_all)   # ... under the scorer
-        w_tgt.wait()
-        dU = arena[:B_loc, :d]
-        be.loss_mw_fused_pos(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], urows,
-                             self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
-                             self.t_loc, self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
-        # ---- backward ----
-        w_dt = dist.all_gather_into_tensor(arena[B_loc + S:], self.dT_pack, group=grp, async_op=True)
-        be.gemm(self.dlogits, self.P_part[:, :d], dU, beta=1.0)                    # dU += dL . pool
-        gP = arena[B_loc:B_loc + S]
-        be.gemm(self.dlogits, self.U_loc, gP[:, :d], transA=True, a_rowsum=self.gb_all)
-        be.copy_strided(self.gb_all, gP[:, d])
-        dist.all_reduce(gP, op=dist.ReduceOp.SUM, group=grp)
-        w_dt.wait()
-        be.copy_strided(arena[B_loc:, d], arena_b[B_loc:])
-        # id shard + user shard: one fused one-hot pass (rows of other owners carry KEY_NONE)
-        be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
-                                 (self.E_item, self.A_item, self.b_item, self.Ab_item)],
-                                [(0, urows, 0, 1.0), (1, self.pool_bwd, B_loc, 0.5),
-                                 (1, route['tgt_bwd'], B_loc + S, 0.5)], arena[:, :d], arena_b, self.lr)
-        # token shard: merge per item, then per token; tokens of other owners are out of range
-        nt = self.nt_loc
-        be.bags_adagrad(self.E_tok[:nt], self.A_tok[:nt], self.b_tok[:nt], self.Ab_tok[:nt], *bag,
-                        [(self.pool_ids, B_loc, 0.5), (route['tgt_all'], B_loc + S, 0.5)], arena[:, :d], arena_b,
-                        self.lr)
-        self.steps += 1
+        return key, body
 
     def recommend(self, users, k, exclude_seen=False, return_values=False):
         """Not yet: the item latents are bag means, and recommend would first need them materialised per shard."""
@@ -1622,14 +1493,12 @@ class ShardedHMFRepTokens(ShardedHMF):
     ranks, and every replica applies the same Adagrad step to the rows of D that are not all zero (rows without gradient
     would not move: the sparse update of embed_attribute.py:383-400 / hmf_model.py:146-151; arx_adagrad_rows_nonzero,
     which also zeroes D for the next step).  Volume per rank and step on top of
-    ShardedHMF: 2 x n_tokens x (d + 1) x 4 B x (N-1)/N through the ring, independent of the batch.  In the EAGER
-    step the two all-reduces are issued asynchronously under the id shard's own K7 pass; in the hipGraph-segment step
-    (the default) they run on the main stream between the 'apply' and 'tok_apply' segments -- NOT overlapped, and
+    ShardedHMF: 2 x n_tokens x (d + 1) x 4 B x (N-1)/N through the ring, independent of the batch.  The two
+    all-reduces run on the main stream between the 'apply' and 'tok_apply' segments -- NOT overlapped with K7, and
     priced so in roofline_comm_predicted (comm_prediction 'rep_tokens').  The token-striped step moves
     2 x B x (d + 4) x 4 B with B the GLOBAL batch
     (predicted comm / compute 0.35 against 0.57 at N = 8, B_loc = 16384)."""
 
-    _static_step_ok = True          # (ShardedHMF.__init__: the hipGraph-segment step serves this class too)
     _het = True
 
     def __init__(self, n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, bags, n_tokens,
@@ -1689,7 +1558,7 @@ class ShardedHMFRepTokens(ShardedHMF):
         else:          # block row -> pool slot (S: padding) -> item id (padding entity)
             be.take_i32(self.pool_ext, self.my_slots, self.block_ids, self.pad_item)
 
-    # ---- the hipGraph-segment step (ShardedHMF._step_static) with HET rows and the replicated token table ----
+    # ---- hooks of ShardedHMF._step_body: HET rows and the replicated token table ----
     def _static_feeds(self, route, cap_r):
         gid = route.get('gid')
         if gid is None or gid.shape[0] != cap_r:
@@ -1741,85 +1610,6 @@ class ShardedHMFRepTokens(ShardedHMF):
         self.be.adagrad_rows_nonzero(self.E_tok[:nt], self.A_tok[:nt], self.b_tok[:nt], self.Ab_tok[:nt], self.D_tok,
                                      self.Db_tok, self.lr)
 
-    def _het_rows(self, rows, ids, out, bias_tmp):
-        """out[:, :d] = (id row + bag mean) / 2, out[:, d] = (id bias + mean token bias) / 2 for the owned items
-        `ids` (global) whose id-shard rows are `rows`."""
-        be, d = self.be, self.d
-        bag = (self.bag_vals, self.bag_starts, self.bag_lens)
-        be.gather_rows(self.E_item, self.b_item, rows, out[:, :d], bias_tmp, scale=0.5)
-        be.gather_bags(self.E_tok, self.b_tok, *bag, ids, out[:, :d], bias_tmp, scale=0.5, accumulate=True)
-        be.copy_strided(bias_tmp, out[:, d])
-
-    def step(self, users, items=None):
-        if self.world > 1 and self.cap <= 0:
-            raise RuntimeError("ShardedHMFRepTokens.step before set_pool()")
-        if self.use_graphs:            # HIP backend: the hipGraph-segment step with the hooks above
-            return ShardedHMF.step(self, users, items)
-        route = users if isinstance(users, dict) else self.prepare_route(users, items)
-        be, W = self.be, self.world
-        B, B_loc, S, Sg, d = self.B, self.B_loc, self.S, self.Sg, self.d
-        grp = self.group
-        send, recv, R = route['send'], route['recv'], route['R']
-        arena, arena_b = self.arena, self.arena_b
-        urows, recv_rows, recv_ids = route['urows'], route['recv_rows'], route['recv_ids']
-        self.urows = urows
-        cap = self.cap
-        # ---- forward: the owner forms the whole HET embedding of its pool block and of the requested targets ----
-        be.gather_rows(self.E_user, None, urows, self.U_loc, None)
-        if W == 1:
-            self._het_rows(self.pool_rows, self.block_ids, self.I_all, self.b_all)
-        else:
-            self._het_rows(self.pool_rows[:cap], self.block_ids[:cap], self.I_pack[:cap], self.b_g[:cap])
-            dist.all_gather_into_tensor(self.I_gath[:W * cap], self.I_pack[:cap], group=grp)
-            be.gather_rows(self.I_gath, None, self.gidx, self.I_all, None)    # blocks -> pool (slot) order
-            be.copy_strided(self.I_all[:, d], self.b_all)
-        T_send = self.T_send[:R]
-        if R > 0:
-            self._het_rows(recv_rows, recv_ids, T_send, self.tb_send[:R])
-        w_rows = _all_to_all(self.T_pack, T_send, send, recv, group=grp, async_op=True)
-        be.gemm(self.U_loc, self.I_all[:, :d], self.logits, transB=True, col_bias=self.b_all)
-        w_rows.wait()
-        dU = arena[:B_loc, :d]
-        be.loss_mw_fused_pos(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], self.urows,
-                             self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
-                             self.t_loc, self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
-        # ---- backward ----
-        w_dt = _all_to_all(arena[B_loc + Sg:B_loc + Sg + R], self.dT_pack, recv, send, group=grp, async_op=True)
-        be.gemm(self.dlogits, self.I_all[:, :d], dU, beta=1.0)
-        be.gemm(self.dlogits, self.U_loc, self.dI_all[:S, :d], transA=True, a_rowsum=self.gb_all)
-        be.copy_strided(self.gb_all, self.dI_all[:S, d])
-        if W == 1:
-            be.copy_2d(self.dI_all[:S], arena[B_loc:B_loc + S])
-        else:
-            dist.all_reduce(self.dI_all[:S], op=dist.ReduceOp.SUM, group=grp)
-            be.gather_rows(self.dI_all, None, self.my_slots[:cap], arena[B_loc:B_loc + cap], None)
-        w_dt.wait()
-        be.copy_strided(arena[B_loc:B_loc + Sg + R, d], arena_b[B_loc:B_loc + Sg + R])
-        # token table: this rank's merged token gradients -> D, summed over the ranks under the id shard's pass
-        nt = self.n_tokens
-        bag = (self.bag_vals, self.bag_starts, self.bag_lens)
-        bsites = [(self.block_ids[:cap], B_loc, 0.5)]       # (D_tok / Db_tok are all zero: _het_tok_apply leaves them so)
-        if R > 0:
-            bsites.append((recv_ids[:R], B_loc + Sg, 0.5))
-        be.bags_grad_dense(self.D_tok, self.Db_tok, *bag, bsites, arena[:, :d], arena_b)
-        w_tok = w_tokb = None
-        if W > 1:
-            w_tok = dist.all_reduce(self.D_tok, op=dist.ReduceOp.SUM, group=grp, async_op=True)
-            w_tokb = dist.all_reduce(self.Db_tok, op=dist.ReduceOp.SUM, group=grp, async_op=True)
-        # id shard + user shard: one fused one-hot pass (the item rows' share of the embedding is 1/2)
-        sites = [(0, self.urows, 0, 1.0), (1, self.pool_rows[:cap], B_loc, 0.5)]
-        if R > 0:
-            sites.append((1, recv_rows, B_loc + Sg, 0.5))
-        ni = self.ni_loc
-        be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
-                                 (self.E_item[:ni], self.A_item[:ni], self.b_item[:ni], self.Ab_item[:ni])],
-                                sites, arena[:, :d], arena_b, self.lr)
-        if w_tok is not None:
-            w_tok.wait()
-            w_tokb.wait()
-        self._het_tok_apply()
-        self.steps += 1
-
     def recommend(self, users, k, exclude_seen=False, return_values=False):
         """Not yet: the item latents are bag means, and recommend would first need them materialised per shard."""
         raise NotImplementedError("%s.recommend: item latents are bag means (ShardedHMF has recommend)"
@@ -1838,9 +1628,6 @@ class ShardedHMFRepTokens(ShardedHMF):
         return out
 
 
-# --------------------------------------------------------------------------
-# bench entry for N > 1 (driver: python -m torch.distributed.run ... bench.py --gpus N)
-# --------------------------------------------------------------------------
 # ---------------------------------------------------------------------------------------------
 # Data-parallel sequence model (the LSTM recommender has no table big enough to shard at
 # C4's size -- 1 M x 64 x 4 B = 256 MB -- so the replicas split the BATCH).
@@ -2428,6 +2215,10 @@ class SeqHybridParallel(SeqDataParallel):
                 out[name] = a.reshape(-1, 1) if a.ndim == 1 else a
         return out
 
+
+# --------------------------------------------------------------------------
+# bench entry for N > 1 (driver: python -m torch.distributed.run ... bench.py --gpus N)
+# --------------------------------------------------------------------------
 def _hash_u32(x, salt):
     x = (x.to(torch.int64) * 2654435761 + salt) & 0xFFFFFFFF
     x = ((x ^ (x >> 15)) * 2246822519) & 0xFFFFFFFF
@@ -2756,7 +2547,8 @@ def bench_run(args, world, rank, local_rank, init_pg=True):
                        "routing_host_ms_per_batch": float(np.median(route_ms)) if route_ms else None,
                        "pool_redraws_timed": redraws[0],
                        "hipgraph_segments": (sorted(model._graphs) if model.use_graphs else None),
-                       "step_form": ("hipGraph segments between the collectives" if model.use_graphs else "eager launches"),
+                       "step_form": ("hipGraph segments between the collectives" if model.use_graphs else
+                                     "the same segments, launched kernel by kernel"),
                        "hipgraph_captures": model.n_captures, "hipgraph_replays": model.n_replays,
                        "sampled_negative_logits_per_s": B * S * args.steps / wall,
                        "final_loss": loss, "setup_s": setup_s},

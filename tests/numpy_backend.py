@@ -29,8 +29,34 @@ class NumpyBackend(object):
             o[r] = (o[r] + row) if accumulate else row
             ob[r] = (ob[r] + bb) if accumulate else bb
 
-    def bags_adagrad(self, E, acc, bias, bias_acc, vals, starts, lens, sites, G, Gb, lr):
-        """sites: [(entity ids, row_base, coef)]; tokens >= E.shape[0] are dropped."""
+    def gather_rows_multi(self, sites):
+        """sites: [(E, bias | None | int column of E, rows, out, bias_out | None | 'packed' (column d of out))]."""
+        for E, bias, rows, out, bias_out in sites:
+            w = E.shape[1]
+            if isinstance(bias, int):
+                bias = E[:, bias]
+            if isinstance(bias_out, str):
+                bias_out = out[:, w]
+            self.gather_rows(E, bias, rows, out[:, :w], bias_out)
+
+    def lookup_het_multi(self, sites):
+        """sites: [(E_id, bias_id, cat_map, E_tok, bias_tok, vals, starts, lens, ids, out, scale, bias_out)]: id row
+        (through cat_map where given) plus, where E_tok is not None, the bag mean -- both times scale."""
+        for E_id, bias_id, cat_map, E_tok, bias_tok, vals, starts, lens, ids, out, scale, bias_out in sites:
+            rows = ids if cat_map is None else cat_map[ids.long()]
+            self.gather_rows(E_id, bias_id, rows, out, bias_out, scale)
+            if E_tok is not None:
+                self.gather_bags(E_tok, bias_tok, vals, starts, lens, ids, out, bias_out, scale, accumulate=True)
+
+    def copy_words(self, feeds):
+        for src, dst in feeds:
+            dst.copy_(src)
+
+    def bags_adagrad(self, E, acc, bias, bias_acc, vals, starts, lens, sites, G, Gb, lr, phase=3):
+        """sites: [(entity ids, row_base, coef)]; tokens >= E.shape[0] are dropped.  phase 1 (the sorts of the
+        kernel: ids only) does nothing, 2 and 3 do the whole pass."""
+        if phase == 1:
+            return
         e, a, b, ba = _n(E), _n(acc), _n(bias), _n(bias_acc)
         v, st, ln = _n(vals), _n(starts), _n(lens)
         g_all, gb_all = _n(G).astype(np.float64), _n(Gb).astype(np.float64)
@@ -51,7 +77,9 @@ class NumpyBackend(object):
         ba[rows] = ba[rows] + gb[rows] ** 2
         b[rows] = b[rows] - lrv * gb[rows] / np.sqrt(ba[rows])
 
-    def bags_grad_dense(self, D, Db, vals, starts, lens, sites, G, Gb):
+    def bags_grad_dense(self, D, Db, vals, starts, lens, sites, G, Gb, phase=3):
+        if phase == 1:
+            return
         e, b = _n(D), _n(Db)
         v, st, ln = _n(vals), _n(starts), _n(lens)
         g_all, gb_all = _n(G).astype(np.float64), _n(Gb).astype(np.float64)
@@ -65,12 +93,6 @@ class NumpyBackend(object):
                         gb[t] += coef / float(ln[i]) * gb_all[base + j]
         e[...] = (e + g).astype(np.float32)
         b[...] = (b + gb).astype(np.float32)
-
-    def adagrad_dense(self, w, acc, g, lr):
-        ww, aa, gg = _n(w), _n(acc), _n(g).astype(np.float64)
-        a2 = aa.astype(np.float64) + gg * gg
-        ww[...] = (ww - float(_n(lr)[0]) * gg / np.sqrt(a2)).astype(np.float32)
-        aa[...] = a2.astype(np.float32)
 
     def adagrad_rows_nonzero(self, W, acc, bias, bias_acc, G, Gb, lr):
         g, gb = _n(G), _n(Gb)
@@ -209,25 +231,11 @@ class NumpyBackend(object):
     def sum_scaled(self, x, scale, out):
         _n(out)[...] = _n(x).astype(np.float64).sum() * scale
 
-    def sparse_adagrad(self, E, acc, bias, bias_acc, keys, G, Gb, lr):
-        k = _n(keys).astype(np.int64)
-        ok = k != KEY_NONE
-        e, a = _n(E), _n(acc)
-        g = np.zeros(e.shape, dtype=np.float64)
-        np.add.at(g, k[ok], _n(G)[ok].astype(np.float64))
-        rows = np.unique(k[ok])
-        lrv = float(_n(lr)[0])
-        a[rows] = a[rows] + g[rows] ** 2
-        e[rows] = e[rows] - lrv * g[rows] / np.sqrt(a[rows])
-        if bias is not None:
-            b, ba = _n(bias), _n(bias_acc)
-            gb = np.zeros(b.shape, dtype=np.float64)
-            np.add.at(gb, k[ok], _n(Gb)[ok].astype(np.float64))
-            ba[rows] = ba[rows] + gb[rows] ** 2
-            b[rows] = b[rows] - lrv * gb[rows] / np.sqrt(ba[rows])
-
-    def sparse_adagrad_multi(self, tables, sites, G, Gb, lr):
-        """tables: [(E, acc, bias|None, bias_acc|None)]; sites: [(table, local_rows, row_base[, coef])]."""
+    def sparse_adagrad_multi(self, tables, sites, G, Gb, lr, phase=3):
+        """tables: [(E, acc, bias|None, bias_acc|None)]; sites: [(table, local_rows, row_base[, coef])]; rows out of
+        the table's range (KEY_NONE, the padding row of a table passed without it) are dropped.  phase as above."""
+        if phase == 1:
+            return
         g_all, gb_all = _n(G).astype(np.float64), _n(Gb).astype(np.float64)
         lrv = float(_n(lr)[0])
         for t, (E, acc, bias, bacc) in enumerate(tables):

@@ -12,6 +12,17 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def _assert_padding_and_growth_seen(dist, world, padded, after_growth):
+    """The step body pads its index vector [user rows ; received target rows] to the receive capacity cap_r, which
+    grows with the largest R a rank has seen.  The steps just taken must have covered both, on some rank: a batch
+    with R < cap_r (the padded tail is live: gathered as zero rows, dropped by K7) and a step after a growth of
+    cap_r (new buffers).  padded / after_growth: this rank's observations."""
+    seen = [None] * world
+    dist.all_gather_object(seen, (bool(padded), bool(after_growth)))
+    assert any(p for p, _ in seen), "no rank saw a batch with R < cap_r"
+    assert any(g for _, g in seen), "no step followed a growth of cap_r"
+
+
 def _worker(rank, world, port, out_dir, exchange='rows'):
     for p in (ROOT, os.path.join(ROOT, "a-recsys_amd"), os.path.join(ROOT, "tests")):
         if p not in sys.path:
@@ -51,6 +62,7 @@ def _worker(rank, world, port, out_dir, exchange='rows'):
     pos = syn.positives_dict()
     ref.prepare_warp(pos, pos)
     rng = np.random.default_rng(5)          # identical stream on both ranks
+    padded = grew = after_growth = False     # ('rows': the padded index vector of the step body, see below)
     for step in range(5):
         pool = None
         if step % 2 == 0:
@@ -88,9 +100,15 @@ def _worker(rank, world, port, out_dir, exchange='rows'):
                 gi[g][:k_] = rng.integers(0, (n_items - (world - 1) + world - 1) // world - 1, size=k_) * world + (world - 1)
         l_ref = ref.step(np.concatenate(gu).tolist(), np.concatenate(gi).tolist(), pool, id2idx,
                          loss='mw')
+        cap_r0 = model.cap_r
         model.step(gu[rank].astype(np.int32), gi[rank].astype(np.int32))
         l_got = float(model.read_loss().item())
         assert abs(l_got - l_ref) <= 1e-5 * abs(l_ref), (step, l_got, l_ref)
+        padded |= int((np.concatenate(gi) % world == rank).sum()) < model.cap_r
+        after_growth |= grew
+        grew |= model.cap_r > cap_r0
+    if exchange == 'rows':
+        _assert_padding_and_growth_seen(dist, world, padded, after_growth)
     got = model.gather_global_tables()
     np.testing.assert_allclose(got['user'], ref.att_emb.params['userembed_cat_0'][2:], rtol=1e-4, atol=1e-6)
     np.testing.assert_allclose(got['item'], ref.att_emb.params['itemembed_cat_0'][2:], rtol=1e-4, atol=1e-6)
@@ -213,6 +231,7 @@ def _bags_worker(rank, world, port, out_dir, replicated=False):
     pos = syn.positives_dict()
     ref.prepare_warp(pos, pos)
     rng = np.random.default_rng(5)
+    padded = grew = after_growth = False
     for step in range(4):
         pool = None
         if step % 2 == 0:
@@ -234,9 +253,15 @@ def _bags_worker(rank, world, port, out_dir, replicated=False):
             for g in range(world):
                 gi[g] = (rng.integers(0, n_items // world, size=B_loc) * world).astype(gi[g].dtype)
         l_ref = ref.step(np.concatenate(gu).tolist(), np.concatenate(gi).tolist(), pool, id2idx, loss='mw')
+        cap_r0 = model.cap_r
         model.step(gu[rank].astype(np.int32), gi[rank].astype(np.int32))
         l_got = float(model.read_loss().item())
         assert abs(l_got - l_ref) <= 1e-5 * abs(l_ref), (step, l_got, l_ref)
+        padded |= int((np.concatenate(gi) % world == rank).sum()) < model.cap_r
+        after_growth |= grew
+        grew |= model.cap_r > cap_r0
+    if replicated:                                 # (the token-striped step has no variable-size exchange)
+        _assert_padding_and_growth_seen(dist, world, padded, after_growth)
     got = model.gather_global_tables()
     P = ref.att_emb.params
     for name, want in (('user', P['userembed_cat_0'][2:]), ('item', P['itemembed_cat_0'][2:]),

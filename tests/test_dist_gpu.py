@@ -13,8 +13,8 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("B,S", [(32, 64), (128, 128)])     # (the second shape is one the bf16-pipe scorer takes)
 @pytest.mark.parametrize("graphs", [True, False, 'logits'])
 def test_sharded_hip_backend_world1(dev, graphs, B, S):
-    """graphs=True: the step is ONE hipGraph (ShardedHMF._step_static: eager on step 0, captured on step
-    1, replayed from step 2 on -- through two pool redraws and fresh batches).  'logits': the step with the
+    """graphs=True: the step is ONE hipGraph (ShardedHMF._run_step: eager on step 0, captured on step
+    1, replayed from step 2 on -- through two pool redraws and fresh batches); False: the same body kernel by kernel.  'logits': the step with the
     all-to-all-of-logits exchange (_step_logits; at world 1 its transposes, block gathers and per-owner GEMMs)."""
     exchange = 'logits' if graphs == 'logits' else 'rows'
     graphs = graphs is True
@@ -65,11 +65,16 @@ def test_sharded_hip_backend_world1(dev, graphs, B, S):
 
 
 @pytest.mark.parametrize("replicated", [False, True])
-@pytest.mark.parametrize("n_users,n_items,V,d,B,S", [(300, 500, 120, 64, 32, 64), (3000, 4000, 900, 32, 2048, 256)])
-def test_token_sharded_bags_hip_backend_world1(dev, n_users, n_items, V, d, B, S, replicated):
+@pytest.mark.parametrize("n_users,n_items,V,d,B,S,graphs", [
+    pytest.param(300, 500, 120, 64, 32, 64, True, id="300-500-120-64-32-64"),
+    pytest.param(300, 500, 120, 64, 32, 64, False, id="300-500-120-64-32-64-graphs_off"),
+    pytest.param(3000, 4000, 900, 32, 2048, 256, True, id="3000-4000-900-32-2048-256")])
+def test_token_sharded_bags_hip_backend_world1(dev, n_users, n_items, V, d, B, S, graphs, replicated):
     """ShardedHMFBags (HET items: id table striped by item, token table striped by token) and ShardedHMFRepTokens
     (token table replicated, its merged gradient all-reduced: round 5) on the HIP backend with a 1-rank RCCL group
-    vs the oracle; the second shape is past the rank-sort limits (radix sort + window apply in both K7 passes)."""
+    vs the oracle; the second shape is past the rank-sort limits (radix sort + window apply in both K7 passes).
+    graphs=False (the small shape): the same step body launched kernel by kernel on the caller's stream -- the only
+    GPU coverage of that form of the two HET bodies."""
     import torch
     import torch.distributed as dist
     from arx.dist import ShardedHMFBags, ShardedHMFRepTokens
@@ -90,7 +95,8 @@ def test_token_sharded_bags_hip_backend_world1(dev, n_users, n_items, V, d, B, S
                   'token_bias': params['item_bias_mulhot_0']}
         bags = (np.asarray(ia.features_mulhot[0]), np.asarray(ia.mulhot_starts[0]), np.asarray(ia.mulhot_lengths[0]))
         cls = ShardedHMFRepTokens if replicated else ShardedHMFBags
-        model = cls(n_users, n_items, d, B, S, 0.5, 0, 1, dev, bags, n_tok, tables=tables)
+        model = cls(n_users, n_items, d, B, S, 0.5, 0, 1, dev, bags, n_tok, tables=tables, graphs=graphs)
+        assert model.use_graphs == graphs
         ptr = np.concatenate([syn.pos_ptr[:n_users + 1], [syn.pos_ptr[n_users]]]).astype(np.int32)
         model.set_positives(ptr, syn.pos_items)
         ref = rg.RefLatentProductModel(d, B, 0.5, syn.u_attr, syn.i_attr, syn.item_ind2logit_ind_dict(),
@@ -99,7 +105,7 @@ def test_token_sharded_bags_hip_backend_world1(dev, n_users, n_items, V, d, B, S
         pos = syn.positives_dict()
         ref.prepare_warp(pos, pos)
         rng = np.random.default_rng(3)
-        for step in range(5):              # eager, captured, replayed x 3 (round 6: both classes run hipGraph segments)
+        for step in range(5):              # graphs: eager, captured, replayed x 3
             pool = None
             if step in (0, 2):
                 pool = syn.sample_pool(S, rng)

@@ -132,7 +132,7 @@ def test_gather_onehot_multi(dev, d, sizes):
 def test_gather_onehot_multi_packed_sites(dev, d, sizes):
     """arx_gather_onehot_multi_ld: sites whose bias goes to column d of their packed out rows ('packed'),
     and a site that reorders PACKED rows and splits off their bias column (bias = column d of the table
-    itself) -- the sharded step's fused lookups (arx.dist.ShardedHMF._step_static)."""
+    itself) -- the sharded step's fused lookups (arx.dist.ShardedHMF._step_body)."""
     from arx import ops
     import torch
     rng = np.random.default_rng(d)

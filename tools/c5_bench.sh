@@ -1,5 +1,6 @@
 #!/bin/bash
-# c5w1 (one rank, graphs on / off) and the N=2 one-GPU gloo rig (path check, not a number)
+# c5w1 (one rank, graphs on / off) and the N=2 one-GPU gloo rig (path check, not a number).  "eager" is the same
+# step body launched kernel by kernel on the caller's stream (ARX_DIST_EAGER=1), not a second implementation
 cd "$(dirname "$0")/.."
 py='import json,sys
 for l in sys.stdin:

@@ -41,6 +41,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import ops as _ops
+
 
 class _Done(object):
     def wait(self):
@@ -712,14 +714,8 @@ class ShardedHMF(object):
         (graphs=False / ARX_DIST_EAGER=1, a backend without kernels, a CPU device) runs the same body eagerly on the
         caller's stream, K7's sort half in line.  A step that raises leaves no captured graph behind: the next one
         runs eagerly again."""
-        outer = torch.cuda.current_stream(self.device) if self.use_graphs else None
-        if outer is not None and outer != self._stream:    # (== : the caller already works on model.stream)
-            self._stream.wait_stream(outer)
-            with torch.cuda.stream(self._stream):
-                self._run_step_here(route)
-            outer.wait_stream(self._stream)
-            return
-        self._run_step_here(route)
+        with _ops.joined(self._stream if self.use_graphs else None):
+            self._run_step_here(route)
 
     def _run_step_here(self, route):
         try:
@@ -757,34 +753,17 @@ class ShardedHMF(object):
         """eager: run; capture: record the launches of `fn` into a hipGraph, keep it, launch it;
         replay: launch the kept graph.  feeds ([(src, dst)], the step's first segment): the copy of the batch's
         index vectors is the graph's first node, its source replaced before every replay
-        (ops.CapturedGraph.set_feeds)."""
+        (ops.CapturedGraph.replay)."""
         be = self.be
         if mode == 'eager':
             if feeds:
                 be.copy_words(feeds)
             fn()
         elif mode == 'capture':
-            g = be.ops.CapturedGraph()
-            g.begin()
-            try:
-                if feeds:
-                    be.copy_words(feeds)
-                fn()
-            except BaseException:
-                g.end()
-                raise
-            g.end(feeds=feeds)
-            self._graphs[name] = g
+            self._graphs[name] = g = be.ops.CapturedGraph.record(fn, feeds)
             g.launch()
         else:
-            g = self._graphs[name]
-            if feeds:
-                if g.feeds_match(feeds):
-                    g.set_feeds(feeds)
-                else:
-                    be.copy_words(feeds)
-                    g.set_feeds(None)
-            g.launch()
+            self._graphs[name].replay(feeds)
 
     def _k7_sorts(self, mode, k7, own_graph):
         """k7(1) -- K7's keys, sorts and run records, which need the ids only -- on the second stream, under the
@@ -1069,16 +1048,7 @@ class ShardedHMF(object):
             raise ValueError("recommend: users must be global ids in [0, %d) owned by rank %d" % (self.n_users, r))
         if exclude_seen and getattr(self, '_rec_ex', None) is None:
             raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
-        if self.use_graphs:
-            outer = torch.cuda.current_stream(self.device)
-            if outer != self._stream:
-                self._stream.wait_stream(outer)
-                with torch.cuda.stream(self._stream):
-                    vo, io = self._recommend(u, k, exclude_seen)
-                outer.wait_stream(self._stream)
-            else:
-                vo, io = self._recommend(u, k, exclude_seen)
-        else:
+        with _ops.joined(self._stream if self.use_graphs else None):
             vo, io = self._recommend(u, k, exclude_seen)
         n = len(u)
         ids = io[:n].clone()
@@ -1171,16 +1141,7 @@ class ShardedHMF(object):
         if loss != 'ce' and getattr(self, '_eval_pos', None) is None:
             raise ValueError("evaluate(loss=%r) needs prepare_eval_positives() first (an empty dict masks nothing)"
                              % loss)
-        if self.use_graphs:
-            outer = torch.cuda.current_stream(self.device)
-            if outer != self._stream:
-                self._stream.wait_stream(outer)
-                with torch.cuda.stream(self._stream):
-                    rows_f, rows_i, sc = self._evaluate(u, it, loss)
-                outer.wait_stream(self._stream)
-            else:
-                rows_f, rows_i, sc = self._evaluate(u, it, loss)
-        else:
+        with _ops.joined(self._stream if self.use_graphs else None):
             rows_f, rows_i, sc = self._evaluate(u, it, loss)
         n = len(u)
         if loss == 'warp_eval':

@@ -1379,9 +1379,7 @@ class Plan(object):
             return                            # (data-parallel: the apply sorts the GATHERED lookups)
         rt = self.rt
         if self._k7_stream is None:
-            # (ARX_K7_STREAM_PRIO=1, experiment: the sort branch captured from a high-priority stream)
-            self._k7_stream = torch.cuda.Stream(device=rt.device,
-                                                priority=-1 if os.environ.get('ARX_K7_STREAM_PRIO') else 0)
+            self._k7_stream = torch.cuda.Stream(device=rt.device)
         main = torch.cuda.current_stream()
         ev = torch.cuda.Event()
         ev.record(main)
@@ -1598,7 +1596,6 @@ class Plan(object):
         self._ring_graphs, self._ring_warm, self._ring_ready = {}, {}, False
 
     def _run_ring(self):
-        rt = self.rt
         par = self._ring_par
         self._ring = True
         try:
@@ -1609,17 +1606,7 @@ class Plan(object):
                 # not worth an opt-in mode that does not pay anyway.)
                 g = self._ring_graphs.get(par)
                 if g is None:
-                    g = ops.CapturedGraph()
-                    side = torch.cuda.Stream(device=rt.device)
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        g.begin()
-                        try:
-                            self._execute()
-                        finally:
-                            g.end()
-                    torch.cuda.current_stream().wait_stream(side)
-                    self._ring_graphs[par] = g
+                    g = self._ring_graphs[par] = ops.CapturedGraph.record(self._execute, fork=True)
                 g.launch()
             else:
                 self._execute()
@@ -1644,56 +1631,33 @@ class Plan(object):
         ring, self.ring_req = self.ring_req, False
         if ring and self._ring_ready and self.ring_capable():
             self._run_ring()
-            if self.train:
-                for n in self.fetch:
-                    if isinstance(n, MeanLoss) and n.lazy and not n.in_scorer():
-                        n._stale = True
+            self._mark_stale()
             return
         self._ring_ready = False
         if rt.use_graph and self.warm >= 1:
             # the step's placeholder feeds travel as the graph's first node(s): their sources are swapped in before
-            # the replay (CapturedGraph.set_feeds) -- one submission per step instead of an eager copy + the graph
+            # the replay (CapturedGraph.replay) -- one submission per step instead of an eager copy + the graph
             pf = rt.take_feeds() if in_graph else []
             if self.graph is None:
-                g = ops.CapturedGraph()
-                side = torch.cuda.Stream(device=rt.device)
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    g.begin()
-                    try:
-                        if pf:
-                            ops.copy_words(pf)
-                        self._execute()
-                    except BaseException:
-                        # (the capture may already be invalidated: ending it raises again -- the ORIGINAL error is the
-                        # one that has to surface; advisor, round 4)
-                        try:
-                            g.end()
-                        except BaseException:
-                            pass
-                        if pf:
-                            rt.pending_feeds = list(pf) + list(getattr(rt, 'pending_feeds', []))
-                        raise
-                    try:
-                        g.end(feeds=pf)
-                    except BaseException:
-                        # feed nodes not found as captured (node count mismatch): the feeds taken out of the queue
-                        # go back in front of it, so that an eager retry of the step still feeds its placeholders
-                        if pf:
-                            rt.pending_feeds = list(pf) + list(getattr(rt, 'pending_feeds', []))
-                        raise
-                torch.cuda.current_stream().wait_stream(side)
-                self.graph = g
-            elif pf and self.graph.feeds_match(pf):
-                self.graph.set_feeds(pf)
+                try:
+                    self.graph = ops.CapturedGraph.record(self._execute, pf, fork=True)
+                except BaseException:
+                    # the body raised, or the feed nodes were not found as captured (node count mismatch): the
+                    # feeds taken out of the queue go back in front of it, so that an eager retry of the step still
+                    # feeds its placeholders
+                    if pf:
+                        rt.pending_feeds = list(pf) + list(getattr(rt, 'pending_feeds', []))
+                    raise
+                self.graph.launch()
             else:
-                if pf:
-                    ops.copy_words(pf)            # other placeholders than the captured ones: fed eagerly
-                self.graph.set_feeds(None)
-            self.graph.launch()
+                self.graph.replay(pf)
         else:
             self._execute()
             self.warm += 1
+        self._mark_stale()
+
+    def _mark_stale(self):
+        """After a train step: the mean of a lazy loss outside the scorer is reduced when it is next read."""
         if self.train:
             for n in self.fetch:
                 if isinstance(n, MeanLoss) and n.lazy and not n.in_scorer():

@@ -7,6 +7,7 @@ torch.cuda events / torch.distributed (RCCL) order correctly against them.
 """
 from __future__ import annotations
 
+import contextlib
 import gc
 import math
 
@@ -1186,9 +1187,25 @@ def seq_weights(w, L, B, out):
     call("arx_seq_weights", _p(w), int(L), int(B), _p(out), _stream())
 
 
+@contextlib.contextmanager
+def joined(stream):
+    """Run the block on `stream`, joined with the current stream on both sides: `stream` waits for the work queued
+    so far, the current stream waits for the block's.  None, or the stream that is current already: nothing to join.
+    (A block that raises is not waited for.)"""
+    outer = torch.cuda.current_stream(stream.device) if stream is not None else None
+    if outer is None or outer == stream:
+        yield
+        return
+    stream.wait_stream(outer)
+    with torch.cuda.stream(stream):
+        yield
+    outer.wait_stream(stream)
+
+
 class CapturedGraph(object):
     """A hipGraph of one step (arx_capture_* in include/arx.h).  end(feeds=...): the placeholder feeds issued inside
-    the capture (copy_words) stay addressable -- set_feeds() swaps their sources before a replay."""
+    the capture (copy_words) stay addressable -- set_feeds() swaps their sources before a replay.  record() and
+    replay() are the one place a step graph is recorded and re-fed; begin / end / set_feeds are their parts."""
 
     def __init__(self):
         import ctypes as C
@@ -1197,6 +1214,40 @@ class CapturedGraph(object):
         self.feed_groups = None      # per captured copy node: the destination pointers of its (<= 8) feeds, in order
         self._node_of = []           # group index -> node index
         self._fed = False            # the nodes hold live sources (else: they copy nothing)
+
+    @classmethod
+    def record(cls, fn, feeds=None, fork=False):
+        """Capture the launches of fn() -- behind the copy of `feeds` ([(src, dst)]: the graph's first node(s), see
+        replay) -- and return the instantiated graph; it has not run.  fork: on a fresh stream forked from and joined
+        back to the current one (the legacy default stream cannot be captured); else on the current stream."""
+        g = cls()
+        with joined(torch.cuda.Stream() if fork else None):
+            g.begin()
+            try:
+                if feeds:
+                    copy_words(feeds)
+                fn()
+            except BaseException:
+                # (the capture may already be invalidated: ending it raises again -- the ORIGINAL error is the
+                # one that has to surface; advisor, round 4)
+                try:
+                    g.end()
+                except BaseException:
+                    pass
+                raise
+            g.end(feeds=feeds)
+        return g
+
+    def replay(self, feeds=None):
+        """Launch with this step's feeds: swapped into the captured feed nodes where they address the captured
+        destinations, else copied eagerly in front (the nodes then copy nothing).  None / []: nothing is fed."""
+        if feeds and self.feeds_match(feeds):
+            self.set_feeds(feeds)
+        else:
+            if feeds:
+                copy_words(feeds)            # other placeholders than the captured ones: fed eagerly
+            self.set_feeds(None)
+        self.launch()
 
     def begin(self):
         # no cyclic garbage collection between begin() and end(): a collection there runs the finalizers of

@@ -534,67 +534,6 @@ int arx_capture_begin(void* stream) {
   return ARX_OK;
 }
 
-// ARX_GRAPH_PRIO=1 (experiment, round 6): the kernel nodes of the step's ids-only sort branch (names matching
-// ARX_GRAPH_PRIO_MATCH, default the radix / extraction / expansion kernels) get the device's greatest stream priority
-// as their hipKernelNodeAttributePriority before the graph is instantiated -- the branch is C3's critical path (190 us
-// under contention with the scorer against 109 us alone) and its kernels wait for wave slots.
-static void prio_nodes(hipGraph_t g, hipStream_t s) {
-  static const char* on = getenv("ARX_GRAPH_PRIO");
-  if (!on || !*on || *on == '0') return;
-  const char* match = getenv("ARX_GRAPH_PRIO_MATCH");
-  if (!match || !*match) match = "k_rs_,k_runs_extract,k_bag_expand,k_head_len,k_site_keys";
-  int least = 0, greatest = 0;
-  if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) return;
-  size_t nn = 0;
-  if (hipGraphGetNodes(g, nullptr, &nn) != hipSuccess || nn == 0) return;
-  hipGraphNode_t* all = new hipGraphNode_t[nn];
-  int hit = 0;
-  if (hipGraphGetNodes(g, all, &nn) == hipSuccess) {
-    for (size_t i = 0; i < nn; ++i) {
-      hipGraphNodeType ty;
-      if (hipGraphNodeGetType(all[i], &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) continue;
-      hipKernelNodeParams kp;
-      if (hipGraphKernelNodeGetParams(all[i], &kp) != hipSuccess || !kp.func) continue;
-      const char* name = hipKernelNameRefByPtr(kp.func, s);
-      if (!name) continue;
-      bool m = false;
-      for (const char* p = match; *p && !m;) {
-        const char* q = strchr(p, ',');
-        const size_t len = q ? (size_t)(q - p) : strlen(p);
-        if (len > 0 && len < 128) {
-          char tok[128];
-          memcpy(tok, p, len);
-          tok[len] = 0;
-          m = strstr(name, tok) != nullptr;
-        }
-        p = q ? q + 1 : p + len;
-      }
-      if (!m) continue;
-      hipKernelNodeAttrValue v = {};
-      v.priority = greatest;
-      if (hipGraphKernelNodeSetAttribute(all[i], hipKernelNodeAttributePriority, &v) == hipSuccess) ++hit;
-    }
-  }
-  delete[] all;
-  if (getenv("ARX_GRAPH_PRIO_VERBOSE")) fprintf(stderr, "arx: %d of %zu graph nodes at priority %d\n", hit, nn, greatest);
-}
-
-int arx_capture_end(void* stream, void** graph_exec_out) {
-  ARX_CHECK_ARG(graph_exec_out, "arx_capture_end: null out pointer");
-  hipGraph_t g = nullptr;
-  ARX_CHECK_HIP(hipStreamEndCapture(as_stream(stream), &g));
-  prio_nodes(g, as_stream(stream));
-  hipGraphExec_t e = nullptr;
-  hipError_t err = hipGraphInstantiate(&e, g, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(g);
-  if (err != hipSuccess) {
-    set_error("hipGraphInstantiate failed: %s", hipGetErrorString(err));
-    return ARX_EHIP;
-  }
-  *graph_exec_out = (void*)e;
-  return ARX_OK;
-}
-
 // ---- placeholder feeds as nodes of the step graph -------------------------------------------------------------
 // The feed of a step (arx_copy_words: the batch's id / weight arrays into the tensors the captured kernels read)
 // was an eager launch in front of every graph launch: two submissions per step, and the graph's first kernel
@@ -606,40 +545,57 @@ struct FeedNodes {
   hipGraphNode_t* node;      // [n]
 };
 
-int arx_capture_end_feeds(void* stream, void** graph_exec_out, void** feeds_out, int* n_feed_nodes) {
-  ARX_CHECK_ARG(graph_exec_out && feeds_out && n_feed_nodes, "arx_capture_end_feeds: null out pointer");
-  hipGraph_t g = nullptr;
-  ARX_CHECK_HIP(hipStreamEndCapture(as_stream(stream), &g));
-  FeedNodes* fn = new FeedNodes();
-  fn->g = g;
-  fn->n = 0;
-  fn->node = nullptr;
+// the k_copy_words kernel nodes of g, in hipGraphGetNodes order
+static hipError_t find_feed_nodes(hipGraph_t g, FeedNodes* fn) {
   size_t nn = 0;
   hipError_t err = hipGraphGetNodes(g, nullptr, &nn);
-  if (err == hipSuccess && nn > 0) {
-    hipGraphNode_t* all = new hipGraphNode_t[nn];
-    fn->node = new hipGraphNode_t[nn];
-    err = hipGraphGetNodes(g, all, &nn);
-    for (size_t i = 0; err == hipSuccess && i < nn; ++i) {
-      hipGraphNodeType ty;
-      if (hipGraphNodeGetType(all[i], &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) continue;
-      hipKernelNodeParams kp;
-      if (hipGraphKernelNodeGetParams(all[i], &kp) != hipSuccess) continue;
-      if (kp.func == reinterpret_cast<void*>(k_copy_words)) fn->node[fn->n++] = all[i];
-    }
-    delete[] all;
+  if (err != hipSuccess || nn == 0) return err;
+  hipGraphNode_t* all = new hipGraphNode_t[nn];
+  fn->node = new hipGraphNode_t[nn];
+  err = hipGraphGetNodes(g, all, &nn);
+  for (size_t i = 0; err == hipSuccess && i < nn; ++i) {
+    hipGraphNodeType ty;
+    if (hipGraphNodeGetType(all[i], &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) continue;
+    hipKernelNodeParams kp;
+    if (hipGraphKernelNodeGetParams(all[i], &kp) != hipSuccess) continue;
+    if (kp.func == reinterpret_cast<void*>(k_copy_words)) fn->node[fn->n++] = all[i];
   }
-  prio_nodes(g, as_stream(stream));
+  delete[] all;
+  return err;
+}
+
+// End the capture on `stream` and instantiate what it recorded.  The hipGraph_t is destroyed on failure; on success
+// it is destroyed too, unless feed nodes were asked for (fn): they are handles into it, so fn keeps it.
+static int end_capture(void* stream, const char* who, void** graph_exec_out, FeedNodes* fn) {
+  hipGraph_t g = nullptr;
+  ARX_CHECK_HIP(hipStreamEndCapture(as_stream(stream), &g));
+  hipError_t err = fn ? find_feed_nodes(g, fn) : hipSuccess;
   hipGraphExec_t e = nullptr;
   if (err == hipSuccess) err = hipGraphInstantiate(&e, g, nullptr, nullptr, 0);
+  if (err != hipSuccess || !fn) (void)hipGraphDestroy(g);
   if (err != hipSuccess) {
-    (void)hipGraphDestroy(g);
-    delete[] fn->node;
-    delete fn;
-    set_error("arx_capture_end_feeds: %s", hipGetErrorString(err));
+    set_error("%s: %s", who, hipGetErrorString(err));
     return ARX_EHIP;
   }
+  if (fn) fn->g = g;
   *graph_exec_out = (void*)e;
+  return ARX_OK;
+}
+
+int arx_capture_end(void* stream, void** graph_exec_out) {
+  ARX_CHECK_ARG(graph_exec_out, "arx_capture_end: null out pointer");
+  return end_capture(stream, "arx_capture_end", graph_exec_out, nullptr);
+}
+
+int arx_capture_end_feeds(void* stream, void** graph_exec_out, void** feeds_out, int* n_feed_nodes) {
+  ARX_CHECK_ARG(graph_exec_out && feeds_out && n_feed_nodes, "arx_capture_end_feeds: null out pointer");
+  FeedNodes* fn = new FeedNodes();     // (value-initialised: no graph, no nodes)
+  const int rc = end_capture(stream, "arx_capture_end_feeds", graph_exec_out, fn);
+  if (rc != ARX_OK) {
+    delete[] fn->node;
+    delete fn;
+    return rc;
+  }
   *feeds_out = (void*)fn;
   *n_feed_nodes = fn->n;
   return ARX_OK;

@@ -247,6 +247,13 @@ class HipBackend(object):
     def copy_i32(self, src, dst):
         dst.copy_(src, non_blocking=True)
 
+    def het_rows_range(self, E_id, bias_id, E_tok, bias_tok, vals, starts, lens, n_items, world, rank, c0, c1, out,
+                       bias_out=None, all_owners=False, scale=0.5, block_rows=0):
+        """HET rows of the shard columns [c0, c1) -- of this rank, or of every owner in owner-major blocks -- with no
+        id array (arx_het_rows_range); bias_out None: column d of the (packed) out rows."""
+        self.ops.het_rows_range(E_id, bias_id, E_tok, bias_tok, vals, starts, lens, n_items, world, rank, c0, c1, out,
+                                bias_out=bias_out, all_owners=all_owners, scale=scale, block_rows=block_rows)
+
     def shard_topk(self, U, E, bias, k, ex, values, indices):
         """Recommend's local stage: values / indices [B, k] = every row's k best of U . E^T + bias over the shard's
         rows, by (value desc, local column asc); ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols of local
@@ -1416,14 +1423,18 @@ class ShardedHMFBags(ShardedHMF):
 
         return key, body
 
+    def item_view(self, chunk_cols=16384):
+        """A serving view of this model (ShardedHetView): recommend / evaluate over its materialised item latents."""
+        return ShardedHetView(self, chunk_cols=chunk_cols)
+
     def recommend(self, users, k, exclude_seen=False, return_values=False):
-        """Not yet: the item latents are bag means, and recommend would first need them materialised per shard."""
-        raise NotImplementedError("%s.recommend: item latents are bag means (ShardedHMF has recommend)"
+        """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
+        raise NotImplementedError("%s.recommend: item latents are bag means -- use item_view().recommend"
                                   % type(self).__name__)
 
     def evaluate(self, users, items, loss='warp', return_rows=False):
-        """Not yet: the item latents are bag means, and evaluate would first need them materialised per shard."""
-        raise NotImplementedError("%s.evaluate: item latents are bag means (ShardedHMF has evaluate)"
+        """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
+        raise NotImplementedError("%s.evaluate: item latents are bag means -- use item_view().evaluate"
                                   % type(self).__name__)
 
     def gather_global_tables(self):
@@ -1571,14 +1582,18 @@ class ShardedHMFRepTokens(ShardedHMF):
         self.be.adagrad_rows_nonzero(self.E_tok[:nt], self.A_tok[:nt], self.b_tok[:nt], self.Ab_tok[:nt], self.D_tok,
                                      self.Db_tok, self.lr)
 
+    def item_view(self, chunk_cols=16384):
+        """A serving view of this model (ShardedHetView): recommend / evaluate over its materialised item latents."""
+        return ShardedHetView(self, chunk_cols=chunk_cols)
+
     def recommend(self, users, k, exclude_seen=False, return_values=False):
-        """Not yet: the item latents are bag means, and recommend would first need them materialised per shard."""
-        raise NotImplementedError("%s.recommend: item latents are bag means (ShardedHMF has recommend)"
+        """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
+        raise NotImplementedError("%s.recommend: item latents are bag means -- use item_view().recommend"
                                   % type(self).__name__)
 
     def evaluate(self, users, items, loss='warp', return_rows=False):
-        """Not yet: the item latents are bag means, and evaluate would first need them materialised per shard."""
-        raise NotImplementedError("%s.evaluate: item latents are bag means (ShardedHMF has evaluate)"
+        """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
+        raise NotImplementedError("%s.evaluate: item latents are bag means -- use item_view().evaluate"
                                   % type(self).__name__)
 
     def gather_global_tables(self):
@@ -1587,6 +1602,89 @@ class ShardedHMFRepTokens(ShardedHMF):
         out['token'] = self.E_tok[:nt].cpu().numpy()
         out['token_bias'] = self.b_tok[:nt].cpu().numpy()
         return out
+
+
+class ShardedHetView(ShardedHMF):
+    """Serving view of a sharded HET model (ShardedHMFBags / ShardedHMFRepTokens; model.item_view()): a SNAPSHOT of
+    the item latents 1/2 (id row + bag mean) and biases, materialised per shard -- E_item [ni_loc + 1, d] (a zero row
+    behind it) and b_item [ni_loc + 1] -- over which ShardedHMF's full-vocabulary recommend and evaluate run as they
+    are (prepare_recommend_exclusions, prepare_eval_positives, recommend, evaluate: inherited; collectives, the same
+    calling rules).  The snapshot costs the size of the id shard once more (ni_loc x (d + 1) x 4 B per rank); the
+    user table is the model's own (by reference).  There are no step buffers: a view does not train.
+
+    refresh() materialises the latents, a collective on the model's stream:
+      ShardedHMFRepTokens   every token is local: ONE arx_het_rows_range launch over this rank's columns, straight
+                            into E_item / b_item; no communication.
+      ShardedHMFBags        an item's tokens live on every rank: per chunk of chunk_cols columns, one launch forms
+                            this rank's PARTIAL of every owner's rows (half its own id row where it owns the item,
+                            half the bag mean over its own tokens: exactly the partials of the step) in owner-major
+                            blocks [W][chunk][d + 4], a reduce-scatter sums them into the owner's [chunk, d + 4], two
+                            copies put them in place.  n_items x (d + 4) x 4 B cross the reduce-scatter per refresh
+                            and rank.  (World 1: one launch, no collective.)
+    The view remembers model.steps; recommend / evaluate refresh first when the model has stepped since (step() is a
+    collective, so every rank decides alike).  Tables written any other way (a checkpoint load, a test) need an
+    explicit refresh().  The view's buffers are its own: captured step graphs are not disturbed."""
+
+    _TAKEN = ('world', 'rank', 'B_loc', 'B', 'd', 'n_users', 'n_items', 'ni_loc', 'zero_row', 'device', 'group', 'be',
+              'use_graphs', '_stream')
+
+    def __init__(self, model, chunk_cols=16384):
+        if not isinstance(model, (ShardedHMFBags, ShardedHMFRepTokens)):
+            raise TypeError("ShardedHetView: a ShardedHMFBags or ShardedHMFRepTokens model (ShardedHMF serves itself)")
+        if int(chunk_cols) < 1:
+            raise ValueError("chunk_cols must be positive")
+        self.model = model
+        for a in self._TAKEN:
+            setattr(self, a, getattr(model, a))
+        self.E_user = model.E_user
+        dev, f32 = self.device, torch.float32
+        self.E_item = torch.zeros((self.ni_loc + 1, self.d), dtype=f32, device=dev)
+        self.b_item = torch.zeros((self.ni_loc + 1,), dtype=f32, device=dev)
+        self.steps = None                                   # model.steps at the last refresh
+        self.n_refresh = 0
+        # the token-striped model at N > 1: every rank walks the columns of the LARGEST shard in equal chunks
+        self._striped = isinstance(model, ShardedHMFBags) and self.world > 1
+        if self._striped:
+            self._cols = (self.n_items + self.world - 1) // self.world
+            self.chunk = max(1, min(int(chunk_cols), self._cols))
+            self._part = torch.zeros((self.world * self.chunk, model.dp), dtype=f32, device=dev)
+            self._sum = torch.zeros((self.chunk, model.dp), dtype=f32, device=dev)
+
+    def refresh(self):
+        """Materialise the item latents from the model's tables as they are now (a collective; see the class)."""
+        with _ops.joined(self._stream if self.use_graphs else None):
+            self._refresh()
+
+    def _refresh(self):
+        m, be, W, d = self.model, self.be, self.world, self.d
+        src = (m.E_item, m.b_item, m.E_tok, m.b_tok, m.bag_vals, m.bag_starts, m.bag_lens, self.n_items, W, self.rank)
+        if not self._striped:
+            be.het_rows_range(*src, 0, self.ni_loc, self.E_item, bias_out=self.b_item, scale=0.5)
+        else:
+            for c0 in range(0, self._cols, self.chunk):
+                c1 = min(c0 + self.chunk, self._cols)
+                n = c1 - c0                                 # (c1 <= ni_loc + 1: a shorter shard's last column is its zero row)
+                be.het_rows_range(*src, c0, c1, self._part, all_owners=True, scale=0.5, block_rows=self.chunk)
+                _reduce_scatter(self._sum, self._part, group=self.group)
+                be.copy_2d(self._sum[:n, :d], self.E_item[c0:c0 + n])
+                be.copy_strided(self._sum[:n, d], self.b_item[c0:c0 + n])
+        self.steps = m.steps
+        self.n_refresh += 1
+
+    def _recommend(self, u, k, exclude_seen):
+        if self.steps != self.model.steps:
+            self._refresh()
+        return super()._recommend(u, k, exclude_seen)
+
+    def _evaluate(self, u, it, loss):
+        if self.steps != self.model.steps:
+            self._refresh()
+        return super()._evaluate(u, it, loss)
+
+    def _no_training(self, *a, **k):
+        raise TypeError("ShardedHetView: a view does not train (step, pools and positives belong to the model)")
+
+    step = set_pool = prepare_route = set_positives = _no_training
 
 
 # ---------------------------------------------------------------------------------------------

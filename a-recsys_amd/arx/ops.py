@@ -188,6 +188,40 @@ def gather_id_plus_bag(E_id, bias_id, cat_map, E_tok, bias_tok, vals, starts, le
          int(bool(accumulate)), _p(out), _ld(out), _p(bias_out), _stream())
 
 
+def het_rows_range(E_id, bias_id, E_tok, bias_tok, vals, starts, lens, n_items, world, rank, c0, c1, out,
+                   bias_out=None, all_owners=False, scale=0.5, block_rows=0):
+    """HET rows (id row + bag mean, times scale) of the shard columns [c0, c1) of owner `rank` -- or, all_owners, of
+    every owner, owner s's rows at out[s * block_rows ...) -- with no id array (arx_het_rows_range).  out: 2-D,
+    at least d wide; bias_out: a 1-D view of any stride, or None: column d of the out rows (packed d+4 rows)."""
+    d = int(E_id.shape[1])
+    _chk(E_id, torch.float32, 'E_id'); _chk(E_tok, torch.float32, 'E_tok'); _chk(out, torch.float32, 'out')
+    for t, n in ((vals, 'vals'), (starts, 'starts'), (lens, 'lens')):
+        _chk(t, torch.int32, n)
+    ldo = _ld(out)
+    own_rows = (int(n_items) - int(rank) + int(world) - 1) // max(int(world), 1)
+    if int(E_id.shape[0]) < own_rows or int(bias_id.shape[0]) < own_rows:
+        raise ValueError("het_rows_range: the id shard holds %d rows, rank %d of %d owns %d"
+                         % (int(E_id.shape[0]), int(rank), int(world), own_rows))
+    if int(starts.shape[0]) < int(n_items) or int(lens.shape[0]) < int(n_items):
+        raise ValueError("het_rows_range: the bag index is shorter than n_items")
+    nown = int(world) if all_owners else 1
+    rows = (nown - 1) * int(block_rows) + int(c1) - int(c0) if nown > 1 else int(c1) - int(c0)
+    if int(out.shape[0]) < rows:
+        raise ValueError("het_rows_range: out holds %d rows, the range writes %d" % (int(out.shape[0]), rows))
+    if bias_out is None:
+        if int(out.shape[1]) <= d:
+            raise ValueError("het_rows_range: packed rows need a column d in out")
+        pb, ldb = _p(out) + 4 * d, ldo
+    else:
+        if int(bias_out.shape[0]) < rows:
+            raise ValueError("het_rows_range: bias_out holds %d cells, the range writes %d"
+                             % (int(bias_out.shape[0]), rows))
+        pb, ldb = _p(bias_out), int(bias_out.stride(0))
+    call("arx_het_rows_range", _p(E_id), _p(bias_id), _p(E_tok), _p(bias_tok), _p(vals), _p(starts), _p(lens),
+         int(n_items), int(world), int(rank), int(c0), int(c1), int(bool(all_owners)), d, float(scale), _p(out), ldo,
+         pb, ldb, int(block_rows), _stream())
+
+
 class GatherSet(object):
     """Descriptor arrays of arx_gather_onehot_multi, built once per plan.
     sites: [(E, bias|None, cat_map|None, ids, out, scale, bias_out|None)], equal width d.

@@ -563,6 +563,144 @@ __global__ __launch_bounds__(256) void k_lookup_multi(LookupSites ls, int d) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// HET rows of a RANGE of shard columns (arx_het_rows_range): the serving view of the sharded HET models
+// materialises its item latents with it.  The entities are consecutive -- owner s, local column c is item
+// c * world + s -- so there is no id array and no id -> row map: a wave takes `rpw` consecutive columns of one
+// owner, lane l loads starts / lens of column l of that block (ONE coalesced load per array and block, issued one
+// block ahead), and the sub-groups pick their bag up by a cross-lane read.  Nothing of the per-row chain
+// ids[r] -> starts[id] -> vals[..] -> rows of k_gather_mulhot is left in front of the token rows but vals[..]
+// itself, and that load is issued one row ahead (the next bag's start and length are already in registers).
+// A sub-group of LPR lanes forms a row with the arithmetic of k_gather_mulhot, bit for bit, but with the rows of
+// eight tokens in flight per lane instead of four (and a bag's tail among them): 94 VGPRs at d = 128, 5 waves per
+// SIMD, no scratch.  (Measured at C3's shape, 1 M bags of ~20 tokens, d = 128: 1.51 ms, the time of k_gather_mulhot
+// on the explicit id vector -- both sit at ~7.5 TB/s of token rows; with four rows in flight and 6 waves this
+// kernel took 1.64 ms.  profiles/r07_het_view_bench.txt)
+// len -1 stands for an item >= n_items (the ragged last column of a stripe): a zero row.
+// ---------------------------------------------------------------------------
+template <int LPR>
+__global__ __launch_bounds__(256, 5) void k_het_rows_range(
+    const float* __restrict__ E_id, const float* __restrict__ bias_id, const float* __restrict__ E,
+    const float* __restrict__ bias, const int32_t* __restrict__ vals, const int32_t* __restrict__ starts,
+    const int32_t* __restrict__ lens, int64_t n_items, int world, int rank, int64_t c0, int64_t ncol,
+    int all_owners, int rpw, int bpo /* blocks of rpw columns per owner */, int nblk, int d, float scale,
+    float* __restrict__ out, int64_t ldo, float* bias_out, int64_t ldb, int64_t block_rows) {
+  constexpr int GPW = 64 / LPR;
+  const int lane = threadIdx.x & 63;
+  const int lig = lane % LPR;
+  const int gid = lane / LPR;
+  const int col = lig * 4;
+  const bool colok = col < d;
+  // (wave-uniform by construction; said so, the block's owner, column base and output base stay in scalar registers)
+  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6));
+  const int nwave = (int)(((int64_t)gridDim.x * blockDim.x) >> 6);
+  const int iters = rpw / GPW;
+
+  // starts / lens of column `lane` of block b (wave-uniform owner and column base)
+  auto load_index = [&](int b, int& st, int& len) {
+    st = 0;
+    len = -1;
+    if (b >= nblk || lane >= rpw) return;
+    const int si = b / bpo;
+    const int64_t cc = (int64_t)(b - si * bpo) * rpw + lane;
+    if (cc >= ncol) return;
+    const int64_t g = (c0 + cc) * world + (all_owners ? si : rank);
+    if (g < n_items) {
+      st = starts[g];
+      len = lens[g];
+    }
+  };
+
+  int nst, nlen;
+  load_index(wave, nst, nlen);
+  for (int b = wave; b < nblk; b += nwave) {
+    const int st_l = nst, len_l = nlen;
+    load_index(b + nwave, nst, nlen);                    // the next block's index, under this block's rows
+    const int si = b / bpo;
+    const int s = all_owners ? si : rank;
+    const bool own = s == rank;
+    const int64_t cbase = (int64_t)(b - si * bpo) * rpw;
+    const int64_t obase = (all_owners ? (int64_t)s * block_rows : 0) + cbase;
+    int st = __shfl(st_l, gid, 64);
+    int len = __shfl(len_l, gid, 64);
+    int ptok = (lig < len) ? vals[st + lig] : 0;         // first pass of the first bag
+    for (int i = 0; i < iters; ++i) {
+      const int lr = i * GPW + gid;
+      // the next row's bag (every lane takes part in the cross-lane reads, whatever it does below)
+      const int lrn = (i + 1 < iters) ? lr + GPW : lr;
+      const int st_n = __shfl(st_l, lrn, 64);
+      const int len_n = (i + 1 < iters) ? __shfl(len_l, lrn, 64) : -1;
+      const int tok_n = (lig < len_n) ? vals[st_n + lig] : 0;
+      const int64_t cc = cbase + lr;
+      if (cc < ncol) {
+        const int64_t orow = obase + lr;
+        if (len < 0) {                                   // item >= n_items
+          if (colok) *reinterpret_cast<float4*>(out + orow * ldo + col) = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (lig == 0) bias_out[orow * ldb] = 0.f;
+        } else {
+          float4 one = make_float4(0.f, 0.f, 0.f, 0.f);
+          float one_b = 0.f;
+          if (own) {
+            const int64_t c = c0 + cc;
+            if (colok) one = *reinterpret_cast<const float4*>(E_id + c * d + col);
+            if (lig == 0) one_b = bias_id[c];
+          }
+          float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
+          float bacc = 0.f;
+          for (int j0 = 0; j0 < len; j0 += LPR) {
+            const int myj = j0 + lig;
+            const int mytok = (j0 == 0) ? ptok : ((myj < len) ? vals[st + myj] : 0);
+            if (myj < len) bacc += bias[mytok];
+            const int cnt = min(LPR, len - j0);
+            // k_gather_mulhot's sums in k_gather_mulhot's order -- token t of a full group of four goes to
+            // accumulator t % 4, the (< 4) tokens behind the last full group go to a0 one after the other -- with
+            // the rows of EIGHT tokens in flight together, the tail's among them (there: four, then one by one)
+            const int full = cnt & ~3;
+            for (int t = 0; t < cnt; t += 8) {
+              float4 v[8];
+#pragma unroll
+              for (int i = 0; i < 8; ++i) {
+                const int ti = __shfl(mytok, (t + i) & (LPR - 1), LPR);
+                v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (colok && t + i < cnt) v[i] = *reinterpret_cast<const float4*>(E + (int64_t)ti * d + col);
+              }
+#pragma unroll
+              for (int i = 0; i < 8; ++i) {
+                const int j = t + i;
+                if (j < full) {
+                  if ((i & 3) == 0) a0 = f4_add(a0, v[i]);
+                  if ((i & 3) == 1) a1 = f4_add(a1, v[i]);
+                  if ((i & 3) == 2) a2 = f4_add(a2, v[i]);
+                  if ((i & 3) == 3) a3 = f4_add(a3, v[i]);
+                } else if (j < cnt) {
+                  a0 = f4_add(a0, v[i]);
+                }
+              }
+            }
+          }
+          a0 = f4_add(f4_add(a0, a1), f4_add(a2, a3));
+          // same arithmetic as k_gather_mulhot: sum / len (a true divide), + id row, * scale
+          const float flen = (float)len;
+          if (colok) {
+            float4 o;
+            o.x = scale * (a0.x / flen + one.x);
+            o.y = scale * (a0.y / flen + one.y);
+            o.z = scale * (a0.z / flen + one.z);
+            o.w = scale * (a0.w / flen + one.w);
+            *reinterpret_cast<float4*>(out + orow * ldo + col) = o;
+          }
+#pragma unroll
+          for (int o = LPR / 2; o > 0; o >>= 1) bacc += __shfl_xor(bacc, o, LPR);
+          if (lig == 0) bias_out[orow * ldb] = scale * (bacc / flen + one_b);
+        }
+      }
+      st = st_n;
+      len = len_n;
+      ptok = tok_n;
+    }
+  }
+}
+
 struct GatherSites {
   const float* E[kMaxSites];
   const float* bias[kMaxSites];
@@ -888,6 +1026,42 @@ int arx_gather_id_plus_bag(const float* E_id, const float* bias_id, const int32_
   ARX_DISPATCH_LPR(lpr, (k_gather_mulhot<LPR><<<grid_waves(nwaves), 256, 0, as_stream(stream)>>>(
                             E_tok, bias_out ? bias_tok : nullptr, vals, starts, lens, ids, B, d, scale,
                             accumulate, out, ldo, bias_out, E_id, bias_out ? bias_id : nullptr, cat_map)));
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_het_rows_range(const float* E_id, const float* bias_id, const float* E_tok, const float* bias_tok,
+                       const int32_t* vals, const int32_t* starts, const int32_t* lens, int64_t n_items, int world,
+                       int rank, int64_t c0, int64_t c1, int all_owners, int d, float scale, float* out, int64_t ldo,
+                       float* bias_out, int64_t ldb, int64_t block_rows, void* stream) {
+  ARX_CHECK_ARG(E_id && bias_id && E_tok && bias_tok && vals && starts && lens && out && bias_out,
+                "arx_het_rows_range: null pointer");
+  ARX_CHECK_ARG(world >= 1 && rank >= 0 && rank < world, "arx_het_rows_range: need world >= 1 and 0 <= rank < world");
+  ARX_CHECK_ARG(n_items >= 0 && c0 >= 0 && c0 <= c1, "arx_het_rows_range: need n_items >= 0 and 0 <= c0 <= c1");
+  int rc = check_d("arx_het_rows_range", d);
+  if (rc) return rc;
+  ARX_CHECK_ARG(ldo % 4 == 0 && ldo >= d && ldb >= 1 && aligned16(E_id) && aligned16(E_tok) && aligned16(out),
+                "arx_het_rows_range: ldo %% 4, ldo >= d, ldb >= 1 and 16-byte alignment required");
+  const int64_t ncol = c1 - c0;
+  const bool all = all_owners != 0;
+  ARX_CHECK_ARG(!(all && world > 1) || block_rows >= ncol,
+                "arx_het_rows_range: the owner blocks overlap (block_rows < c1 - c0)");
+  ARX_CHECK_ARG(c1 <= ((int64_t)1 << 40) / world, "arx_het_rows_range: column range too large");
+  if (ncol == 0) return ARX_OK;
+  const int lpr = lanes_per_row(d);
+  const int gpw = 64 / lpr;
+  // columns per wave: 64 (one coalesced index load per block) while that still fills the device, fewer for a
+  // short range -- the bag chains are latency-bound, waves in flight come first
+  const int64_t nown = all ? world : 1;
+  const int64_t want = (int64_t)cu_count() * 32;
+  int rpw = 64;
+  while (rpw > gpw && nown * ceil_div(ncol, rpw) < want) rpw >>= 1;
+  const int64_t bpo = ceil_div(ncol, rpw);
+  ARX_CHECK_ARG(nown * bpo < ((int64_t)1 << 30), "arx_het_rows_range: too many rows");
+  const int nblk = (int)(nown * bpo);
+  ARX_DISPATCH_LPR(lpr, (k_het_rows_range<LPR><<<grid_waves(nblk), 256, 0, as_stream(stream)>>>(
+                            E_id, bias_id, E_tok, bias_tok, vals, starts, lens, n_items, world, rank, c0, ncol,
+                            all ? 1 : 0, rpw, (int)bpo, nblk, d, scale, out, ldo, bias_out, ldb, block_rows)));
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

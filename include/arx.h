@@ -131,6 +131,23 @@ int arx_gather_id_plus_bag(const float* E_id, const float* bias_id, const int32_
                            int d, float scale, int accumulate, float* out, int64_t ldo,
                            float* bias_out, void* stream);
 
+/* The HET rows (id row + bag mean, arx_gather_id_plus_bag) of a RANGE of columns of a row-sharded item table,
+ * without an id array or an id -> row map: what the serving view of the sharded HET models materialises its item
+ * latents with (arx.dist.ShardedHetView.refresh).  E_id / bias_id: THIS rank's id shard, row c = item c * world +
+ * rank; vals / starts / lens: the bag index by GLOBAL item id.  The kernel walks owner s (rank alone when
+ * all_owners == 0, else 0 .. world-1) and local column c in [c0, c1): item g = c * world + s, output row
+ * (all_owners ? s * block_rows : 0) + (c - c0).  For g < n_items
+ *   out[row, 0:d] = scale * ( sum over the bag of E_tok rows / len + idrow ),  idrow = E_id[c] if s == rank else 0,
+ * bias_out[row * ldb] the same combination of the bias cells (bias_out = out + d, ldb = ldo: the packed d+4 rows of
+ * the exchanges); g >= n_items (the ragged last column of a stripe): a zero row, zero bias.  Other columns of out
+ * are not written.  The arithmetic is arx_gather_id_plus_bag's on ids = c * world + s, bit for bit.  all_owners
+ * with world > 1 writes the owner-major blocks [world][block_rows] a reduce-scatter consumes: block_rows >= c1 - c0.
+ * d % 4 == 0, d <= 256, ldo % 4 == 0, ldo >= d. */
+int arx_het_rows_range(const float* E_id, const float* bias_id, const float* E_tok, const float* bias_tok,
+                       const int32_t* vals, const int32_t* starts, const int32_t* lens, int64_t n_items, int world,
+                       int rank, int64_t c0, int64_t c1, int all_owners, int d, float scale, float* out, int64_t ldo,
+                       float* bias_out, int64_t ldb, int64_t block_rows, void* stream);
+
 /* Several lookups of a step in ONE launch (embed_attribute.py:371-407 for the users, the target
  * items and the sampled pool of a step -- three independent launches otherwise).  Site s has a one-hot
  * feature (E_id[s], nullable, with cat_map[s] / bias_id[s]), a multi-hot feature (E_tok[s], nullable,

@@ -225,6 +225,7 @@ PROTOTYPES = {
                                             cint, i32p, f32p, i64, i32p, i64, i32p, i32p, vp]),
     "arx_topk_mark_empty": (cint, [f32p, i64, i32p, i64, i64, cint, vp]),
     "arx_topk_merge_shards": (cint, [f32p, i32p, i64, cint, cint, f32p, i32p, vp]),
+    "arx_topk_softmax_merge_shards": (cint, [f32p, i32p, f32p, i64, cint, cint, f32p, i32p, f32p, vp]),
     "arx_gemm_nt_eval_parts": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, f32p, f32p, f32p, i64, vp]),
     "arx_gemm_nt_eval_rank_parts": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, f32p, i32p, f32p, i32p, i64,
                                            vp]),

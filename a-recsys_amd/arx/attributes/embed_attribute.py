@@ -610,6 +610,7 @@ class EmbeddingAttribute(object):
         if self._item2logit_np is None:
             raise ValueError("recommend exclusions need item_ind2logit_ind")
         ptr, cols = exclusion_csr(item_sets, self.n_users + 1, self._item2logit_np)   # users 0..n_users (_pos_csr)
+        self._ex_host = (ptr, cols)        # (the striped model re-expresses them per shard: arx.dist.SeqHybridParallel)
         self._ex_dev = (self.rt.upload(ptr, torch.int32), self.rt.upload(cols, torch.int32))
 
     def exclusion_args(self):

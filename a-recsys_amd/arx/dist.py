@@ -254,12 +254,14 @@ class HipBackend(object):
         self.ops.het_rows_range(E_id, bias_id, E_tok, bias_tok, vals, starts, lens, n_items, world, rank, c0, c1, out,
                                 bias_out=bias_out, all_owners=all_owners, scale=scale, block_rows=block_rows)
 
-    def shard_topk(self, U, E, bias, k, ex, values, indices):
+    def shard_topk(self, U, E, bias, k, ex, values, indices, lse=None):
         """Recommend's local stage: values / indices [B, k] = every row's k best of U . E^T + bias over the shard's
         rows, by (value desc, local column asc); ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols of local
         columns) or None.  The streaming top-k of StreamTopK (hmf_model.TopKScan: fused filter GEMM, the chunked path
         after an overflow or for shapes the fused kernel does not take); a shard with fewer than k rows fills the rest
-        with (-inf, -1).  Buffers and GEMM workspace are this stage's own (captured step graphs keep theirs)."""
+        with (-inf, -1).  lse [B] (optional): the log-sum-exp of every row's logits over ALL the shard's rows, excluded
+        ones included (TopKScan's want_lse); -inf for a shard without rows.  Buffers and GEMM workspace are this
+        stage's own (captured step graphs keep theirs)."""
         from .hmf.hmf_model import TopKScan
         ops = self.ops
         B, V, d = int(U.shape[0]), int(E.shape[0]), int(U.shape[1])
@@ -269,16 +271,18 @@ class HipBackend(object):
             ops.fill_f32(values, float('-inf'))
             ops.fill_i32(indices, -1)
             if V == 0 or B == 0:
+                if lse is not None and B:
+                    ops.fill_f32(lse, float('-inf'))
                 return
             kk = V
         else:
             kk = k
-        key = (B, V, d, kk)
+        key = (B, V, d, kk, lse is not None)
         scan = self._scans.get(key)
         if scan is None:
             if len(self._scans) > 8:
                 self._scans.clear()
-            scan = self._scans[key] = TopKScan(B, V, d, kk, U.device)
+            scan = self._scans[key] = TopKScan(B, V, d, kk, U.device, want_lse=lse is not None)
             scan.fused = scan.fused and int(E.shape[1]) == d
             if kk < k:
                 scan.short = (torch.empty((B, kk), dtype=torch.float32, device=U.device),
@@ -294,6 +298,8 @@ class HipBackend(object):
         if kk < k:
             values[:, :kk].copy_(vo)
             indices[:, :kk].copy_(io)
+        if lse is not None:
+            lse.copy_(scan.lse)
 
     def topk_merge_shards(self, v, c, vo, io):
         """[W, B, k] per-shard lists (local columns) -> [B, k] global ids (arx_topk_merge_shards)."""
@@ -1933,17 +1939,44 @@ class SeqHybridParallel(SeqDataParallel):
     lookup, permutation, split sizes) is host work per batch on the ids the step is fed with: one D2H read of the
     ids per lookup node (data-loader work in a production loop, like ShardedHMF.prepare_route).
 
-    Scope: training steps (step(..., forward_only=False)) of models whose trained lookups are one-hot,
-    mean-combined features (the restriction SeqDataParallel has; C4); full-vocabulary evaluation over striped
-    tables is not built -- global_params() reassembles the tables for a single-process model.  Steps run eagerly
-    (collectives between the kernels).  No multi-GPU box was in reach of the builder: verified with gloo ranks
-    sharing one GPU (tests/test_seq_hybrid_gpu.py) and on CPU for the routing (tests/test_dist_cpu.py)."""
+    The serving side scores the full vocabulary shard by shard -- no rank ever holds a whole table (B = world *
+    B_loc, k = topk_n, n = L * B_loc; DESIGN.md section 7 has the bytes per call):
+
+      model.step_recommend(...)  (step_recommend below; lstm/run.py:550-640, lstm/seqModel.py:326-353,514-517)
+        (local)      lookups (fetch) -> LSTM layers -> RowsAt: latents [B_loc, d] at the positions asked for
+        all_gather   latents -> [B, d], user indices -> [B]
+        (local)      top-k + log-sum-exp over the shard's rows (backend.shard_topk, TopKScan with want_lse), the
+                     excluding filter with exclude_seen; local columns -> logit ids (col2logit)
+        all_to_all   values, logit ids [B, k], log-sum-exp [B] -> the ranks that own the rows
+        (local)      W-way merge + softmax values (arx_topk_softmax_merge_shards)
+
+      model.step(..., forward_only=True)  (step_eval below; the dev loss of lstm/run.py:505-519)
+        (local)      lookups (fetch) -> LSTM layers: hs [n, d]
+        all_gather   hs, mapped targets, row keys -- in row blocks of at most 16384 global rows
+        (local)      target score: the owner's row, every other rank's padding row; all_reduce(SUM)
+        (local)      the shard's 'ce' / 'warp' partial per row (backend.shard_eval, the eval positives masked)
+        all_to_all   partials -> the ranks that own the rows; arx_eval_merge_shards
+        (local)      sum_t loss_t w_t / (sum_t w_t + 1e-12), summed over this rank's sequences
+
+    Per rank, built once on first use (_serving): col2logit [rows] (local table row -> logit index, -1 for the START
+    row, items outside the logit vocabulary and the padding of the last stripe), a bias vector that is -inf at those
+    rows, and the exclusion lists / eval positives as CSR over this rank's local columns (every rank holds the full
+    host-side sets, as the single-process model does: no collective).
+
+    Scope: models whose trained lookups are one-hot, mean-combined features (the restriction SeqDataParallel has;
+    C4), output_feat 0 / 1; serving also needs the output side to be ONE one-hot feature whose logit -> row map is
+    injective (the id feature).  Steps run eagerly (collectives between the kernels).  No multi-GPU box was in reach
+    of the builder: verified with gloo ranks sharing one GPU (tests/test_seq_hybrid_gpu.py,
+    tests/test_seq_hybrid_serve_gpu.py) and on CPU for the routing and the serving maps (tests/test_dist_cpu.py,
+    tests/test_seq_hybrid_serve_cpu.py)."""
 
     def __init__(self, model, group=None):
         super().__init__(model, group)
         self._feat = {}            # id(Feature) -> dict(full_h, route)
         self._fetch = {}           # (id(node), k) -> this step's exchange record
         self._hstate = {}
+        self._serve_fetch = {}     # (id(node), k) -> receive buffers of the forward-only plans (no gradient arena)
+        self._serve = None         # serving state of this rank (_serving)
         self._shard_tables()
 
     # ---- striping -----------------------------------------------------------------------------
@@ -2050,8 +2083,7 @@ class SeqHybridParallel(SeqDataParallel):
         """Plan._execute, in front of the lookups: every EntityEmbed node of the plan is served here."""
         from . import graph as G, ops
         if not plan.train:
-            raise NotImplementedError("SeqHybridParallel: training steps only (evaluate a single-process model built "
-                                      "from global_params())")
+            return self._fetch_forward(plan)
         pools = self._pool_nodes(plan)
         dev = self.rt.device
         done = set()
@@ -2117,6 +2149,328 @@ class SeqHybridParallel(SeqDataParallel):
                                   bias_out=n.bias_value if n.with_bias else None)
             done.add(id(n))
         return done
+
+    def _fetch_forward(self, plan):
+        """fetch() of a forward-only plan (the serving side: step_recommend, step(forward_only=True)): the same id ->
+        owner -> rows -> back exchange for every batch lookup, with receive buffers of its own (_serve_fetch) -- no
+        gradient arena is allocated, _fetch and _hstate stay as the last training step left them.  A forward-only plan
+        that scores a pool (a Prediction node) is refused: the full vocabulary is scored shard by shard, never looked
+        up as one pool."""
+        from . import graph as G, ops
+        dev = self.rt.device
+        if any(isinstance(n, G.Prediction) for n in plan.order):
+            raise NotImplementedError("SeqHybridParallel: a forward-only plan over striped tables cannot score a pool; "
+                                      "use model.step_recommend / model.step(..., forward_only=True)")
+        done = set()
+        for n in plan.order:
+            if not isinstance(n, G.EntityEmbed):
+                continue
+            if n.concat or any(f.kind != 'cat' for f in n.feats):
+                raise NotImplementedError("SeqHybridParallel: one-hot, mean-combined features only")
+            n.alloc_value()
+            F = len(n.feats)
+            ids_h = n.inputs[0].value.cpu().numpy()
+            nloc = int(ids_h.shape[0])
+            for k, f in enumerate(n.feats):
+                fs = self._feature(f)
+                t = f.table
+                d = int(t.E.shape[1])
+                order, send_rows, sc = self.route_rows(fs['full_h'][ids_h], self.world)
+                sc, rc = self._exchange_counts(sc)
+                R = sum(rc)
+                rec = self._serve_fetch.get((id(n), k))
+                if rec is None or rec['cap'] < R:
+                    cap = max(R, nloc + nloc // 2 + 64) if self.world > 1 else nloc
+                    rec = self._serve_fetch[(id(n), k)] = dict(
+                        cap=cap, recv_rows=torch.empty(cap, dtype=torch.int32, device=dev),
+                        rows=torch.empty((cap, d), dtype=torch.float32, device=dev),
+                        rows_b=torch.empty((cap,), dtype=torch.float32, device=dev),
+                        got=torch.empty((nloc, d), dtype=torch.float32, device=dev),
+                        got_b=torch.empty((nloc,), dtype=torch.float32, device=dev))
+                inv = np.empty_like(order)
+                inv[order] = np.arange(order.shape[0], dtype=np.int32)
+                self._a2a(rec['recv_rows'][:R], torch.from_numpy(send_rows).to(dev), rc, sc)      # ids -> owners
+                wb = n.with_bias and t.bias is not None
+                if R:
+                    ops.gather_onehot(t.E, t.bias if wb else None, None, rec['recv_rows'][:R], rec['rows'][:R],
+                                      bias_out=rec['rows_b'][:R] if wb else None)
+                self._a2a(rec['got'], rec['rows'][:R], sc, rc)                                    # rows -> back
+                if wb:
+                    self._a2a(rec['got_b'], rec['rows_b'][:R], sc, rc)
+                ops.gather_onehot(rec['got'], rec['got_b'] if wb else None, None, torch.from_numpy(inv).to(dev),
+                                  n.value, scale=n.out_scale / F, accumulate=k > 0,
+                                  bias_out=n.bias_value if n.with_bias else None)
+            done.add(id(n))
+        return done
+
+    # ---- serving: the host side (no GPU needed) ------------------------------------------------------
+    @staticmethod
+    def serve_col2logit(cmap, rows, world, rank):
+        """col2logit [rows] int32 of one rank: local table row -> logit index, -1 for the rows outside the logit
+        vocabulary (the START row, items filtered out of the vocabulary, the ragged end of the last stripe).  cmap: the
+        output feature's logit -> GLOBAL table row map (_pool_embed('full', ...)'s cmap); it must be injective -- one
+        one-hot id feature -- or a table row would stand for several logits (NotImplementedError)."""
+        cmap = np.asarray(cmap, dtype=np.int64).reshape(-1)
+        if cmap.size and (cmap.min() < 0 or cmap.max() >= int(rows) * int(world)):
+            raise ValueError("serve_col2logit: the logit -> row map leaves the table")
+        if np.unique(cmap).size != cmap.size:
+            raise NotImplementedError("SeqHybridParallel serving: the output side must be a single one-hot feature "
+                                      "whose logit -> row map is injective (the id feature); this map sends several "
+                                      "logits to one table row")
+        out = np.full(int(rows), -1, dtype=np.int32)
+        mine = np.nonzero(cmap % world == rank)[0]
+        out[cmap[mine] // world] = mine.astype(np.int32)
+        return out
+
+    @staticmethod
+    def serve_shard_csr(ptr, cols, cmap, world, rank):
+        """Per-key lists of LOGIT columns (ptr [n_keys + 1], cols: exclusion_csr's form) -> (ptr int32 [n_keys + 1],
+        cols int32 [>= 1]) over the LOCAL columns of one rank: the logits whose table row cmap[logit] this rank owns
+        (row % world == rank), as row // world, every list sorted ascending without duplicates -- the (ex_ptr, ex_cols)
+        that shard_topk and shard_eval take."""
+        ptr = np.asarray(ptr, dtype=np.int64).reshape(-1)
+        cmap = np.asarray(cmap, dtype=np.int64).reshape(-1)
+        n_keys = len(ptr) - 1
+        c = np.asarray(cols, dtype=np.int64).reshape(-1)[:ptr[-1]]
+        keys = np.repeat(np.arange(n_keys, dtype=np.int64), np.diff(ptr))
+        ok = (c >= 0) & (c < len(cmap))
+        keys, g = keys[ok], cmap[c[ok]]
+        own = g % world == rank
+        keys, loc = keys[own], g[own] // world
+        o = np.lexsort((loc, keys))
+        keys, loc = keys[o], loc[o]
+        if len(keys):
+            keep = np.ones(len(keys), dtype=bool)
+            keep[1:] = (keys[1:] != keys[:-1]) | (loc[1:] != loc[:-1])
+            keys, loc = keys[keep], loc[keep]
+        out_ptr = np.zeros(n_keys + 1, dtype=np.int64)
+        np.cumsum(np.bincount(keys, minlength=n_keys), out=out_ptr[1:])
+        if len(loc) == 0:
+            loc = np.zeros(1, dtype=np.int64)           # (a valid device pointer; every list is empty)
+        return out_ptr.astype(np.int32), loc.astype(np.int32)
+
+    # ---- serving: per-rank state ----------------------------------------------------------------------
+    def _serving(self):
+        """Built once: the output feature, col2logit, the -inf mask of the out-of-vocabulary rows, the backend."""
+        sv = self._serve
+        if sv is not None:
+            return sv
+        model, m, dev = self.model, self.model.att_emb, self.rt.device
+        pe = m._pool_embed('full', model.output_feat)
+        if len(pe.feats) != 1 or pe.feats[0].kind != 'cat':
+            raise NotImplementedError("SeqHybridParallel serving: the output side must be a single one-hot feature "
+                                      "(the id feature); got %s" % [f.kind for f in pe.feats])
+        f = pe.feats[0]
+        fs, t = self._feature(f), f.table
+        rows = t.shard['rows']
+        c2l = self.serve_col2logit(fs['full_h'], rows, self.world, self.rank)
+        neg = np.where(c2l < 0, -np.inf, 0.0).astype(np.float32)
+        sv = self._serve = dict(f=f, fs=fs, t=t, rows=rows, col2logit=torch.from_numpy(c2l).to(dev),
+                                neg=torch.from_numpy(neg).to(dev),
+                                bias=torch.empty(rows, dtype=torch.float32, device=dev),
+                                be=HipBackend(dev), ex=None, pos=None, rec={}, ev={})
+        return sv
+
+    def _serve_bias(self, sv):
+        """The shard's bias over its local rows, -inf where a row is outside the logit vocabulary: such a row never
+        wins and adds nothing to a log-sum-exp or a margin sum."""
+        from . import ops
+        b, t = sv['bias'], sv['t']
+        b.copy_(sv['neg'])
+        if t.bias is not None:
+            ops.axpby(1.0, t.bias[:sv['rows']], 1.0, b)
+        return b
+
+    def _serve_lists(self, sv, slot, src, ptr, cols):
+        """Device CSR over this rank's local columns of host lists of logit columns; rebuilt when the lists change."""
+        if sv[slot] is None or sv[slot][0] is not src:
+            p, c = self.serve_shard_csr(ptr, cols, sv['fs']['full_h'], self.world, self.rank)
+            dev = self.rt.device
+            sv[slot] = (src, torch.from_numpy(p).to(dev), torch.from_numpy(c).to(dev))
+        return sv[slot][1], sv[slot][2]
+
+    def _serve_exclusions(self, sv):
+        src = getattr(self.model.att_emb, '_ex_host', None)
+        if src is None:
+            raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
+        return self._serve_lists(sv, 'ex', src, src[0], src[1])
+
+    def _serve_positives(self, sv):
+        from .attributes.embed_attribute import exclusion_csr
+        m = self.model.att_emb
+        if not hasattr(m, 'pos_item_set_eval'):
+            raise ValueError("the 'warp' dev loss needs prepare_warp() first")
+        src = m.pos_item_set_eval
+        if sv['pos'] is not None and sv['pos'][0] is src:
+            return sv['pos'][1], sv['pos'][2]
+        ptr, cols = exclusion_csr(src if src is not None else {}, m.n_users + 1, m._item2logit_np)
+        if src is None:
+            src = sv                                    # (any stable object: no positives were given)
+        return self._serve_lists(sv, 'pos', src, ptr, cols)
+
+    def _gather(self, src, dst):
+        """dst[w * n : (w + 1) * n] = src of rank w (host-staged under gloo, like _a2a)."""
+        if self.world == 1:
+            dst.copy_(src)
+            return
+        if src.is_cuda and dist.get_backend(self.group) != 'nccl':
+            o = torch.empty(dst.shape, dtype=dst.dtype)
+            dist.all_gather_into_tensor(o, src.cpu().contiguous(), group=self.group)
+            dst.copy_(o)
+            return
+        dist.all_gather_into_tensor(dst, src.contiguous(), group=self.group)
+
+    # ---- serving: recommend ----------------------------------------------------------------------------
+    def step_recommend(self, session, user_input, item_inputs, positions, bucket_id, exclude_seen=False):
+        """SeqModel.step_recommend of the striped model (the model dispatches here): same arguments, same return --
+        [(uid, values[topk_n], indexes[topk_n])] for this rank's sequences.  A collective: every rank calls it with
+        its own batch_size sequences, the same bucket and the same exclude_seen.  B = world * B_loc, k = topk_n:
+
+          (local)      lookups (fetch: ids -> owners, rows back) -> LSTM layers -> RowsAt: latents [B_loc, d]
+          all_gather   latents -> [B, d], user indices -> [B]
+          (local)      top-k + log-sum-exp of U_all . E[:rows]^T + bias over the shard's rows (backend.shard_topk:
+                       TopKScan with want_lse; bias = -inf at rows outside the logit vocabulary); exclude_seen: the
+                       excluding filter over this rank's local columns, the log-sum-exp stays over all columns;
+                       chunked once more after an overflow, on this rank only; local columns -> logit ids (col2logit)
+          all_to_all   values, logit ids [B, k] and log-sum-exp [B] -> the ranks that own the rows: [W][B_loc][k]
+          (local)      W-way merge, softmax values exp(v - lse) (arx_topk_softmax_merge_shards)
+
+        Ties among exactly equal scores come out as (score desc, logit id asc) whenever logit ids increase with the
+        table rows on each shard (identity maps, C4, the synthetic sets without a logit permutation); otherwise tied
+        entries of ONE shard keep that shard's row order.  exclude_seen without prepare_recommend_exclusions raises
+        ValueError before any collective; where fewer than topk_n items remain the tail is index -1, value 0."""
+        from . import graph as G, ops
+        from .lstm.seqModel import RowsAt
+        model, rt, W = self.model, self.rt, self.world
+        m, dev = model.att_emb, self.rt.device
+        sv = self._serving()
+        exl = self._serve_exclusions(sv) if exclude_seen else None
+        L, Bl = model.buckets[bucket_id], model.batch_size
+        B = Bl * W
+        k = min(int(model.topk_n), int(m.logit_size))
+        if not 1 <= k <= 1024:
+            raise ValueError("step_recommend over striped tables: need 1 <= topk_n <= 1024")
+        if len(positions) > Bl:
+            raise ValueError("step_recommend: at most batch_size positions")
+        it = item_inputs
+        if not isinstance(it, torch.Tensor):
+            it = torch.from_numpy(np.ascontiguousarray(np.asarray(it, dtype=np.int32)[:L].reshape(-1)))
+        m.input_all.value[:L * Bl].copy_(it.reshape(-1), non_blocking=True)
+        m.add_input({}, user_input, None, forward_only=True, recommend=True, loss=model.loss)
+        users = user_input.cpu().numpy() if isinstance(user_input, torch.Tensor) else user_input
+        bk = model._bucket(bucket_id)
+        if 'serve_rec' not in bk['plans']:
+            bk['serve_rows'] = G.IdsInput(rt, Bl, 'serve_rows_%d' % L)
+            bk['serve_sel'] = RowsAt(rt, bk['hs'], bk['serve_rows'])
+            bk['plans']['serve_rec'] = G.Plan(rt, [bk['serve_sel']], False, [])
+        rows_h = np.zeros(Bl, dtype=np.int32)
+        rows_h[:len(positions)] = [int(pos) * Bl + i for i, pos in enumerate(positions)]
+        bk['serve_rows'].feed(rows_h)
+        bk['plans']['serve_rec'].run()
+        lat = bk['serve_sel'].value
+        d = int(lat.shape[1])
+        buf = sv['rec'].get((Bl, k, d))
+        if buf is None:
+            e = lambda dt, *sh: torch.empty(sh, dtype=dt, device=dev)
+            f32, i32 = torch.float32, torch.int32
+            buf = sv['rec'][(Bl, k, d)] = (e(f32, B, d), e(i32, B), e(f32, B, k), e(i32, B, k), e(i32, B, k), e(f32, B),
+                                           e(f32, W, Bl, k), e(i32, W, Bl, k), e(f32, W, Bl), e(f32, Bl, k),
+                                           e(i32, Bl, k), e(f32, Bl))
+        U_all, keys_all, out_v, out_c, out_g, lse, recv_v, recv_g, recv_l, po, io, lse_o = buf
+        keys_loc = torch.from_numpy(np.asarray(users, dtype=np.int32).reshape(-1)).to(dev)
+        self._gather(lat, U_all)
+        self._gather(keys_loc, keys_all)
+        rows = sv['rows']
+        ex = (keys_all, B, exl[0], exl[1]) if exclude_seen else None
+        sv['be'].shard_topk(U_all, sv['t'].E[:rows], self._serve_bias(sv), k, ex, out_v, out_c, lse=lse)
+        ops.take_i32(sv['col2logit'], out_c.view(-1), out_g.view(-1), fill=-1)
+        self._a2a(recv_v.view(B, k), out_v, None, None)
+        self._a2a(recv_g.view(B, k), out_g, None, None)
+        self._a2a(recv_l.view(B), lse, None, None)
+        ops.topk_softmax_merge_shards(recv_v, recv_g, recv_l, po, io, lse_o)
+        vals, idx = po.cpu().numpy(), io.cpu().numpy()
+        return [(users[i], vals[i], idx[i]) for i in range(len(positions))]
+
+    # ---- serving: the dev loss ---------------------------------------------------------------------------
+    EVAL_BLOCK_ROWS = 16384
+
+    def step_eval(self, session, user_input, item_inputs, targets, target_weights, bucket_id):
+        """SeqModel.step(..., forward_only=True) of the striped model (the model dispatches here): this rank's summed
+        sequence loss over the FULL vocabulary -- 'warp' (each user's eval positives masked) for a model trained with
+        'mw', 'ce' for 'mce' (seqModel.py:510) -- so that global_loss(local) is the single-process forward-only loss
+        of the global batch.  A collective.  n = L * B_loc rows per rank, in row blocks of at most 16384 global rows:
+
+          (local)      lookups (fetch) -> LSTM layers: hs [n, d]; forward-only plans never drop
+          all_gather   hs, the mapped targets (logit indices) and the row keys (the user index of each row)
+          (local)      the target score: the owner's row, every other rank's padding row, dot; all_reduce(SUM)
+          (local)      this shard's partial per row over E[:rows] (backend.shard_eval 'ce' / 'warp', bias = -inf at
+                       rows outside the logit vocabulary, the eval positives as lists of local columns)
+          all_to_all   partials -> the ranks that own the rows: [W][rows of the block]
+          (local)      the loss per row (arx_eval_merge_shards); after the last block sum_t loss_t w_t /
+                       (sum_t w_t + 1e-12) summed over the sequences (seqModel.py:551-567,596: arx_seq_weights,
+                       arx_dot_scaled)
+
+        Rows of weight 0 (positions past a sequence's end) are scored like any other and weigh nothing."""
+        from . import graph as G, ops
+        from .lstm.seqModel import SeqWeights
+        model, rt, W, r = self.model, self.rt, self.world, self.rank
+        m, dev = model.att_emb, self.rt.device
+        kind = {'mw': 'warp', 'mce': 'ce'}.get(model.loss)
+        if kind is None:
+            raise NotImplementedError("SeqHybridParallel: the dev loss of models trained with 'mw' / 'mce' only "
+                                      "(full-vocabulary training losses are not striped)")
+        sv = self._serving()
+        pos = self._serve_positives(sv) if kind == 'warp' else None
+        L, Bl = model.buckets[bucket_id], model.batch_size
+        n = L * Bl
+        tg_h = targets.cpu().numpy() if isinstance(targets, torch.Tensor) else np.asarray(targets, dtype=np.int64)[:L]
+        lg_h = m._item2logit_np[tg_h.reshape(-1).astype(np.int64)]
+        if (lg_h < 0).any():
+            raise KeyError(int(tg_h.reshape(-1)[np.argmax(lg_h < 0)]))         # (target_mapping's error)
+        model._feed(user_input, item_inputs, targets, target_weights, L, None, None, True)
+        users = user_input.cpu().numpy() if isinstance(user_input, torch.Tensor) else user_input
+        bk = model._bucket(bucket_id)
+        if 'serve_eval' not in bk['plans']:
+            bk['serve_wn'] = SeqWeights(rt, bk['eval'].inputs[1].inputs[0], L, Bl)
+            bk['plans']['serve_eval'] = G.Plan(rt, [bk['hs'], bk['serve_wn']], False, [])
+        bk['plans']['serve_eval'].run()
+        hs, wn = bk['hs'].value, bk['serve_wn'].value
+        tg = model.targets_all.value[:n]
+        d = int(hs.shape[1])
+        nb = max(1, min(n, self.EVAL_BLOCK_ROWS // W))
+        buf = sv['ev'].get((n, nb, d))
+        if buf is None:
+            e = lambda dt, *sh: torch.empty(sh, dtype=dt, device=dev)
+            f32, i32 = torch.float32, torch.int32
+            N = W * nb
+            # gathered hs / targets / keys; target rows, bias (zeros without a bias table), score, local column; the
+            # shard's partials (+ unused counts), the received [W][c]; this rank's row losses; the weighted sum
+            buf = sv['ev'][(n, nb, d)] = (e(f32, N, d), e(i32, N), e(i32, N), e(f32, N, d),
+                                          torch.zeros(N, dtype=f32, device=dev), e(f32, N), e(i32, N), e(f32, N),
+                                          e(i32, N), e(f32, N), e(f32, n), e(f32, 1))
+        H_all, T_all, K_all, Tg, tb, t, tcol, part, cnt, recv, loss_rows, out = buf
+        keys = torch.from_numpy(np.tile(np.asarray(users, dtype=np.int32).reshape(-1), L)).to(dev)
+        tab, rows, route = sv['t'], sv['rows'], sv['fs']['route']
+        E, bias = tab.E[:rows], self._serve_bias(sv)
+        for a in range(0, n, nb):
+            b = min(n, a + nb)
+            c = b - a
+            N = W * c
+            self._gather(hs[a:b], H_all[:N])
+            self._gather(tg[a:b], T_all[:N])
+            self._gather(keys[a:b], K_all[:N])
+            # the target logit: the owner's row, every other rank's padding row -- one non-zero summand per row
+            ops.gather_onehot(tab.E, tab.bias, route, T_all[:N], Tg[:N],
+                              bias_out=tb[:N] if tab.bias is not None else None)
+            ops.take_i32(route, T_all[:N], tcol[:N], fill=rows)          # (the padding row: "not on this shard")
+            ops.dot_score(H_all[:N], Tg[:N], tb[:N], t[:N])
+            self._reduce_host_staged(t[:N])
+            ex = (K_all[:N], N, pos[0], pos[1]) if kind == 'warp' else None
+            sv['be'].shard_eval(H_all[:N], E, bias, t[:N], tcol[:N], kind, ex, part[:N], cnt[:N])
+            self._a2a(recv[:N], part[:N], None, None)
+            sv['be'].eval_merge_shards(kind, recv[:N].view(W, c), None, t[r * c:(r + 1) * c], loss_rows[a:b], None)
+        ops.dot_scaled(loss_rows, wn, 1.0, out)
+        return float(out.item())
 
     # ---- backward: gradients to the owners ----------------------------------------------------------
     def _state(self, plan):

@@ -465,7 +465,7 @@ class SeqModel(SeqBatching):
         wn = SeqWeights(rt, self.weights_all if L == Lmax else _FloatView(rt, self.weights_all, n), L, B)
         tid = view(self.target_ids_all, 'target_id_%d' % L)
         tgt = view(self.targets_all, 'target_%d' % L)
-        bk = {'L': L, 'dropouts': bk_drop}
+        bk = {'L': L, 'dropouts': bk_drop, 'hs': hs}
         seq_pred = lambda lat, pe: SeqPrediction(rt, lat, pe, L, B)     # scorer of all L time steps at once
         if self.loss in ('mw', 'mce'):       # ('mce': build-defined sampled softmax, see arx.h)
             logits = m.get_prediction(hs, 'sampled', output_feat=self.output_feat, pred_cls=seq_pred, steps=(L, B))  # :492
@@ -790,7 +790,11 @@ class SeqModel(SeqBatching):
 
     def step(self, session, user_input, item_inputs, targets, target_weights, bucket_id,
              item_sampled=None, item_sampled_id2idx=None, forward_only=False, recommend=False):
-        """seqModel.py:289-324 -> summed sequence loss of the batch (float)."""
+        """seqModel.py:289-324 -> summed sequence loss of the batch (float).  Under arx.dist.SeqHybridParallel a
+        forward-only step is that wrapper's collective (step_eval): this rank's share of the global loss."""
+        dp = self.rt.dp
+        if forward_only and dp is not None and hasattr(dp, 'step_eval'):
+            return dp.step_eval(session, user_input, item_inputs, targets, target_weights, bucket_id)
         node = self.step_async(session, user_input, item_inputs, targets, target_weights, bucket_id,
                                item_sampled, item_sampled_id2idx, forward_only, recommend)
         return float(node.read().item())
@@ -823,7 +827,11 @@ class SeqModel(SeqBatching):
         and the fused full-vocabulary top-k + log-sum-exp of hmf_model.StreamTopK runs on them (round 5).
         exclude_seen: leave out user_input[i]'s items of prepare_recommend_exclusions (plan 'recommend_ex'); the
         softmax normaliser stays over the full vocabulary, so a winner's value equals the non-excluding one; where
-        a user has fewer than topk_n eligible items the tail has index -1 and value 0."""
+        a user has fewer than topk_n eligible items the tail has index -1 and value 0.  Under
+        arx.dist.SeqHybridParallel the call is that wrapper's collective of the same name."""
+        dp = self.rt.dp
+        if dp is not None and hasattr(dp, 'step_recommend'):
+            return dp.step_recommend(session, user_input, item_inputs, positions, bucket_id, exclude_seen)
         if exclude_seen:
             self.att_emb.exclusion_args()      # ValueError before any feed when nothing was prepared
         L = self.buckets[bucket_id]

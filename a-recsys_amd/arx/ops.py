@@ -1138,6 +1138,26 @@ def topk_merge_shards(v, c, vo, io):
     call("arx_topk_merge_shards", _p(v), _p(c), B, W, k, _p(vo), _p(io), _stream())
 
 
+def topk_softmax_merge_shards(v, id, lse_part, po, io, lse_out=None):
+    """W-way merge of per-shard top-k lists of GLOBAL logit ids into softmax winners (arx.h): v / id [W, B, k] (shard
+    s's lists in block s, -1 = empty), lse_part [W, B] (each shard's log-sum-exp over all its columns, -inf: none) ->
+    io [B, k] by (value desc, id asc), po [B, k] = exp(value - lse) (0 where io is -1), lse_out [B] (optional)."""
+    W, B, k = (int(x) for x in v.shape)
+    for t in (v, id, lse_part, po, io, lse_out):
+        if t is not None and not t.is_contiguous():
+            raise ValueError("topk_softmax_merge_shards: contiguous tensors only")
+    if v.dtype != torch.float32 or id.dtype != torch.int32 or lse_part.dtype != torch.float32 or \
+            po.dtype != torch.float32 or io.dtype != torch.int32 or \
+            (lse_out is not None and lse_out.dtype != torch.float32):
+        raise ValueError("topk_softmax_merge_shards: v / lse_part / po / lse_out float32, id / io int32")
+    if tuple(id.shape) != (W, B, k) or tuple(lse_part.shape) != (W, B) or tuple(po.shape) != (B, k) or \
+            tuple(io.shape) != (B, k) or (lse_out is not None and tuple(lse_out.shape) != (B,)):
+        raise ValueError("topk_softmax_merge_shards: v / id [W, B, k], lse_part [W, B], po / io [B, k], lse_out [B]")
+    if B == 0:
+        return                              # (empty tensors have no pointer to pass)
+    call("arx_topk_softmax_merge_shards", _p(v), _p(id), _p(lse_part), B, W, k, _p(po), _p(io), _p(lse_out), _stream())
+
+
 def gemm_nt_eval_parts(A, Bm, col_bias, tscore, lse_part, relu_part):
     """Full-vocabulary evaluation sums out of the scorer GEMM, no logits (arx.h)."""
     ref = lse_part if lse_part is not None else relu_part

@@ -10,7 +10,8 @@
 // row in total, whatever k is.
 // Recommend without each user's seen items: arx_topk_exclude_fill masks them in a logits chunk, arx_topk_mark_empty
 // turns the -inf tails of short rows into index -1.
-// Recommend of the row-sharded model: arx_topk_merge_shards folds the W shards' lists into global ids in one launch.
+// Recommend of the row-sharded model: arx_topk_merge_shards folds the W shards' lists into global ids in one launch;
+// arx_topk_softmax_merge_shards does it for lists of logit ids and turns the winners' values into softmax values.
 #include "common.h"
 
 namespace arx {
@@ -303,6 +304,70 @@ __global__ __launch_bounds__(64 * kMergeRowsPerBlock) void k_topk_merge_shards(
   }
 }
 
+// The softmax twin of k_topk_merge_shards (recommend of the row-striped SeqModel): the lists carry GLOBAL logit ids
+// (the owner mapped its columns before sending), lse_part [W][B] is each shard's log-sum-exp of the row over ALL of
+// its vocabulary columns.  The lanes s < W that hold the list heads also hold the parts: a wave max, a wave sum of
+// exp(part - max) -> the row's lse (-inf when every part is -inf: no NaN out of -inf - -inf); the merge then stores
+// exp(value - lse) for each winner, 0 next to an index -1.
+__device__ __forceinline__ uint64_t shard_head_gid(const float* __restrict__ v, const int32_t* __restrict__ id,
+                                                   int64_t base, int& pos, int k) {
+  for (; pos < k; ++pos) {
+    const int32_t g = id[base + pos];
+    if (g < 0) continue;                                     // an empty entry is no candidate
+    return ((uint64_t)ord_key(v[base + pos]) << 32) | (uint64_t)(0xffffffffu - (uint32_t)g);
+  }
+  return 0;
+}
+
+__global__ __launch_bounds__(64 * kMergeRowsPerBlock) void k_topk_softmax_merge_shards(
+    const float* __restrict__ v, const int32_t* __restrict__ id, const float* __restrict__ lse_part, int64_t B, int W,
+    int k, float* __restrict__ po, int32_t* __restrict__ io, float* __restrict__ lse_out) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * kMergeRowsPerBlock + (threadIdx.x >> 6);
+  if (r >= B) return;                                        // (whole waves: B is per wave)
+  const float ninf = -__builtin_inff();
+  const float part = lane < W ? lse_part[(int64_t)lane * B + r] : ninf;
+  float mx = part;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) mx = fmaxf(mx, __shfl_xor(mx, m, 64));
+  float sum = part == ninf ? 0.f : expf(part - mx);          // (mx = -inf only when every part is)
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) sum += __shfl_xor(sum, m, 64);
+  const float lse = mx == ninf ? ninf : mx + logf(sum);
+  if (lse_out && lane == 0) lse_out[r] = lse;
+  const int64_t base = ((int64_t)lane * B + r) * k;          // list of shard `lane` for row r
+  int pos = 0;
+  uint64_t head = lane < W ? shard_head_gid(v, id, base, pos, k) : 0;
+  float keep_p = 0.f;
+  int32_t keep_i = -1;
+  for (int j = 0; j < k; ++j) {
+    uint64_t best = head;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      const uint32_t lo = __shfl_xor((uint32_t)best, m, 64), hi = __shfl_xor((uint32_t)(best >> 32), m, 64);
+      const uint64_t o = ((uint64_t)hi << 32) | lo;
+      best = o > best ? o : best;
+    }
+    if (best != 0 && head == best) {                         // the one winning lane (logit ids are distinct)
+      ++pos;
+      head = shard_head_gid(v, id, base, pos, k);
+    }
+    if (lane == (j & 63)) {
+      const float bv = ord_val((uint32_t)(best >> 32));
+      const bool none = best == 0 || bv == ninf;
+      keep_p = none ? 0.f : expf(bv - lse);
+      keep_i = none ? -1 : (int32_t)(0xffffffffu - (uint32_t)best);
+    }
+    if ((j & 63) == 63 || j == k - 1) {
+      const int64_t o = r * k + (j & ~63) + lane;
+      if (lane <= (j & 63)) {
+        po[o] = keep_p;
+        io[o] = keep_i;
+      }
+    }
+  }
+}
+
 }  // namespace
 
 int topk_select_launch(const float* logits, int64_t ld, int64_t B, int64_t V, int k, int32_t idx_base,
@@ -380,6 +445,20 @@ int arx_topk_merge_shards(const float* v, const int32_t* c, int64_t B, int W, in
   if (B == 0) return ARX_OK;
   k_topk_merge_shards<<<(int)ceil_div(B, (int64_t)kMergeRowsPerBlock), 64 * kMergeRowsPerBlock, 0, as_stream(stream)>>>(
       v, c, B, W, k, vo, io);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_topk_softmax_merge_shards(const float* v, const int32_t* id, const float* lse_part, int64_t B, int W, int k,
+                                  float* po, int32_t* io, float* lse_out, void* stream) {
+  ARX_CHECK_ARG(v && id && lse_part && po && io, "arx_topk_softmax_merge_shards: null pointer");
+  ARX_CHECK_ARG(W >= 1 && W <= 64, "arx_topk_softmax_merge_shards: need 1 <= W <= 64");
+  ARX_CHECK_ARG(k > 0 && k <= kMaxK, "arx_topk_softmax_merge_shards: need 0 < k <= 1024");
+  ARX_CHECK_ARG(B >= 0 && ceil_div(B, (int64_t)kMergeRowsPerBlock) <= 0x7fffffff,
+                "arx_topk_softmax_merge_shards: need 0 <= B, B / 4 < 2^31");
+  if (B == 0) return ARX_OK;
+  k_topk_softmax_merge_shards<<<(int)ceil_div(B, (int64_t)kMergeRowsPerBlock), 64 * kMergeRowsPerBlock, 0,
+                                as_stream(stream)>>>(v, id, lse_part, B, W, k, po, io, lse_out);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

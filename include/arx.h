@@ -972,6 +972,17 @@ int arx_topk_mark_empty(const float* values, int64_t ldv, int32_t* indices, int6
  * deterministic. */
 int arx_topk_merge_shards(const float* v, const int32_t* c, int64_t B, int W, int k, float* vo, int32_t* io,
                           void* stream);
+/* Recommend of the row-striped sequence model (arx.dist.SeqHybridParallel.step_recommend): the same W-way merge for
+ * lists that already carry GLOBAL logit indices, with the softmax values of the winners.  v / id: [W][B][k] contiguous,
+ * list (s, r) sorted by (value descending, id ascending); id is the logit index (the owner maps its local columns before
+ * sending), id < 0 marks an empty entry (skipped wherever it stands).  lse_part [W][B]: shard s's log-sum-exp of row
+ * r's logits over ALL of its vocabulary columns, taken before any exclusion; -inf for a shard that holds none.
+ * lse_out [B] (may be NULL) = logsumexp_s lse_part[s][r], max-shifted: a -inf part adds nothing, all parts -inf give
+ * -inf, never NaN.  io [B][k]: the ids ordered by (value descending, id ascending) -- tf.nn.top_k's rule; -1 where
+ * fewer than k candidates exist or the winner's value is -inf.  po [B][k] = exp(value - lse), 0 where io is -1.
+ * One wave per row; 1 <= W <= 64, 1 <= k <= 1024, B >= 0 (0: no launch); deterministic. */
+int arx_topk_softmax_merge_shards(const float* v, const int32_t* id, const float* lse_part, int64_t B, int W, int k,
+                                  float* po, int32_t* io, float* lse_out, void* stream);
 /* The evaluation losses over the full vocabulary (hmf_model.py:130,144; seqModel.py:510: the full-softmax / full-WMRB
  * loss a sampled-loss model is selected on) in ONE pass of the same GEMM, no logits: per row and column range p
  * (arx_gemm_nt_topk_parts) lse_part[row][p] = log sum exp of the logits ('ce': loss = logsumexp_p(lse_part) - t) and /

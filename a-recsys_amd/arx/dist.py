@@ -161,6 +161,10 @@ class HipBackend(object):
     def copy_strided(self, src, dst):
         self.ops.copy_strided(src, dst)
 
+    def rows_fingerprint(self, x, row0, row_step, out):
+        """out (an int64 device word) += the striping-independent fingerprint of the rows of x (arx_rows_fingerprint)."""
+        self.ops.rows_fingerprint(x, row0, row_step, out)
+
     def transpose(self, src, dst):
         self.ops.transpose(src, dst)
 
@@ -441,10 +445,17 @@ class ShardedHMF(object):
             self.E_item[ni].zero_()
             self.b_item = torch.empty((ni + 1,), dtype=f32, device=dev).uniform_(-lim_i, lim_i, generator=g)
             self.b_item[ni] = 0.0
+        self.acc0 = float(acc0)
         self.A_user = torch.full_like(self.E_user, acc0)
         self.A_item = torch.full_like(self.E_item, acc0)
         self.Ab_item = torch.full_like(self.b_item, acc0)
         self.lr = torch.tensor([float(learning_rate)], dtype=f32, device=dev)
+        # save / restore (collectives; utils/checkpoint.py ShardedSaver): per-rank files of the owned rows, restorable
+        # on another world size.  n_restores: what a serving view compares beside `steps` (a restore may land on the
+        # step count the view has seen)
+        from .utils.checkpoint import ShardedSaver
+        self.saver = ShardedSaver(self)
+        self.n_restores = 0
 
         Sg, W = self.Sg, world
         dp = d + 4                                          # packed row: d values + bias (+ pad)
@@ -1215,13 +1226,46 @@ class ShardedHMF(object):
             dist.all_reduce(sc, op=dist.ReduceOp.SUM, group=self.group)
         return rows_f, rows_i, sc
 
-    # ---- helpers for tests / checkpoints ----
-    def gather_global_tables(self):
-        """Reassemble the striped tables on every rank (tests only; O(table))."""
+    # ---- checkpoints (utils/checkpoint.py ShardedSaver) and the full gather of the tests ----
+    def _checkpoint_arrays(self):
+        """(name, tensor, global rows, layout) of every table and Adagrad slot ('<name>/Adagrad'); the tensors are the
+        whole buffers, zero row included -- the saver takes the owned rows."""
+        return [('user', self.E_user, self.n_users, 'rows'), ('user/Adagrad', self.A_user, self.n_users, 'rows'),
+                ('item', self.E_item, self.n_items, 'rows'), ('item/Adagrad', self.A_item, self.n_items, 'rows'),
+                ('item_bias', self.b_item, self.n_items, 'rows'),
+                ('item_bias/Adagrad', self.Ab_item, self.n_items, 'rows')]
+
+    def _token_arrays(self, layout):
+        return [('token', self.E_tok, self.n_tokens, layout), ('token/Adagrad', self.A_tok, self.n_tokens, layout),
+                ('token_bias', self.b_tok, self.n_tokens, layout),
+                ('token_bias/Adagrad', self.Ab_tok, self.n_tokens, layout)]
+
+    def _checkpoint_scalars(self):
+        sc = {'steps': int(self.steps), 'learning_rate': float(self.lr.item()), 'd': int(self.d),
+              'n_users': int(self.n_users), 'n_items': int(self.n_items)}
+        if hasattr(self, 'n_tokens'):
+            sc['n_tokens'] = int(self.n_tokens)
+        return sc
+
+    def _checkpoint_set_scalars(self, sc):
+        self.steps = int(sc['steps'])
+        self.lr.fill_(float(sc['learning_rate']))           # (in place: captured graphs read this word)
+
+    def _checkpoint_restored(self):
+        self.n_restores += 1                                # every ShardedHetView of this model is stale now
+
+    def gather_global_tables(self, slots=False):
+        """Reassemble the striped tables on every rank (tests only; O(table)); slots: the Adagrad slots too, as
+        '<name>/Adagrad'.  (Checkpoints do not come this way: model.saver writes each rank's rows.)"""
         W = self.world
         out = {}
-        for name, t, n in (('user', self.E_user, self.n_users), ('item', self.E_item[:self.ni_loc], self.n_items),
-                           ('item_bias', self.b_item[:self.ni_loc], self.n_items)):
+        for name, t, n, layout in self._checkpoint_arrays():
+            if name.endswith('/Adagrad') and not slots:
+                continue
+            if layout == 'replicated':
+                out[name] = t[:n].cpu().numpy()
+                continue
+            t = t[:(n - self.rank + W - 1) // W]
             rows = (n + W - 1) // W
             pad = torch.zeros((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
             pad[:t.shape[0]] = t
@@ -1443,18 +1487,8 @@ class ShardedHMFBags(ShardedHMF):
         raise NotImplementedError("%s.evaluate: item latents are bag means -- use item_view().evaluate"
                                   % type(self).__name__)
 
-    def gather_global_tables(self):
-        out = super().gather_global_tables()
-        W = self.world
-        for name, t, n in (('token', self.E_tok[:self.nt_loc], self.n_tokens),
-                           ('token_bias', self.b_tok[:self.nt_loc], self.n_tokens)):
-            rows = (n + W - 1) // W
-            pad = torch.zeros((rows,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-            pad[:t.shape[0]] = t
-            parts = [torch.empty_like(pad) for _ in range(W)]
-            dist.all_gather(parts, pad, group=self.group)
-            out[name] = torch.stack(parts, 1).reshape((rows * W,) + tuple(t.shape[1:]))[:n].cpu().numpy()
-        return out
+    def _checkpoint_arrays(self):
+        return super()._checkpoint_arrays() + self._token_arrays('rows')
 
 
 class ShardedHMFRepTokens(ShardedHMF):
@@ -1602,12 +1636,8 @@ class ShardedHMFRepTokens(ShardedHMF):
         raise NotImplementedError("%s.evaluate: item latents are bag means -- use item_view().evaluate"
                                   % type(self).__name__)
 
-    def gather_global_tables(self):
-        out = super().gather_global_tables()
-        nt = self.n_tokens
-        out['token'] = self.E_tok[:nt].cpu().numpy()
-        out['token_bias'] = self.b_tok[:nt].cpu().numpy()
-        return out
+    def _checkpoint_arrays(self):
+        return super()._checkpoint_arrays() + self._token_arrays('replicated')
 
 
 class ShardedHetView(ShardedHMF):
@@ -1627,9 +1657,11 @@ class ShardedHetView(ShardedHMF):
                             blocks [W][chunk][d + 4], a reduce-scatter sums them into the owner's [chunk, d + 4], two
                             copies put them in place.  n_items x (d + 4) x 4 B cross the reduce-scatter per refresh
                             and rank.  (World 1: one launch, no collective.)
-    The view remembers model.steps; recommend / evaluate refresh first when the model has stepped since (step() is a
-    collective, so every rank decides alike).  Tables written any other way (a checkpoint load, a test) need an
-    explicit refresh().  The view's buffers are its own: captured step graphs are not disturbed."""
+    The view remembers model.steps and model.n_restores; recommend / evaluate refresh first when the model has stepped
+    or been restored from a checkpoint since (step() and model.saver.restore() are collectives, so every rank decides
+    alike; a restore counts even where it lands on the step count the view has seen).  Tables written any other way
+    (a test poking at the buffers) need an explicit refresh().  A view has no saver: it holds no state of its own.
+    The view's buffers are its own: captured step graphs are not disturbed."""
 
     _TAKEN = ('world', 'rank', 'B_loc', 'B', 'd', 'n_users', 'n_items', 'ni_loc', 'zero_row', 'device', 'group', 'be',
               'use_graphs', '_stream')
@@ -1647,6 +1679,7 @@ class ShardedHetView(ShardedHMF):
         self.E_item = torch.zeros((self.ni_loc + 1, self.d), dtype=f32, device=dev)
         self.b_item = torch.zeros((self.ni_loc + 1,), dtype=f32, device=dev)
         self.steps = None                                   # model.steps at the last refresh
+        self._seen = None                                   # (model.steps, model.n_restores) at the last refresh
         self.n_refresh = 0
         # the token-striped model at N > 1: every rank walks the columns of the LARGEST shard in equal chunks
         self._striped = isinstance(model, ShardedHMFBags) and self.world > 1
@@ -1675,15 +1708,16 @@ class ShardedHetView(ShardedHMF):
                 be.copy_2d(self._sum[:n, :d], self.E_item[c0:c0 + n])
                 be.copy_strided(self._sum[:n, d], self.b_item[c0:c0 + n])
         self.steps = m.steps
+        self._seen = (m.steps, m.n_restores)
         self.n_refresh += 1
 
     def _recommend(self, u, k, exclude_seen):
-        if self.steps != self.model.steps:
+        if self._seen != (self.model.steps, self.model.n_restores):
             self._refresh()
         return super()._recommend(u, k, exclude_seen)
 
     def _evaluate(self, u, it, loss):
-        if self.steps != self.model.steps:
+        if self._seen != (self.model.steps, self.model.n_restores):
             self._refresh()
         return super()._evaluate(u, it, loss)
 
@@ -1978,6 +2012,11 @@ class SeqHybridParallel(SeqDataParallel):
         self._serve_fetch = {}     # (id(node), k) -> receive buffers of the forward-only plans (no gradient arena)
         self._serve = None         # serving state of this rank (_serving)
         self._shard_tables()
+        # the wrapped model's Saver would write this rank's stripe, padding row included, under the global name: a
+        # runner's model.saver.save / restore go through the sharded saver (collectives) from here on
+        from .utils.checkpoint import ShardedSaver
+        self.device = self.rt.device
+        self.saver = model.saver = ShardedSaver(self)
 
     # ---- striping -----------------------------------------------------------------------------
     def _shard_tables(self):
@@ -2605,7 +2644,32 @@ class SeqHybridParallel(SeqDataParallel):
     def gathered_tables(self, plan):
         return [(view, [g for _, g, _, _ in gs], gbufs, rows) for view, gs, gbufs, rows in self._state(plan)['tables']]
 
-    # ---- tables back together (tests, checkpoints) ----------------------------------------------------
+    # ---- checkpoints (utils/checkpoint.py ShardedSaver) ------------------------------------------------
+    def _checkpoint_arrays(self):
+        """(name, tensor, global rows, layout) under the reference's variable names: tables, biases and their
+        '/Adagrad' slots striped by row, the dense parameters and their slots replicated."""
+        out = []
+        for t in self.model.att_emb.tables.values():
+            V = t.shard['V']
+            out += [(t.name, t.E, V, 'rows'), (t.name + '/Adagrad', t.acc, V, 'rows')]
+            if t.bias is not None:
+                out += [(t.bias_name, t.bias, V, 'rows'), (t.bias_name + '/Adagrad', t.bias_acc, V, 'rows')]
+        for p in self.rt.dense.values():
+            out += [(p.name, p.w, int(p.w.shape[0]), 'replicated'),
+                    (p.name + '/Adagrad', p.acc, int(p.w.shape[0]), 'replicated')]
+        return out
+
+    def _checkpoint_scalars(self):
+        return {'global_step': int(self.rt.global_step), 'learning_rate': float(self.rt.lr_host)}
+
+    def _checkpoint_set_scalars(self, sc):
+        self.rt.global_step = int(sc['global_step'])
+        self.rt.set_learning_rate(float(sc['learning_rate']))
+
+    def _checkpoint_restored(self):
+        return                  # (the serving state holds maps and lists only: _serve_bias reads the bias per call)
+
+    # ---- tables back together (tests only; checkpoints go through model.saver) -------------------------
     def global_params(self, slots=False):
         """{reference variable name: numpy array} of the WHOLE tables (att_emb.get_params() of a single-process
         model): the shards of all ranks, interleaved.  O(table) traffic -- not a step-path call."""

@@ -150,6 +150,25 @@ def copy_strided(src, dst):
          int(src.shape[0]), _stream())
 
 
+def rows_fingerprint(x, row0, row_step, out):
+    """out (one int64 device word, zeroed by the caller) += the striping-independent fingerprint of the rows of x
+    (1-D of unit stride: rows of width 1; 2-D: any row stride), row j standing for global row row0 + row_step * j
+    (arx_rows_fingerprint)."""
+    _chk(x, torch.float32, 'x')
+    if out.dtype != torch.int64 or out.numel() != 1 or not out.is_cuda:
+        raise ValueError("out must be one int64 device word")
+    if x.dim() == 1:
+        if x.shape[0] > 1 and x.stride(0) != 1:
+            raise ValueError("a 1-D x must have unit stride")
+        rows, width, ld = int(x.shape[0]), 1, 1
+    else:
+        rows, width = int(x.shape[0]), int(x.shape[1])
+        if rows and width > 1 and x.stride(1) != 1:
+            raise ValueError("inner dimension must be contiguous")
+        ld = max(width, int(x.stride(0)) if rows > 1 else width)
+    call("arx_rows_fingerprint", _p(x), ld, rows, width, int(row0), int(row_step), _p(out), _stream())
+
+
 # ---- a5 ---------------------------------------------------------------------
 def transpose(src, dst):
     """dst[c, r] = src[r, c] for 2-D fp32 views with unit inner stride."""

@@ -271,6 +271,53 @@ __global__ __launch_bounds__(256) void k_transpose(const float* __restrict__ src
   }
 }
 
+// ---- striping-independent fingerprint of table rows (sharded checkpoints) ----------------------------------------
+// sum_j ((2 g_j + 1) K) * sum_c bits(x[j, c]) (2c + 1)  mod 2^64,  g_j = row0 + row_step * j: integer arithmetic only,
+// so the value is exact and independent of the order of the adds -- and the sum over the stripes of a table does not
+// depend on how the table was striped.  L lanes (a power of two <= 64) share a row and walk its columns, V floats
+// per load (V = 4: float4); two rows in flight per lane; the row factor is applied once per (row, lane).
+constexpr uint64_t kFpK = 0x9E3779B97F4A7C15ull;
+
+template <int V>
+__device__ __forceinline__ uint64_t fp_row(const float* __restrict__ p, int64_t width, int c0, int L) {
+  uint64_t s = 0;
+  if (V == 4) {
+    for (int64_t c = (int64_t)c0 * 4; c < width; c += (int64_t)L * 4) {
+      const uint4 v = *reinterpret_cast<const uint4*>(p + c);
+      const uint64_t m = 2 * (uint64_t)c + 1;
+      s += (uint64_t)v.x * m + (uint64_t)v.y * (m + 2) + (uint64_t)v.z * (m + 4) + (uint64_t)v.w * (m + 6);
+    }
+  } else {
+    for (int64_t c = c0; c < width; c += L) s += (uint64_t)__float_as_uint(p[c]) * (2 * (uint64_t)c + 1);
+  }
+  return s;
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void k_rows_fingerprint(const float* __restrict__ x, int64_t ldx, int64_t rows,
+                                                          int64_t width, int64_t row0, int64_t row_step, int lshift,
+                                                          unsigned long long* __restrict__ out) {
+  __shared__ uint64_t part[4];
+  const int L = 1 << lshift;
+  const int64_t tid = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t rstride = ((int64_t)gridDim.x * blockDim.x) >> lshift;      // rows the grid covers per sweep
+  const int c0 = (int)(tid & (L - 1));
+  uint64_t acc = 0;
+  int64_t j = tid >> lshift;
+  for (; j + rstride < rows; j += 2 * rstride) {
+    const uint64_t a = fp_row<V>(x + j * ldx, width, c0, L);
+    const uint64_t b = fp_row<V>(x + (j + rstride) * ldx, width, c0, L);
+    acc += (2 * (uint64_t)(row0 + row_step * j) + 1) * kFpK * a;
+    acc += (2 * (uint64_t)(row0 + row_step * (j + rstride)) + 1) * kFpK * b;
+  }
+  if (j < rows) acc += (2 * (uint64_t)(row0 + row_step * j) + 1) * kFpK * fp_row<V>(x + j * ldx, width, c0, L);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += (uint64_t)__shfl_xor((unsigned long long)acc, o, 64);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(out, (unsigned long long)(part[0] + part[1] + part[2] + part[3]));
+}
+
 }  // namespace arx
 
 using namespace arx;
@@ -422,6 +469,26 @@ int arx_gather_rows_wide(const float* src, int64_t lds, int64_t src_rows, const 
   // one workgroup per 1024-float piece of a row
   dim3 grid((unsigned)ceil_div(width, 1024), (unsigned)(n < 65535 ? n : 65535));
   k_gather_rows_wide<<<grid, 256, 0, as_stream(stream)>>>(src, lds, src_rows, rows, n, width, dst, ldd);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_rows_fingerprint(const float* x, int64_t ldx, int64_t rows, int64_t width, int64_t row0, int64_t row_step,
+                         uint64_t* out, void* stream) {
+  ARX_CHECK_ARG(out && (x || rows == 0), "arx_rows_fingerprint: null pointer");
+  ARX_CHECK_ARG(rows >= 0 && width >= 1 && ldx >= width, "arx_rows_fingerprint: rows >= 0, width >= 1, ldx >= width");
+  ARX_CHECK_ARG(row0 >= 0 && row_step >= 1, "arx_rows_fingerprint: row0 >= 0, row_step >= 1");
+  if (rows == 0) return ARX_OK;
+  const bool vec = width % 4 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0;
+  const int64_t per_row = vec ? width / 4 : width;
+  int lshift = 0;
+  while ((1 << lshift) < per_row && lshift < 6) ++lshift;
+  const int grid = grid_for(rows << lshift, 256);
+  unsigned long long* o = reinterpret_cast<unsigned long long*>(out);
+  if (vec)
+    k_rows_fingerprint<4><<<grid, 256, 0, as_stream(stream)>>>(x, ldx, rows, width, row0, row_step, lshift, o);
+  else
+    k_rows_fingerprint<1><<<grid, 256, 0, as_stream(stream)>>>(x, ldx, rows, width, row0, row_step, lshift, o);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

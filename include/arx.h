@@ -105,6 +105,18 @@ int arx_transpose_f32(const float* src, int64_t lds, int64_t rows, int64_t cols,
 int arx_gather_rows_wide(const float* src, int64_t lds, int64_t src_rows, const int32_t* rows, int64_t n,
                          int64_t width, float* dst, int64_t ldd, void* stream);
 
+/* Fingerprint of table rows that does not depend on how the table is striped (sharded checkpoints,
+ * arx/utils/checkpoint.py ShardedSaver).  *out is a device word the CALLER has zeroed; the kernel adds, in uint64
+ * arithmetic mod 2^64 with K = 0x9E3779B97F4A7C15,
+ *   sum_{j < rows} ((2 g_j + 1) K) * sum_{c < width} bits(x[j * ldx + c]) (2c + 1),   g_j = row0 + row_step * j
+ * (bits: the float's 32-bit pattern, zero-extended; row0 = rank and row_step = world for a row-striped shard).
+ * Integer arithmetic only: exact, independent of the order of the adds, and the sum over the stripes of ANY
+ * striping of one table is the same number -- after a re-stripe it shows that every row arrived once, in its place.
+ * Calls accumulate into *out.  Any rows >= 0 (0: nothing is added), any width >= 1, ldx >= width; float4 reads where
+ * width % 4 == 0 and the rows are 16-byte aligned.  One 64-bit atomic add per workgroup. */
+int arx_rows_fingerprint(const float* x, int64_t ldx, int64_t rows, int64_t width, int64_t row0, int64_t row_step,
+                         uint64_t* out, void* stream);
+
 /* ---- a5: one-hot attribute gather --------------------------------------
  * embed_attribute.py:371-381: rows = cat_map[ids]; E[rows] (+ bias[rows]).
  * out[r, 0:d] = (accumulate ? out : 0) + scale * E[cat_map[ids[r]], :]

@@ -61,6 +61,10 @@ PROTOTYPES = {
                                           f32p, i64, f32p, vp]),
     "arx_dot_score_fwd": (cint, [f32p, i64, f32p, i64, f32p, i64, cint, f32p, vp]),
     "arx_dot_score_bwd": (cint, [f32p, i64, f32p, i64, f32p, i64, cint, f32p, i64, cint, f32p, i64, vp]),
+    "arx_pair_loss_fwdbwd": (cint, [f32p, i64, f32p, i64, f32p, f32p, i64, f32p, i32p, f32p, i64, cint, cint, f32,
+                                    f32p, f32p, f32p, f32p, i64, cint, f32p, i64, f32p, f32p, i64, f32p, vp]),
+    "arx_pair_auc": (cint, [f32p, f32p, i32p, i64, f32p, vp]),
+    "arx_neg_draw_uniform": (cint, [i32p, i64, i64, i32p, i32p, i64, i32p, u64, vp, u64, i32p, i32p, i32p, vp]),
     "arx_gemm_f32_workspace_bytes": (sz, [i64, i64, i64]),
     "arx_gemm_nt_bx6_workspace_bytes": (sz, [i64, i64]),
     "arx_gemm_nt_bx6": (cint, [i64, i64, i64, f32p, i64, f32p, i64, f32p, f32p, i64, vp, sz, vp]),

@@ -544,10 +544,15 @@ class EmbeddingAttribute(object):
         'rs', 'rs-sig', 'rs-sig2', 'bbpr' (loss_func log/exp/poly/poly2/linear/square), and 'mce'
         -- accepted by the reference's assert (:527) but without a branch there: BUILD-DEFINED as
         the sampled softmax log(1 + sum_s m_rs exp(x_rs - t_r)) in the shape of 'mw' (arx.h).
-        bpr* needs feeds the reference commented out."""
+        'bpr' / 'bpr-hinge' (:541-544): `logits` is the NegPos handle of the pair (neg_pos of
+        hmf_model.py:106); item_target is not used, as in the reference."""
         if loss not in ['ce', 'mce', 'warp', 'warp_eval', 'rs', 'rs-sig', 'rs-sig2', 'mw', 'bbpr',
                         'bpr', 'bpr-hinge']:
             raise ValueError("unknown loss %r" % loss)
+        if loss in ('bpr', 'bpr-hinge'):
+            if not isinstance(logits, NegPos):
+                raise ValueError("compute_loss(%r): the first argument is the NegPos handle of the pair" % loss)
+            return G.PairLoss(self.rt, loss, logits.latent, logits.pos_embed, logits.neg_embed)
         if loss in ('ce',):
             return G.BatchLoss(self.rt, 'ce', logits, item_target)
         if loss in ('warp', 'mw', 'mce', 'warp_eval'):
@@ -621,6 +626,24 @@ class EmbeddingAttribute(object):
             raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
         return (self.u_indices['input'].value, self.batch_size, ex[0], ex[1])
 
+    def prepare_pair_negatives(self, hist, seed=0):
+        """The items a drawn negative of the pair losses must not hit, per user -- typically the training history:
+        {user_index: items} or a (ptr, items) CSR pair in item-index space (the forms of
+        prepare_recommend_exclusions).  Uploaded as sorted logit columns together with logit_ind2item_ind; steps
+        without neg_item_input then draw their negatives on the device (graph.NegPairDraw).  BUILD-DEFINED: the
+        reference's draw is a commented-out host rejection loop (hmf_model.py:263-274).  A second call replaces the
+        lists and the seed."""
+        if self._item2logit_np is None or self.logit_ind2item_ind is None:
+            raise ValueError("pair negatives need item_ind2logit_ind and logit_ind2item_ind")
+        ptr, cols = exclusion_csr(hist, self.n_users + 1, self._item2logit_np)      # users 0..n_users (_pos_csr)
+        rt = self.rt
+        self._pair_lists = (rt.upload(ptr, torch.int32), rt.upload(cols, torch.int32),
+                            rt.upload(_np_i32(self.logit_ind2item_ind), torch.int32))
+        if getattr(self, 'neg_draw', None) is None:
+            self.neg_draw = G.NegPairDraw(rt, self.u_indices['input'], self.i_indices['neg'],
+                                          lambda: self._pair_lists, self.logit_size, seed)
+        self.neg_draw.seed = int(seed)
+
     def set_pos_mode(self, forward_only):
         self._pos_mode = 'eval' if forward_only else 'train'      # :727
 
@@ -660,6 +683,10 @@ class EmbeddingAttribute(object):
                     pad = np.zeros((self.input_steps - arr.shape[0], arr.shape[1]), dtype=np.int32)
                     arr = np.concatenate([arr, pad], 0)
                 self.input_all.feed(arr.reshape(-1))
+        if self.item_attributes is not None and loss in ['bpr', 'bpr-hinge'] and recommend is False:   # :704-706
+            self.i_indices['pos'].feed(item_input)
+            if neg_item_input is not None:           # (None: the plan draws them, prepare_pair_negatives)
+                self.i_indices['neg'].feed(neg_item_input)
         update_sampled = []
         input_feed_sampled = {}
         if (self.item_attributes is not None and recommend is False and item_sampled is not None
@@ -684,6 +711,15 @@ class EmbeddingAttribute(object):
             return (sum(ia._embedding_size_list_cat[0:ia.num_features_cat]) +
                     sum(ia._embedding_size_list_mulhot[0:ia.num_features_mulhot]))
         return ia._embedding_size_list_cat[0]
+
+
+class NegPos(object):
+    """neg_pos = neg_score - pos_score of hmf_model.py:104-106 as the reference hands it to compute_loss: here the
+    three operands (user latent, 'pos' lookup, 'neg' lookup) -- the loss kernel forms the scores itself."""
+
+    def __init__(self, latent, pos_embed, neg_embed):
+        self.latent, self.pos_embed, self.neg_embed = latent, pos_embed, neg_embed
+        self.shape = (latent.shape[0],)
 
 
 def reduce_mean(x, axis=0):

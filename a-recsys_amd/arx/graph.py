@@ -721,6 +721,100 @@ def _bl_forward_gemm_fused(self, bl, rw, uid, ptr, items, i2s):
 BatchLoss._forward_gemm_fused = _bl_forward_gemm_fused
 
 
+class PairLoss(Node):
+    """The pairwise losses 'bpr' / 'bpr-hinge' (hmf_model.py:96-107,132-133, embed_attribute.py:541-544) over the
+    user latent and the lookups of the 'pos' and 'neg' items: scores, loss and all gradients in ONE launch
+    (arx_pair_loss_fwdbwd), so -- like BatchLoss -- the reduction downstream tells this node its
+    d(total)/d(batch_loss) up front (gscale, row_w).  The two lookups receive their gradient rows and bias gradients
+    here, like the target lookup of TargetScore: K7 sees two ordinary sites on every item table.
+    draw: the NegPairDraw of the plan about to run (the model sets it), None with fed negatives -- its -1 ids mark
+    the void rows (no eligible negative: loss 0, no gradient)."""
+
+    requires_grad = True
+
+    def __init__(self, rt, kind, latent, pos_embed, neg_embed):
+        if kind not in ops.PAIR_KINDS:
+            raise NotImplementedError("pair loss %r" % (kind,))
+        for e in (pos_embed, neg_embed):
+            if not (isinstance(e, EntityEmbed) and e.with_bias and e.shape == latent.shape):
+                raise ValueError("PairLoss: the items are mean-combined lookups with bias, of the latent's shape")
+        super().__init__(rt, (latent.shape[0],), (latent, pos_embed, neg_embed))
+        self.kind = kind
+        self.gscale = 1.0
+        self.row_w = None
+        self.loss_sink = None
+        self.draw = None
+        n = latent.shape[0]
+        self.pos_score = torch.zeros(n, dtype=torch.float32, device=rt.device)
+        self.neg_score = torch.zeros(n, dtype=torch.float32, device=rt.device)
+
+    def void_ids(self):
+        return self.draw.value if self.draw is not None else None
+
+    def forward(self, train):
+        lat, pe, ne = self.inputs
+        bl = self.alloc_value()
+        rw = self.row_w.value if self.row_w is not None else None
+        g = {}
+        if train:
+            if not (lat.requires_grad and pe.train_tables and ne.train_tables):
+                raise NotImplementedError("PairLoss trains the latent and both item lookups")
+            dU = lat.alloc_grad()
+            acc = lat.grad_beta() != 0.0
+            for e in (pe, ne):
+                e.alloc_grad()
+                e.grad_beta()
+                e.bias_grad_used = True
+            g = dict(dU=dU, acc_dU=acc, dP=pe.grad, dpbias=pe.bias_grad, dN=ne.grad, dnbias=ne.bias_grad)
+        ops.pair_loss(lat.value, pe.value, pe.bias_value, ne.value, ne.bias_value, self.kind, self.gscale,
+                      self.pos_score, self.neg_score, bl, neg_ids=self.void_ids(), row_w=rw, **g)
+
+
+class PairOutput(Node):
+    """pos_score / neg_score (hmf_model.py:104-105) and auc (:107) of a PairLoss as handles with .read(): the scores
+    are what the last step's launch left; the auc is one small launch when somebody asks for it."""
+
+    def __init__(self, rt, pair, what):
+        super().__init__(rt, (1,) if what == 'auc' else pair.shape, (pair,))
+        self.what = what
+        if what == 'auc':
+            self.value = torch.zeros(1, dtype=torch.float32, device=rt.device)
+        else:
+            self.value = pair.pos_score if what == 'pos' else pair.neg_score
+
+    def forward(self, train):
+        if self.what == 'auc':
+            pair = self.inputs[0]
+            ops.pair_auc(pair.pos_score, pair.neg_score, pair.void_ids(), self.value)
+
+    def read(self):
+        self.forward(False)
+        return self.value
+
+
+class NegPairDraw(Node):
+    """The 'neg' ids of a pair-loss step drawn INSIDE the plan (arx_neg_draw_uniform): one item per row, uniform over
+    the logit columns that are not in the row's user's list.  value int32 [mb]: the drawn items, -1 for a user whose
+    list covers the vocabulary; the placeholder `target` gets the same ids with a valid item in place of -1 (that
+    row's gradients are zero: PairLoss).  The node owns a device counter and bumps it after every draw, so a replayed
+    graph draws anew.  pre_step: the plan runs it before its lookups and before the K7 sort branch forks -- both read
+    the placeholder."""
+
+    pre_step = True
+
+    def __init__(self, rt, users, target, lists, V, seed):
+        super().__init__(rt, target.shape, (users,))
+        self.target, self.lists, self.V, self.seed = target, lists, int(V), int(seed)
+        self.value = torch.zeros(target.shape[0], dtype=torch.int32, device=rt.device)
+        self.counter = torch.zeros(1, dtype=torch.int64, device=rt.device)
+
+    def forward(self, train):
+        ptr, cols, col2item = self.lists()
+        ops.neg_draw_uniform(self.inputs[0].value, ptr, cols, self.V, col2item, self.seed, self.counter, 0,
+                             self.value, lookup_items=self.target.value)
+        ops.counter_add(self.counter, 1)
+
+
 class StreamEvalLoss(Node):
     """Full-vocabulary 'ce' / 'warp' batch loss WITHOUT the [rows, V] logits (forward only:
     hmf_model.py:130,144, seqModel.py:510 -- the evaluation loss of a sampled-loss model): chunked
@@ -942,6 +1036,11 @@ class Plan(object):
             n._grad_written = False
             if isinstance(n, EntityEmbed):
                 n.bias_grad_used = False
+        # nodes that WRITE the ids of a lookup (NegPairDraw) go first: the lookups below and the K7 sort branch,
+        # which forks in _early_sort, read them
+        first = [n for n in self.order if getattr(n, 'pre_step', False)]
+        for n in first:
+            n.forward(self.train)
         # Row-striped tables (arx.dist.SeqHybridParallel): the lookups of this step are exchanges -- ids to the owners
         # of the rows, rows back -- done by the wrapper; the nodes it served are skipped below
         fetched = rt.dp.fetch(self) if (rt.dp is not None and hasattr(rt.dp, 'fetch')) else ()
@@ -986,7 +1085,7 @@ class Plan(object):
                     self._pregather.append((ops.LookupSet(sites), grp))
         if self.train:
             self._early_sort()
-        pre = set()
+        pre = set(id(n) for n in first)
         for gs, grp in self._pregather:
             if isinstance(gs, ops.LookupSet):
                 ops.lookup_multi(gs)

@@ -341,9 +341,6 @@ class LatentProductModel(object):
         self.data_length = None
         self.train_permutation = None
         self.start_index = None
-        if loss_function in ('bpr', 'bpr-hinge'):
-            raise NotImplementedError("bpr losses: the reference's pos/neg feeds are commented out "
-                                      "(embed_attribute.py:704-706); not on the hot path")
         self.loss_func, self.loss_exp_p = loss_func, loss_exp_p
 
         self.rt = rt = G.Runtime(learning_rate=learning_rate, use_graph=use_graph)
@@ -379,6 +376,15 @@ class LatentProductModel(object):
         loss = self.loss_function
         self._plans = {}
         self.set_mask, self.reset_mask = {}, {}
+        self.pos_score = self.neg_score = self.auc = None
+        neg_pos = None
+        if loss in ('bpr', 'bpr-hinge'):
+            # :96-107.  Built for the pair losses only: no other loss reads the 'pos' / 'neg' placeholders, and the
+            # reference never fed them (embed_attribute.py:704-706 is commented out there)
+            pos_embs_item, _pos_item_b = m.get_batch_item('pos', mb)
+            neg_embs_item, _neg_item_b = m.get_batch_item('neg', mb)
+            neg_pos = embed_attribute.NegPos(embedded_user, embed_attribute.reduce_mean(pos_embs_item, 0),
+                                             embed_attribute.reduce_mean(neg_embs_item, 0))
         sampled_logits = target_score = None
         if self.n_sampled is not None:
             sampled_logits = m.get_prediction(embedded_user, 'sampled')       # :112
@@ -414,6 +420,12 @@ class LatentProductModel(object):
             # run_hmf.py:255,304 groups it with
             batch_loss = m.compute_loss(sampled_logits, target_score, loss)
             batch_loss_eval = m.compute_loss(logits, self.item_target, 'ce')
+        elif loss in ('bpr', 'bpr-hinge'):                                       # :132-133
+            # one launch forms both scores, the loss and every gradient; no [mb, V] logits in training
+            batch_loss = m.compute_loss(neg_pos, self.item_target, loss)
+            self.pos_score = G.PairOutput(rt, batch_loss, 'pos')                 # :104
+            self.neg_score = G.PairOutput(rt, batch_loss, 'neg')                 # :105
+            self.auc = G.PairOutput(rt, batch_loss, 'auc')                       # :107
         else:
             raise NotImplementedError("not implemented!")
         if loss in ('warp', 'warp_eval', 'mw', 'mce', 'rs', 'rs-sig', 'rs-sig2', 'bbpr'):   # :137
@@ -446,6 +458,18 @@ class LatentProductModel(object):
         self._plans.pop('recommend_ex', None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
+    def prepare_pair_negatives(self, hist, seed=0):
+        """'bpr' / 'bpr-hinge': the items a DRAWN negative must not hit, per user -- typically the training history:
+        {user_index: items} or a (ptr, items) CSR pair in item-index space.  After this call a step without
+        neg_item_input draws one negative per row on the device, uniform over the user's other items
+        (EmbeddingAttribute.prepare_pair_negatives).  A second call replaces the lists (the drawing plans are
+        dropped)."""
+        if self.loss_function not in ('bpr', 'bpr-hinge'):
+            raise ValueError("prepare_pair_negatives: a model of the 'bpr' / 'bpr-hinge' losses")
+        for key in ('train_draw', 'eval_draw'):
+            self._plans.pop(key, None)
+        self.att_emb.prepare_pair_negatives(hist, seed=seed)
+
     def _topk_ex(self):
         """The excluding twin of self.topk (built on first use; the plain node and its plan stay as they are)."""
         if getattr(self, 'topk_ex', None) is None:
@@ -471,6 +495,10 @@ class LatentProductModel(object):
             if isinstance(self.loss_eval.inputs[0], G.StreamEvalLoss):
                 masks = []                 # the streaming loss reads the positives CSR itself
             p = G.Plan(rt, [self.loss_eval], False, masks)
+        elif key == 'train_draw':              # pair losses, the negatives drawn in the plan (NegPairDraw goes first)
+            p = G.Plan(rt, [m.neg_draw, self.loss], True, [])
+        elif key == 'eval_draw':
+            p = G.Plan(rt, [m.neg_draw, self.loss_eval], False, [])
         elif key == 'recommend':
             p = G.Plan(rt, [self.topk], False, [])
         elif key == 'recommend_ex':
@@ -484,7 +512,7 @@ class LatentProductModel(object):
         return p
 
     def _feed(self, user_input, item_input, recommend, loss, item_sampled, item_sampled_id2idx,
-              forward_only):
+              forward_only, neg_item_input=None):
         m = self.att_emb
         if not recommend:
             if not isinstance(item_input, torch.Tensor) and (self.loss_function not in ('mw', 'mce') or forward_only):
@@ -492,7 +520,8 @@ class LatentProductModel(object):
                 # dict lookup (:173); the plan maps item_id_target again on device (same values)
                 self.item_target.feed(m.target_mapping([item_input])[0])
             self.item_id_target.feed(item_input)                              # :176
-        update_sampled, _, _ = m.add_input({}, user_input, item_input, item_sampled=item_sampled,
+        update_sampled, _, _ = m.add_input({}, user_input, item_input, neg_item_input=neg_item_input,
+                                           item_sampled=item_sampled,
                                            item_sampled_id2idx=item_sampled_id2idx,
                                            forward_only=forward_only, recommend=recommend, loss=loss)
         for op in update_sampled:                                             # :206-207
@@ -569,9 +598,19 @@ class LatentProductModel(object):
             loss = self.loss_function
         if exclude_seen and recommend:
             self.att_emb.exclusion_args()      # ValueError before any feed when nothing was prepared
+        # pair losses: a step without negatives draws them inside its plan (prepare_pair_negatives)
+        pair = self.loss_function in ('bpr', 'bpr-hinge') and not recommend
+        draw = pair and (neg_item_input is None or len(neg_item_input) == 0)
+        if draw and getattr(self.att_emb, 'neg_draw', None) is None:
+            raise ValueError("a '%s' step needs neg_item_input, or prepare_pair_negatives() to draw the negatives "
+                             "on the device" % self.loss_function)
         self._cur = (user_input, item_input)
         self._feed(user_input, item_input, recommend, loss, item_sampled, item_sampled_id2idx,
-                   forward_only)
+                   forward_only, neg_item_input=None if draw else neg_item_input)
+        if pair:
+            if draw:
+                self.rt.drop_feed(self.att_emb.i_indices['neg'].value)    # (a queued older feed must not overwrite the draw)
+            self.batch_loss.draw = self.att_emb.neg_draw if draw else None
         if recommend and exclude_seen:
             self._plan('recommend_ex').run()
             return self.topk_ex.indices
@@ -582,9 +621,9 @@ class LatentProductModel(object):
             self._plan('warp_eval').run()
             return [self.batch_loss.value, self.batch_loss.rank_value]
         if forward_only:
-            self._plan('eval').run()
+            self._plan('eval_draw' if draw else 'eval').run()
             return self.loss_eval
-        plan = self._plan('train')
+        plan = self._plan('train_draw' if draw else 'train')
         if getattr(self, '_next_batch', None) is not None:
             self._ring_feed(plan, item_sampled)
         else:
@@ -598,6 +637,9 @@ class LatentProductModel(object):
              loss=None, run_op=None, run_meta=None, exclude_seen=False):
         """hmf_model.py:162-228.  Returns: train -> mean loss (float); forward_only ->
         loss_eval (float); recommend -> int32 [mb, top_N]; warp_eval -> [loss, rank].
+        'bpr' / 'bpr-hinge': neg_item_input (list, array or device tensor) holds one negative item per row; None or
+        empty draws them on the device (prepare_pair_negatives first, else ValueError).  self.pos_score /
+        neg_score / auc .read() give the last step's scores (hmf_model.py:104-107).
         recommend with exclude_seen=True: the top_N logit indices without each user's items of
         prepare_recommend_exclusions (ValueError if none were prepared); -1 where a user has fewer eligible items."""
         out = self.step_async(session, user_input, item_input, neg_item_input, item_sampled,

@@ -324,6 +324,38 @@ def dot_score_bwd(U, T, dscore, dU, acc_dU, dT):
          _ld(dT) if dT is not None else 0, _stream())
 
 
+PAIR_KINDS = {'bpr': 0, 'bpr-hinge': 1}
+
+
+def pair_loss(U, P, pbias, N, nbias, kind, gscale, pos_score, neg_score, batch_loss, neg_ids=None, row_w=None,
+              dU=None, acc_dU=False, dP=None, dpbias=None, dN=None, dnbias=None):
+    """'bpr' / 'bpr-hinge' over the rows of (U, P, N): scores, loss and -- unless all five gradient tensors are
+    None -- the gradients, in one launch (arx.h arx_pair_loss_fwdbwd).  neg_ids: rows with a negative id are void."""
+    call("arx_pair_loss_fwdbwd", _p(U), _ld(U), _p(P), _ld(P), _p(pbias), _p(N), _ld(N), _p(nbias), _p(neg_ids),
+         _p(row_w), int(U.shape[0]), int(U.shape[1]), PAIR_KINDS[kind], float(gscale), _p(pos_score),
+         _p(neg_score), _p(batch_loss), _p(dU), _ld(dU) if dU is not None else 0, int(bool(acc_dU)), _p(dP),
+         _ld(dP) if dP is not None else 0, _p(dpbias), _p(dN), _ld(dN) if dN is not None else 0, _p(dnbias),
+         _stream())
+
+
+def pair_auc(pos_score, neg_score, neg_ids, out):
+    """out[0] = 0.5 - 0.5 * mean sign(neg_score - pos_score) over the rows that are not void (arx.h)."""
+    call("arx_pair_auc", _p(pos_score), _p(neg_score), _p(neg_ids), int(pos_score.shape[0]), _p(out), _stream())
+    return out
+
+
+def neg_draw_uniform(users, ex_ptr, ex_cols, V, col2item, seed, step_dev, counter, neg_items, lookup_items=None,
+                     out_rank=None):
+    """One negative per row, uniform over the logit columns outside the user's sorted list (arx.h
+    arx_neg_draw_uniform); -1 for a user without an eligible column."""
+    _chk(users, torch.int32, "users")
+    _chk(neg_items, torch.int32, "neg_items")
+    call("arx_neg_draw_uniform", _p(users), int(users.shape[0]), int(ex_ptr.shape[0]) - 1, _p(ex_ptr), _p(ex_cols),
+         int(V), _p(col2item), int(seed) & (2 ** 64 - 1), _p(step_dev), int(counter) & (2 ** 64 - 1),
+         _p(neg_items), _p(lookup_items), _p(out_rank), _stream())
+    return neg_items
+
+
 # ---- a8 -----------------------------------------------------------------------
 # The scorer products run on the bf16 matrix pipe, f32-exact (three exact bf16 pieces per operand, six MFMA terms,
 # f32 accumulation: csrc/gemm_bx6.hip) -- the default since round 4; ARX_SCORER_F32=1 selects the f32-input MFMA

@@ -53,6 +53,16 @@ static inline int lanes_per_row(int d) {
   return l;
 }
 
+// The counter RNG of the dropout kernels and the negative draw (util.hip, pair.hip): splitmix64 finaliser -> 32 bits;
+// counter-based, order independent
+__device__ __forceinline__ uint32_t mix32(uint64_t z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  z = z ^ (z >> 31);
+  return (uint32_t)(z >> 32);
+}
+
 // number of CUs of the current device (cached)
 int cu_count();
 

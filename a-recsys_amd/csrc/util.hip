@@ -160,15 +160,6 @@ __global__ void k_sum_scaled(const float* __restrict__ x, int64_t n, float scale
   }
 }
 
-__device__ __forceinline__ uint32_t mix32(uint64_t z) {
-  // splitmix64 finaliser -> 32 bits; counter-based, order independent
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  z = z ^ (z >> 31);
-  return (uint32_t)(z >> 32);
-}
-
 // `step` (nullable): device-side step counter added into the seed, so that a captured
 // (hipGraph-replayed) launch draws a fresh mask every replay
 __global__ void k_dropout_fwd(const float* __restrict__ x, int64_t n, float keep_prob,

@@ -213,6 +213,41 @@ int arx_dot_score_bwd(const float* U, int64_t ldu, const float* T, int64_t ldt,
                       const float* dscore, int64_t B, int d, float* dU, int64_t lddu,
                       int acc_dU, float* dT, int64_t lddt, void* stream);
 
+/* ---- a9b: pairwise losses 'bpr' / 'bpr-hinge' ----------------------------
+ * hmf_model.py:104-106 and embed_attribute.py:541-544, forward and backward in one launch.  Per row r:
+ *   pos_score = sum_d U*P + pbias, neg_score = sum_d U*N + nbias, x = neg_score - pos_score
+ *   kind 0 'bpr':       loss = log(1 + exp(x)) (as max(x,0) + log1p(exp(-|x|))), g = sigmoid(x)
+ *   kind 1 'bpr-hinge': loss = max(1 + x, 0),                                   g = [1 + x > 0]
+ *   c = gscale * row_w[r] * g (row_w nullable = 1)
+ *   dU = (acc_dU ? dU : 0) + c (N - P), dP = -c U, dN = c U, dpbias = -c, dnbias = c
+ * The five gradient pointers are all NULL (forward only) or all set.  BUILD-DEFINED: a row with neg_ids[r] < 0
+ * (neg_ids nullable) is void -- loss 0, zero gradient rows (dU keeps what acc_dU found), scores still written.
+ * d % 4 == 0, d <= 256, leading dims % 4, 16-byte aligned matrices; B == 0 is legal.  No atomics, one sub-group
+ * of a wave per row: bit-reproducible. */
+int arx_pair_loss_fwdbwd(const float* U, int64_t ldu, const float* P, int64_t ldp, const float* pbias,
+                         const float* N, int64_t ldn, const float* nbias, const int32_t* neg_ids,
+                         const float* row_w, int64_t B, int d, int kind, float gscale, float* pos_score,
+                         float* neg_score, float* batch_loss, float* dU, int64_t lddu, int acc_dU, float* dP,
+                         int64_t lddp, float* dpbias, float* dN, int64_t lddn, float* dnbias, void* stream);
+/* hmf_model.py:107: *auc = 0.5 - 0.5 * mean_r sign(neg_score[r] - pos_score[r]) over the rows that are not void
+ * (neg_ids nullable); no such row gives 0.5.  One workgroup, integer sums.  B == 0 leaves *auc alone. */
+int arx_pair_auc(const float* pos_score, const float* neg_score, const int32_t* neg_ids, int64_t B, float* auc,
+                 void* stream);
+/* BUILD-DEFINED negative draw (the reference's is a commented-out host rejection loop, hmf_model.py:263-274):
+ * one item per row, uniform over the logit columns that are NOT in the row's user's list, by exact rank-select.
+ * ex_ptr [n_users + 1] / ex_cols: CSR over users of sorted, unique columns in [0, V); a user outside
+ * [0, n_users) has no list.  n_elig = V - len(u); k = mulhi32(rand32, n_elig) with rand32 from the counter RNG of
+ * the dropout kernels keyed by (seed, *step_dev + counter, r) (step_dev nullable = 0); col = k + #{j : p_j - j <= k}
+ * (binary search); neg_items[r] = col2item ? col2item[col] : col, or -1 when n_elig == 0 (a void row).
+ * lookup_items (nullable): the same ids with col2item[0] (or 0) in place of -1, for lookups that take no empty id.
+ * out_rank (nullable) receives k (-1 for a void row).  The multiply-high mapping gives every column a probability
+ * within V / 2^32 (relative) of 1 / n_elig.  A captured launch draws anew on every replay once the graph also
+ * bumps *step_dev (arx_counter_add). */
+int arx_neg_draw_uniform(const int32_t* users, int64_t B, int64_t n_users, const int32_t* ex_ptr,
+                         const int32_t* ex_cols, int64_t V, const int32_t* col2item, uint64_t seed,
+                         const uint64_t* step_dev, uint64_t counter, int32_t* neg_items, int32_t* lookup_items,
+                         int32_t* out_rank, void* stream);
+
 /* ---- a8: scorer GEMM on fp32 MFMA (v_mfma_f32_32x32x2_f32) --------------
  * embed_attribute.py:171,188-193,205 in embedding-space form:
  *   C[M,N] = alpha * op(A)[M,K] . op(B)[K,N] + beta * C + col_bias[n]

@@ -1,0 +1,155 @@
+"""The 'bpr' train step at the C2 / C3 shapes (bench.py's workloads: 1 M users, 1 M items, B = 16384, d = 128):
+negatives fed from a device-resident ring and negatives drawn inside the step, beside the 'mw' step of the same build.
+HIP-event time of regions of --steps steps, the median of --repeats regions.  Not part of bench.py.
+
+usage: python tools/bench_bpr.py [--workloads c2,c3] [--steps 100] [--warmup 20] [--out FILE.json]
+       python tools/bench_bpr.py --kernel-only        # the pair kernel alone (a run for rocprofv3 --kernel-trace --stats)
+"""
+import argparse
+import gc
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(ROOT, 'a-recsys_amd'), ROOT]
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+HBM_PEAK_GBS = 8000.0        # bench.py's
+WORKLOADS = {'c2': dict(), 'c3': dict(item_mulhot=True)}
+
+
+def region_ms(fn, steps, warmup, repeats):
+    for k in range(warmup):
+        fn(k)
+    out = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for k in range(warmup, warmup + steps):
+            fn(k)
+        e1.record()
+        torch.cuda.synchronize()
+        out.append(e0.elapsed_time(e1) / steps)
+    return sorted(out)[len(out) // 2]
+
+
+def pair_kernel_us(B, d, dev, iters=200):
+    """arx_pair_loss_fwdbwd alone on random operands; the algorithmic bytes are B (6 d + 7) 4."""
+    from arx import ops
+    g = torch.Generator(device=dev)
+    g.manual_seed(0)
+    U, P, N = (torch.randn(B, d, device=dev, generator=g) * 0.1 for _ in range(3))
+    pb, nb = torch.randn(B, device=dev, generator=g), torch.randn(B, device=dev, generator=g)
+    ps, ns, bl, dpb, dnb = (torch.empty(B, device=dev) for _ in range(5))
+    dU, dP, dN = (torch.empty(B, d, device=dev) for _ in range(3))
+    fn = lambda k: ops.pair_loss(U, P, pb, N, nb, 'bpr', 1.0 / B, ps, ns, bl, dU=dU, dP=dP, dpbias=dpb, dN=dN,
+                                 dnbias=dnb)
+    ms = region_ms(fn, iters, 10, 3)
+    nbytes = B * (6 * d + 7) * 4
+    return {'us': ms * 1e3, 'algorithmic_bytes': nbytes, 'gbs': nbytes / ms / 1e6,
+            'frac_of_hbm_peak': nbytes / ms / 1e6 / HBM_PEAK_GBS,
+            'note': 'operands are cache-resident at this size: descriptive, not an HBM rate'}
+
+
+def run_workload(name, args, dev):
+    from arx.hmf.hmf_model import LatentProductModel
+    from arx.utils.prepare_train import DeviceSampler
+    from arx.utils.synthetic import SyntheticHMF
+    B, d, S = args.batch, args.dim, args.n_sampled
+    syn = SyntheticHMF(n_users=args.n_users, n_items=args.n_items, permute_logits=False, seed=0,
+                       zipf_items=args.zipf_items, **WORKLOADS[name])
+    rng = np.random.default_rng(1)
+    nb = 64
+    batches = []
+    for _ in range(nb):
+        u, i = syn.sample_batch(B, rng)
+        n = rng.integers(0, args.n_items, size=B).astype(np.int32)
+        batches.append(tuple(torch.from_numpy(a).to(dev) for a in (u, i, n)))
+    res = {}
+
+    def build(loss):
+        m = LatentProductModel(args.n_users, args.n_items, d, 1, B, 0.1, 1.0, syn.u_attr, syn.i_attr,
+                               syn.item2logit[:args.n_items], syn.logit_ind2item_ind, loss_function=loss,
+                               n_sampled=S if loss == 'mw' else None)
+        return m
+
+    want = args.losses.split(',')
+    if 'mw' in want:
+        # for context: bench.py's step without the pool redraws
+        model = build('mw')
+        model.prepare_warp(syn.positives_csr(), syn.positives_csr())
+        pool = DeviceSampler(syn.item_population, syn.p_sample, device=dev, seed=1).sample(S)
+
+        def mw_step(k):
+            u, i, _ = batches[k % nb]
+            model.step_async(None, u, i, None, pool if k == 0 else None, None, loss='mw')
+        res['mw_ms'] = region_ms(mw_step, args.steps, args.warmup, args.repeats)
+        del model
+        gc.collect()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+
+    for loss in ('bpr', 'bpr-hinge'):
+        if loss not in want:
+            continue
+        model = build(loss)
+
+        def fed(k):
+            u, i, n = batches[k % nb]
+            model.step_async(None, u, i, n)
+        res[loss + '_fed_ms'] = region_ms(fed, args.steps, args.warmup, args.repeats)
+        res[loss + '_fed_loss'] = float(model.loss.read().item())
+        if loss == 'bpr' and 'bpr-drawn' in want:
+            model.prepare_pair_negatives(syn.positives_csr(), seed=1)
+
+            def drawn(k):
+                u, i, _ = batches[k % nb]
+                model.step_async(None, u, i, None)
+            res['bpr_drawn_ms'] = region_ms(drawn, args.steps, args.warmup, args.repeats)
+            res['bpr_drawn_loss'] = float(model.loss.read().item())
+            res['auc_last_step'] = float(model.auc.read().item())
+        del model
+        gc.collect()
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--workloads', default='c2,c3')
+    ap.add_argument('--steps', type=int, default=100)
+    ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--repeats', type=int, default=3)
+    ap.add_argument('--batch', type=int, default=16384)
+    ap.add_argument('--dim', type=int, default=128)
+    ap.add_argument('--n-items', type=int, default=1000000)
+    ap.add_argument('--n-users', type=int, default=1000000)
+    ap.add_argument('--n-sampled', type=int, default=1024)
+    ap.add_argument('--zipf-items', type=float, default=1.05)
+    ap.add_argument('--losses', default='mw,bpr,bpr-drawn,bpr-hinge',
+                    help="which steps to time ('bpr-drawn' needs 'bpr'); one loss alone gives a clean kernel trace")
+    ap.add_argument('--kernel-only', action='store_true')
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    dev = torch.device('cuda:0')
+    out = {'batch': args.batch, 'dim': args.dim, 'n_items': args.n_items, 'n_users': args.n_users,
+           'steps': args.steps, 'repeats': args.repeats,
+           'pair_kernel': pair_kernel_us(args.batch, args.dim, dev)}
+    if not args.kernel_only:
+        for name in [w for w in args.workloads.split(',') if w]:
+            out[name] = run_workload(name, args, dev)
+            print(name, json.dumps(out[name]), flush=True)
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()

@@ -63,6 +63,8 @@ PROTOTYPES = {
     "arx_dot_score_bwd": (cint, [f32p, i64, f32p, i64, f32p, i64, cint, f32p, i64, cint, f32p, i64, vp]),
     "arx_pair_loss_fwdbwd": (cint, [f32p, i64, f32p, i64, f32p, f32p, i64, f32p, i32p, f32p, i64, cint, cint, f32,
                                     f32p, f32p, f32p, f32p, i64, cint, f32p, i64, f32p, f32p, i64, f32p, vp]),
+    "arx_pair_loss_slots": (cint, [f32p, i64, f32p, i64, i64, i32p, i32p, f32p, i64, cint, cint, f32, f32p, f32p, f32p,
+                                   f32p, i64, cint, f32p, i64, i32p, vp]),
     "arx_pair_auc": (cint, [f32p, f32p, i32p, i64, f32p, vp]),
     "arx_neg_draw_uniform": (cint, [i32p, i64, i64, i32p, i32p, i64, i32p, u64, vp, u64, i32p, i32p, i32p, vp]),
     "arx_gemm_f32_workspace_bytes": (sz, [i64, i64, i64]),

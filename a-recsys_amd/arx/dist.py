@@ -181,9 +181,24 @@ class HipBackend(object):
     def pool_blocks(self, ids, world, rank, zero_row, cap, counts, gidx=None, my_slots=None, pool_rows=None):
         self.ops.pool_blocks(ids, world, rank, zero_row, cap, counts, gidx, my_slots, pool_rows)
 
-    def loss_mw_fused_pos(self, logits, U, T, tb, urows, ptr, items, i2s, bl, dl, t_out, dt, dU, dT, gscale):
-        """loss + target score + rank-one gradients in one kernel; tb / dt may be strided columns."""
-        self.ops.loss_mw_fused_pos(logits, U, T, tb, urows, ptr, items, i2s, bl, dl, t_out, dt, dU, dT, gscale)
+    def loss_mw_fused_pos(self, logits, U, T, tb, urows, ptr, items, i2s, bl, dl, t_out, dt, dU, dT, gscale,
+                          kind='mw'):
+        """loss ('mw' | 'mce') + target score + rank-one gradients in one kernel; tb / dt may be strided columns."""
+        self.ops.loss_mw_fused_pos(logits, U, T, tb, urows, ptr, items, i2s, bl, dl, t_out, dt, dU, dT, gscale,
+                                   kind=kind)
+
+    def pair_loss_slots(self, U, R, pos_slot, neg_slot, kind, gscale, pos_score, neg_score, bl, dU, dR, counts):
+        """'bpr' / 'bpr-hinge' of row r against the packed rows R[pos_slot[r]] / R[neg_slot[r]] (bias in column d):
+        scores, loss, dU (written) and the two gradient rows into the same slots of dR; neg_slot < 0: a void row.
+        counts: int32 [2] = (sum of sign(neg - pos), rows that are not void) (arx_pair_loss_slots)."""
+        self.ops.pair_loss_slots(U, R, pos_slot, neg_slot, kind, gscale, pos_score, neg_score, bl, dU=dU, dR=dR,
+                                 auc_counts=counts)
+
+    def neg_draw_uniform(self, urows, ex_ptr, ex_cols, V, seed, counter, out):
+        """out[r] = one item of [0, V) outside the sorted, unique list of local user row urows[r] (CSR ex_ptr /
+        ex_cols), uniform by rank-select, keyed by (seed, counter, r); -1 where the list is all of [0, V)
+        (arx_neg_draw_uniform, no col2item)."""
+        self.ops.neg_draw_uniform(urows, ex_ptr, ex_cols, V, None, seed, None, counter, out)
 
     def sum_scaled(self, x, scale, out):
         self.ops.sum_scaled(x, scale, out)
@@ -376,23 +391,43 @@ class HipBackend(object):
         self.ops.eval_merge_shards(loss, parts, cnts, t, out, cnt_out)
 
 
+PAIR_LOSSES = ('bpr', 'bpr-hinge')
+
+
 class ShardedHMF(object):
-    """id-only HMF ('mw' loss) with row-sharded tables.  Global ids everywhere in
+    """id-only HMF with row-sharded tables.  Global ids everywhere in
     the API; `users` passed to step() must all be owned by this rank.
+
+    loss: 'mw' (the default) or 'mce' -- the sampled losses over the shared pool, the same step with another loss
+    kernel -- or a pair loss, 'bpr' / 'bpr-hinge' (exchange='rows' only): no pool, one negative per interaction, fed
+    with the batch or drawn on the device (prepare_pair_negatives); _step_body_pair.
 
     The step of this class and of its two subclasses is ONE body each (_step_body: named segments of kernels between
     the collectives), run by one driver (_run_step): as captured hipGraph segments on the product backend, kernel by
     kernel everywhere else (graphs=False, ARX_DIST_EAGER=1, the numpy double of the CPU tests) -- the same launches,
     padding and exchanges either way.  exchange='logits' is a separate, eager-only step (_step_logits)."""
 
+    loss_name, pair, n_draws = 'mw', False, 0          # (instances set their own; a serving view keeps these)
+
     def __init__(self, n_users, n_items, d, B_loc, S, learning_rate, rank, world, device,
-                 backend=None, group=None, tables=None, seed=0, acc0=0.1, graphs=None, exchange='rows'):
+                 backend=None, group=None, tables=None, seed=0, acc0=0.1, graphs=None, exchange='rows', loss='mw'):
         if S % 4 != 0 or d % 4 != 0:
             raise ValueError("n_sampled and d must be multiples of 4")
         if exchange not in ('rows', 'logits'):
             raise ValueError("exchange: 'rows' (gather the pool rows) or 'logits' (all-to-all of the logits)")
         if exchange == 'logits' and type(self) is not ShardedHMF:
             raise ValueError("exchange='logits' is the id-only step's alternative (ShardedHMF)")
+        if loss not in ('mw', 'mce') + PAIR_LOSSES:
+            raise ValueError("loss: 'mw', 'mce', 'bpr' or 'bpr-hinge', got %r" % (loss,))
+        pair = loss in PAIR_LOSSES
+        if pair and type(self) is not ShardedHMF:
+            raise NotImplementedError("%s: loss=%r -- the pair losses are on the id-only ShardedHMF; the HET classes "
+                                      "train 'mw' and 'mce'" % (type(self).__name__, loss))
+        if pair and exchange == 'logits':
+            raise ValueError("loss=%r has no pool to score: exchange='logits' moves pool logits (use 'rows')" % (loss,))
+        self.loss_name, self.pair = loss, pair
+        self.seed, self.n_draws = int(seed), 0              # the pair draw: keyed by (seed, rank, n_draws)
+        self._neg_csr = None                                # (ptr, cols) of prepare_pair_negatives
         # 'logits' (SURVEY 8e steps 1-5, the exchange north_star words): the latents are all-gathered, every owner
         # scores the WHOLE batch against its pool block, the [B, S_g] partial logits cross by all_to_all, and their
         # gradients cross back -- _step_logits.  Eager launches (no graph segments).
@@ -409,6 +444,9 @@ class ShardedHMF(object):
         self.device = torch.device(device)
         self.group = group
         self.be = backend if backend is not None else HipBackend(self.device)
+        # (a backend that knows 'mw' alone -- the default -- is never handed a kind)
+        self._loss_fused = self.be.loss_mw_fused_pos if loss == 'mw' else \
+            (lambda *a: self.be.loss_mw_fused_pos(*a, kind=loss))
         # "this model captures graphs" (_run_step): the product backend on a GPU, unless switched off -- otherwise the
         # same step body runs kernel by kernel on the caller's stream
         if graphs is None:
@@ -464,6 +502,20 @@ class ShardedHMF(object):
         zi = lambda *s: torch.zeros(s, dtype=i32, device=dev)
         self.urows = zi(B_loc)
         self.U_loc = z(B_loc, d)
+        self.bl, self.loss = z(B_loc), z(1)
+        self.steps = 0
+        self.cap_r = 0                                      # capacity for received target rows
+        if pair:
+            # no pool and nothing sized by it (S may be 0; Sg = 0 lays the K7 arena out as [dU ; received rows]);
+            # an interaction asks for TWO rows: the received block and its gradient block hold 2 B_loc packed rows
+            self.S = self.Sg = 0
+            self.cap = 0
+            self.R_pack, self.dR_pack = z(2 * B_loc, dp), z(2 * B_loc, dp)
+            self.pos_score, self.neg_score = z(B_loc), z(B_loc)
+            self.auc_counts, self.g_slots = zi(2), zi(2 * B_loc)
+            self._alloc_recv(2 * B_loc)
+            self.pos_ptr, self.pos_items = zi(nu + 2), zi(1)
+            return
         self.pool_ids = zi(S)                               # owner-major global ids
         self.pool_rows = zi(Sg)                             # local rows of the owned block (padding row behind it)
         self.cap = S if world == 1 else 0                   # rows of a block in the current exchange
@@ -480,15 +532,12 @@ class ShardedHMF(object):
         self.logits = z(B_loc, S)
         self.T_pack, self.tb = z(B_loc, dp), z(B_loc)       # target rows as received back
         self.t_loc, self.dt_loc = z(B_loc), z(B_loc)
-        self.bl, self.loss = z(B_loc), z(1)
         self.dlogits = z(B_loc, S)
         self.dI_all, self.gb_all = z(S + 1, dp), z(S)       # pool-gradient partials (all columns) + a zero row
         self.dT_pack = z(B_loc, dp)                         # target-row gradients to send
-        self.cap_r = 0                                      # capacity for received target rows
         self._alloc_recv(B_loc)
         self.pos_ptr = zi(nu + 2)
         self.pos_items = zi(1)
-        self.steps = 0
 
     def _alloc_recv(self, cap):
         """Buffers that scale with R = target rows this rank owns in a batch.  The gradient
@@ -523,6 +572,9 @@ class ShardedHMF(object):
         items: embed_attribute.py:320-348 update_sampled, sharded).  Every rank sees the same ids and
         derives the same block layout: owner g's pool items, in slot order, are rows [0, count_g) of
         its block; all blocks travel padded to cap = max_g count_g rows."""
+        if self.pair:
+            raise RuntimeError("set_pool: a %r model has no pool (its negatives come with the batch: prepare_route)"
+                               % self.loss_name)
         be = self.be
         new = pool_ids if isinstance(pool_ids, torch.Tensor) else \
             torch.as_tensor(np.asarray(pool_ids, dtype=np.int32))
@@ -582,10 +634,113 @@ class ShardedHMF(object):
             self.dU_red = z(B_loc, self.d)
 
     # ------------------------------------------------------------------ route
-    def prepare_route(self, users, items):
+    def prepare_pair_negatives(self, seed=None):
+        """Makes this rank's set_positives lists the exclusion lists of the pair draw (prepare_route without
+        neg_items): checks the ids, sorts every user's list and drops its duplicates -- the rank-select draw
+        (arx_neg_draw_uniform) needs sorted, unique lists.  The lists set_positives holds stay as they are.
+        seed: the draw's seed (default: the constructor's); the draw counter starts again only with a new seed."""
+        if not self.pair:
+            raise RuntimeError("prepare_pair_negatives: a %r model draws no negatives" % self.loss_name)
+        ptr = self.pos_ptr.cpu().numpy().astype(np.int64)
+        items = self.pos_items.cpu().numpy().astype(np.int64)
+        if len(ptr) < 2 or ptr[0] != 0 or np.any(np.diff(ptr) < 0) or ptr[-1] > len(items):
+            raise ValueError("prepare_pair_negatives: set_positives' ptr must start at 0, not decrease and end "
+                             "within the items")
+        items = items[:ptr[-1]]
+        if len(items) and (items.min() < 0 or items.max() >= self.n_items):
+            raise ValueError("prepare_pair_negatives: item ids must lie in [0, %d)" % self.n_items)
+        row = np.repeat(np.arange(len(ptr) - 1, dtype=np.int64), np.diff(ptr))
+        o = np.lexsort((items, row))
+        row, items = row[o], items[o]
+        if len(items):
+            keep = np.ones(len(items), dtype=bool)
+            keep[1:] = (row[1:] != row[:-1]) | (items[1:] != items[:-1])
+            row, items = row[keep], items[keep]
+        nptr = np.zeros(len(ptr), dtype=np.int64)
+        np.cumsum(np.bincount(row, minlength=len(ptr) - 1), out=nptr[1:])
+        if len(items) == 0:
+            items = np.zeros(1, dtype=np.int64)             # (a valid device pointer; every list is empty)
+        self._neg_csr = (torch.from_numpy(nptr.astype(np.int32)).to(self.device),
+                         torch.from_numpy(items.astype(np.int32)).to(self.device))
+        if seed is not None and int(seed) != self.seed:
+            self.seed, self.n_draws = int(seed), 0
+
+    def _prepare_route_pair(self, users, items, neg_items):
+        """The loader side of a pair step.  An interaction asks for TWO item rows -- its positive and its negative,
+        owners unrelated -- so the received rows cannot be lined up with the batch rows by sorting the batch: the
+        2 B_loc requests (positives, then negatives; a void row asks for no negative) are ordered by owner, the
+        packed rows come back in that order, and every batch row is told the SLOT of its positive and of its
+        negative row in the received block (neg_slot -1: void).  Every slot belongs to one request: an item asked for
+        twice travels twice and K7 merges its gradient rows.  The batch itself keeps the caller's order.
+        neg_items None: one negative per row is drawn here, on the device, from the lists of
+        prepare_pair_negatives -- here and not inside the captured step because the variable-size exchange needs
+        the per-owner counts on the host."""
+        W, B_loc, dev = self.world, self.B_loc, self.device
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        it = items.cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
+        u, it = u.astype(np.int32).reshape(-1), it.astype(np.int32).reshape(-1)
+        if len(u) != B_loc or len(it) != B_loc:
+            raise ValueError("prepare_route: B_loc = %d users and items per rank" % B_loc)
+        if len(it) and (it.min() < 0 or it.max() >= self.n_items):
+            raise ValueError("prepare_route: item ids must lie in [0, %d)" % self.n_items)
+        users_d = torch.from_numpy(np.ascontiguousarray(u)).to(dev)
+        urows = torch.zeros((B_loc,), dtype=torch.int32, device=dev)
+        self.be.shard_route(users_d, W, self.rank, 0, urows, None)         # all owned: local rows
+        if neg_items is None:
+            if self._neg_csr is None:
+                raise RuntimeError("prepare_route without neg_items draws the negatives: call "
+                                   "prepare_pair_negatives() first (after set_positives)")
+            drawn = torch.zeros((B_loc,), dtype=torch.int32, device=dev)
+            self.be.neg_draw_uniform(urows, self._neg_csr[0], self._neg_csr[1], self.n_items,
+                                     self.seed * 1000003 + self.rank, self.n_draws, drawn)
+            self.n_draws += 1
+            ng = drawn.cpu().numpy().astype(np.int32)
+        else:
+            ng = neg_items.cpu().numpy() if isinstance(neg_items, torch.Tensor) else np.asarray(neg_items)
+            ng = ng.astype(np.int32).reshape(-1)
+            if len(ng) != B_loc:
+                raise ValueError("prepare_route: one negative per interaction (%d for %d)" % (len(ng), B_loc))
+            if ng.max(initial=-1) >= self.n_items:
+                raise ValueError("prepare_route: negative ids must lie below %d (< 0: a void row)" % self.n_items)
+        live = ng >= 0
+        req = np.concatenate([it, ng[live]])                                # the requests: positives, live negatives
+        row_of_neg = np.nonzero(live)[0]
+        owner = req % W
+        perm = np.argsort(owner, kind='stable')
+        slot = np.empty(len(req), dtype=np.int32)
+        slot[perm] = np.arange(len(req), dtype=np.int32)                    # request -> its row of the received block
+        pos_slot = slot[:B_loc]
+        neg_slot = np.full(B_loc, -1, dtype=np.int32)
+        neg_slot[row_of_neg] = slot[B_loc:]
+        send = np.bincount(owner, minlength=W).astype(np.int64)
+        st = torch.from_numpy(send).to(dev)
+        rt = torch.empty_like(st)
+        _all_to_all(rt, st, group=self.group)
+        recv = [int(v) for v in rt.cpu().tolist()]
+        R = int(sum(recv))
+        self._alloc_recv(R)
+        req_d = torch.from_numpy(np.ascontiguousarray(req[perm])).to(dev)
+        recv_ids = torch.zeros((R,), dtype=torch.int32, device=dev)
+        _all_to_all(recv_ids, req_d, recv, [int(v) for v in send.tolist()], group=self.group)
+        recv_rows = torch.zeros((R,), dtype=torch.int32, device=dev)
+        if R > 0:
+            self.be.shard_route(recv_ids, W, self.rank, self.zero_row, recv_rows, None)
+        return {'users': users_d, 'items': torch.from_numpy(np.ascontiguousarray(it)).to(dev),
+                'neg_items': torch.from_numpy(np.ascontiguousarray(ng)).to(dev),
+                'slots': torch.from_numpy(np.concatenate([pos_slot, neg_slot])).to(dev), 'n_req': int(len(req)),
+                'send': [int(v) for v in send.tolist()], 'recv': recv, 'R': R, 'recv_ids': recv_ids,
+                'recv_rows': recv_rows, 'urows': urows}
+
+    def prepare_route(self, users, items, neg_items=None):
         """Data-loader side of a batch (host): orders the interactions by the owner of their
         target item and returns what the variable-size exchanges need.  One tiny all_to_all
-        of the per-destination counts (not on the step path)."""
+        of the per-destination counts (not on the step path).  A pair model ('bpr' / 'bpr-hinge') routes two rows per
+        interaction, the negatives fed (neg_items; < 0: a void row) or drawn: _prepare_route_pair."""
+        if self.pair:
+            return self._prepare_route_pair(users, items, neg_items)
+        if neg_items is not None:
+            raise ValueError("prepare_route: neg_items belong to the pair losses, this model trains %r"
+                             % self.loss_name)
         W = self.world
         u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
         it = items.cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
@@ -617,14 +772,19 @@ class ShardedHMF(object):
         return route
 
     # ------------------------------------------------------------------- step
-    def step(self, users, items=None):
+    def step(self, users, items=None, neg_items=None):
         """One training step.  `users` is either a route from prepare_route() (the fast way:
         nothing but kernels and collectives on the step path) or a users array with `items`
-        (routed here on the host)."""
-        if self.world > 1 and self.cap <= 0:
+        (routed here on the host; a pair model: with neg_items too, or drawn)."""
+        if self.world > 1 and self.cap <= 0 and not self.pair:
             raise RuntimeError("%s.step before set_pool(): the pool's block layout sizes the exchanges"
                                % type(self).__name__)
-        route = users if isinstance(users, dict) else self.prepare_route(users, items)
+        if isinstance(users, dict):
+            route = users
+        elif self.pair:
+            route = self.prepare_route(users, items, neg_items)
+        else:
+            route = self.prepare_route(users, items)
         if self.exchange == 'logits':
             return self._step_logits(route)
         self._run_step(route)
@@ -679,9 +839,9 @@ class ShardedHMF(object):
         be.transpose(self.logitsT, self.logits)
         w_rows.wait()
         dU = arena[:B_loc, :d]
-        be.loss_mw_fused_pos(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], self.urows,
-                             self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
-                             self.t_loc, self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
+        self._loss_fused(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], self.urows,
+                         self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
+                         self.t_loc, self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
         # ---- backward ----
         w_dt = _all_to_all(arena[B_loc + Sg:B_loc + Sg + R], self.dT_pack, recv, send, group=grp, async_op=True)
         be.transpose(self.dlogits, self.dlogitsT[:S])
@@ -714,10 +874,14 @@ class ShardedHMF(object):
     def _fused_scorer(self):
         """True when the step takes the bf16-pipe scorer (switches on, shapes it supports); allocates its buffers."""
         ops_ = getattr(self.be, 'ops', None)          # (the numpy test double has no kernels to pick from)
-        if ops_ is None or not ops_.mw_scorer_supported(self.B_loc, self.S, self.d):
+        if ops_ is None:
+            return False
+        # 'mce': the same surface (MceScorer: fwd() writes the COMPLETE latent gradient, bwd_dU(beta=1) adds nothing)
+        mce = self.loss_name == 'mce'
+        if not (ops_.mce_scorer_supported if mce else ops_.mw_scorer_supported)(self.B_loc, self.S, self.d):
             return False
         if getattr(self, 'scorer', None) is None:
-            self.scorer = ops_.MwScorer(self.B_loc, self.S, self.d, self.device)
+            self.scorer = (ops_.MceScorer if mce else ops_.MwScorer)(self.B_loc, self.S, self.d, self.device)
         return True
 
     @property
@@ -825,6 +989,8 @@ class ShardedHMF(object):
         large exchanges (target rows out, target-row gradients back: B_loc x (d+4) floats each) are issued
         asynchronously and waited for only where their result is needed, so that they travel under the scorer and
         under the two backward GEMMs.  Returns (graph key, body(mode)) for _run_step."""
+        if self.pair:
+            return self._step_body_pair(route)
         be, W = self.be, self.world
         B, B_loc, S, Sg, d = self.B, self.B_loc, self.S, self.Sg, self.d
         grp, dev = self.group, self.device
@@ -889,9 +1055,9 @@ class ShardedHMF(object):
                                 urows, self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.t_loc, dt, dU,
                                 dT[:, :d], 1.0 / B)
                 return
-            be.loss_mw_fused_pos(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], urows,
-                                 self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
-                                 self.t_loc, dt, dU, dT[:, :d], 1.0 / B)
+            self._loss_fused(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], urows,
+                             self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
+                             self.t_loc, dt, dU, dT[:, :d], 1.0 / B)
 
         def bwd_gemms():
             if fused:
@@ -970,6 +1136,106 @@ class ShardedHMF(object):
 
     def _static_feeds(self, route, cap_r):
         return []
+
+    def _step_body_pair(self, route):
+        """The 'bpr' / 'bpr-hinge' step (hmf_model.py:96-107 on the global batch, gscale = 1 / B), a body for the same
+        driver: no pool, so no scorer and no pool exchange -- lookups, ONE pair kernel, K7.
+
+          fwd_gather   user rows -> U_loc; the requested rows (positives and negatives of any rank) -> the send block
+          all_to_all   packed rows [2 B_loc - voids, d+4] out, in request order (route: slots)
+          pair         arx_pair_loss_slots: scores, loss, dU into the arena, (-c U | -c) and (c U | c) into the slots
+                       of the gradient block, the two integers of the auc
+          all_to_all   gradient rows back to the owners, into the K7 arena [dU ; received rows]
+          apply        one sparse_adagrad_multi over the user shard and the item shard: an item that is the positive
+                       of one row and the negative of another -- on any ranks -- is one merged key, one update
+
+        The per-batch vectors -- [user rows ; received rows, padded to cap_r with the shard's zero row] and the
+        2 B_loc slots -- are fed by the segment's first node; K7's ids-only half runs on the side stream.  World 1:
+        ONE graph, the rows gathered straight into the block the kernel reads and the gradient rows written straight
+        into the arena.  Rows of the blocks that no slot names (behind the requests of a batch with void rows) are
+        never read by the kernel, and their arena rows carry the padding key: K7 drops them."""
+        be, W = self.be, self.world
+        B, B_loc, d = self.B, self.B_loc, self.d
+        grp, dev = self.group, self.device
+        send, recv, R, n_req = route['send'], route['recv'], route['R'], route['n_req']
+        if R > self.cap_r:
+            self._alloc_recv(R)
+        cap_r = self.cap_r
+        n_idx = B_loc + cap_r
+        idx = route.get('idx')
+        if idx is None or idx.shape[0] != n_idx:
+            idx = torch.full((n_idx,), self.zero_row, dtype=torch.int32, device=dev)
+            idx[:B_loc] = route['urows']
+            if R > 0:
+                idx[B_loc:B_loc + R] = route['recv_rows']
+            route['idx'] = idx
+        if self.g_idx is None or self.g_idx.shape[0] != n_idx:
+            self.g_idx = torch.empty(n_idx, dtype=torch.int32, device=dev)
+        feed = [(idx, self.g_idx), (route['slots'], self.g_slots)]
+        key = ('pair', cap_r, self.g_idx.data_ptr(), self.arena.data_ptr(), self.g_slots.data_ptr())
+        arena, arena_b = self.arena, self.arena_b
+        urows, rrows = self.g_idx[:B_loc], self.g_idx[B_loc:]
+        self.urows = urows
+        ni = self.ni_loc
+        n_rows = 2 * B_loc if W == 1 else cap_r            # rows of the gather / of K7's item site
+        rrows = rrows[:n_rows]
+        dU = arena[:B_loc, :d]
+        T_in = self.R_pack if W == 1 else self.T_send[:cap_r]
+        dR = arena[B_loc:B_loc + 2 * B_loc] if W == 1 else self.dR_pack
+        pos_slot, neg_slot = self.g_slots[:B_loc], self.g_slots[B_loc:]
+        kind = self.loss_name
+
+        def fwd_gather():
+            be.gather_rows_multi([(self.E_user, None, urows, self.U_loc, None),
+                                  (self.E_item, self.b_item, rrows, T_in, 'packed')])
+
+        def pair():
+            be.pair_loss_slots(self.U_loc, self.R_pack, pos_slot, neg_slot, kind, 1.0 / B, self.pos_score,
+                               self.neg_score, self.bl, dU, dR, self.auc_counts)
+
+        def k7(phase):
+            be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
+                                     (self.E_item[:ni], self.A_item[:ni], self.b_item[:ni], self.Ab_item[:ni])],
+                                    [(0, urows, 0), (1, rrows, B_loc)], arena[:, :d], arena_b, self.lr, phase=phase)
+
+        def apply():
+            be.copy_strided(arena[B_loc:B_loc + n_rows, d], arena_b[B_loc:B_loc + n_rows])
+            k7(2)
+
+        def body(mode):
+            seg = lambda name, fn, feeds=None: self._segment(mode, name, fn, feeds)
+
+            def whole_step():
+                fwd_gather()
+                sorted_ = self._k7_sorts(mode, k7, False)
+                pair()
+                self._k7_join(sorted_)
+                apply()
+
+            if W == 1:
+                return seg('step', whole_step, feed)
+            seg('fwd_gather', fwd_gather, feed)
+            sorted_ = self._k7_sorts(mode, k7, True)
+            w_rows = _all_to_all(self.R_pack[:n_req], self.T_send[:R], send, recv, group=grp, async_op=True)
+            w_rows.wait()
+            seg('pair', pair)
+            w_dr = _all_to_all(arena[B_loc:B_loc + R], self.dR_pack[:n_req], recv, send, group=grp, async_op=True)
+            w_dr.wait()
+            self._k7_join(sorted_)
+            seg('apply', apply)
+
+        return key, body
+
+    def read_auc(self):
+        """auc of the last pair step over the global batch: 0.5 - 0.5 * mean sign(neg_score - pos_score) over the rows
+        that are not void (0.5 without such a row), as a python float.  A collective: the two integers of every rank
+        (sign sum, live rows) are summed first."""
+        if not self.pair:
+            raise RuntimeError("read_auc: a pair-loss model's figure, this model trains %r" % self.loss_name)
+        c = self.auc_counts.clone()
+        dist.all_reduce(c, op=dist.ReduceOp.SUM, group=self.group)
+        sg, cnt = (int(v) for v in c.cpu().tolist())
+        return 0.5 - 0.5 * sg / cnt if cnt > 0 else 0.5
 
     def read_loss(self):
         """Global mean loss of the last step (device scalar; one tiny all-reduce)."""
@@ -1245,11 +1511,15 @@ class ShardedHMF(object):
               'n_users': int(self.n_users), 'n_items': int(self.n_items)}
         if hasattr(self, 'n_tokens'):
             sc['n_tokens'] = int(self.n_tokens)
+        # the loss that trained the tables (a note: they restore into a model of any loss) and the pair draw's counter
+        sc['loss'] = self.loss_name
+        sc['n_draws'] = int(self.n_draws)
         return sc
 
     def _checkpoint_set_scalars(self, sc):
         self.steps = int(sc['steps'])
         self.lr.fill_(float(sc['learning_rate']))           # (in place: captured graphs read this word)
+        self.n_draws = int(sc.get('n_draws', self.n_draws)) # (a manifest from before the pair losses has none)
 
     def _checkpoint_restored(self):
         self.n_restores += 1                                # every ShardedHetView of this model is stale now
@@ -1302,9 +1572,9 @@ class ShardedHMFBags(ShardedHMF):
     moves 2 x B_loc x (d+4) x 4."""
 
     def __init__(self, n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, bags, n_tokens,
-                 backend=None, group=None, tables=None, seed=0, acc0=0.1, graphs=None):
+                 backend=None, group=None, tables=None, seed=0, acc0=0.1, graphs=None, loss='mw'):
         super().__init__(n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, backend=backend,
-                         group=group, tables=tables, seed=seed, acc0=acc0, graphs=graphs)
+                         group=group, tables=tables, seed=seed, acc0=acc0, graphs=graphs, loss=loss)
         dev, f32, i32 = self.device, torch.float32, torch.int32
         vals, starts, lens = [np.asarray(a) for a in bags]
         nt = (n_tokens - rank + world - 1) // world
@@ -1410,9 +1680,9 @@ class ShardedHMFBags(ShardedHMF):
                                 urows, self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.t_loc,
                                 self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
                 return
-            be.loss_mw_fused_pos(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], urows,
-                                 self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
-                                 self.t_loc, self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
+            self._loss_fused(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], urows,
+                             self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
+                             self.t_loc, self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
 
         def bwd():
             if fused:
@@ -1514,9 +1784,9 @@ class ShardedHMFRepTokens(ShardedHMF):
     _het = True
 
     def __init__(self, n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, bags, n_tokens,
-                 backend=None, group=None, tables=None, seed=0, acc0=0.1, graphs=None):
+                 backend=None, group=None, tables=None, seed=0, acc0=0.1, graphs=None, loss='mw'):
         super().__init__(n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, backend=backend,
-                         group=group, tables=tables, seed=seed, acc0=acc0, graphs=graphs)
+                         group=group, tables=tables, seed=seed, acc0=acc0, graphs=graphs, loss=loss)
         dev, f32, i32 = self.device, torch.float32, torch.int32
         vals, starts, lens = [np.asarray(a) for a in bags]
         nt = int(n_tokens)

@@ -338,6 +338,21 @@ def pair_loss(U, P, pbias, N, nbias, kind, gscale, pos_score, neg_score, batch_l
          _stream())
 
 
+def pair_loss_slots(U, R, pos_slot, neg_slot, kind, gscale, pos_score, neg_score, batch_loss, row_w=None, dU=None,
+                    acc_dU=False, dR=None, auc_counts=None):
+    """'bpr' / 'bpr-hinge' over packed rows named by slot (arx.h arx_pair_loss_slots): row r scores U[r] against
+    R[pos_slot[r]] and R[neg_slot[r]] (bias in column d) and writes their gradient rows to the same rows of dR.
+    neg_slot < 0: a void row.  No slot may be named twice.  auc_counts: int32 [2], (sign sum, live rows)."""
+    _chk(pos_slot, torch.int32, "pos_slot")
+    _chk(neg_slot, torch.int32, "neg_slot")
+    if pos_slot.shape[0] != U.shape[0] or neg_slot.shape[0] != U.shape[0]:
+        raise ValueError("pair_loss_slots: one positive and one negative slot per row of U")
+    call("arx_pair_loss_slots", _p(U), _ld(U), _p(R), _ld(R), int(R.shape[0]), _p(pos_slot), _p(neg_slot), _p(row_w),
+         int(U.shape[0]), int(U.shape[1]), PAIR_KINDS[kind], float(gscale), _p(pos_score), _p(neg_score),
+         _p(batch_loss), _p(dU), _ld(dU) if dU is not None else 0, int(bool(acc_dU)), _p(dR),
+         _ld(dR) if dR is not None else 0, _p(auc_counts), _stream())
+
+
 def pair_auc(pos_score, neg_score, neg_ids, out):
     """out[0] = 0.5 - 0.5 * mean sign(neg_score - pos_score) over the rows that are not void (arx.h)."""
     call("arx_pair_auc", _p(pos_score), _p(neg_score), _p(neg_ids), int(pos_score.shape[0]), _p(out), _stream())

@@ -229,6 +229,24 @@ int arx_pair_loss_fwdbwd(const float* U, int64_t ldu, const float* P, int64_t ld
                          const float* row_w, int64_t B, int d, int kind, float gscale, float* pos_score,
                          float* neg_score, float* batch_loss, float* dU, int64_t lddu, int acc_dU, float* dP,
                          int64_t lddp, float* dpbias, float* dN, int64_t lddn, float* dnbias, void* stream);
+/* The same arithmetic over PACKED rows named by slot -- the pair step of the row-sharded model (arx/dist.py), where
+ * the positive and the negative row of an interaction arrive as two rows of one received block.
+ *   R [n_slots, ldr]: packed rows, d values + the bias in column d (ldr >= d + 4);  P_r = R[pos_slot[r]],
+ *   N_r = R[neg_slot[r]];  scores, loss, c and dU as above.
+ *   dR [n_slots, lddr]: row pos_slot[r] = (-c U_r | -c in column d), row neg_slot[r] = (c U_r | c); columns behind d
+ *   and rows that no slot names are NOT written.
+ * PRECONDITION: every slot is named by at most one batch row (pos_slot and neg_slot together hold no slot twice) --
+ * then each row of dR has one writer: no atomics, bit-reproducible.  neg_slot[r] < 0: a void row -- the negative is
+ * not read, neg_score = 0, loss 0, dU keeps what acc_dU found, the positive's dR row is exact zeros.  A slot outside
+ * [0, n_slots) is never dereferenced (the row is void, the missing score 0).  dU and dR are both NULL (forward only)
+ * or both set.  auc_counts (nullable, int32 [2]): the sum of sign(neg_score - pos_score) and the number of rows that
+ * are not void, out of a second one-workgroup launch -- what a caller sums over its ranks before forming the auc
+ * of arx_pair_auc.  d % 4 == 0, d <= 256, leading dims % 4, 16-byte aligned matrices; B == 0 is legal and writes
+ * nothing. */
+int arx_pair_loss_slots(const float* U, int64_t ldu, const float* R, int64_t ldr, int64_t n_slots,
+                        const int32_t* pos_slot, const int32_t* neg_slot, const float* row_w, int64_t B, int d,
+                        int kind, float gscale, float* pos_score, float* neg_score, float* batch_loss, float* dU,
+                        int64_t lddu, int acc_dU, float* dR, int64_t lddr, int32_t* auc_counts, void* stream);
 /* hmf_model.py:107: *auc = 0.5 - 0.5 * mean_r sign(neg_score[r] - pos_score[r]) over the rows that are not void
  * (neg_ids nullable); no such row gives 0.5.  One workgroup, integer sums.  B == 0 leaves *auc alone. */
 int arx_pair_auc(const float* pos_score, const float* neg_score, const int32_t* neg_ids, int64_t B, float* auc,

@@ -4,6 +4,7 @@ HIP-event time of regions of --steps steps, the median of --repeats regions.  No
 
 usage: python tools/bench_bpr.py [--workloads c2,c3] [--steps 100] [--warmup 20] [--out FILE.json]
        python tools/bench_bpr.py --kernel-only        # the pair kernel alone (a run for rocprofv3 --kernel-trace --stats)
+       python tools/bench_bpr.py --sharded            # the world-1 ShardedHMF 'bpr' step at the C2 shape, fed and drawn
 """
 import argparse
 import gc
@@ -119,6 +120,69 @@ def run_workload(name, args, dev):
     return res
 
 
+def run_sharded(args, dev):
+    """The pair step of the row-sharded model on ONE rank (1-rank RCCL group: the exchanges are local copies) at the
+    C2 shape: negatives fed through routes prepared ahead (prepare_route is the loader side, off the step path) and
+    negatives drawn (the draw sits in prepare_route: route + step are timed together, and the route alone)."""
+    import time
+    import torch.distributed as dist
+    from arx.dist import ShardedHMF
+    from arx.utils.synthetic import SyntheticHMF
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", "29761")
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    B, d = args.batch, args.dim
+    syn = SyntheticHMF(n_users=args.n_users, n_items=args.n_items, permute_logits=False, seed=0,
+                       zipf_items=args.zipf_items)
+    rng = np.random.default_rng(1)
+    nb = 64
+    batches = []
+    for _ in range(nb):
+        u, i = syn.sample_batch(B, rng)
+        batches.append((u, i, rng.integers(0, args.n_items, size=B).astype(np.int32)))
+    res = {}
+    try:
+        for loss in [x for x in ('bpr', 'bpr-hinge') if x in args.losses.split(',')]:
+            model = ShardedHMF(args.n_users, args.n_items, d, B, 0, 0.1, 0, 1, dev, loss=loss, seed=1)
+            routes = [model.prepare_route(u, i, n) for u, i, n in batches]
+            with torch.cuda.stream(model.stream):                 # (saves the two stream joins per step)
+                res[loss + '_fed_ms'] = region_ms(lambda k: model.step(routes[k % nb]), args.steps, args.warmup,
+                                                  args.repeats)
+            res[loss + '_fed_loss'] = float(model.read_loss().item())
+            res[loss + '_n_captures'], res[loss + '_n_replays'] = model.n_captures, model.n_replays
+            if loss == 'bpr' and 'bpr-drawn' in args.losses.split(','):
+                ptr = np.concatenate([syn.pos_ptr[:args.n_users + 1], [syn.pos_ptr[args.n_users]]]).astype(np.int32)
+                model.set_positives(ptr, syn.pos_items)
+                model.prepare_pair_negatives()
+
+                def drawn(k):
+                    u, i, _ = batches[k % nb]
+                    model.step(model.prepare_route(u, i))
+                with torch.cuda.stream(model.stream):
+                    res['bpr_drawn_route_and_step_ms'] = region_ms(drawn, args.steps, args.warmup, args.repeats)
+                res['bpr_drawn_loss'] = float(model.read_loss().item())
+                res['auc_last_step'] = model.read_auc()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for k in range(args.steps):
+                    model.prepare_route(*batches[k % nb][:2])
+                torch.cuda.synchronize()
+                res['bpr_drawn_route_ms'] = (time.perf_counter() - t0) / args.steps * 1e3
+                t0 = time.perf_counter()
+                for k in range(args.steps):
+                    model.prepare_route(*batches[k % nb])
+                torch.cuda.synchronize()
+                res['bpr_fed_route_ms'] = (time.perf_counter() - t0) / args.steps * 1e3
+            del model, routes
+            gc.collect()
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+    finally:
+        dist.destroy_process_group()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--workloads', default='c2,c3')
@@ -134,13 +198,18 @@ def main():
     ap.add_argument('--losses', default='mw,bpr,bpr-drawn,bpr-hinge',
                     help="which steps to time ('bpr-drawn' needs 'bpr'); one loss alone gives a clean kernel trace")
     ap.add_argument('--kernel-only', action='store_true')
+    ap.add_argument('--sharded', action='store_true',
+                    help="the world-1 ShardedHMF pair step (C2 shape) instead of the single-GPU workloads")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     out = {'batch': args.batch, 'dim': args.dim, 'n_items': args.n_items, 'n_users': args.n_users,
            'steps': args.steps, 'repeats': args.repeats,
            'pair_kernel': pair_kernel_us(args.batch, args.dim, dev)}
-    if not args.kernel_only:
+    if args.sharded:
+        out['sharded_c2'] = run_sharded(args, dev)
+        print('sharded_c2', json.dumps(out['sharded_c2']), flush=True)
+    elif not args.kernel_only:
         for name in [w for w in args.workloads.split(',') if w]:
             out[name] = run_workload(name, args, dev)
             print(name, json.dumps(out[name]), flush=True)

@@ -56,9 +56,9 @@ class SparseSite(object):
 
     def __init__(self, table, kind, ids_node, maps, n, max_len, coef, node):
         self.table = table
-        self.kind = kind          # 'cat' | 'mulhot'
+        self.kind = kind          # 'cat' | 'mulhot' | 'window' (max_len one-hot lookups per gradient row: WindowEmbed)
         self.ids_node = ids_node
-        self.maps = maps          # cat: (cat_map,) ; mulhot: (vals, starts, lens)
+        self.maps = maps          # cat, window: (cat_map,) ; mulhot: (vals, starts, lens)
         self.n = n                # lookups (rows of the gradient source)
         self.cap = n if kind == 'cat' else n * max_len
         self.max_len = max_len
@@ -298,6 +298,49 @@ class EntityEmbed(Node):
                 col += f.d
             res.append(s)
         return res
+
+
+class WindowEmbed(EntityEmbed):
+    """The context window of the skip-gram / CBOW recommenders (cbow_model.py:83-90) as ONE lookup:
+        value[b] = base_scale * base[b] + out_scale * sum_{t < n} E[cat_map[ids[t * mb + b]]]      ([mb, d])
+    over the time-major id list of n * mb entries and ONE one-hot feature (arx_gather_window_fwd).  base: the user
+    half of the input embedding (a node of shape [mb, d], or None).  The n lookups of a batch row share one gradient
+    row, so the node's gradient is [mb, d] in the plan's arena and its K7 site (kind 'window') has n * mb keys over
+    mb source rows (arx_sparse_site_window); the base receives base_scale * grad."""
+
+    pregather = False             # not one of the plain one-hot leaves Plan._execute gathers in a shared launch
+
+    def __init__(self, rt, ids_node, feats, n, mb, out_scale=1.0, base=None, base_scale=1.0):
+        if len(feats) != 1 or feats[0].kind != 'cat':
+            raise NotImplementedError("WindowEmbed: exactly one one-hot feature")
+        if ids_node.shape[0] != n * mb:
+            raise ValueError("WindowEmbed: %d ids are not %d windows of %d" % (ids_node.shape[0], mb, n))
+        d = feats[0].d
+        if base is not None and base.shape != (mb, d):
+            raise ValueError("WindowEmbed: base must be [mb, d]")
+        Node.__init__(self, rt, (mb, d), (ids_node,) + ((base,) if base is not None else ()))
+        self.feats, self.concat, self.with_bias = feats, False, False
+        self.n_window, self.out_scale, self.base_scale = int(n), float(out_scale), float(base_scale)
+        self.bias_value = self.bias_grad = None
+        self.train_tables = True
+        self.bias_grad_used = False
+
+    def forward(self, train):
+        f = self.feats[0]
+        base = self.inputs[1].value if len(self.inputs) > 1 else None
+        ops.gather_window(f.table.E, f.maps[0], self.inputs[0].value, self.n_window, self.alloc_value(),
+                          scale=self.out_scale, base=base, base_scale=self.base_scale)
+
+    def backward(self):
+        if len(self.inputs) > 1 and self.inputs[1].requires_grad:
+            base = self.inputs[1]
+            ops.add_rows_bcast(self.base_scale, self.grad, base.grad_beta(), base.alloc_grad())
+
+    def sites(self):
+        f = self.feats[0]
+        s = SparseSite(f.table, 'window', self.inputs[0], f.maps, self.shape[0], self.n_window, self.out_scale, self)
+        s.bias_coef = 1.0
+        return [s]
 
 
 class Prediction(Node):
@@ -1053,6 +1096,7 @@ class Plan(object):
                 if id(n) in fetched:
                     continue
                 if (kinds in (('cat',), ('mulhot',), ('cat', 'mulhot')) and not n.concat
+                        and getattr(n, 'pregather', True)
                         and all(f.d == n.feats[0].d for f in n.feats)
                         and type(n.inputs[0]).__name__ in ('IdsInput', 'IdsSlice')
                         and n.inputs[0].value.dtype == torch.int32):
@@ -1163,6 +1207,8 @@ class Plan(object):
             return None
         if any(s.col_off != 0 for s in live):
             return None
+        if any(s.kind == 'window' for s in live):
+            return None                   # a context window: many keys per gradient row, the general pass (_apply_one)
         if self._bags_ok(live):
             return None                   # multi-hot table with its own two-stage pass (_bag_pass)
         return [s for s in live if s.kind == 'cat'], [s for s in live if s.kind != 'cat']
@@ -1628,6 +1674,8 @@ class Plan(object):
                 cs = bufs['coef'][s.key_off:s.key_off + s.cap]
                 if s.kind == 'cat':
                     ops.sparse_site_onehot(s.maps[0], s.ids_node.value, node.row0, s.coef, ks, ss, cs)
+                elif s.kind == 'window':
+                    ops.sparse_site_window(s.maps[0], s.ids_node.value, s.max_len, node.row0, s.coef, ks, ss, cs)
                 else:
                     ops.bag_expand_padded(s.maps[0], s.maps[1], s.maps[2], s.ids_node.value, s.max_len,
                                           node.row0, s.coef, ks, ss, cs)

@@ -128,6 +128,33 @@ def sparse_site_onehot(cat_map, ids, row_base, coef, keys_out, src_out, coef_out
          float(coef), _p(keys_out), _p(src_out), _p(coef_out), _stream())
 
 
+def sparse_site_window(cat_map, ids, n, row_base, coef, keys_out, src_out, coef_out):
+    """K7 contributions of a context-window lookup (arx_sparse_site_window): ids = n * mb time-major lookups, the n
+    lookups of batch row b share gradient row row_base + b."""
+    total, n = int(ids.shape[0]), int(n)
+    if n < 1 or total % n:
+        raise ValueError("sparse_site_window: %d ids are not n = %d windows" % (total, n))
+    if int(keys_out.shape[0]) < total:
+        raise ValueError("sparse_site_window: output buffers hold %d < %d entries" % (int(keys_out.shape[0]), total))
+    call("arx_sparse_site_window", _p(cat_map), _p(ids), n, total // n, int(row_base), float(coef),
+         _p(keys_out), _p(src_out), _p(coef_out), _stream())
+
+
+def gather_window(E, cat_map, ids, n, out, scale=1.0, base=None, base_scale=1.0):
+    """out[b] = base_scale * base[b] + scale * sum_t E[cat_map[ids[t * mb + b]]] (arx_gather_window_fwd): the
+    context window of mb = len(ids) / n batch rows in one launch; base: [mb, d] or None."""
+    _chk(E, torch.float32, 'E'); _chk(ids, torch.int32, 'ids'); _chk(out, torch.float32, 'out')
+    _chk(base, torch.float32, 'base')
+    total, n = int(ids.shape[0]), int(n)
+    if n < 1 or total % n or int(out.shape[0]) != total // n:
+        raise ValueError("gather_window: %d ids, n = %d, %d output rows" % (total, n, int(out.shape[0])))
+    if base is not None and tuple(base.shape) != (total // n, int(E.shape[1])):
+        raise ValueError("gather_window: base must be [mb, d]")
+    call("arx_gather_window_fwd", _p(E), _p(cat_map), _p(ids), n, total // n, int(E.shape[1]), float(scale),
+         _p(base), _ld(base) if base is not None else 0, float(base_scale), _p(out), _ld(out), _stream())
+    return out
+
+
 def shard_route(ids, world, rank, zero_row, rows_out, keys_out):
     call("arx_shard_route", _p(ids), int(ids.shape[0]), int(world), int(rank), int(zero_row),
          _p(rows_out), _p(keys_out), _stream())

@@ -8,8 +8,16 @@ The two models differ only in the item half of the input embedding:
 user's features).  With use_sep_item the context items read the 'item' tables and the scorer
 the separate 'item_output' tables (embed_attribute.py:96-108).  All n context lookups are ONE
 gather launch over the time-major id list; the mean over context positions is a column sum.
+Where the context items have exactly one one-hot feature and n >= 2 the whole input embedding
+x = 0.5 * user + (0.5 / n) * sum_t item_t is ONE launch (graph.WindowEmbed, fuse_window).
+
+Losses: 'warp', 'ce', 'bbpr' score the whole catalogue in training; 'mw' / 'mce' train on the sampled pool
+(n_sampled items, staged by step(item_sampled=...)) like the HMF model and only evaluate / recommend over the
+catalogue -- streamed, without [mb, V] logits, past ARX_STREAM_TOPK_BYTES.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -18,7 +26,7 @@ from .. import graph as G
 from .. import ops
 from ..attributes import embed_attribute
 from ..attributes.embed_attribute import Dropout
-from ..hmf.hmf_model import TopK, _Op, _Var
+from ..hmf.hmf_model import StreamTopK, TopK, _Op, _Var
 from ..utils.checkpoint import Saver
 
 
@@ -67,7 +75,7 @@ class LinearSeq(object):
                  item_ind2logit_ind=None, logit_ind2item_ind=None, n_input_items=0,
                  loss_function='ce', logit_size_test=None, dropout=1.0, top_N_items=100,
                  use_sep_item=True, n_sampled=None, output_feat=1, indices_item=None,
-                 dtype='float32', params=None, use_graph=True, seed=0, cbow=False):
+                 dtype='float32', params=None, use_graph=True, seed=0, cbow=False, fuse_window=None):
         self.user_size = user_size
         self.item_size = item_size
         self.top_N_items = top_N_items
@@ -89,10 +97,18 @@ class LinearSeq(object):
         self.batch_size = mb = batch_size
         self.dropout = dropout
         self.dtype = dtype
-        if loss not in ('warp', 'ce', 'bbpr'):
-            # 'mw' is accepted by the reference's constructor but `batch_loss_test` is never
-            # defined on that branch (skipgram_model.py:113-125): the graph cannot be built
-            raise NotImplementedError("loss %r (the reference builds 'warp', 'ce', 'bbpr' here)" % loss)
+        if loss not in ('warp', 'ce', 'bbpr', 'mw', 'mce'):
+            raise NotImplementedError("loss %r (built here: 'warp', 'ce', 'bbpr', 'mw', 'mce')" % loss)
+        sampled = loss in ('mw', 'mce')
+        if sampled:
+            # the reference builds sampled_logits / target_score / compute_loss(.., 'mw') for this family
+            # (skipgram_model.py:104-116, cbow_model.py:107-119) and only forgets to assign batch_loss_test on
+            # that branch; this build defines it: 'mw' evaluates with the full-vocabulary 'warp' (run_w2v.py:377),
+            # 'mce' (build-defined sampled softmax, arx.h) with the full softmax 'ce' (run_w2v.py:335,385)
+            if n_sampled is None:
+                raise ValueError("loss %r trains on the sampled pool: n_sampled must be given" % loss)
+            if int(n_sampled) <= 0 or int(n_sampled) % 4 != 0:
+                raise ValueError("n_sampled must be a positive multiple of 4, got %r" % (n_sampled,))
 
         self.rt = rt = G.Runtime(learning_rate=learning_rate, use_graph=use_graph)
         self._lr_decay = learning_rate_decay_factor
@@ -110,8 +126,15 @@ class LinearSeq(object):
         self.att_emb = m
         user, _ = m.get_batch_user(1.0, False)                                    # :80
         feats = m._select_feats(m.item_feats, m.item_attributes)
-        ctx_all = G.EntityEmbed(rt, m.input_all, feats, with_bias=False, out_scale=0.5 / n_input)
-        mean_all = ContextMean(rt, ctx_all, user, n_input, mb)
+        eligible = len(feats) == 1 and feats[0].kind == 'cat' and n_input >= 2
+        self.fuse_window = bool(eligible and (fuse_window is None or fuse_window))
+        if self.fuse_window:
+            # x = 0.5 * user + (0.5 / n) * sum_t item_t in one launch; one [mb, d] gradient row per window
+            mean_all = G.WindowEmbed(rt, m.input_all, feats, n_input, mb, out_scale=0.5 / n_input, base=user,
+                                     base_scale=0.5)
+        else:
+            ctx_all = G.EntityEmbed(rt, m.input_all, feats, with_bias=False, out_scale=0.5 / n_input)
+            mean_all = ContextMean(rt, ctx_all, user, n_input, mb)
         if cbow or n_input == 1:
             x_train = mean_all                                                    # cbow_model.py:87-90
         else:
@@ -121,17 +144,38 @@ class LinearSeq(object):
             rt.keep_prob = float(dropout)
             x_train = Dropout(rt, x_train)                                      # :88
         x_test = user if n_input_items == 0 else mean_all                         # :91-99
-        logits = m.get_prediction(x_train, output_feat=output_feat)
         logits_test = m.get_prediction(x_test, output_feat=output_feat)
-        batch_loss = m.compute_loss(logits, self.item_target, loss)
-        batch_loss_test = m.compute_loss(logits_test, self.item_target, loss)
+        stream_min = int(os.environ.get('ARX_STREAM_TOPK_BYTES', str(1 << 30)))
+        can_stream = isinstance(logits_test, G.Prediction)        # (output_feat 2 / 3 pool in score space)
+        if sampled:
+            # no [mb, V] node on the training side (skipgram_model.py:104-116)
+            sampled_logits = m.get_prediction(x_train, 'sampled', output_feat=output_feat)
+            target_score = m.get_target_score(x_train, self.item_id_target)
+            batch_loss = m.compute_loss(sampled_logits, target_score, loss)
+            loss_eval = 'warp' if loss == 'mw' else 'ce'
+            if can_stream and mb * self.logit_size * 4 > stream_min:
+                ms = m._mask_state('warp', mb) if loss_eval == 'warp' else None
+                batch_loss_test = G.StreamEvalLoss(rt, loss_eval, x_test, logits_test.inputs[1], self.item_target,
+                                                   mask=ms, mask_rows=mb if ms is not None else 0)
+            else:
+                batch_loss_test = m.compute_loss(logits_test, self.item_target, loss_eval)
+        else:
+            logits = m.get_prediction(x_train, output_feat=output_feat)
+            batch_loss = m.compute_loss(logits, self.item_target, loss)
+            batch_loss_test = m.compute_loss(logits_test, self.item_target, loss)
         self.set_mask, self.reset_mask = {}, {}
-        if loss in ('warp', 'bbpr'):
+        if loss in ('warp', 'bbpr', 'mw', 'mce'):
             self.set_mask, self.reset_mask = m.get_warp_mask()
         self.loss = G.MeanLoss(rt, batch_loss)
         self.loss_test = G.MeanLoss(rt, batch_loss_test)
         self.output = logits_test
-        self.topk = TopK(rt, logits_test, min(top_N_items, self.logit_size))       # :135
+        kk = min(top_N_items, self.logit_size)
+        fused_ok = self.logit_size > 65536 and x_test.shape[1] in (32, 64, 128)
+        if can_stream and kk <= 1024 and (mb * self.logit_size * 4 > stream_min or fused_ok):
+            # the rule of hmf_model.py: streaming scorer + top-k instead of [mb, V] logits
+            self.topk = StreamTopK(rt, x_test, logits_test.inputs[1], kk)
+        else:
+            self.topk = TopK(rt, logits_test, kk)                                  # :135
         self.indices = self.topk
         self._plans = {}
         self.saver = Saver(self)
@@ -148,18 +192,43 @@ class LinearSeq(object):
     def _plan(self, key):
         if key not in self._plans:
             rt, m, loss = self.rt, self.att_emb, self.loss_function
-            masks = [m.mask[loss]] if loss in m.mask else []
             if key == 'train':
+                masks = [m.mask[loss]] if loss in m.mask else []
                 self._plans[key] = G.Plan(rt, [self.loss], True, masks)
             elif key == 'eval':
+                l = 'warp' if loss == 'mw' else ('ce' if loss == 'mce' else loss)
+                masks = [m.mask[l]] if l in m.mask else []
+                if isinstance(self.loss_test.inputs[0], G.StreamEvalLoss):
+                    masks = []                 # the streaming loss reads the positives CSR itself
                 self._plans[key] = G.Plan(rt, [self.loss_test], False, masks)
             elif key == 'recommend_ex':
                 if getattr(self, 'topk_ex', None) is None:      # the excluding twin of self.topk, on first use
-                    self.topk_ex = TopK(rt, self.topk.inputs[0], self.topk.k, exclude=m.exclusion_args)
+                    t = self.topk
+                    if isinstance(t, StreamTopK):
+                        self.topk_ex = StreamTopK(rt, t.inputs[0], t.inputs[1], t.k, chunk=t.chunk,
+                                                  exclude=m.exclusion_args, share=t)
+                    else:
+                        self.topk_ex = TopK(rt, t.inputs[0], t.k, exclude=m.exclusion_args)
                 self._plans[key] = G.Plan(rt, [self.topk_ex], False, [])
             else:
                 self._plans[key] = G.Plan(rt, [self.topk], False, [])
         return self._plans[key]
+
+    def _recommend(self, key):
+        """Run the 'recommend' / 'recommend_ex' plan; a streaming top-k whose fused candidate lists overflowed runs
+        once more on the chunked path (as LatentProductModel.step)."""
+        self._plan(key).run()
+        node = self.topk_ex if key == 'recommend_ex' else self.topk
+        if isinstance(node, StreamTopK) and node.overflowed():
+            node.fused = False
+            self._plans.pop(key, None)
+            try:
+                self._plan(key).run()          # (the placeholders still hold this request's ids)
+                return node.indices.cpu().numpy()
+            finally:
+                node.fused = True
+                self._plans.pop(key, None)
+        return node.indices.cpu().numpy()
 
     def step(self, session, user_input, item_input=None, item_output=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
@@ -167,27 +236,36 @@ class LinearSeq(object):
         """linear_seq.py:67-121.  item_input: [n_input][mb] context items (time-major);
         item_output: [mb] target items.  Returns the mean loss (train / forward_only) or the
         top-N logit indices [mb, top_N] (recommend; exclude_seen=True: without each user's items of
-        prepare_recommend_exclusions, -1 where a user has fewer eligible items)."""
+        prepare_recommend_exclusions, -1 where a user has fewer eligible items).
+        'mw' / 'mce': item_sampled (n_sampled item ids) stages a new pool -- the first training step needs one,
+        later steps keep it until the next is given (run_w2v.py:315-317); item_sampled_id2idx is the host twin of
+        the pool's item -> slot map.  forward_only evaluates 'mw' with the full-vocabulary 'warp' loss and 'mce'
+        with 'ce' (the runner passes loss='warp' there, run_w2v.py:377)."""
         m = self.att_emb
+        sampled = self.loss_function in ('mw', 'mce')
         if recommend_new:
             raise NotImplementedError("indices_test is never built by the reference (linear_seq.py:98)")
         if recommend and exclude_seen:
             m.exclusion_args()                 # ValueError before any feed when nothing was prepared
+        if sampled and not (recommend or forward_only) and item_sampled is None and m._old_pool is None:
+            raise ValueError("the first %r training step needs item_sampled (the pool of n_sampled items)"
+                             % self.loss_function)
         if not recommend:
             if isinstance(item_output, torch.Tensor):
                 self.item_id_target.feed(item_output)
                 m.target_mapping_device(self.item_id_target.value, self.item_target.value)
             else:
                 self.item_target.feed(m.target_mapping([item_output])[0])          # :76-77
-        m.add_input({}, user_input, item_input, neg_item_input=None, item_sampled=item_sampled,
-                    item_sampled_id2idx=item_sampled_id2idx, forward_only=forward_only,
-                    recommend=recommend, loss=loss or self.loss_function)
-        if recommend and exclude_seen:
-            self._plan('recommend_ex').run()
-            return self.topk_ex.indices.cpu().numpy()
+                if sampled:
+                    self.item_id_target.feed(item_output)                          # raw ids: the target score (:79-80)
+        update_sampled, _, _ = m.add_input({}, user_input, item_input, neg_item_input=None,
+                                           item_sampled=item_sampled, item_sampled_id2idx=item_sampled_id2idx,
+                                           forward_only=forward_only, recommend=recommend,
+                                           loss=loss or self.loss_function)
+        for op in update_sampled:              # stage the pool (embed_attribute.py:320-348)
+            op()
         if recommend:
-            self._plan('recommend').run()
-            return self.topk.indices.cpu().numpy()
+            return self._recommend('recommend_ex' if exclude_seen else 'recommend')
         if forward_only:
             self._plan('eval').run()
             return float(self.loss_test.read().item())

@@ -71,6 +71,12 @@ int arx_bag_expand_padded(const int32_t* vals, const int32_t* starts, const int3
 int arx_sparse_site_onehot(const int32_t* cat_map, const int32_t* ids, int64_t n,
                            int32_t row_base, float coef, int32_t* keys_out, int32_t* src_out,
                            float* coef_out, void* stream);
+/* The same for a context WINDOW (arx_gather_window_fwd): ids is the time-major list of n * mb lookups and all n
+ * lookups of batch row b share ONE gradient row.  For k < n * mb: keys_out[k] = cat_map ? cat_map[ids[k]] : ids[k]
+ * (ARX_KEY_NONE for ids[k] < 0), src_out[k] = row_base + k % mb, coef_out[k] = coef (src_out / coef_out nullable).
+ * n >= 1, n * mb < 2^31. */
+int arx_sparse_site_window(const int32_t* cat_map, const int32_t* ids, int n, int64_t mb, int32_t row_base,
+                           float coef, int32_t* keys_out, int32_t* src_out, float* coef_out, void* stream);
 
 /* Row-sharded item table: table rows are striped over the
  * ranks, owner = id % world, local row = id / world.  rows_out[i] = local row if
@@ -125,6 +131,17 @@ int arx_rows_fingerprint(const float* x, int64_t ldx, int64_t rows, int64_t widt
 int arx_gather_onehot_fwd(const float* E, const float* bias, const int32_t* cat_map,
                           const int32_t* ids, int64_t B, int d, float scale, int accumulate,
                           float* out, int64_t ldo, float* bias_out, void* stream);
+
+/* The context window of the skip-gram / CBOW recommenders (word2vec/cbow_model.py:83-90) in one launch:
+ *   out[b, 0:d] = base_scale * base[b, 0:d] + scale * sum_{t < n} E[cat_map[ids[t * mb + b]], :],   b < mb
+ * ids: the time-major int32 list of n * mb lookups; cat_map may be NULL (identity); ids and rows are not range
+ * checked, exactly as in arx_gather_onehot_fwd.  base (nullable; then ldb / base_scale are ignored): [mb, >= d]
+ * rows ldb floats apart -- the user half of the input embedding.  The sum over t runs in ascending t in fp32 in
+ * one lane, without atomics: the result does not depend on the launch shape.  n >= 1, n * mb < 2^31, d % 4 == 0,
+ * d <= 256 (else ARX_EUNSUPPORTED), ldo / ldb % 4 == 0 and >= d, E / base / out 16-byte aligned (ARX_EINVAL). */
+int arx_gather_window_fwd(const float* E, const int32_t* cat_map, const int32_t* ids, int n, int64_t mb, int d,
+                          float scale, const float* base, int64_t ldb, float base_scale, float* out, int64_t ldo,
+                          void* stream);
 
 /* Packed form for the sharded exchanges (no reference counterpart): row r of the
  * output holds [ scale * E[row] (d floats) | scale * bias[row] | pad ], ldo > d -- the bias rides

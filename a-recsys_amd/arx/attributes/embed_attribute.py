@@ -23,6 +23,11 @@ import torch
 
 from .. import graph as G
 from .. import ops
+from ..topk import logits_too_big
+
+# the full-vocabulary loss a model trained with a sampled loss evaluates with (hmf_model.py:130,144; 'mce' -> 'ce':
+# run_hmf.py:255,304)
+EVAL_LOSS_OF = {'mw': 'warp', 'mce': 'ce'}
 
 
 def _np_i32(x):
@@ -566,6 +571,27 @@ class EmbeddingAttribute(object):
             return G.BatchLoss(self.rt, loss, logits, item_target, mask=ms, mask_rows=self.batch_size,
                                loss_func=loss_func, exp_p=exp_p)
         raise NotImplementedError('Error: not implemented other loss!!')   # :548
+
+    def sampled_eval_loss(self, loss, latent, logits, item_target, rows, mask_rows, pool=None, masked=True):
+        """The dev loss of a model that trains with the sampled `loss` ('mw' / 'mce'): EVAL_LOSS_OF[loss] over the
+        full vocabulary -- streamed from `latent` and `pool` (the full pool's embedding node; None: the output
+        features cannot stream) where the [rows, V] `logits` are too big, on the logits otherwise.  'warp' masks
+        the user's positives (mask rows repeat every mask_rows) unless masked is False; 'ce' never takes a mask."""
+        kind = EVAL_LOSS_OF[loss]
+        ms = self._mask_state('warp', rows) if kind == 'warp' and masked else None
+        if pool is not None and logits_too_big(rows, self.logit_size):
+            return G.StreamEvalLoss(self.rt, kind, latent, pool, item_target, mask=ms, mask_rows=mask_rows)
+        if kind == 'warp' and not masked:
+            return G.BatchLoss(self.rt, 'warp', logits, item_target, mask=None, mask_rows=mask_rows)
+        return self.compute_loss(logits, item_target, kind)
+
+    def eval_masks(self, loss, batch_loss):
+        """The mask list of the plan that evaluates `batch_loss`, the dev loss of a `loss` model (a streamed loss
+        reads the positives CSR itself)."""
+        kind = EVAL_LOSS_OF.get(loss, loss)
+        if isinstance(batch_loss, G.StreamEvalLoss) or kind not in self.mask:
+            return []
+        return [self.mask[kind]]
 
     def get_warp_mask(self, device='/gpu:0'):
         """embed_attribute.py:662-672 -> (set_mask, reset_mask) callables per loss."""

@@ -42,6 +42,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops as _ops
+from .topk import TopKScan, run_complete
 
 
 class _Done(object):
@@ -276,12 +277,11 @@ class HipBackend(object):
     def shard_topk(self, U, E, bias, k, ex, values, indices, lse=None):
         """Recommend's local stage: values / indices [B, k] = every row's k best of U . E^T + bias over the shard's
         rows, by (value desc, local column asc); ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols of local
-        columns) or None.  The streaming top-k of StreamTopK (hmf_model.TopKScan: fused filter GEMM, the chunked path
+        columns) or None.  The streaming top-k of StreamTopK (topk.TopKScan: fused filter GEMM, the chunked path
         after an overflow or for shapes the fused kernel does not take); a shard with fewer than k rows fills the rest
         with (-inf, -1).  lse [B] (optional): the log-sum-exp of every row's logits over ALL the shard's rows, excluded
         ones included (TopKScan's want_lse); -inf for a shard without rows.  Buffers and GEMM workspace are this
         stage's own (captured step graphs keep theirs)."""
-        from .hmf.hmf_model import TopKScan
         ops = self.ops
         B, V, d = int(U.shape[0]), int(E.shape[0]), int(U.shape[1])
         if getattr(self, 'ws_rec', None) is None:
@@ -307,13 +307,8 @@ class HipBackend(object):
                 scan.short = (torch.empty((B, kk), dtype=torch.float32, device=U.device),
                               torch.empty((B, kk), dtype=torch.int32, device=U.device))
         vo, io = (values, indices) if kk == k else scan.short
-        scan.run(U, E, bias, self.ws_rec, vo, io, ex)
-        if scan.overflowed():                 # a candidate segment was too short: this rank once more, chunked
-            scan.fused = False
-            try:
-                scan.run(U, E, bias, self.ws_rec, vo, io, ex)
-            finally:
-                scan.fused = True
+        # (a candidate segment too short: this rank once more, chunked)
+        run_complete(scan, lambda: scan.run(U, E, bias, self.ws_rec, vo, io, ex))
         if kk < k:
             values[:, :kk].copy_(vo)
             indices[:, :kk].copy_(io)
@@ -2721,10 +2716,11 @@ class SeqHybridParallel(SeqDataParallel):
 
         Rows of weight 0 (positions past a sequence's end) are scored like any other and weigh nothing."""
         from . import graph as G, ops
+        from .attributes.embed_attribute import EVAL_LOSS_OF
         from .lstm.seqModel import SeqWeights
         model, rt, W, r = self.model, self.rt, self.world, self.rank
         m, dev = model.att_emb, self.rt.device
-        kind = {'mw': 'warp', 'mce': 'ce'}.get(model.loss)
+        kind = EVAL_LOSS_OF.get(model.loss)
         if kind is None:
             raise NotImplementedError("SeqHybridParallel: the dev loss of models trained with 'mw' / 'mce' only "
                                       "(full-vocabulary training losses are not striped)")

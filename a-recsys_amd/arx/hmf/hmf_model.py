@@ -10,14 +10,13 @@ from __future__ import annotations
 
 import random
 
-import os
-
 import numpy as np
 import torch
 
 from .. import graph as G
 from .. import ops
 from ..attributes import embed_attribute
+from ..topk import StreamTopK, TopK, TopKScan, excluding_twin, recommend_node, run_complete  # noqa: F401 (re-exported)
 from ..utils.checkpoint import Saver
 
 
@@ -126,183 +125,6 @@ class MLP(G.Node):
             p.touched = True
 
 
-class TopK(G.Node):
-    """hmf_model.py:154 tf.nn.top_k(logits, top_N_items, sorted=True).
-    exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
-    each row's excluded columns are set to -inf IN the logits before the select (nothing after this node may read
-    them), and winners of value -inf (rows with fewer than k eligible columns) get index -1."""
-
-    def __init__(self, rt, logits, k, exclude=None):
-        super().__init__(rt, (logits.shape[0], k), (logits,))
-        self.k = k
-        self.exclude = exclude
-        self.indices = torch.empty((logits.shape[0], k), dtype=torch.int32, device=rt.device)
-
-    def forward(self, train):
-        x = self.inputs[0].value
-        if self.exclude is not None:
-            ops.topk_exclude_fill(x, 0, self.exclude())
-        ops.topk(x, self.k, self.alloc_value(), self.indices)
-        if self.exclude is not None:
-            ops.topk_mark_empty(self.value, self.indices)
-
-
-class TopKScan(object):
-    """The streaming full-vocabulary top-k of StreamTopK without a Runtime: its buffers and its algorithm on plain
-    tensors, run(latent, pool, bias, ...) -- StreamTopK runs on it, and so does the per-shard stage of the row-sharded
-    recommend (arx.dist.ShardedHMF.recommend), whose tables are no graph nodes.  B rows, V pool rows of width d."""
-
-    def __init__(self, B, V, d, k, device, chunk=65536, want_lse=False, share=None):
-        self.k, self.chunk = k, max(int(chunk), k)
-        self._rows, self._dev = B, device
-        # want_lse: also self.lse [B] = log sum exp over ALL the row's logits (seqModel.py:514-517 reports the winners'
-        # softmax values exp(v - lse)): per column range out of the fused GEMM / per chunk, combined at the end
-        self.want_lse = bool(want_lse)
-        self.lse = torch.empty(B, dtype=torch.float32, device=device) if want_lse else None
-        self._lse_parts = None
-        dev = device
-        f32, i32 = torch.float32, torch.int32
-        self.indices = torch.empty((B, k), dtype=i32, device=dev)
-        if share is not None and tuple(share._buf.shape) == (B, min(self.chunk, V)):
-            self._buf = share._buf
-        else:
-            self._buf = torch.empty((B, min(self.chunk, V)), dtype=f32, device=dev)
-        self._cv, self._ci = torch.empty((B, k), dtype=f32, device=dev), torch.empty((B, k), dtype=i32, device=dev)
-        self._ov, self._oi = torch.empty((B, k), dtype=f32, device=dev), torch.empty((B, k), dtype=i32, device=dev)
-        tail = V % self.chunk                       # a last chunk narrower than k keeps only `tail` entries
-        kt = tail if 0 < tail < k else k
-        self._tv, self._ti = torch.empty((B, kt), dtype=f32, device=dev), torch.empty((B, kt), dtype=i32, device=dev)
-        self.fused = os.environ.get('ARX_TOPK_FUSED', '1') != '0' and d in (32, 64, 128)
-        self.overflow = torch.zeros(1, dtype=i32, device=dev)
-        self.slack, self.min_capp = 4.0, 32          # candidate segment = slack x the expected survivors, >= min_capp
-        self._cand = None
-
-    def _cand_bufs(self, n0, V):
-        """Candidate rows [B, parts * capp]: a column range's expected survivors are k (V - n0) / n0 / parts (scores in
-        no particular order along the vocabulary); four times that, at least 32."""
-        key = (n0, V, self.slack, self.min_capp)
-        if self._cand is None or self._cand[0] != key:
-            B, k, dev = self._rows, self.k, self._dev
-            parts = ops.gemm_nt_topk_parts(B, V - n0)
-            expect = k * (V - n0) / float(n0) / parts
-            capp = self.min_capp
-            while capp < self.slack * expect + self.min_capp:
-                capp *= 2
-            while parts * capp < k:
-                capp *= 2
-            cap = parts * capp
-            self._cand = (key, capp, torch.empty((B, cap), dtype=torch.float32, device=dev),
-                          torch.zeros((B, cap), dtype=torch.int32, device=dev),
-                          torch.empty((B, k), dtype=torch.int32, device=dev), parts)
-        return self._cand[1:]
-
-    def _lse_buf(self, ncols):
-        if self._lse_parts is None or self._lse_parts.shape[1] != ncols:
-            B, dev = self._rows, self._dev
-            self._lse_parts = torch.empty((B, ncols), dtype=torch.float32, device=dev)
-            self._lse0 = torch.empty(B, dtype=torch.float32, device=dev)
-        return self._lse_parts
-
-    def overflowed(self):
-        """True when the last fused run dropped candidates (device -> host read)."""
-        return bool(self.fused and int(self.overflow.item()) != 0)
-
-    def run(self, latent, pool, bias, ws, values, indices, ex=None):
-        """values / indices [B, k] = the top-k of latent . pool^T + bias (bias may be None) over all V >= k pool rows;
-        ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace."""
-        V, k = pool.shape[0], self.k
-        run_v, run_i = values, indices
-        out_v, out_i = self._ov, self._oi
-        if self.fused and V > self.chunk and pool.stride(0) % 4 == 0 and latent.stride(0) % 4 == 0:
-            n0 = self.chunk
-            lg = self._buf[:, :n0]
-            ops.gemm(latent, pool[:n0], lg, ws, transB=True, col_bias=bias[:n0] if bias is not None else None)
-            capp, cand_v, cand_i, cpos, parts = self._cand_bufs(n0, V)
-            lp = None
-            if self.want_lse:
-                lp = self._lse_buf(parts + 1)
-                ops.row_logsumexp(lg, self._lse0)               # (over the whole chunk: before the exclusion fill)
-                lp[:, parts].copy_(self._lse0)
-            if ex is not None:
-                ops.topk_exclude_fill(lg, 0, ex)                # threshold = the k-th best ELIGIBLE column
-            ops.topk_chunk(lg, k, 0, run_v, run_i)
-            ops.fill_f32(cand_v.view(-1), float('-inf'))
-            ops.fill_i32(self.overflow, 0)
-            if ex is not None:
-                ops.gemm_nt_topk_filter_excl(latent, pool[n0:], bias[n0:] if bias is not None else None,
-                                             run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, ex,
-                                             lse_part=lp)
-            else:
-                ops.gemm_nt_topk_filter(latent, pool[n0:], bias[n0:] if bias is not None else None,
-                                        run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, lse_part=lp)
-            if self.want_lse:
-                ops.row_logsumexp(lp, self.lse)
-            ops.topk_chunk(cand_v, k, 0, self._cv, cpos)
-            ops.take_rows_i32(cand_i, cpos, self._ci)
-            ops.topk_merge(run_v, run_i, self._cv, self._ci, k, out_v, out_i)
-            values.copy_(out_v)
-            indices.copy_(out_i)
-            if ex is not None:
-                ops.topk_mark_empty(values, indices)
-            return
-        nch = (V + self.chunk - 1) // self.chunk
-        lp = self._lse_buf(nch) if self.want_lse else None
-        for c0 in range(0, V, self.chunk):
-            c1 = min(V, c0 + self.chunk)
-            kc = min(k, c1 - c0)
-            lg = self._buf[:, :c1 - c0]
-            ops.gemm(latent, pool[c0:c1], lg, ws, transB=True, col_bias=bias[c0:c1] if bias is not None else None)
-            if self.want_lse:
-                ops.row_logsumexp(lg, self._lse0)
-                lp[:, c0 // self.chunk].copy_(self._lse0)
-            if ex is not None:
-                ops.topk_exclude_fill(lg, c0, ex)
-            if c0 == 0:                              # chunk >= k and V >= k: the first chunk fills all k
-                ops.topk_chunk(lg, k, 0, run_v, run_i)
-                continue
-            cv, ci = (self._cv, self._ci) if kc == k else (self._tv, self._ti)
-            ops.topk_chunk(lg, kc, c0, cv, ci)
-            ops.topk_merge(run_v, run_i, cv, ci, k, out_v, out_i)
-            run_v, out_v = out_v, run_v
-            run_i, out_i = out_i, run_i
-        if run_v.data_ptr() != values.data_ptr():
-            values.copy_(run_v)
-            indices.copy_(run_i)
-        if ex is not None:
-            ops.topk_mark_empty(values, indices)
-        if self.want_lse:
-            ops.row_logsumexp(lp, self.lse)
-
-
-class StreamTopK(G.Node, TopKScan):
-    """top_k over the FULL vocabulary without the [mb, V] logits -- same indices / values as
-    TopK(Prediction), tf.nn.top_k's tie rule included.
-    fused (round 5, the default where the scorer GEMM's small-K kernel applies): the first chunk of the pool gives
-    every row its k best (GEMM -> radix select); the scorer GEMM over ALL the other columns then writes no logits --
-    arx_gemm_nt_topk_filter keeps only what beats the row's k-th best so far, as short candidate lists in column order;
-    one select over the lists and one merge finish.  A candidate list that overflows (scores rising along the
-    vocabulary) sets a flag: overflowed() -- LatentProductModel.step re-runs the request on the chunked path.
-    chunked: the GEMM runs over chunks of the pool rows, every chunk keeps its k best per row (radix select) and a
-    merge folds them into the running result.
-    exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
-    each row's excluded columns never enter the result (the first chunk and every chunked-path chunk are filled with
-    -inf at them, the fused GEMM's candidates skip them); winners of value -inf get index -1.  The log-sum-exp
-    (want_lse) stays over ALL the columns.  share: another StreamTopK over the same shapes whose logits chunk buffer
-    this one re-uses (plans run one after the other on one stream).  The algorithm and its buffers: TopKScan."""
-
-    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None):
-        G.Node.__init__(self, rt, (latent.shape[0], k), (latent, pool))
-        TopKScan.__init__(self, latent.shape[0], pool.shape[0], latent.shape[1], k, rt.device, chunk=chunk,
-                          want_lse=want_lse, share=share)
-        self.exclude = exclude
-        self.fused = self.fused and pool.shape[1] == latent.shape[1]
-
-    def forward(self, train):
-        latent, pool = self.inputs
-        ex = self.exclude() if self.exclude is not None else None
-        self.run(latent.value, pool.value, pool.bias_value, self.rt.ws, self.alloc_value(), self.indices, ex)
-
-
 class LatentProductModel(object):
     def __init__(self, user_size, item_size, size, num_layers, batch_size, learning_rate,
                  learning_rate_decay_factor, user_attributes=None, item_attributes=None,
@@ -392,34 +214,18 @@ class LatentProductModel(object):
         logits = m.get_prediction(embedded_user)                              # :118
         self.output = logits
         batch_loss_eval = None
-        # [mb, V] logits of the evaluation loss are streamed, not materialised, past this size
-        stream_eval = batch_size * self.logit_size * 4 > int(os.environ.get('ARX_STREAM_TOPK_BYTES', str(1 << 30)))
         if loss in ('warp', 'ce', 'rs', 'rs-sig', 'rs-sig2', 'bbpr'):            # :121-122
             batch_loss = m.compute_loss(logits, self.item_target, loss, loss_func=self.loss_func,
                                         exp_p=self.loss_exp_p)
         elif loss == 'warp_eval':
             batch_loss, _ = m.compute_loss(logits, self.item_target, loss)
-        elif loss == 'mw' and stream_eval:
+        elif loss in ('mw', 'mce'):
+            # 'mce': build-defined sampled softmax (the reference has no arithmetic for it, see arx.h): trains like
+            # 'mw' on the sampled pool; evaluates with the full softmax 'ce', the loss run_hmf.py:255,304 groups it with
             batch_loss = m.compute_loss(sampled_logits, target_score, loss)
-            ms = None if self.mw_eval_unmasked else m._mask_state('warp', batch_size)
-            batch_loss_eval = G.StreamEvalLoss(rt, 'warp', embedded_user, m._pool_embed('full', 1),
-                                               self.item_target, mask=ms, mask_rows=batch_size)
-        elif loss == 'mce' and stream_eval:
-            batch_loss = m.compute_loss(sampled_logits, target_score, loss)
-            batch_loss_eval = G.StreamEvalLoss(rt, 'ce', embedded_user, m._pool_embed('full', 1), self.item_target)
-        elif loss == 'mw':
-            batch_loss = m.compute_loss(sampled_logits, target_score, loss)
-            if self.mw_eval_unmasked:
-                batch_loss_eval = G.BatchLoss(rt, 'warp', logits, self.item_target, mask=None,
-                                              mask_rows=batch_size)
-            else:
-                batch_loss_eval = m.compute_loss(logits, self.item_target, 'warp')  # :130
-        elif loss == 'mce':
-            # build-defined sampled softmax (the reference has no arithmetic for 'mce', see arx.h):
-            # trains like 'mw' on the sampled pool; evaluates with the full softmax 'ce', the loss
-            # run_hmf.py:255,304 groups it with
-            batch_loss = m.compute_loss(sampled_logits, target_score, loss)
-            batch_loss_eval = m.compute_loss(logits, self.item_target, 'ce')
+            batch_loss_eval = m.sampled_eval_loss(loss, embedded_user, logits, self.item_target, batch_size,  # :130
+                                                  batch_size, m._pool_embed('full', 1),
+                                                  masked=not self.mw_eval_unmasked)
         elif loss in ('bpr', 'bpr-hinge'):                                       # :132-133
             # one launch forms both scores, the loss and every gradient; no [mb, V] logits in training
             batch_loss = m.compute_loss(neg_pos, self.item_target, loss)
@@ -434,16 +240,7 @@ class LatentProductModel(object):
         self.loss = G.MeanLoss(rt, batch_loss)                                # :140
         self.loss.lazy = True
         self.loss_eval = G.MeanLoss(rt, batch_loss_eval) if loss in ('mw', 'mce') else self.loss  # :144
-        kk = min(self.top_N_items, self.logit_size)
-        stream_min = int(os.environ.get('ARX_STREAM_TOPK_BYTES', str(1 << 30)))
-        lat_w = logits.inputs[0].shape[1] if hasattr(logits, 'inputs') and logits.inputs else 0
-        fused_ok = self.logit_size > 65536 and lat_w in (32, 64, 128) and isinstance(logits, G.Prediction)
-        if kk <= 1024 and (batch_size * self.logit_size * 4 > stream_min or fused_ok):
-            # [mb, V] is not worth materialising: streaming scorer + top-k.  Past 65 536 items the fused form beats the
-            # materialising one at every batch size (V = 1 M: 1.0 against 8.1 ms at mb = 64, 3.3 against 13.8 at 1 024)
-            self.topk = StreamTopK(rt, logits.inputs[0], logits.inputs[1], kk)
-        else:
-            self.topk = TopK(rt, logits, kk)                                     # :154
+        self.topk = recommend_node(rt, logits, min(self.top_N_items, self.logit_size), batch_size)
         self.indices = self.topk
         self.saver = Saver(self)
 
@@ -470,17 +267,6 @@ class LatentProductModel(object):
             self._plans.pop(key, None)
         self.att_emb.prepare_pair_negatives(hist, seed=seed)
 
-    def _topk_ex(self):
-        """The excluding twin of self.topk (built on first use; the plain node and its plan stay as they are)."""
-        if getattr(self, 'topk_ex', None) is None:
-            m, t = self.att_emb, self.topk
-            if isinstance(t, StreamTopK):
-                self.topk_ex = StreamTopK(self.rt, t.inputs[0], t.inputs[1], t.k, chunk=t.chunk,
-                                          exclude=m.exclusion_args, share=t)
-            else:
-                self.topk_ex = TopK(self.rt, t.inputs[0], t.k, exclude=m.exclusion_args)
-        return self.topk_ex
-
     def _plan(self, key):
         if key in self._plans:
             return self._plans[key]
@@ -490,11 +276,7 @@ class LatentProductModel(object):
             masks = [m.mask[loss]] if loss in m.mask else []
             p = G.Plan(rt, [self.loss], True, masks)
         elif key == 'eval':
-            l = 'warp' if loss == 'mw' else ('ce' if loss == 'mce' else loss)
-            masks = [m.mask[l]] if l in m.mask else []
-            if isinstance(self.loss_eval.inputs[0], G.StreamEvalLoss):
-                masks = []                 # the streaming loss reads the positives CSR itself
-            p = G.Plan(rt, [self.loss_eval], False, masks)
+            p = G.Plan(rt, [self.loss_eval], False, m.eval_masks(loss, self.loss_eval.inputs[0]))
         elif key == 'train_draw':              # pair losses, the negatives drawn in the plan (NegPairDraw goes first)
             p = G.Plan(rt, [m.neg_draw, self.loss], True, [])
         elif key == 'eval_draw':
@@ -503,7 +285,9 @@ class LatentProductModel(object):
             p = G.Plan(rt, [self.topk], False, [])
         elif key == 'recommend_ex':
             m.exclusion_args()                 # (raises before anything is built when no lists were prepared)
-            p = G.Plan(rt, [self._topk_ex()], False, [])
+            if getattr(self, 'topk_ex', None) is None:
+                self.topk_ex = excluding_twin(rt, self.topk, m.exclusion_args)
+            p = G.Plan(rt, [self.topk_ex], False, [])
         elif key == 'warp_eval':
             p = G.Plan(rt, [self.batch_loss], False, [m.mask['warp_eval']])
         else:
@@ -642,24 +426,16 @@ class LatentProductModel(object):
         neg_score / auc .read() give the last step's scores (hmf_model.py:104-107).
         recommend with exclude_seen=True: the top_N logit indices without each user's items of
         prepare_recommend_exclusions (ValueError if none were prepared); -1 where a user has fewer eligible items."""
-        out = self.step_async(session, user_input, item_input, neg_item_input, item_sampled,
-                              item_sampled_id2idx, forward_only, recommend, recommend_new, loss,
-                              run_op, run_meta, exclude_seen=exclude_seen)
+        run = lambda: self.step_async(session, user_input, item_input, neg_item_input, item_sampled,
+                                      item_sampled_id2idx, forward_only, recommend, recommend_new, loss,
+                                      run_op, run_meta, exclude_seen=exclude_seen)
         if recommend:
-            node, key = (self.topk_ex, 'recommend_ex') if exclude_seen else (self.topk, 'recommend')
-            if isinstance(node, StreamTopK) and node.overflowed():
-                # a candidate list of the fused top-k was too short for this batch: once more on the chunked path
-                node.fused = False
-                self._plans.pop(key, None)
-                try:
-                    out = self.step_async(session, user_input, item_input, neg_item_input, item_sampled,
-                                          item_sampled_id2idx, forward_only, recommend, recommend_new, loss, run_op,
-                                          run_meta, exclude_seen=exclude_seen)
-                    return out.cpu().numpy()
-                finally:
-                    node.fused = True
-                    self._plans.pop(key, None)
-            return out.cpu().numpy()
+            # (a candidate list of the fused top-k too short for this batch: the request once more, chunked)
+            key = 'recommend_ex' if exclude_seen else 'recommend'
+            self._plan(key)                    # builds topk_ex / raises as the step would
+            node = self.topk_ex if exclude_seen else self.topk
+            return run_complete(node, run, lambda: self._plans.pop(key, None)).cpu().numpy()
+        out = run()
         if isinstance(out, list):
             return [o.cpu().numpy() for o in out]
         return float(out.read().item())

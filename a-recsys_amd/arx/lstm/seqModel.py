@@ -23,6 +23,7 @@ from .. import graph as G
 from .. import ops
 from ..attributes.embed_attribute import Dropout, ZeroEmbed
 from ..hmf.hmf_model import _Op, _Var
+from ..topk import StreamTopK, excluding_twin, logits_too_big, run_complete
 from ..utils.checkpoint import Saver
 from .batching import SeqBatching
 
@@ -480,27 +481,19 @@ class SeqModel(SeqBatching):
         if self.loss in ('mw', 'mce'):
             wn2 = SeqWeights(rt, wn.inputs[0], L, B)
             full = m.get_prediction(hs, 'full', output_feat=self.output_feat, steps=(L, B))
-            kind_full = 'warp' if self.loss == 'mw' else 'ce'
-            import os as _os
-            big = n * m.logit_size * 4 > int(_os.environ.get('ARX_STREAM_TOPK_BYTES', str(1 << 30)))
-            if big and self.output_feat in (0, 1):     # [L*mb, V] logits streamed, not materialised
-                ms = m._mask_state('warp', n) if kind_full == 'warp' else None
-                bl_full = G.StreamEvalLoss(rt, kind_full, hs, m._pool_embed('full', self.output_feat), tgt,
-                                           mask=ms, mask_rows=B)
-                bk['eval_streamed'] = True
-            else:
-                bl_full = m.compute_loss(full, tgt, kind_full)
+            # (output_feat 2 / 3 pool in score space: their [L*mb, V] logits are always materialised)
+            pool = m._pool_embed('full', self.output_feat) if self.output_feat in (0, 1) else None
+            bl_full = m.sampled_eval_loss(self.loss, hs, full, tgt, n, B, pool)
+            bk['eval_streamed'] = isinstance(bl_full, G.StreamEvalLoss)
             bk['eval'] = SeqLoss(rt, bl_full, wn2)
         else:
             bk['eval'] = bk['train']
             full = logits
         bk['recommend'] = TopKSoftmax(rt, full, min(self.topk_n, full.shape[1]))      # :514-517
-        import os as _os2
-        if self.output_feat in (0, 1) and n * m.logit_size * 4 > int(_os2.environ.get('ARX_STREAM_TOPK_BYTES',
-                                                                                      str(1 << 30))):
+        if self.output_feat in (0, 1) and logits_too_big(n, m.logit_size):
             # [L*mb, V] logits are not worth materialising for ONE position per sequence: the rows asked for are
             # gathered first, then the fused full-vocabulary top-k (+ the softmax normaliser) runs on [mb, d]
-            from ..hmf.hmf_model import StreamTopK
+            # (this model's own rule, on purpose: no fused_ok clause and no bound on k, unlike topk.streams_topk)
             bk['rec_rows'] = G.IdsInput(rt, B, 'recommend_rows_%d' % L)
             sel = RowsAt(rt, hs, bk['rec_rows'])
             bk['recommend_stream'] = StreamTopK(rt, sel, m._pool_embed('full', self.output_feat),
@@ -520,11 +513,14 @@ class SeqModel(SeqBatching):
             elif key == 'recommend':
                 bk['plans'][key] = G.Plan(self.rt, [bk.get('recommend_stream', bk['recommend'])], False, [])
             elif key == 'recommend_ex':
-                bk['plans'][key] = G.Plan(self.rt, [self._recommend_ex_node(bk)], False, [])
+                # the excluding twin of the bucket's recommend node, on first use.  Its rows are the time-major [L*mb]
+                # logits rows (user_input[r % mb]) or, streamed, the mb gathered rows (user_input[r])
+                if 'recommend_ex' not in bk:
+                    bk['recommend_ex'] = excluding_twin(self.rt, bk.get('recommend_stream', bk['recommend']),
+                                                        m.exclusion_args)
+                bk['plans'][key] = G.Plan(self.rt, [bk['recommend_ex']], False, [])
             else:
-                l = 'warp' if self.loss == 'mw' else ('ce' if self.loss == 'mce' else self.loss)
-                masks = [m.mask[l]] if (l in m.mask and not bk.get('eval_streamed')) else []
-                bk['plans'][key] = G.Plan(self.rt, [bk['eval']], False, masks)
+                bk['plans'][key] = G.Plan(self.rt, [bk['eval']], False, m.eval_masks(self.loss, bk['eval'].inputs[0]))
         return bk['plans'][key]
 
     # ------------------------------------------------ clip_by_global_norm (:180)
@@ -806,25 +802,11 @@ class SeqModel(SeqBatching):
             bk['plans'].pop('recommend_ex', None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
-    def _recommend_ex_node(self, bk):
-        """The excluding twin of the bucket's recommend node (built on first use).  Rows are the time-major [L*mb]
-        logits rows (user_input[r % mb]) or, streamed, the mb gathered rows (user_input[r])."""
-        if 'recommend_ex' not in bk:
-            m = self.att_emb
-            if 'recommend_stream' in bk:
-                from ..hmf.hmf_model import StreamTopK
-                t = bk['recommend_stream']
-                bk['recommend_ex'] = StreamTopK(self.rt, t.inputs[0], t.inputs[1], t.k, chunk=t.chunk, want_lse=True,
-                                                exclude=m.exclusion_args, share=t)
-            else:
-                bk['recommend_ex'] = TopKSoftmax(self.rt, bk['full'], bk['recommend'].k, exclude=m.exclusion_args)
-        return bk['recommend_ex']
-
     def step_recommend(self, session, user_input, item_inputs, positions, bucket_id, exclude_seen=False):
         """seqModel.py:326-353 -> [(uid, values[topk_n], indexes[topk_n])]: the top-k softmax
         values / logit indexes at time position positions[i] of sequence i.  Small vocabularies: the full
         [L*mb, V] logits are materialised; past ARX_STREAM_TOPK_BYTES (1 GB) the mb rows asked for are gathered
-        and the fused full-vocabulary top-k + log-sum-exp of hmf_model.StreamTopK runs on them (round 5).
+        and the fused full-vocabulary top-k + log-sum-exp of topk.StreamTopK runs on them (round 5).
         exclude_seen: leave out user_input[i]'s items of prepare_recommend_exclusions (plan 'recommend_ex'); the
         softmax normaliser stays over the full vocabulary, so a winner's value equals the non-excluding one; where
         a user has fewer than topk_n eligible items the tail has index -1 and value 0.  Under
@@ -845,21 +827,14 @@ class SeqModel(SeqBatching):
         users = user_input.cpu().numpy() if isinstance(user_input, torch.Tensor) else user_input
         key = 'recommend_ex' if exclude_seen else 'recommend'
         if 'recommend_stream' in bk:
-            node = self._recommend_ex_node(bk) if exclude_seen else bk['recommend_stream']
             bk['rec_rows'].feed(np.asarray([int(pos) * B + i for i, pos in enumerate(positions)], dtype=np.int32))
-            self._plan(bucket_id, key).run()
-            if node.overflowed():             # a candidate list of the fused top-k was too short: the chunked path
-                node.fused = False
-                bk['plans'].pop(key, None)
-                try:
-                    self._plan(bucket_id, key).run()
-                finally:
-                    node.fused = True
-                    bk['plans'].pop(key, None)
+            self._plan(bucket_id, key)
+            node = bk['recommend_ex' if exclude_seen else 'recommend_stream']
+            run_complete(node, lambda: self._plan(bucket_id, key).run(), lambda: bk['plans'].pop(key, None))
             vals, idx, lse = node.value.cpu().numpy(), node.indices.cpu().numpy(), node.lse.cpu().numpy()
             return [(users[i], np.exp(vals[i] - lse[i]), idx[i]) for i in range(len(positions))]
         self._plan(bucket_id, key).run()
-        node = self._recommend_ex_node(bk) if exclude_seen else bk['recommend']
+        node = bk['recommend_ex' if exclude_seen else 'recommend']
         vals = node.value.cpu().numpy()
         idx = node.indices.cpu().numpy()
         lse = node.lse.cpu().numpy()

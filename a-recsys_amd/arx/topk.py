@@ -1,0 +1,251 @@
+"""Full-vocabulary top-k: the nodes (TopK, StreamTopK on TopKScan) and the serving rules every model shares --
+when the [rows, V] logits are too big to materialise (ARX_STREAM_TOPK_BYTES), which node recommends, the excluding
+twin of a node, and the chunked re-run after the fused candidate lists overflowed.  Depends on graph and ops only.
+"""
+from __future__ import annotations
+
+import contextlib
+import os
+
+import torch
+
+from . import graph as G
+from . import ops
+
+
+def stream_min_bytes():
+    """[rows, V] f32 logits above this many bytes are streamed, not materialised (read at every call: the
+    variable may change between two model constructions)."""
+    return int(os.environ.get('ARX_STREAM_TOPK_BYTES', str(1 << 30)))
+
+
+def logits_too_big(rows, V):
+    return rows * V * 4 > stream_min_bytes()
+
+
+def streams_topk(rows, V, k, d, plain_prediction):
+    """The HMF / LinearSeq rule: stream where the logits (a plain G.Prediction of a width-d latent) are too big, and
+    past 65 536 items wherever the fused form applies -- it beats the materialising one at every batch size
+    (V = 1 M: 1.0 against 8.1 ms at mb = 64, 3.3 against 13.8 at 1 024).  (SeqModel's rule is its own: _bucket.)"""
+    fused_ok = V > 65536 and d in (32, 64, 128)
+    return bool(plain_prediction and k <= 1024 and (logits_too_big(rows, V) or fused_ok))
+
+
+class TopK(G.Node):
+    """hmf_model.py:154 tf.nn.top_k(logits, top_N_items, sorted=True).
+    exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
+    each row's excluded columns are set to -inf IN the logits before the select (nothing after this node may read
+    them), and winners of value -inf (rows with fewer than k eligible columns) get index -1."""
+
+    def __init__(self, rt, logits, k, exclude=None):
+        super().__init__(rt, (logits.shape[0], k), (logits,))
+        self.k = k
+        self.exclude = exclude
+        self.indices = torch.empty((logits.shape[0], k), dtype=torch.int32, device=rt.device)
+
+    def forward(self, train):
+        x = self.inputs[0].value
+        if self.exclude is not None:
+            ops.topk_exclude_fill(x, 0, self.exclude())
+        ops.topk(x, self.k, self.alloc_value(), self.indices)
+        if self.exclude is not None:
+            ops.topk_mark_empty(self.value, self.indices)
+
+
+class TopKScan(object):
+    """The streaming full-vocabulary top-k of StreamTopK without a Runtime: its buffers and its algorithm on plain
+    tensors, run(latent, pool, bias, ...) -- StreamTopK runs on it, and so does the per-shard stage of the row-sharded
+    recommend (arx.dist.ShardedHMF.recommend), whose tables are no graph nodes.  B rows, V pool rows of width d."""
+
+    def __init__(self, B, V, d, k, device, chunk=65536, want_lse=False, share=None):
+        self.k, self.chunk = k, max(int(chunk), k)
+        self._rows, self._dev = B, device
+        # want_lse: also self.lse [B] = log sum exp over ALL the row's logits (seqModel.py:514-517 reports the winners'
+        # softmax values exp(v - lse)): per column range out of the fused GEMM / per chunk, combined at the end
+        self.want_lse = bool(want_lse)
+        self.lse = torch.empty(B, dtype=torch.float32, device=device) if want_lse else None
+        self._lse_parts = None
+        dev = device
+        f32, i32 = torch.float32, torch.int32
+        self.indices = torch.empty((B, k), dtype=i32, device=dev)
+        if share is not None and tuple(share._buf.shape) == (B, min(self.chunk, V)):
+            self._buf = share._buf
+        else:
+            self._buf = torch.empty((B, min(self.chunk, V)), dtype=f32, device=dev)
+        self._cv, self._ci = torch.empty((B, k), dtype=f32, device=dev), torch.empty((B, k), dtype=i32, device=dev)
+        self._ov, self._oi = torch.empty((B, k), dtype=f32, device=dev), torch.empty((B, k), dtype=i32, device=dev)
+        tail = V % self.chunk                       # a last chunk narrower than k keeps only `tail` entries
+        kt = tail if 0 < tail < k else k
+        self._tv, self._ti = torch.empty((B, kt), dtype=f32, device=dev), torch.empty((B, kt), dtype=i32, device=dev)
+        self.fused = os.environ.get('ARX_TOPK_FUSED', '1') != '0' and d in (32, 64, 128)
+        self.overflow = torch.zeros(1, dtype=i32, device=dev)
+        self.slack, self.min_capp = 4.0, 32          # candidate segment = slack x the expected survivors, >= min_capp
+        self._cand = None
+
+    def _cand_bufs(self, n0, V):
+        """Candidate rows [B, parts * capp]: a column range's expected survivors are k (V - n0) / n0 / parts (scores in
+        no particular order along the vocabulary); four times that, at least 32."""
+        key = (n0, V, self.slack, self.min_capp)
+        if self._cand is None or self._cand[0] != key:
+            B, k, dev = self._rows, self.k, self._dev
+            parts = ops.gemm_nt_topk_parts(B, V - n0)
+            expect = k * (V - n0) / float(n0) / parts
+            capp = self.min_capp
+            while capp < self.slack * expect + self.min_capp:
+                capp *= 2
+            while parts * capp < k:
+                capp *= 2
+            cap = parts * capp
+            self._cand = (key, capp, torch.empty((B, cap), dtype=torch.float32, device=dev),
+                          torch.zeros((B, cap), dtype=torch.int32, device=dev),
+                          torch.empty((B, k), dtype=torch.int32, device=dev), parts)
+        return self._cand[1:]
+
+    def _lse_buf(self, ncols):
+        if self._lse_parts is None or self._lse_parts.shape[1] != ncols:
+            B, dev = self._rows, self._dev
+            self._lse_parts = torch.empty((B, ncols), dtype=torch.float32, device=dev)
+            self._lse0 = torch.empty(B, dtype=torch.float32, device=dev)
+        return self._lse_parts
+
+    def overflowed(self):
+        """True when the last fused run dropped candidates (device -> host read)."""
+        return bool(self.fused and int(self.overflow.item()) != 0)
+
+    @contextlib.contextmanager
+    def chunked(self):
+        """Inside: run() takes the chunked path; the fused setting comes back on exit, also when the body raises."""
+        was, self.fused = self.fused, False
+        try:
+            yield self
+        finally:
+            self.fused = was
+
+    def run(self, latent, pool, bias, ws, values, indices, ex=None):
+        """values / indices [B, k] = the top-k of latent . pool^T + bias (bias may be None) over all V >= k pool rows;
+        ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace."""
+        V, k = pool.shape[0], self.k
+        run_v, run_i = values, indices
+        out_v, out_i = self._ov, self._oi
+        if self.fused and V > self.chunk and pool.stride(0) % 4 == 0 and latent.stride(0) % 4 == 0:
+            n0 = self.chunk
+            lg = self._buf[:, :n0]
+            ops.gemm(latent, pool[:n0], lg, ws, transB=True, col_bias=bias[:n0] if bias is not None else None)
+            capp, cand_v, cand_i, cpos, parts = self._cand_bufs(n0, V)
+            lp = None
+            if self.want_lse:
+                lp = self._lse_buf(parts + 1)
+                ops.row_logsumexp(lg, self._lse0)               # (over the whole chunk: before the exclusion fill)
+                lp[:, parts].copy_(self._lse0)
+            if ex is not None:
+                ops.topk_exclude_fill(lg, 0, ex)                # threshold = the k-th best ELIGIBLE column
+            ops.topk_chunk(lg, k, 0, run_v, run_i)
+            ops.fill_f32(cand_v.view(-1), float('-inf'))
+            ops.fill_i32(self.overflow, 0)
+            if ex is not None:
+                ops.gemm_nt_topk_filter_excl(latent, pool[n0:], bias[n0:] if bias is not None else None,
+                                             run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, ex,
+                                             lse_part=lp)
+            else:
+                ops.gemm_nt_topk_filter(latent, pool[n0:], bias[n0:] if bias is not None else None,
+                                        run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, lse_part=lp)
+            if self.want_lse:
+                ops.row_logsumexp(lp, self.lse)
+            ops.topk_chunk(cand_v, k, 0, self._cv, cpos)
+            ops.take_rows_i32(cand_i, cpos, self._ci)
+            ops.topk_merge(run_v, run_i, self._cv, self._ci, k, out_v, out_i)
+            values.copy_(out_v)
+            indices.copy_(out_i)
+            if ex is not None:
+                ops.topk_mark_empty(values, indices)
+            return
+        nch = (V + self.chunk - 1) // self.chunk
+        lp = self._lse_buf(nch) if self.want_lse else None
+        for c0 in range(0, V, self.chunk):
+            c1 = min(V, c0 + self.chunk)
+            kc = min(k, c1 - c0)
+            lg = self._buf[:, :c1 - c0]
+            ops.gemm(latent, pool[c0:c1], lg, ws, transB=True, col_bias=bias[c0:c1] if bias is not None else None)
+            if self.want_lse:
+                ops.row_logsumexp(lg, self._lse0)
+                lp[:, c0 // self.chunk].copy_(self._lse0)
+            if ex is not None:
+                ops.topk_exclude_fill(lg, c0, ex)
+            if c0 == 0:                              # chunk >= k and V >= k: the first chunk fills all k
+                ops.topk_chunk(lg, k, 0, run_v, run_i)
+                continue
+            cv, ci = (self._cv, self._ci) if kc == k else (self._tv, self._ti)
+            ops.topk_chunk(lg, kc, c0, cv, ci)
+            ops.topk_merge(run_v, run_i, cv, ci, k, out_v, out_i)
+            run_v, out_v = out_v, run_v
+            run_i, out_i = out_i, run_i
+        if run_v.data_ptr() != values.data_ptr():
+            values.copy_(run_v)
+            indices.copy_(run_i)
+        if ex is not None:
+            ops.topk_mark_empty(values, indices)
+        if self.want_lse:
+            ops.row_logsumexp(lp, self.lse)
+
+
+class StreamTopK(G.Node, TopKScan):
+    """top_k over the FULL vocabulary without the [mb, V] logits -- same indices / values as
+    TopK(Prediction), tf.nn.top_k's tie rule included.
+    fused (round 5, the default where the scorer GEMM's small-K kernel applies): the first chunk of the pool gives
+    every row its k best (GEMM -> radix select); the scorer GEMM over ALL the other columns then writes no logits --
+    arx_gemm_nt_topk_filter keeps only what beats the row's k-th best so far, as short candidate lists in column order;
+    one select over the lists and one merge finish.  A candidate list that overflows (scores rising along the
+    vocabulary) sets a flag: overflowed() -- run_complete runs the request once more on the chunked path.
+    chunked: the GEMM runs over chunks of the pool rows, every chunk keeps its k best per row (radix select) and a
+    merge folds them into the running result.
+    exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
+    each row's excluded columns never enter the result (the first chunk and every chunked-path chunk are filled with
+    -inf at them, the fused GEMM's candidates skip them); winners of value -inf get index -1.  The log-sum-exp
+    (want_lse) stays over ALL the columns.  share: another StreamTopK over the same shapes whose logits chunk buffer
+    this one re-uses (plans run one after the other on one stream).  The algorithm and its buffers: TopKScan."""
+
+    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None):
+        G.Node.__init__(self, rt, (latent.shape[0], k), (latent, pool))
+        TopKScan.__init__(self, latent.shape[0], pool.shape[0], latent.shape[1], k, rt.device, chunk=chunk,
+                          want_lse=want_lse, share=share)
+        self.exclude = exclude
+        self.fused = self.fused and pool.shape[1] == latent.shape[1]
+
+    def forward(self, train):
+        latent, pool = self.inputs
+        ex = self.exclude() if self.exclude is not None else None
+        self.run(latent.value, pool.value, pool.bias_value, self.rt.ws, self.alloc_value(), self.indices, ex)
+
+
+def recommend_node(rt, logits, k, rows):
+    """The recommend node over `logits` [rows, V]: streaming scorer + top-k (streams_topk) or tf.nn.top_k of the
+    materialised logits (hmf_model.py:154)."""
+    plain = isinstance(logits, G.Prediction)
+    if streams_topk(rows, logits.shape[1], k, logits.inputs[0].shape[1] if plain else 0, plain):
+        return StreamTopK(rt, logits.inputs[0], logits.inputs[1], k)
+    return TopK(rt, logits, k)
+
+
+def excluding_twin(rt, node, exclusion_args):
+    """The excluding twin of a recommend node (the plain node and its plan stay as they are); a streaming twin
+    shares the plain node's chunk buffer."""
+    if isinstance(node, StreamTopK):
+        return StreamTopK(rt, node.inputs[0], node.inputs[1], node.k, chunk=node.chunk, want_lse=node.want_lse,
+                          exclude=exclusion_args, share=node)
+    return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args)
+
+
+def run_complete(scan, run, forget=None):
+    """run(); where the fused candidate lists of `scan` overflowed, once more on the chunked path.  forget() drops
+    a captured plan: one captured with the fused launch sequence must not replay the chunked one, nor the other way
+    round.  A node without overflowed() (a dense top-k) runs once.  Returns what the last run() returned."""
+    forget = forget or (lambda: None)
+    out = run()
+    if getattr(scan, 'overflowed', lambda: False)():
+        forget()
+        try:
+            with scan.chunked():
+                out = run()
+        finally:
+            forget()
+    return out

@@ -17,8 +17,6 @@ catalogue -- streamed, without [mb, V] logits, past ARX_STREAM_TOPK_BYTES.
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
@@ -26,7 +24,8 @@ from .. import graph as G
 from .. import ops
 from ..attributes import embed_attribute
 from ..attributes.embed_attribute import Dropout
-from ..hmf.hmf_model import StreamTopK, TopK, _Op, _Var
+from ..hmf.hmf_model import _Op, _Var
+from ..topk import excluding_twin, recommend_node, run_complete
 from ..utils.checkpoint import Saver
 
 
@@ -145,20 +144,14 @@ class LinearSeq(object):
             x_train = Dropout(rt, x_train)                                      # :88
         x_test = user if n_input_items == 0 else mean_all                         # :91-99
         logits_test = m.get_prediction(x_test, output_feat=output_feat)
-        stream_min = int(os.environ.get('ARX_STREAM_TOPK_BYTES', str(1 << 30)))
-        can_stream = isinstance(logits_test, G.Prediction)        # (output_feat 2 / 3 pool in score space)
         if sampled:
             # no [mb, V] node on the training side (skipgram_model.py:104-116)
             sampled_logits = m.get_prediction(x_train, 'sampled', output_feat=output_feat)
             target_score = m.get_target_score(x_train, self.item_id_target)
             batch_loss = m.compute_loss(sampled_logits, target_score, loss)
-            loss_eval = 'warp' if loss == 'mw' else 'ce'
-            if can_stream and mb * self.logit_size * 4 > stream_min:
-                ms = m._mask_state('warp', mb) if loss_eval == 'warp' else None
-                batch_loss_test = G.StreamEvalLoss(rt, loss_eval, x_test, logits_test.inputs[1], self.item_target,
-                                                   mask=ms, mask_rows=mb if ms is not None else 0)
-            else:
-                batch_loss_test = m.compute_loss(logits_test, self.item_target, loss_eval)
+            # (output_feat 2 / 3 pool in score space: no pool node to stream from)
+            pool = logits_test.inputs[1] if isinstance(logits_test, G.Prediction) else None
+            batch_loss_test = m.sampled_eval_loss(loss, x_test, logits_test, self.item_target, mb, mb, pool)
         else:
             logits = m.get_prediction(x_train, output_feat=output_feat)
             batch_loss = m.compute_loss(logits, self.item_target, loss)
@@ -169,13 +162,7 @@ class LinearSeq(object):
         self.loss = G.MeanLoss(rt, batch_loss)
         self.loss_test = G.MeanLoss(rt, batch_loss_test)
         self.output = logits_test
-        kk = min(top_N_items, self.logit_size)
-        fused_ok = self.logit_size > 65536 and x_test.shape[1] in (32, 64, 128)
-        if can_stream and kk <= 1024 and (mb * self.logit_size * 4 > stream_min or fused_ok):
-            # the rule of hmf_model.py: streaming scorer + top-k instead of [mb, V] logits
-            self.topk = StreamTopK(rt, x_test, logits_test.inputs[1], kk)
-        else:
-            self.topk = TopK(rt, logits_test, kk)                                  # :135
+        self.topk = recommend_node(rt, logits_test, min(top_N_items, self.logit_size), mb)    # :135
         self.indices = self.topk
         self._plans = {}
         self.saver = Saver(self)
@@ -196,19 +183,10 @@ class LinearSeq(object):
                 masks = [m.mask[loss]] if loss in m.mask else []
                 self._plans[key] = G.Plan(rt, [self.loss], True, masks)
             elif key == 'eval':
-                l = 'warp' if loss == 'mw' else ('ce' if loss == 'mce' else loss)
-                masks = [m.mask[l]] if l in m.mask else []
-                if isinstance(self.loss_test.inputs[0], G.StreamEvalLoss):
-                    masks = []                 # the streaming loss reads the positives CSR itself
-                self._plans[key] = G.Plan(rt, [self.loss_test], False, masks)
+                self._plans[key] = G.Plan(rt, [self.loss_test], False, m.eval_masks(loss, self.loss_test.inputs[0]))
             elif key == 'recommend_ex':
-                if getattr(self, 'topk_ex', None) is None:      # the excluding twin of self.topk, on first use
-                    t = self.topk
-                    if isinstance(t, StreamTopK):
-                        self.topk_ex = StreamTopK(rt, t.inputs[0], t.inputs[1], t.k, chunk=t.chunk,
-                                                  exclude=m.exclusion_args, share=t)
-                    else:
-                        self.topk_ex = TopK(rt, t.inputs[0], t.k, exclude=m.exclusion_args)
+                if getattr(self, 'topk_ex', None) is None:      # on first use
+                    self.topk_ex = excluding_twin(rt, self.topk, m.exclusion_args)
                 self._plans[key] = G.Plan(rt, [self.topk_ex], False, [])
             else:
                 self._plans[key] = G.Plan(rt, [self.topk], False, [])
@@ -217,17 +195,10 @@ class LinearSeq(object):
     def _recommend(self, key):
         """Run the 'recommend' / 'recommend_ex' plan; a streaming top-k whose fused candidate lists overflowed runs
         once more on the chunked path (as LatentProductModel.step)."""
-        self._plan(key).run()
+        self._plan(key)
         node = self.topk_ex if key == 'recommend_ex' else self.topk
-        if isinstance(node, StreamTopK) and node.overflowed():
-            node.fused = False
-            self._plans.pop(key, None)
-            try:
-                self._plan(key).run()          # (the placeholders still hold this request's ids)
-                return node.indices.cpu().numpy()
-            finally:
-                node.fused = True
-                self._plans.pop(key, None)
+        # (the placeholders still hold this request's ids in the second run)
+        run_complete(node, lambda: self._plan(key).run(), lambda: self._plans.pop(key, None))
         return node.indices.cpu().numpy()
 
     def step(self, session, user_input, item_input=None, item_output=None, item_sampled=None,

@@ -387,7 +387,46 @@ def test_seq_step_recommend_exclude_seen(dev, monkeypatch, stream):
         assert (got[1][2][3:] == -1).all() and (got[1][2][:3] >= 0).all()
 
 
-def test_linear_seq_exclude_seen(dev):
+def test_seq_overflow_reruns_on_the_chunked_path(dev, monkeypatch):
+    """SeqModel.step_recommend when the fused candidate lists overflow: one user excludes the whole first chunk, so
+    that row's threshold is -inf and every 64-column range behind the chunk exceeds its 8-entry segment -- the call
+    runs once more on the chunked path and gives what the materialised model gives."""
+    syn, mat = _seq(11)
+    mat._bucket(0)                                   # (materialised: built before the streaming switch below)
+    monkeypatch.setenv('ARX_STREAM_TOPK_BYTES', '0')
+    _, model = _seq(11)
+    B, L = 16, 4
+    bk = model._bucket(0)
+    assert 'recommend_stream' in bk and 'recommend_stream' not in mat._bucket(0)
+    bk['recommend_stream'].chunk = 128
+    bk['recommend_stream']._buf = bk['recommend_stream']._buf[:, :128].contiguous()
+    rng = np.random.default_rng(2)
+    users = rng.choice(syn.n_users, B, replace=False).astype(np.int32)
+    tg = np.stack([syn.sample_batch(B, rng)[1] for _ in range(L)], 0)
+    inp = np.concatenate([np.full((1, B), syn.n_items, dtype=np.int32), tg[:-1]], 0)
+    positions = rng.integers(0, L, size=B).tolist()
+    l2i = syn.logit_ind2item_ind
+    sets = {int(u): rng.integers(0, syn.n_items, 30).tolist() for u in users}
+    for m in (mat, model):
+        m.prepare_recommend_exclusions(sets)
+    rec = lambda m: m.step_recommend(None, list(users), inp.tolist(), positions, 0, exclude_seen=True)
+    rec(model)                                       # (builds the excluding twin)
+    node = bk['recommend_ex']
+    node.slack, node.min_capp = 0.0, 8               # segments shorter than the columns of a range
+    bk['plans'].pop('recommend_ex', None)
+    sets[int(users[0])] = [int(i) for i in l2i[:128]]
+    for m in (mat, model):
+        m.prepare_recommend_exclusions(sets)
+    exp, got = rec(mat), rec(model)
+    assert int(node.overflow.item()) != 0 and node.fused     # (overflowed, re-ran chunked, restored)
+    for i in range(B):
+        assert int(got[i][0]) == int(exp[i][0]) == int(users[i])
+        np.testing.assert_array_equal(got[i][2], exp[i][2], err_msg='row %d' % i)
+        np.testing.assert_allclose(got[i][1], exp[i][1], rtol=1e-5, atol=0, err_msg='row %d' % i)
+    assert (got[0][2] >= 128).all()
+
+
+def _skipgram():
     from arx.utils.synthetic import SyntheticHMF
     from arx.word2vec import skipgram_model
     syn = SyntheticHMF(seed=21, n_users=300, n_items=500, logit_size=400)
@@ -399,6 +438,12 @@ def test_linear_seq_exclude_seen(dev):
     model = skipgram_model.Model(syn.n_users, syn.n_items, d, B, 0.5, 1.0, syn.u_attr, syn.i_attr, i2l, l2i,
                                  n_input_items=1, loss_function='ce', use_sep_item=True, top_N_items=8,
                                  params=params)
+    return syn, model
+
+
+def test_linear_seq_exclude_seen(dev):
+    syn, model = _skipgram()
+    B, l2i = model.batch_size, syn.logit_ind2item_ind
     rng = np.random.default_rng(9)
     users = rng.choice(syn.n_users, B, replace=False).astype(np.int32)
     ctx = syn.sample_batch(B, rng)[1][None, :]
@@ -414,6 +459,37 @@ def test_linear_seq_exclude_seen(dev):
         _, exp = oracle_topk(logits, _row_cols(syn, sets, users), 8)
         np.testing.assert_array_equal(got, exp, err_msg='run %d' % rep)
     np.testing.assert_array_equal(model.step(None, list(users), ctx.tolist(), recommend=True), plain)
+
+
+def test_linear_seq_overflow_reruns_on_the_chunked_path(dev, monkeypatch):
+    """LinearSeq.step(recommend, exclude_seen) when the fused candidate lists overflow (the construction of
+    test_hmf_exclude_seen_streamed_equals_materialised): the streamed model against the materialised twin."""
+    from arx.hmf import hmf_model as hm
+    syn, mat = _skipgram()
+    monkeypatch.setenv('ARX_STREAM_TOPK_BYTES', '0')
+    _, st = _skipgram()
+    assert isinstance(st.topk, hm.StreamTopK) and isinstance(mat.topk, hm.TopK)
+    st.topk.chunk = 128
+    st.topk._buf = st.topk._buf[:, :128].contiguous()
+    B, l2i = mat.batch_size, syn.logit_ind2item_ind
+    rng = np.random.default_rng(9)
+    users = rng.choice(syn.n_users, B, replace=False).astype(np.int32)
+    ctx = syn.sample_batch(B, rng)[1][None, :]
+    sets = {int(u): rng.integers(0, syn.n_items, 50).tolist() for u in users}
+    for m in (mat, st):
+        m.prepare_recommend_exclusions(sets)
+    rec = lambda m: m.step(None, list(users), ctx.tolist(), recommend=True, exclude_seen=True)
+    np.testing.assert_array_equal(rec(st), rec(mat))         # (builds the excluding twin)
+    assert isinstance(st.topk_ex, hm.StreamTopK) and st.topk_ex.fused
+    st.topk_ex.slack, st.topk_ex.min_capp = 0.0, 8           # segments shorter than the columns of a range
+    st._plans.pop('recommend_ex', None)
+    sets[int(users[0])] = [int(i) for i in l2i[:128]]        # all of the first chunk: that row's threshold is -inf
+    for m in (mat, st):
+        m.prepare_recommend_exclusions(sets)
+    exp, got = rec(mat), rec(st)
+    assert int(st.topk_ex.overflow.item()) != 0 and st.topk_ex.fused     # (overflowed, re-ran chunked, restored)
+    np.testing.assert_array_equal(got, exp)
+    assert (got[0] >= 128).all()
 
 
 def test_ml1m_excluding_equals_host_side_removal(dev, tmp_path):

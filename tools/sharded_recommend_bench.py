@@ -24,7 +24,7 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 from arx import graph as G  # noqa: E402
 from arx.dist import ShardedHMF  # noqa: E402
-from arx.hmf.hmf_model import StreamTopK  # noqa: E402
+from arx.topk import StreamTopK, run_complete  # noqa: E402
 
 PEAK_F32_MFMA = 155e12
 
@@ -96,11 +96,7 @@ def bench_shape(V, B, d, k, Hs, with_stream, calls, rounds):
                             exclude=(lambda: ex) if ex is not None else None)
 
             def stream_call():
-                st.forward(False)
-                if st.overflowed():
-                    st.fused = False
-                    st.forward(False)
-                    st.fused = True
+                run_complete(st, lambda: st.forward(False))
                 st.indices.clone()
             stream_call()
         t_rec, t_st, t_loc, t_mrg = [], [], [], []

@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "a-recsys_amd"))
 import torch  # noqa: E402
 from arx import graph as G  # noqa: E402
-from arx.hmf.hmf_model import StreamTopK  # noqa: E402
+from arx.topk import StreamTopK, run_complete  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--B", type=int, default=4096)
@@ -73,10 +73,7 @@ results = []
 for H in [int(x) for x in args.H.split(",")]:
     draws = {'uniform': torch.randint(0, V, (B, H), device=dev, generator=g)}
     top = StreamTopK(rt, lat, pool, H)                      # the rows' own H best columns
-    top.forward(False)
-    if top.overflowed():
-        top.fused = False
-        top.forward(False)
+    run_complete(top, lambda: top.forward(False))
     draws['adversarial'] = top.indices.clone()
     del top
     for draw, cols in draws.items():

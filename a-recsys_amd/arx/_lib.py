@@ -38,6 +38,8 @@ PROTOTYPES = {
     "arx_sparse_site_onehot": (cint, [i32p, i32p, i64, i32, f32, i32p, i32p, f32p, vp]),
     "arx_sparse_site_window": (cint, [i32p, i32p, cint, i64, i32, f32, i32p, i32p, f32p, vp]),
     "arx_gather_window_fwd": (cint, [f32p, i32p, i32p, cint, i64, cint, f32, f32p, i64, f32, f32p, i64, vp]),
+    "arx_window_slots_fwd": (cint, [f32p, i64, i32p, cint, i64, cint, f32, f32p, i64, f32, f32p, i64, vp]),
+    "arx_window_slots_bwd": (cint, [f32p, i64, i32p, cint, i64, cint, f32, f32, f32p, i64, cint, f32p, i64, vp]),
     "arx_shard_route": (cint, [i32p, i64, cint, cint, i32, i32p, i32p, vp]),
     "arx_pool_blocks": (cint, [i32p, i64, cint, cint, i32, i64, i32p, i32p, i32p, i32p, vp]),
     "arx_copy_2d": (cint, [f32p, i64, f32p, i64, i64, i64, vp]),

@@ -195,6 +195,15 @@ class HipBackend(object):
         self.ops.pair_loss_slots(U, R, pos_slot, neg_slot, kind, gscale, pos_score, neg_score, bl, dU=dU, dR=dR,
                                  auc_counts=counts)
 
+    def window_slots_fwd(self, R, slots, n, scale, base, base_scale, out):
+        """out[b] = base_scale * base[b] + scale * sum_t R[slots[t * mb + b]], ascending t (arx_window_slots_fwd)."""
+        self.ops.window_slots_fwd(R, slots, n, out, scale=scale, base=base, base_scale=base_scale)
+
+    def window_slots_bwd(self, dX, slots, n, scale, base_scale, dbase, acc_dbase, dR):
+        """dbase[b] (+)= base_scale * dX[b]; dR[slots[t * mb + b]] = scale * dX[b] for every t; rows of dR that no
+        slot names keep what they held (arx_window_slots_bwd)."""
+        self.ops.window_slots_bwd(dX, slots, n, dbase, dR, scale=scale, base_scale=base_scale, acc_dbase=acc_dbase)
+
     def neg_draw_uniform(self, urows, ex_ptr, ex_cols, V, seed, counter, out):
         """out[r] = one item of [0, V) outside the sorted, unique list of local user row urows[r] (CSR ex_ptr /
         ex_cols), uniform by rank-select, keyed by (seed, counter, r); -1 where the list is all of [0, V)
@@ -1359,9 +1368,7 @@ class ShardedHMF(object):
         kh = np.full(B_loc, -1, dtype=np.int32)
         kh[:n] = u
         keys_loc.copy_(torch.from_numpy(kh))
-        if n:
-            rows = torch.from_numpy((u // W).astype(np.int32)).to(dev)
-            be.gather_rows(self.E_user, None, rows, U_loc[:n], None)
+        self._serve_latents(u, U_loc[:n])
         if n < B_loc:
             be.fill_zero(U_loc[n:])
         if W > 1:
@@ -1377,6 +1384,13 @@ class ShardedHMF(object):
             _all_to_all(recv_c.view(B, k), out_i, group=self.group)
         be.topk_merge_shards(recv_v, recv_c, vo, io)
         return vo, io
+
+    def _serve_latents(self, u, out):
+        """The latents recommend / evaluate score against the item shard, for the users u (global ids this rank owns)
+        -> out [len(u), d]: this model's are its user rows."""
+        if len(u):
+            rows = torch.from_numpy((u // self.world).astype(np.int32)).to(self.device)
+            self.be.gather_rows(self.E_user, None, rows, out, None)
 
     # -------------------------------------------------------------- evaluate
     def prepare_eval_positives(self, item_sets):
@@ -1454,9 +1468,7 @@ class ShardedHMF(object):
         kh[:n], th[:n] = u, it
         keys_loc.copy_(torch.from_numpy(kh))
         tgt_loc.copy_(torch.from_numpy(th))
-        if n:
-            rows = torch.from_numpy((u // W).astype(np.int32)).to(dev)
-            be.gather_rows(self.E_user, None, rows, U_loc[:n], None)
+        self._serve_latents(u, U_loc[:n])
         if n < B_loc:
             be.fill_zero(U_loc[n:])
         if W > 1:
@@ -1539,6 +1551,366 @@ class ShardedHMF(object):
             full = torch.stack(parts, 1).reshape((rows * W,) + tuple(t.shape[1:]))[:n]
             out[name] = full.cpu().numpy()
         return out
+
+
+W2V_TABLES = ('userembed_cat_0', 'itemembed_cat_0', 'item_outputembed_cat_0', 'item_output_bias_cat_0')
+
+
+class ShardedW2V(ShardedHMF):
+    """The id-only skip-gram / CBOW recommender (word2vec/linear_seq.py LinearSeq, use_sep_item=True) with row-sharded
+    tables: the user table, the CONTEXT (input) item table without bias and the OUTPUT item table with bias, all
+    striped by id % world; the context shard has its own padding (zero) row.  A batch row is (user, n_input context
+    items, target) and its model input is
+        CBOW, train and test:   x = 0.5 u + (0.5 / n) sum_t C[ctx_t]
+        skip-gram, train:       x = 0.5 u + 0.5 C[ctx_0]          (test: the CBOW form)
+    The pool logits, the target score, the positive mask, the loss ('mw' | 'mce'), gscale = 1 / B of the global batch
+    and read_loss() are ShardedHMF's with x in the place of the user row; du = 0.5 dx and context position t gets
+    w_t dx (0.5 / n; skip-gram training: 0.5 for t = 0 and nothing else).
+
+    tables / checkpoint arrays carry the names the single-process model gives these tables -- 'userembed_cat_0',
+    'itemembed_cat_0' (context), 'item_outputembed_cat_0', 'item_output_bias_cat_0' -- with one row per id (the
+    single-process tables without their two reserved leading rows).
+
+    The context rows of a batch live on any ranks, so they are routed like the two rows of a pair step
+    (_prepare_route_pair): the n B_loc requests (skip-gram training: the B_loc of t = 0) are ordered by owner, the
+    rows come back in that order and every (t, b) knows the SLOT of its row in the received block.  One slot serves one
+    request: an item asked for twice travels twice and K7 merges its gradient rows.  _step_body is ShardedHMF's with
+    one more gather site, one more pair of all-to-alls and the two slot-addressed window kernels
+    (arx_window_slots_fwd / _bwd); K7 is one pass over the three tables.
+
+    loss: 'mw' | 'mce'; exchange: 'rows'; n_input >= 1 (ValueError otherwise).  Out of scope: use_sep_item=False (one
+    shared item table), multi-hot or several features per entity, output_feat != 1, dropout, n_input_items = 0."""
+
+    def __init__(self, n_users, n_items, d, B_loc, S, n_input, learning_rate, rank, world, device, cbow=True,
+                 loss='mw', tables=None, backend=None, group=None, seed=0, acc0=0.1, graphs=None, exchange='rows'):
+        if loss not in ('mw', 'mce'):
+            raise ValueError("ShardedW2V: loss is 'mw' or 'mce' (the sampled losses of this family), got %r" % (loss,))
+        if exchange != 'rows':
+            raise ValueError("ShardedW2V: exchange='rows' only (the window's rows travel, not the logits), got %r"
+                             % (exchange,))
+        if int(n_input) < 1:
+            raise ValueError("ShardedW2V: n_input >= 1 context items per row, got %r" % (n_input,))
+        if d > 256:
+            raise ValueError("ShardedW2V: d <= 256 (the window kernels)")
+        self.n_input, self.cbow = int(n_input), bool(cbow)
+        # rows of the window a TRAINING row asks for, and their weight in x
+        self.n_train = self.n_input if self.cbow else 1
+        self.cap_c = 0                                      # capacity for received context requests
+        t = None
+        if tables is not None:
+            missing = [k for k in W2V_TABLES if k not in tables]
+            if missing:
+                raise ValueError("ShardedW2V: tables lacks %s" % ', '.join(missing))
+            t = {'user': tables['userembed_cat_0'], 'item': tables['item_outputembed_cat_0'],
+                 'item_bias': tables['item_output_bias_cat_0']}
+        super().__init__(n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, backend=backend,
+                         group=group, tables=t, seed=seed, acc0=acc0, graphs=graphs, exchange='rows', loss=loss)
+        dev, f32, ni = self.device, torch.float32, self.ni_loc
+        if tables is not None:
+            C = np.asarray(tables['itemembed_cat_0'], dtype=np.float32)[rank::world]
+            self.E_ctx = torch.zeros((ni + 1, d), dtype=f32, device=dev)
+            self.E_ctx[:ni].copy_(torch.from_numpy(np.ascontiguousarray(C)))
+        else:
+            g = torch.Generator(device=dev)
+            g.manual_seed(seed * 1009 + rank + 500009)
+            lim = float(np.sqrt(6.0 / (n_items + 2 + d)))
+            self.E_ctx = torch.empty((ni + 1, d), dtype=f32, device=dev).uniform_(-lim, lim, generator=g)
+            self.E_ctx[ni].zero_()
+        self.A_ctx = torch.full_like(self.E_ctx, self.acc0)
+        n_req = self.n_train * B_loc
+        self.X = torch.zeros((B_loc, d), dtype=f32, device=dev)              # the model input, its gradient
+        self.dX = torch.zeros((B_loc, d), dtype=f32, device=dev)
+        self.C_pack = torch.zeros((n_req, d), dtype=f32, device=dev)         # context rows as received, by slot
+        self.dC_pack = torch.zeros((n_req, self.dp), dtype=f32, device=dev) if world > 1 else None
+        self.g_cslots = torch.zeros((n_req,), dtype=torch.int32, device=dev)
+        self._serve_ctx = None
+        self._alloc_recv(self.cap_r, n_req)
+
+    def _alloc_recv(self, cap, cap_c=0):
+        """ShardedHMF's buffers, and what scales with the context requests this rank serves: the arena is
+        [dU_loc (B_loc) ; dI_g (Sg) ; received dT (cap_r) ; received context gradient rows (cap_c)]."""
+        cap_r0, cap_c0 = self.cap_r, self.cap_c
+        super()._alloc_recv(cap)
+        if cap_c > cap_c0:
+            if self.use_graphs and cap_c0 > 0:
+                cap_c = (cap_c + cap_c // 8 + 63) // 64 * 64
+            self.cap_c = cap_c
+            self.C_send = torch.zeros((cap_c, self.d), dtype=torch.float32, device=self.device)
+        if self.cap_r != cap_r0 or self.cap_c != cap_c0:
+            rows = self.B_loc + self.Sg + self.cap_r + self.cap_c
+            self.arena = torch.zeros((rows, self.dp), dtype=torch.float32, device=self.device)
+            self.arena_b = torch.zeros((rows,), dtype=torch.float32, device=self.device)
+
+    # ------------------------------------------------------------------ route
+    def _context_array(self, context, m, what):
+        c = context.cpu().numpy() if isinstance(context, torch.Tensor) else np.asarray(context)
+        c = c.astype(np.int64)
+        if c.size != self.n_input * m:
+            raise ValueError("%s: context is [n_input = %d][%d] (time-major), got %s"
+                             % (what, self.n_input, m, tuple(np.shape(context))))
+        c = c.reshape(self.n_input, m)
+        if c.size and (c.min() < 0 or c.max() >= self.n_items):
+            raise ValueError("%s: context ids must lie in [0, %d)" % (what, self.n_items))
+        return c
+
+    def _route_context(self, ctx):
+        """The requests ctx [n_win][m] (time-major) of this rank, ordered by owner: one count exchange and one id
+        exchange resolve them to local rows of the owners' context shards; cslots[t * m + b] = the row of request
+        (t, b) in the block that comes back."""
+        W, dev = self.world, self.device
+        req = ctx.reshape(-1).astype(np.int32)
+        owner = req % W
+        perm = np.argsort(owner, kind='stable')
+        slot = np.empty(len(req), dtype=np.int32)
+        slot[perm] = np.arange(len(req), dtype=np.int32)
+        send = np.bincount(owner, minlength=W).astype(np.int64)
+        st = torch.from_numpy(send).to(dev)
+        rt = torch.empty_like(st)
+        _all_to_all(rt, st, group=self.group)
+        recv = [int(v) for v in rt.cpu().tolist()]
+        Rc = int(sum(recv))
+        req_d = torch.from_numpy(np.ascontiguousarray(req[perm])).to(dev)
+        recv_ids = torch.zeros((Rc,), dtype=torch.int32, device=dev)
+        _all_to_all(recv_ids, req_d, recv, [int(v) for v in send.tolist()], group=self.group)
+        rows = torch.zeros((Rc,), dtype=torch.int32, device=dev)
+        if Rc > 0:
+            self.be.shard_route(recv_ids, W, self.rank, self.zero_row, rows, None)
+        return {'cslots': torch.from_numpy(slot).to(dev), 'csend': [int(v) for v in send.tolist()], 'crecv': recv,
+                'Rc': Rc, 'crecv_rows': rows, 'n_win': int(ctx.shape[0]), 'n_req': int(len(req))}
+
+    def prepare_route(self, users, items, context):
+        """ShardedHMF.prepare_route for (users, targets) -- the batch ordered by the target's owner -- with the
+        context columns permuted alongside and the window's requests routed by slot (_route_context).  context:
+        [n_input][B_loc], time-major, as LinearSeq.step takes item_input; a skip-gram model asks for row t = 0 only.
+        Ids outside [0, n_items) raise before anything is sent."""
+        B_loc = self.B_loc
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        it = items.cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
+        u, it = u.astype(np.int32).reshape(-1), it.astype(np.int32).reshape(-1)
+        if len(u) != B_loc or len(it) != B_loc:
+            raise ValueError("prepare_route: B_loc = %d users and items per rank" % B_loc)
+        if it.min() < 0 or it.max() >= self.n_items:
+            raise ValueError("prepare_route: item ids must lie in [0, %d)" % self.n_items)
+        ctx = self._context_array(context, B_loc, "prepare_route")
+        perm = np.argsort(it % self.world, kind='stable')
+        route = super().prepare_route(u[perm], it[perm])         # (sorted already: its own stable sort keeps the order)
+        ctx = ctx[:, perm]
+        route['context'] = torch.from_numpy(np.ascontiguousarray(ctx.astype(np.int32))).to(self.device)
+        route.update(self._route_context(ctx[:self.n_train]))
+        self._alloc_recv(route['R'], route['Rc'])
+        return route
+
+    def step(self, users, items=None, context=None):
+        """One training step: a route of prepare_route(), or (users, items, context), routed here."""
+        if self.world > 1 and self.cap <= 0:
+            raise RuntimeError("ShardedW2V.step before set_pool(): the pool's block layout sizes the exchanges")
+        route = users if isinstance(users, dict) else self.prepare_route(users, items, context)
+        self._run_step(route)
+
+    def _static_feeds(self, route, cap_r):
+        return [(route['cslots'], self.g_cslots)]
+
+    # ------------------------------------------------------------------- step
+    def _step_body(self, route):
+        """ShardedHMF._step_body with the window in front of the scorer:
+
+          fwd_gather   + one site: the requested context rows -> the packed send block [cap_c, d]
+          all_to_all   context rows out, in request order (asynchronous, beside the target-row exchange)
+          fwd_score    arx_window_slots_fwd: X = 0.5 U_loc + w sum_t C_pack[slot(t, b)]; then the scorer on X
+          loss, bwd_gemms   as ShardedHMF with X / dX for U_loc / dU; then arx_window_slots_bwd: 0.5 dX into the
+                       arena's user rows, w dX into the n slots of the gradient block
+          all_to_all   context gradient rows back to their owners, into the arena behind the received target rows
+          apply        ONE sparse_adagrad_multi over the three tables: user rows, pool, received targets, received
+                       context rows
+
+        The per-batch vectors -- [user rows ; received target rows (cap_r) ; received context rows (cap_c)], padded
+        with the shard's zero row, and the slots -- are fed by the first node.  World 1: ONE graph; the context rows
+        are gathered straight into the block the window kernel reads and their gradient rows written straight into
+        the arena.  Arena rows behind the received requests carry the padding key: K7 drops them."""
+        be, W = self.be, self.world
+        B, B_loc, S, Sg, d = self.B, self.B_loc, self.S, self.Sg, self.d
+        grp, dev = self.group, self.device
+        n_w, n_req = self.n_train, self.n_train * B_loc
+        if route.get('n_win') != n_w:
+            raise ValueError("step: the route asks for %r window rows, a training step of this model for %d"
+                             % (route.get('n_win'), n_w))
+        send, recv, R = route['send'], route['recv'], route['R']
+        csend, crecv, Rc = route['csend'], route['crecv'], route['Rc']
+        if R > self.cap_r or Rc > self.cap_c:
+            self._alloc_recv(R, Rc)
+        cap, cap_r, cap_c = self.cap, self.cap_r, self.cap_c
+        n_idx = B_loc + cap_r + cap_c
+        idx = route.get('idx')
+        if idx is None or idx.shape[0] != n_idx or route.get('idx_cap_r') != cap_r:
+            idx = torch.full((n_idx,), self.zero_row, dtype=torch.int32, device=dev)
+            idx[:B_loc] = route['urows']
+            if R > 0:
+                idx[B_loc:B_loc + R] = route['recv_rows']
+            if Rc > 0:
+                idx[B_loc + cap_r:B_loc + cap_r + Rc] = route['crecv_rows']
+            route['idx'], route['idx_cap_r'] = idx, cap_r
+        if self.g_idx is None or self.g_idx.shape[0] != n_idx:
+            self.g_idx = torch.empty(n_idx, dtype=torch.int32, device=dev)
+        feed = [(idx, self.g_idx)] + self._static_feeds(route, cap_r)
+        key = ('w2v', cap, cap_r, cap_c, self.g_idx.data_ptr(), self.arena.data_ptr(), self.C_send.data_ptr(),
+               self.g_cslots.data_ptr(), self.pos_ptr.data_ptr(), self.pos_items.data_ptr())
+        arena, arena_b = self.arena, self.arena_b
+        urows, rrows, crows = self.g_idx[:B_loc], self.g_idx[B_loc:B_loc + cap_r], self.g_idx[B_loc + cap_r:]
+        if W == 1:
+            rrows, crows = rrows[:B_loc], crows[:n_req]
+        self.urows = urows
+        ni = self.ni_loc
+        base_t, base_c = B_loc + Sg, B_loc + Sg + cap_r
+        X, dX, cslots = self.X, self.dX, self.g_cslots
+        w = 0.5 / n_w
+        T_in = self.T_pack if W == 1 else self.T_send[:cap_r]
+        dT = arena[base_t:base_t + B_loc] if W == 1 else self.dT_pack
+        C_in = self.C_pack if W == 1 else self.C_send[:cap_c]
+        dC = arena[base_c:base_c + n_req] if W == 1 else self.dC_pack
+
+        def fwd_gather():      # the step's four lookups, one launch
+            pool = (self.E_item, self.b_item, self.pool_rows, self.I_all, self.b_all) if W == 1 else \
+                (self.E_item, self.b_item, self.pool_rows[:cap], self.I_pack[:cap], 'packed')
+            be.gather_rows_multi([(self.E_user, None, urows, self.U_loc, None), pool,
+                                  (self.E_item, self.b_item, rrows, T_in, 'packed'),
+                                  (self.E_ctx, None, crows, C_in, None)])
+
+        fused = self._fused_scorer()
+
+        def fwd_score():
+            be.window_slots_fwd(self.C_pack, cslots, n_w, w, self.U_loc, 0.5, X)
+            if W > 1:
+                be.gather_rows_multi([(self.I_gath, d, self.gidx, self.I_all, self.b_all)])
+            if not fused:
+                be.gemm(X, self.I_all[:, :d], self.logits, transB=True, col_bias=self.b_all)
+
+        def loss():
+            dt = arena_b[base_t:base_t + B_loc] if W == 1 else dT[:, d]
+            if fused:
+                self.scorer.fwd(X, self.I_all[:, :d], self.b_all, self.T_pack[:, :d], self.T_pack[:, d], urows,
+                                self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.t_loc, dt, dX, dT[:, :d],
+                                1.0 / B)
+                return
+            self._loss_fused(self.logits, X, self.T_pack[:, :d], self.T_pack[:, d], urows, self.pos_ptr,
+                             self.pos_items, self.item2slot, self.bl, self.dlogits, self.t_loc, dt, dX, dT[:, :d],
+                             1.0 / B)
+
+        def bwd_gemms():
+            if fused:
+                self.scorer.bwd_dU(dX, beta=1.0)
+                if W == 1:
+                    self.scorer.bwd_dI(arena[B_loc:B_loc + S, :d], db=arena_b[B_loc:B_loc + S])
+                else:
+                    self.scorer.bwd_dI(self.dI_all[:S, :d], db=self.gb_all)
+                    be.copy_strided(self.gb_all, self.dI_all[:S, d])
+            else:
+                be.gemm(self.dlogits, self.I_all[:, :d], dX, beta=1.0)
+                if W == 1:
+                    be.gemm(self.dlogits, X, arena[B_loc:B_loc + S, :d], transA=True,
+                            a_rowsum=arena_b[B_loc:B_loc + S])
+                else:
+                    be.gemm(self.dlogits, X, self.dI_all[:S, :d], transA=True, a_rowsum=self.gb_all)
+                    be.copy_strided(self.gb_all, self.dI_all[:S, d])
+            # dX -> 0.5 dX into the user rows of the arena, w dX into the window's slots
+            be.window_slots_bwd(dX, cslots, n_w, w, 0.5, arena[:B_loc, :d], False, dC[:, :d])
+
+        def k7(phase):         # one fused scatter + Adagrad pass over the three shards
+            be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
+                                     (self.E_item[:ni], self.A_item[:ni], self.b_item[:ni], self.Ab_item[:ni]),
+                                     (self.E_ctx[:ni], self.A_ctx[:ni], None, None)],
+                                    [(0, urows, 0), (1, self.pool_rows[:cap], B_loc), (1, rrows, base_t),
+                                     (2, crows, base_c)], arena[:, :d], arena_b, self.lr, phase=phase)
+
+        def apply():
+            if W > 1:
+                be.gather_rows_multi([(self.dI_all, d, self.my_slots[:cap], arena[B_loc:B_loc + cap],
+                                       arena_b[B_loc:B_loc + cap])])
+                be.copy_strided(arena[base_t:base_t + cap_r, d], arena_b[base_t:base_t + cap_r])
+            k7(2)
+
+        def body(mode):
+            seg = lambda name, fn, feeds=None: self._segment(mode, name, fn, feeds)
+
+            def whole_step():
+                fwd_gather()
+                sorted_ = self._k7_sorts(mode, k7, False)
+                fwd_score()
+                loss()
+                bwd_gemms()
+                self._k7_join(sorted_)
+                apply()
+
+            if W == 1:
+                return seg('step', whole_step, feed)
+            seg('fwd_gather', fwd_gather, feed)
+            sorted_ = self._k7_sorts(mode, k7, True)
+            dist.all_gather_into_tensor(self.I_gath[:W * cap], self.I_pack[:cap], group=grp)
+            w_rows = _all_to_all(self.T_pack, self.T_send[:R], send, recv, group=grp, async_op=True)
+            w_ctx = _all_to_all(self.C_pack[:n_req], self.C_send[:Rc], csend, crecv, group=grp, async_op=True)
+            w_ctx.wait()
+            seg('fwd_score', fwd_score)                       # window + scorer GEMM under the target-row exchange
+            w_rows.wait()
+            seg('loss', loss)
+            w_dt = _all_to_all(arena[base_t:base_t + R], self.dT_pack, recv, send, group=grp, async_op=True)
+            seg('bwd_gemms', bwd_gemms)
+            w_dc = _all_to_all(arena[base_c:base_c + Rc], self.dC_pack[:n_req], crecv, csend, group=grp,
+                               async_op=True)
+            dist.all_reduce(self.dI_all[:S], op=dist.ReduceOp.SUM, group=grp)
+            w_dt.wait()
+            w_dc.wait()
+            self._k7_join(sorted_)
+            seg('apply', apply)
+
+        return key, body
+
+    # ---------------------------------------------------------------- serving
+    def _serve_latents(self, u, out):
+        """x_test = 0.5 u + (0.5 / n) sum_t C[ctx_t] over the FULL window (skip-gram too), eagerly: the window's
+        requests are routed (a collective, like the calls that use it), the rows cross and the forward window
+        kernel forms the latents."""
+        be, W, d, n, m = self.be, self.world, self.d, self.n_input, len(u)
+        f32, dev = torch.float32, self.device
+        ctx = self._serve_ctx
+        r = self._route_context(ctx)
+        send_blk = torch.zeros((max(r['Rc'], 1), d), dtype=f32, device=dev)
+        if r['Rc'] > 0:
+            be.gather_rows(self.E_ctx, None, r['crecv_rows'], send_blk[:r['Rc']], None)
+        if W == 1:
+            block = send_blk
+        else:
+            block = torch.zeros((max(r['n_req'], 1), d), dtype=f32, device=dev)
+            _all_to_all(block[:r['n_req']], send_blk[:r['Rc']], r['csend'], r['crecv'], group=self.group)
+        if m:
+            base = torch.zeros((m, d), dtype=f32, device=dev)
+            super()._serve_latents(u, base)
+            be.window_slots_fwd(block, r['cslots'], n, 0.5 / n, base, 0.5, out)
+
+    def recommend(self, users, context, k, exclude_seen=False, return_values=False):
+        """ShardedHMF.recommend over x_test of (users, context): context is [n_input][len(users)], time-major."""
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        self._serve_ctx = self._context_array(context, int(u.size), "recommend")
+        try:
+            return super().recommend(users, k, exclude_seen=exclude_seen, return_values=return_values)
+        finally:
+            self._serve_ctx = None
+
+    def evaluate(self, users, context, items, loss='warp', return_rows=False):
+        """ShardedHMF.evaluate over x_test of (users, context): context is [n_input][len(users)], time-major."""
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        self._serve_ctx = self._context_array(context, int(u.size), "evaluate")
+        try:
+            return super().evaluate(users, items, loss=loss, return_rows=return_rows)
+        finally:
+            self._serve_ctx = None
+
+    def _checkpoint_arrays(self):
+        nu, ni = self.n_users, self.n_items
+        return [('userembed_cat_0', self.E_user, nu, 'rows'), ('userembed_cat_0/Adagrad', self.A_user, nu, 'rows'),
+                ('itemembed_cat_0', self.E_ctx, ni, 'rows'), ('itemembed_cat_0/Adagrad', self.A_ctx, ni, 'rows'),
+                ('item_outputembed_cat_0', self.E_item, ni, 'rows'),
+                ('item_outputembed_cat_0/Adagrad', self.A_item, ni, 'rows'),
+                ('item_output_bias_cat_0', self.b_item, ni, 'rows'),
+                ('item_output_bias_cat_0/Adagrad', self.Ab_item, ni, 'rows')]
 
 
 class ShardedHMFBags(ShardedHMF):

@@ -155,6 +155,35 @@ def gather_window(E, cat_map, ids, n, out, scale=1.0, base=None, base_scale=1.0)
     return out
 
 
+def window_slots_fwd(R, slots, n, out, scale=1.0, base=None, base_scale=1.0):
+    """out[b] = base_scale * base[b] + scale * sum_t R[slots[t * mb + b], :d] (arx_window_slots_fwd): the context
+    window over the rows of a received block, named by slot; d = out's width, R / base / out may be wider views."""
+    _chk(R, torch.float32, 'R'); _chk(slots, torch.int32, 'slots'); _chk(out, torch.float32, 'out')
+    _chk(base, torch.float32, 'base')
+    total, n, d = int(slots.shape[0]), int(n), int(out.shape[1])
+    if n < 1 or total % n or int(out.shape[0]) != total // n:
+        raise ValueError("window_slots_fwd: %d slots, n = %d, %d output rows" % (total, n, int(out.shape[0])))
+    if int(R.shape[1]) != d or (base is not None and tuple(base.shape) != (total // n, d)):
+        raise ValueError("window_slots_fwd: R must be [*, d] and base [mb, d]")
+    call("arx_window_slots_fwd", _p(R), _ld(R), _p(slots), n, total // n, d, float(scale), _p(base),
+         _ld(base) if base is not None else 0, float(base_scale), _p(out), _ld(out), _stream())
+    return out
+
+
+def window_slots_bwd(dX, slots, n, dbase, dR, scale=1.0, base_scale=1.0, acc_dbase=False):
+    """dbase[b] (+)= base_scale * dX[b]; dR[slots[t * mb + b]] = scale * dX[b] for every t (arx_window_slots_bwd)."""
+    for t, nm in ((dX, 'dX'), (dbase, 'dbase'), (dR, 'dR')):
+        _chk(t, torch.float32, nm)
+    _chk(slots, torch.int32, 'slots')
+    total, n, mb, d = int(slots.shape[0]), int(n), int(dX.shape[0]), int(dX.shape[1])
+    if n < 1 or total != n * mb:
+        raise ValueError("window_slots_bwd: %d slots, n = %d, %d gradient rows" % (total, n, mb))
+    if tuple(dbase.shape) != (mb, d) or int(dR.shape[1]) != d:
+        raise ValueError("window_slots_bwd: dbase must be [mb, d] and dR [*, d]")
+    call("arx_window_slots_bwd", _p(dX), _ld(dX), _p(slots), n, mb, d, float(scale), float(base_scale), _p(dbase),
+         _ld(dbase), 1 if acc_dbase else 0, _p(dR), _ld(dR), _stream())
+
+
 def shard_route(ids, world, rank, zero_row, rows_out, keys_out):
     call("arx_shard_route", _p(ids), int(ids.shape[0]), int(world), int(rank), int(zero_row),
          _p(rows_out), _p(keys_out), _stream())

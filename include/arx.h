@@ -143,6 +143,24 @@ int arx_gather_window_fwd(const float* E, const int32_t* cat_map, const int32_t*
                           float scale, const float* base, int64_t ldb, float base_scale, float* out, int64_t ldo,
                           void* stream);
 
+/* The same window over the rows of a RECEIVED block (the row-sharded skip-gram / CBOW model, arx.dist.ShardedW2V:
+ * the context rows arrive from their owners in request order and every (t, b) is told the slot of its row):
+ *   out[b, 0:d] = base_scale * base[b, 0:d] + scale * sum_{t < n} R[slots[t * mb + b], 0:d],   b < mb
+ * R: rows ldr floats apart (ldr >= d: a packed block may be wider than d); slots are not range checked; the sum runs
+ * in ascending t as above (the same kernel).  base nullable.  n >= 1, n * mb < 2^31, d % 4 == 0, d <= 256 (else
+ * ARX_EUNSUPPORTED), ldr / ldo / ldb % 4 == 0 and >= d, R / base / out 16-byte aligned (ARX_EINVAL). */
+int arx_window_slots_fwd(const float* R, int64_t ldr, const int32_t* slots, int n, int64_t mb, int d, float scale,
+                         const float* base, int64_t ldb, float base_scale, float* out, int64_t ldo, void* stream);
+/* Its backward: one gradient row dX[b] in, n + 1 rows out --
+ *   dbase[b, 0:d] = (acc_dbase ? dbase[b, 0:d] : 0) + base_scale * dX[b, 0:d]
+ *   dR[slots[t * mb + b], 0:d] = scale * dX[b, 0:d]   for every t < n
+ * One slot has one writer (a slot named twice: either writer's row), no atomics; rows of dR that no slot names and
+ * the columns behind d are not written.  Every element is one fp32 multiply (acc_dbase: and one add, unfused).
+ * Limits as above for ldx / ldbase / ldr and dX / dbase / dR; acc_dbase is 0 or 1. */
+int arx_window_slots_bwd(const float* dX, int64_t ldx, const int32_t* slots, int n, int64_t mb, int d, float scale,
+                         float base_scale, float* dbase, int64_t ldbase, int acc_dbase, float* dR, int64_t ldr,
+                         void* stream);
+
 /* Packed form for the sharded exchanges (no reference counterpart): row r of the
  * output holds [ scale * E[row] (d floats) | scale * bias[row] | pad ], ldo > d -- the bias rides
  * in column d of the row that is sent to the peer, no second buffer and no copy. */

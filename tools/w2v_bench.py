@@ -9,8 +9,11 @@ n = 5 context items, d = 128, a 1 M-row item table, Zipf ids (SyntheticHMF, the 
       fused : gather_window, one add_rows_bcast (user gradient), sparse_site_window + sparse_adagrad over mb rows
     GB/s = algorithmic bytes (from the shapes, stage_bytes()) / median time.
 (b) whole step: CBOW 'mw', S = 1024, interactions/s = mb / step time, fuse_window True and False.
+(c) --sharded: the world-1 step of the row-sharded model (arx.dist.ShardedW2V, routes prepared ahead, one captured
+    graph) next to the single-process LinearSeq step (fused window) of the same shape and --loss; replaces (a), (b).
 
 usage: python tools/w2v_bench.py [--steps 50] [--warmup 10] [--repeats 21] [--skip-step] [--out FILE.json]
+       python tools/w2v_bench.py --sharded [--loss mw|mce] [--out FILE.json]
 """
 import argparse
 import gc
@@ -130,7 +133,65 @@ def input_stage(args, syn, dev):
             'fused_frac_of_hbm_peak': b_fus / t_fus / 1e6 / HBM_PEAK_GBS}
 
 
-def whole_step(args, syn, dev):
+def _median_step_ms(step, args):
+    """Median over regions of --steps calls of step(k), after --warmup calls."""
+    for k in range(args.warmup):
+        step(k)
+    times = []
+    for _ in range(max(3, args.repeats // 4)):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        for k in range(args.warmup, args.warmup + args.steps):
+            last = step(k)
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1) / args.steps)
+    return sorted(times)[len(times) // 2], last
+
+
+def sharded_step(args, syn, dev):
+    """(c): CBOW, --loss, the shape of (b).  Both models start from their own random tables (the timing does not
+    depend on the values); the sharded one is timed twice -- reading the loss back every step, as LinearSeq.step
+    does, and without."""
+    import torch.distributed as dist
+    from arx.dist import ShardedW2V
+    from arx.utils.prepare_train import DeviceSampler
+    mb, n, d, S = args.batch, args.n_input, args.dim, args.n_sampled
+    res = whole_step(args, syn, dev, variants=(('fused', True),), loss=args.loss)
+    res = {'linear_seq': res['fused']}
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    os.environ.setdefault("MASTER_PORT", "29777")
+    os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    dist.init_process_group("nccl", rank=0, world_size=1, device_id=dev)
+    model = ShardedW2V(args.n_users, args.n_items, d, mb, S, n, 0.1, 0, 1, dev, cbow=True, loss=args.loss)
+    model.set_positives(syn.pos_ptr, syn.pos_items)
+    model.set_pool(DeviceSampler(syn.item_population, syn.p_sample, device=dev, seed=1).sample(S))
+    rng = np.random.default_rng(2)
+    routes = []
+    for _ in range(16):
+        u, t = syn.sample_batch(mb, rng)
+        ctx = np.stack([syn.sample_batch(mb, rng)[1] for _ in range(n)], 0)
+        routes.append(model.prepare_route(u, t, ctx))
+
+    def step(k):
+        model.step(routes[k % len(routes)])
+
+    def step_read(k):
+        model.step(routes[k % len(routes)])
+        return float(model.read_loss().item())
+    with torch.cuda.stream(model.stream):
+        ms_read, loss = _median_step_ms(step_read, args)
+        ms, _ = _median_step_ms(step, args)
+    res['sharded_world1'] = {'ms_per_step': ms_read, 'interactions_per_s': mb / ms_read * 1e3,
+                             'ms_per_step_no_readback': ms, 'interactions_per_s_no_readback': mb / ms * 1e3,
+                             'last_loss': loss, 'n_captures': model.n_captures, 'n_replays': model.n_replays,
+                             'fused_scorer': bool(model._fused_scorer())}
+    dist.destroy_process_group()
+    return res
+
+
+def whole_step(args, syn, dev, variants=(('fused', True), ('unfused', False)), loss='mw'):
     from arx.utils.prepare_train import DeviceSampler
     from arx.word2vec import cbow_model
     mb, n, d, S = args.batch, args.n_input, args.dim, args.n_sampled
@@ -143,30 +204,18 @@ def whole_step(args, syn, dev):
         batches.append(tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (u, ctx, t)))
     pool = DeviceSampler(syn.item_population, syn.p_sample, device=dev, seed=1).sample(S)
     res = {}
-    for name, fuse in (('fused', True), ('unfused', False)):
+    for name, fuse in variants:
         model = cbow_model.Model(args.n_users, args.n_items, d, mb, 0.1, 1.0, syn.u_attr, syn.i_attr,
                                  syn.item2logit[:args.n_items], syn.logit_ind2item_ind, n_input_items=n,
-                                 loss_function='mw', use_sep_item=True, n_sampled=S, fuse_window=fuse)
+                                 loss_function=loss, use_sep_item=True, n_sampled=S, fuse_window=fuse)
         model.prepare_warp(syn.positives_csr(), syn.positives_csr())
         assert model.fuse_window == fuse
 
         def step(k):
             u, ctx, t = batches[k % nb]
             return model.step(None, u, ctx, t, item_sampled=pool if k == 0 else None)
-        for k in range(args.warmup):
-            step(k)
-        times = []
-        for _ in range(max(3, args.repeats // 4)):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            e0.record()
-            for k in range(args.warmup, args.warmup + args.steps):
-                loss = step(k)
-            e1.record()
-            torch.cuda.synchronize()
-            times.append(e0.elapsed_time(e1) / args.steps)
-        ms = sorted(times)[len(times) // 2]
-        res[name] = {'ms_per_step': ms, 'interactions_per_s': mb / ms * 1e3, 'last_loss': float(loss),
+        ms, last = _median_step_ms(step, args)
+        res[name] = {'ms_per_step': ms, 'interactions_per_s': mb / ms * 1e3, 'last_loss': float(last),
                      'note': 'step() reads the loss back every step (one device -> host sync per step)'}
         del model
         gc.collect()
@@ -187,6 +236,8 @@ def main():
     ap.add_argument('--n-users', type=int, default=1000000)
     ap.add_argument('--n-sampled', type=int, default=1024)
     ap.add_argument('--skip-step', action='store_true', help="(a) only")
+    ap.add_argument('--sharded', action='store_true', help="(c): world-1 ShardedW2V step next to LinearSeq's")
+    ap.add_argument('--loss', default='mw', choices=['mw', 'mce'], help="the loss of (c)")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     if args.repeats < 20:
@@ -196,9 +247,13 @@ def main():
     from arx.utils.synthetic import SyntheticHMF
     dev = torch.device('cuda:0')
     syn = SyntheticHMF(n_users=args.n_users, n_items=args.n_items, permute_logits=False, seed=0)
-    out = {'input_stage': input_stage(args, syn, dev)}
-    print('input_stage', json.dumps(out['input_stage']), flush=True)
-    if not args.skip_step:
+    out = {}
+    if args.sharded:
+        out['sharded_step_' + args.loss] = sharded_step(args, syn, dev)
+    else:
+        out['input_stage'] = input_stage(args, syn, dev)
+        print('input_stage', json.dumps(out['input_stage']), flush=True)
+    if not args.skip_step and not args.sharded:
         gc.collect()
         torch.cuda.synchronize()
         torch.cuda.empty_cache()

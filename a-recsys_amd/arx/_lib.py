@@ -71,6 +71,8 @@ PROTOTYPES = {
                                    f32p, i64, cint, f32p, i64, i32p, vp]),
     "arx_pair_auc": (cint, [f32p, f32p, i32p, i64, f32p, vp]),
     "arx_neg_draw_uniform": (cint, [i32p, i64, i64, i32p, i32p, i64, i32p, u64, vp, u64, i32p, i32p, i32p, vp]),
+    "arx_neg_draw_weighted": (cint, [i32p, i64, i64, i32p, i32p, vp, vp, i64, i32p, u64, vp, u64, i32p, i32p, vp,
+                                     vp]),
     "arx_gemm_f32_workspace_bytes": (sz, [i64, i64, i64]),
     "arx_gemm_nt_bx6_workspace_bytes": (sz, [i64, i64]),
     "arx_gemm_nt_bx6": (cint, [i64, i64, i64, f32p, i64, f32p, i64, f32p, f32p, i64, vp, sz, vp]),

@@ -24,6 +24,7 @@ import torch
 from .. import graph as G
 from .. import ops
 from ..topk import logits_too_big
+from ..utils.prepare_train import pair_draw_tables
 
 # the full-vocabulary loss a model trained with a sampled loss evaluates with (hmf_model.py:130,144; 'mce' -> 'ce':
 # run_hmf.py:255,304)
@@ -652,19 +653,36 @@ class EmbeddingAttribute(object):
             raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
         return (self.u_indices['input'].value, self.batch_size, ex[0], ex[1])
 
-    def prepare_pair_negatives(self, hist, seed=0):
+    def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
         """The items a drawn negative of the pair losses must not hit, per user -- typically the training history:
         {user_index: items} or a (ptr, items) CSR pair in item-index space (the forms of
         prepare_recommend_exclusions).  Uploaded as sorted logit columns together with logit_ind2item_ind; steps
         without neg_item_input then draw their negatives on the device (graph.NegPairDraw).  BUILD-DEFINED: the
-        reference's draw is a commented-out host rejection loop (hmf_model.py:263-274).  A second call replaces the
-        lists and the seed."""
+        reference's draw is a commented-out host rejection loop (hmf_model.py:263-274).
+        power None: uniform over the user's other columns (arx_neg_draw_uniform).  A number: in proportion to
+        (counts + smooth) ** power (arx_neg_draw_weighted; 0.75 is the unigram rule of word2vec) -- counts per ITEM
+        index, by default the number of users whose list holds the item; an item with counts + smooth == 0 is never
+        drawn.  The two int64 tables of that draw (prepare_train.pair_draw_tables) are built here, once.
+        A second call replaces the lists, the tables and the seed."""
         if self._item2logit_np is None or self.logit_ind2item_ind is None:
             raise ValueError("pair negatives need item_ind2logit_ind and logit_ind2item_ind")
         ptr, cols = exclusion_csr(hist, self.n_users + 1, self._item2logit_np)      # users 0..n_users (_pos_csr)
         rt = self.rt
+        l2i = _np_i32(self.logit_ind2item_ind)
+        tables = (None, None)
+        if power is not None:
+            V = self.logit_size
+            if counts is None:
+                col_counts = np.bincount(cols[:ptr[-1]], minlength=V)[:V]          # (the lists are deduplicated)
+            else:
+                counts = np.asarray(counts).reshape(-1)
+                if len(l2i) and (l2i.min() < 0 or l2i.max() >= len(counts)):
+                    raise ValueError("prepare_pair_negatives: counts holds one entry per item index")
+                col_counts = counts[l2i[:V]]
+            cum, ex_cum = pair_draw_tables(col_counts, power, smooth, ptr, cols)
+            tables = (rt.upload(ex_cum, torch.int64), rt.upload(cum, torch.int64))
         self._pair_lists = (rt.upload(ptr, torch.int32), rt.upload(cols, torch.int32),
-                            rt.upload(_np_i32(self.logit_ind2item_ind), torch.int32))
+                            rt.upload(l2i, torch.int32)) + tables
         if getattr(self, 'neg_draw', None) is None:
             self.neg_draw = G.NegPairDraw(rt, self.u_indices['input'], self.i_indices['neg'],
                                           lambda: self._pair_lists, self.logit_size, seed)

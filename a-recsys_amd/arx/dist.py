@@ -43,6 +43,7 @@ import torch.distributed as dist
 
 from . import ops as _ops
 from .topk import TopKScan, run_complete
+from .utils.prepare_train import pair_draw_tables
 
 
 class _Done(object):
@@ -209,6 +210,12 @@ class HipBackend(object):
         ex_cols), uniform by rank-select, keyed by (seed, counter, r); -1 where the list is all of [0, V)
         (arx_neg_draw_uniform, no col2item)."""
         self.ops.neg_draw_uniform(urows, ex_ptr, ex_cols, V, None, seed, None, counter, out)
+
+    def neg_draw_weighted(self, urows, ex_ptr, ex_cols, ex_cum, cum, V, seed, counter, out):
+        """out[r] = one item of [0, V) outside the list of local user row urows[r], drawn in proportion to the integer
+        weights whose exclusive prefix sum is cum (int64 [V + 1]; ex_cum: the prefix sums along each list), keyed by
+        (seed, counter, r); -1 where no weight is left outside the list (arx_neg_draw_weighted, no col2item)."""
+        self.ops.neg_draw_weighted(urows, ex_ptr, ex_cols, ex_cum, cum, V, None, seed, None, counter, out)
 
     def sum_scaled(self, x, scale, out):
         self.ops.sum_scaled(x, scale, out)
@@ -432,6 +439,7 @@ class ShardedHMF(object):
         self.loss_name, self.pair = loss, pair
         self.seed, self.n_draws = int(seed), 0              # the pair draw: keyed by (seed, rank, n_draws)
         self._neg_csr = None                                # (ptr, cols) of prepare_pair_negatives
+        self._neg_tables = None                             # (ex_cum, cum) of a weighted draw, None: uniform
         # 'logits' (the exchange north_star words): the latents are all-gathered, every owner
         # scores the WHOLE batch against its pool block, the [B, S_g] partial logits cross by all_to_all, and their
         # gradients cross back -- _step_logits.  Eager launches (no graph segments).
@@ -638,11 +646,16 @@ class ShardedHMF(object):
             self.dU_red = z(B_loc, self.d)
 
     # ------------------------------------------------------------------ route
-    def prepare_pair_negatives(self, seed=None):
+    def prepare_pair_negatives(self, seed=None, power=None, smooth=1.0, counts=None):
         """Makes this rank's set_positives lists the exclusion lists of the pair draw (prepare_route without
         neg_items): checks the ids, sorts every user's list and drops its duplicates -- the rank-select draw
         (arx_neg_draw_uniform) needs sorted, unique lists.  The lists set_positives holds stay as they are.
-        seed: the draw's seed (default: the constructor's); the draw counter starts again only with a new seed."""
+        seed: the draw's seed (default: the constructor's); the draw counter starts again only with a new seed.
+        power None: the draw is uniform over the items outside the list.  A number: in proportion to (counts +
+        smooth) ** power (arx_neg_draw_weighted) -- counts int [n_items] per global item id, the same on every rank;
+        by default the number of users of ALL ranks whose list holds the item (one all-reduce of n_items int64 over
+        the model's group: a collective, every rank calls with power set).  The prefix sums of the weights are
+        replicated: 8 bytes per item and 8 bytes per local history entry on every rank."""
         if not self.pair:
             raise RuntimeError("prepare_pair_negatives: a %r model draws no negatives" % self.loss_name)
         ptr = self.pos_ptr.cpu().numpy().astype(np.int64)
@@ -664,6 +677,21 @@ class ShardedHMF(object):
         np.cumsum(np.bincount(row, minlength=len(ptr) - 1), out=nptr[1:])
         if len(items) == 0:
             items = np.zeros(1, dtype=np.int64)             # (a valid device pointer; every list is empty)
+        tables = None
+        if power is not None:
+            if counts is None:
+                cnt = torch.from_numpy(np.bincount(items[:nptr[-1]], minlength=self.n_items).astype(np.int64))
+                if self.world > 1:
+                    cnt = cnt.to(self.device)
+                    dist.all_reduce(cnt, op=dist.ReduceOp.SUM, group=self.group)
+                counts = cnt.cpu().numpy()
+            counts = np.asarray(counts).reshape(-1)
+            if len(counts) != self.n_items:
+                raise ValueError("prepare_pair_negatives: counts holds one entry per item (%d, not %d)"
+                                 % (self.n_items, len(counts)))
+            cum, ex_cum = pair_draw_tables(counts, power, smooth, nptr, items)
+            tables = (torch.from_numpy(ex_cum).to(self.device), torch.from_numpy(cum).to(self.device))
+        self._neg_tables = tables
         self._neg_csr = (torch.from_numpy(nptr.astype(np.int32)).to(self.device),
                          torch.from_numpy(items.astype(np.int32)).to(self.device))
         if seed is not None and int(seed) != self.seed:
@@ -695,8 +723,13 @@ class ShardedHMF(object):
                 raise RuntimeError("prepare_route without neg_items draws the negatives: call "
                                    "prepare_pair_negatives() first (after set_positives)")
             drawn = torch.zeros((B_loc,), dtype=torch.int32, device=dev)
-            self.be.neg_draw_uniform(urows, self._neg_csr[0], self._neg_csr[1], self.n_items,
-                                     self.seed * 1000003 + self.rank, self.n_draws, drawn)
+            if self._neg_tables is None:
+                self.be.neg_draw_uniform(urows, self._neg_csr[0], self._neg_csr[1], self.n_items,
+                                         self.seed * 1000003 + self.rank, self.n_draws, drawn)
+            else:
+                self.be.neg_draw_weighted(urows, self._neg_csr[0], self._neg_csr[1], self._neg_tables[0],
+                                          self._neg_tables[1], self.n_items, self.seed * 1000003 + self.rank,
+                                          self.n_draws, drawn)
             self.n_draws += 1
             ng = drawn.cpu().numpy().astype(np.int32)
         else:

@@ -841,7 +841,10 @@ class NegPairDraw(Node):
     list covers the vocabulary; the placeholder `target` gets the same ids with a valid item in place of -1 (that
     row's gradients are zero: PairLoss).  The node owns a device counter and bumps it after every draw, so a replayed
     graph draws anew.  pre_step: the plan runs it before its lookups and before the K7 sort branch forks -- both read
-    the placeholder."""
+    the placeholder.
+    lists() -> (ptr, cols, col2item, ex_cum, cum): with the two int64 weight tables set the draw is the weighted one
+    (arx_neg_draw_weighted: in proportion to the column weights, -1 for a user whose list covers every column that
+    has weight); with None for both it is the uniform one."""
 
     pre_step = True
 
@@ -852,9 +855,13 @@ class NegPairDraw(Node):
         self.counter = torch.zeros(1, dtype=torch.int64, device=rt.device)
 
     def forward(self, train):
-        ptr, cols, col2item = self.lists()
-        ops.neg_draw_uniform(self.inputs[0].value, ptr, cols, self.V, col2item, self.seed, self.counter, 0,
-                             self.value, lookup_items=self.target.value)
+        ptr, cols, col2item, ex_cum, cum = self.lists()
+        if cum is None:
+            ops.neg_draw_uniform(self.inputs[0].value, ptr, cols, self.V, col2item, self.seed, self.counter, 0,
+                                 self.value, lookup_items=self.target.value)
+        else:
+            ops.neg_draw_weighted(self.inputs[0].value, ptr, cols, ex_cum, cum, self.V, col2item, self.seed,
+                                  self.counter, 0, self.value, lookup_items=self.target.value)
         ops.counter_add(self.counter, 1)
 
 

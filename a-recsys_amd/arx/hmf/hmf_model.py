@@ -255,17 +255,18 @@ class LatentProductModel(object):
         self._plans.pop('recommend_ex', None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
-    def prepare_pair_negatives(self, hist, seed=0):
+    def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
         """'bpr' / 'bpr-hinge': the items a DRAWN negative must not hit, per user -- typically the training history:
         {user_index: items} or a (ptr, items) CSR pair in item-index space.  After this call a step without
-        neg_item_input draws one negative per row on the device, uniform over the user's other items
-        (EmbeddingAttribute.prepare_pair_negatives).  A second call replaces the lists (the drawing plans are
-        dropped)."""
+        neg_item_input draws one negative per row on the device: uniform over the user's other items (power None),
+        or in proportion to (counts + smooth) ** power -- counts per item index, by default the number of users
+        whose list holds the item; 0.75 is the usual unigram rule (EmbeddingAttribute.prepare_pair_negatives).
+        A second call replaces the lists, the weights and the seed (the drawing plans are dropped)."""
         if self.loss_function not in ('bpr', 'bpr-hinge'):
             raise ValueError("prepare_pair_negatives: a model of the 'bpr' / 'bpr-hinge' losses")
         for key in ('train_draw', 'eval_draw'):
             self._plans.pop(key, None)
-        self.att_emb.prepare_pair_negatives(hist, seed=seed)
+        self.att_emb.prepare_pair_negatives(hist, seed=seed, power=power, smooth=smooth, counts=counts)
 
     def _plan(self, key):
         if key in self._plans:

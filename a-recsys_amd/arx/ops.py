@@ -427,6 +427,27 @@ def neg_draw_uniform(users, ex_ptr, ex_cols, V, col2item, seed, step_dev, counte
     return neg_items
 
 
+def neg_draw_weighted(users, ex_ptr, ex_cols, ex_cum, cum, V, col2item, seed, step_dev, counter, neg_items,
+                      lookup_items=None, out_mass=None):
+    """One negative per row, drawn in proportion to integer column weights over the logit columns outside the user's
+    sorted list (arx.h arx_neg_draw_weighted); -1 for a user without eligible weight.  cum int64 [V + 1]: the
+    exclusive prefix sum of the weights; ex_cum int64, aligned with ex_cols: the prefix sums along each list
+    (arx.utils.prepare_train.pair_draw_tables).  out_mass int64 [B]: the drawn point of the eligible mass."""
+    _chk(users, torch.int32, "users")
+    _chk(neg_items, torch.int32, "neg_items")
+    _chk(ex_cols, torch.int32, "ex_cols")
+    _chk(ex_cum, torch.int64, "ex_cum")
+    _chk(cum, torch.int64, "cum")
+    if int(cum.shape[0]) != int(V) + 1 or int(ex_cum.shape[0]) != int(ex_cols.shape[0]):
+        raise ValueError("neg_draw_weighted: cum holds V + 1 entries and ex_cum one per entry of ex_cols")
+    if out_mass is not None:
+        _chk(out_mass, torch.int64, "out_mass")
+    call("arx_neg_draw_weighted", _p(users), int(users.shape[0]), int(ex_ptr.shape[0]) - 1, _p(ex_ptr), _p(ex_cols),
+         _p(ex_cum), _p(cum), int(V), _p(col2item), int(seed) & (2 ** 64 - 1), _p(step_dev),
+         int(counter) & (2 ** 64 - 1), _p(neg_items), _p(lookup_items), _p(out_mass), _stream())
+    return neg_items
+
+
 # ---- a8 -----------------------------------------------------------------------
 # The scorer products run on the bf16 matrix pipe, f32-exact (three exact bf16 pieces per operand, six MFMA terms,
 # f32 accumulation: csrc/gemm_bx6.hip) -- the default since round 4; ARX_SCORER_F32=1 selects the f32-input MFMA

@@ -43,6 +43,45 @@ def positive_items(data_tr, data_va):
     return by_user(data_tr), by_user(data_va)
 
 
+def pair_draw_weights(counts, power, smooth=1.0):
+    """The integer column weights of the weighted pair draw (arx_neg_draw_weighted): w = (counts + smooth) ** power in
+    float64, 0 where counts + smooth == 0 (also for power 0); q = 0 where w == 0, else max(1, floor(w / max(w) * 2^32))
+    as int64 -- the heaviest column weighs 2^32, every column with weight keeps at least one quantum."""
+    power, smooth = float(power), float(smooth)
+    if not power >= 0 or not np.isfinite(power):
+        raise ValueError("pair draw: power must be finite and >= 0, got %r" % (power,))
+    if not smooth >= 0 or not np.isfinite(smooth):
+        raise ValueError("pair draw: smooth must be finite and >= 0, got %r" % (smooth,))
+    base = np.asarray(counts, dtype=np.float64).reshape(-1) + smooth
+    if len(base) and (not np.isfinite(base).all() or base.min() < 0):
+        raise ValueError("pair draw: counts must be finite and >= 0")
+    w = np.where(base == 0, 0.0, np.power(base, power))
+    if not len(w) or w.max() <= 0:
+        raise ValueError("pair draw: every column has weight zero")
+    q = np.floor(w / w.max() * 4294967296.0).astype(np.int64)
+    return np.where(w == 0, 0, np.maximum(q, 1)).astype(np.int64)
+
+
+def pair_draw_tables(counts, power, smooth, ptr, cols):
+    """The two host tables of the weighted pair draw: counts [V] per column, (ptr, cols) the CSR of sorted, unique
+    exclusion lists in the same column space.  -> (cum int64 [V + 1], the exclusive prefix sum of pair_draw_weights;
+    ex_cum int64 [len(cols)], ex_cum[ptr[u] + j] = the weight of the first j entries of user u's list).  Built once
+    per prepare_pair_negatives: a few numpy passes over the columns and the history entries."""
+    q = pair_draw_weights(counts, power, smooth)
+    cum = np.zeros(len(q) + 1, dtype=np.int64)
+    np.cumsum(q, out=cum[1:])
+    ptr = np.asarray(ptr, dtype=np.int64)
+    cols = np.asarray(cols, dtype=np.int64)
+    n = int(ptr[-1])
+    if n and (cols[:n].min() < 0 or cols[:n].max() >= len(q)):
+        raise ValueError("pair draw: list entries must lie in [0, %d)" % len(q))
+    run = np.zeros(n + 1, dtype=np.int64)                    # prefix sums along ALL entries ...
+    np.cumsum(q[cols[:n]], out=run[1:])
+    ex_cum = np.zeros(len(cols), dtype=np.int64)             # ... minus the value at each list's start
+    ex_cum[:n] = run[:n] - np.repeat(run[ptr[:-1]], np.diff(ptr))
+    return cum, ex_cum
+
+
 class DeviceSampler(object):
     """On-device twin of sample_items(items, n, p, replace=False) for large item sets
     (SURVEY 8f #1): same distribution (sequential weighted draws without replacement), drawn as

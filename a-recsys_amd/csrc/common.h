@@ -63,6 +63,14 @@ __device__ __forceinline__ uint32_t mix32(uint64_t z) {
   return (uint32_t)(z >> 32);
 }
 
+// All 64 bits of the same finaliser (mix32 is its high half): the weighted negative draw scales a 64-bit mass
+__device__ __forceinline__ uint64_t mix64(uint64_t z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+
 // number of CUs of the current device (cached)
 int cu_count();
 

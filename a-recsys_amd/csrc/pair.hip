@@ -6,6 +6,7 @@
 //                         negative row of an interaction are two rows of ONE received block, arx/dist.py)
 //  arx_pair_auc         : auc = 0.5 - 0.5 * mean sign(neg_score - pos_score) (hmf_model.py:107)
 //  arx_neg_draw_uniform : one negative per row, uniform over the columns that are NOT in the user's list
+//  arx_neg_draw_weighted: the same with integer column weights (popularity^power), two binary searches per row
 //
 // The loss kernel streams: 3 B d floats in, 3 B d out, nothing is read twice.  A row of d floats belongs to a sub-group
 // of LPR = pow2ceil(d / 4) lanes, one float4 per lane (the layout of gather.hip), so a wave holds 64 / LPR rows -- 8 at
@@ -281,6 +282,65 @@ __global__ __launch_bounds__(256) void k_neg_draw_uniform(
   }
 }
 
+// Weighted rank-select draw.  Column c weighs q[c] >= 0, cum[c] = sum_{i<c} q[i] (cum[V]: the whole mass), and the
+// user's list p_0 < ... < p_{len-1} comes with H(j) = sum_{i<j} q[p_i] (ex_cum[lo + j]; H(len) adds the last entry's
+// weight).  The eligible mass is M = cum[V] - H(len) and t = mulhi64(rnd64, M) is a point of it.  cum[p_j] - H(j) is the
+// eligible mass below p_j and does not decrease with j, so a = #{ j : cum[p_j] - H(j) <= t } is one binary search; the
+// point sits at t' = t + H(a) of the whole mass, and the column is the LARGEST c with cum[c] <= t' -- a second binary
+// search, which steps over zero-weight columns.  Nothing is rejected and no loop depends on the weights.
+// A list entry is clamped to [0, V] before it indexes cum, and the second search never leaves [0, V): lists that are
+// not sorted, unique and in range give some column of [0, V), never a read outside the tables.
+__global__ __launch_bounds__(256) void k_neg_draw_weighted(
+    const int32_t* __restrict__ users, int64_t B, int64_t n_users, const int32_t* __restrict__ ex_ptr,
+    const int32_t* __restrict__ ex_cols, const int64_t* __restrict__ ex_cum, const int64_t* __restrict__ cum,
+    int32_t V, const int32_t* __restrict__ col2item, uint64_t seed, const uint64_t* __restrict__ step_dev,
+    uint64_t counter, int32_t* __restrict__ neg_items, int32_t* __restrict__ lookup_items,
+    int64_t* __restrict__ out_mass) {
+  const uint64_t step = (step_dev ? *step_dev : 0ull) + counter;
+  seed += step * 0x9e3779b97f4a7c15ull;                   // (the keying of k_neg_draw_uniform)
+  const int64_t total = cum[V];
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < B;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const int32_t u = users[r];
+    int32_t lo = 0, len = 0;
+    if (u >= 0 && u < n_users) {
+      lo = ex_ptr[u];
+      len = ex_ptr[u + 1] - lo;
+    }
+    int64_t h_len = 0;                                    // H(len)
+    if (len > 0) {
+      const int32_t p = ex_cols[lo + len - 1];
+      const int32_t pc = p < 0 ? 0 : (p > V ? V : p);
+      const int32_t pn = p < 0 ? 0 : (p >= V ? V : p + 1);
+      h_len = ex_cum[lo + len - 1] + (cum[pn] - cum[pc]);
+    }
+    const int64_t M = total - h_len;
+    int64_t t = -1;
+    int32_t item = -1;
+    if (M > 0 && len >= 0) {
+      const uint64_t rnd = mix64(seed * 0x100000001b3ull + (uint64_t)r);
+      t = (int64_t)__umul64hi(rnd, (uint64_t)M);
+      int32_t a = 0, b = len;                             // first j with cum[p_j] - H(j) > t
+      while (a < b) {
+        const int32_t m = a + ((b - a) >> 1);
+        const int32_t p = ex_cols[lo + m];
+        const int32_t pc = p < 0 ? 0 : (p > V ? V : p);
+        if (cum[pc] - ex_cum[lo + m] <= t) a = m + 1; else b = m;
+      }
+      const int64_t tp = t + (a < len ? ex_cum[lo + a] : h_len);
+      int32_t c0 = 0, c1 = V;                             // cum[c0] <= t' (cum[0] = 0), c1 = V or cum[c1] > t'
+      while (c1 - c0 > 1) {
+        const int32_t m = c0 + ((c1 - c0) >> 1);
+        if (cum[m] <= tp) c0 = m; else c1 = m;
+      }
+      item = col2item ? col2item[c0] : c0;
+    }
+    neg_items[r] = item;
+    if (lookup_items) lookup_items[r] = item >= 0 ? item : (col2item ? col2item[0] : 0);
+    if (out_mass) out_mass[r] = item >= 0 ? t : -1;
+  }
+}
+
 }  // namespace arx
 
 using namespace arx;
@@ -394,6 +454,24 @@ int arx_neg_draw_uniform(const int32_t* users, int64_t B, int64_t n_users, const
   k_neg_draw_uniform<<<(int)g, 256, 0, as_stream(stream)>>>(users, B, n_users, ex_ptr, ex_cols, (int32_t)V, col2item,
                                                             seed, step_dev, counter, neg_items, lookup_items,
                                                             out_rank);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_neg_draw_weighted(const int32_t* users, int64_t B, int64_t n_users, const int32_t* ex_ptr,
+                          const int32_t* ex_cols, const int64_t* ex_cum, const int64_t* cum, int64_t V,
+                          const int32_t* col2item, uint64_t seed, const uint64_t* step_dev, uint64_t counter,
+                          int32_t* neg_items, int32_t* lookup_items, int64_t* out_mass, void* stream) {
+  ARX_CHECK_ARG(B >= 0 && n_users >= 0, "arx_neg_draw_weighted: B < 0 or n_users < 0");
+  ARX_CHECK_ARG(V > 0 && V < ((int64_t)1 << 31), "arx_neg_draw_weighted: need 0 < V < 2^31");
+  ARX_CHECK_ARG(users && ex_ptr && ex_cols && ex_cum && cum && neg_items, "arx_neg_draw_weighted: null pointer");
+  if (B == 0) return ARX_OK;
+  int64_t g = ceil_div(B, 256);
+  const int64_t cap = (int64_t)cu_count() * 8;
+  if (g > cap) g = cap;
+  k_neg_draw_weighted<<<(int)g, 256, 0, as_stream(stream)>>>(users, B, n_users, ex_ptr, ex_cols, ex_cum, cum,
+                                                             (int32_t)V, col2item, seed, step_dev, counter, neg_items,
+                                                             lookup_items, out_mass);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

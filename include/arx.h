@@ -300,6 +300,25 @@ int arx_neg_draw_uniform(const int32_t* users, int64_t B, int64_t n_users, const
                          const int32_t* ex_cols, int64_t V, const int32_t* col2item, uint64_t seed,
                          const uint64_t* step_dev, uint64_t counter, int32_t* neg_items, int32_t* lookup_items,
                          int32_t* out_rank, void* stream);
+/* The weighted sibling: one item per row, drawn with probability proportional to an integer column weight q[c] >= 0
+ * over the columns that are NOT in the row's user's list -- exact, no rejection, two binary searches.
+ *   cum    int64 [V + 1]: exclusive prefix sum of q, cum[0] = 0, cum[V] < 2^63
+ *   ex_cum int64, aligned with ex_cols: ex_cum[ex_ptr[u] + j] = sum_{i<j} q[p_i] =: H(j) over the user's list
+ *          p_0 < ... < p_{len-1};  H(len) = H(len - 1) + cum[p + 1] - cum[p] of the last entry p
+ *   M = cum[V] - H(len), the eligible mass; M <= 0: a void row (-1; lookup_items gets col2item[0] / 0, as above)
+ *   t = mulhi64(rand64, M) with rand64 ALL 64 bits of the finaliser whose high half is the uniform draw's rand32,
+ *       keyed the same way by (seed, *step_dev + counter, r)
+ *   a = #{ j : cum[p_j] - H(j) <= t } (the left side does not decrease with j: one binary search)
+ *   col = the largest c in [0, V) with cum[c] <= t + H(a) (a binary search over cum; steps over zero weights)
+ * Then col is outside the list and q[col] > 0; column c is drawn with probability q[c] / M within 2^-64 M.
+ * out_mass (nullable, int64 [B]) receives t (-1 for a void row).  Users outside [0, n_users) draw as users with an
+ * empty list; list entries are clamped to [0, V] before they index cum and the second search stays inside [0, V), so
+ * lists that are not sorted, unique and in range give SOME column, never a read outside cum, ex_cols or ex_cum.
+ * The tables are built on the host (arx.utils.prepare_train.pair_draw_tables).  No atomics; graph-capturable. */
+int arx_neg_draw_weighted(const int32_t* users, int64_t B, int64_t n_users, const int32_t* ex_ptr,
+                          const int32_t* ex_cols, const int64_t* ex_cum, const int64_t* cum, int64_t V,
+                          const int32_t* col2item, uint64_t seed, const uint64_t* step_dev, uint64_t counter,
+                          int32_t* neg_items, int32_t* lookup_items, int64_t* out_mass, void* stream);
 
 /* ---- a8: scorer GEMM on fp32 MFMA (v_mfma_f32_32x32x2_f32) --------------
  * embed_attribute.py:171,188-193,205 in embedding-space form:

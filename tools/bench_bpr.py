@@ -5,6 +5,8 @@ HIP-event time of regions of --steps steps, the median of --repeats regions.  No
 usage: python tools/bench_bpr.py [--workloads c2,c3] [--steps 100] [--warmup 20] [--out FILE.json]
        python tools/bench_bpr.py --kernel-only        # the pair kernel alone (a run for rocprofv3 --kernel-trace --stats)
        python tools/bench_bpr.py --sharded            # the world-1 ShardedHMF 'bpr' step at the C2 shape, fed and drawn
+       python tools/bench_bpr.py --weighted [--sharded]   # also: the drawn step with the popularity^0.75 draw, and the
+                                                          # two draw kernels alone on the workload's lists
 """
 import argparse
 import gc
@@ -54,6 +56,22 @@ def pair_kernel_us(B, d, dev, iters=200):
     return {'us': ms * 1e3, 'algorithmic_bytes': nbytes, 'gbs': nbytes / ms / 1e6,
             'frac_of_hbm_peak': nbytes / ms / 1e6 / HBM_PEAK_GBS,
             'note': 'operands are cache-resident at this size: descriptive, not an HBM rate'}
+
+
+def draw_kernels_us(users, ptr, cols, ex_cum, cum, V, col2item, dev, iters=200):
+    """arx_neg_draw_uniform and arx_neg_draw_weighted alone: one batch of users on the model's own lists and tables,
+    a new counter per launch.  Latency-bound chains of dependent loads: microseconds, no rate."""
+    from arx import ops
+    B = int(users.shape[0])
+    out, look = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
+    uni = lambda k: ops.neg_draw_uniform(users, ptr, cols, V, col2item, 1, None, k, out, lookup_items=look)
+    wtd = lambda k: ops.neg_draw_weighted(users, ptr, cols, ex_cum, cum, V, col2item, 1, None, k, out,
+                                          lookup_items=look)
+    res = {}
+    for _ in range(2):                                   # alternating: uniform, weighted, uniform, weighted
+        for name, fn in (('uniform_us', uni), ('weighted_us', wtd)):
+            res.setdefault(name, []).append(region_ms(fn, iters, 10, 3) * 1e3)
+    return {k: min(v) for k, v in res.items()}
 
 
 def run_workload(name, args, dev):
@@ -113,6 +131,16 @@ def run_workload(name, args, dev):
             res['bpr_drawn_ms'] = region_ms(drawn, args.steps, args.warmup, args.repeats)
             res['bpr_drawn_loss'] = float(model.loss.read().item())
             res['auc_last_step'] = float(model.auc.read().item())
+            if args.weighted:
+                model.prepare_pair_negatives(syn.positives_csr(), seed=1, power=0.75)
+                res['bpr_drawn_weighted_ms'] = region_ms(drawn, args.steps, args.warmup, args.repeats)
+                res['bpr_drawn_weighted_loss'] = float(model.loss.read().item())
+                res['auc_last_step_weighted'] = float(model.auc.read().item())
+                m = model.att_emb
+                ptr, cols, c2i, ex_cum, cum = m._pair_lists
+                res['draw_kernels'] = draw_kernels_us(batches[0][0], ptr, cols, ex_cum, cum, m.logit_size, c2i, dev)
+                model.prepare_pair_negatives(syn.positives_csr(), seed=1)        # the uniform step once more: spread
+                res['bpr_drawn_again_ms'] = region_ms(drawn, args.steps, args.warmup, args.repeats)
         del model
         gc.collect()
         torch.cuda.synchronize()
@@ -174,6 +202,26 @@ def run_sharded(args, dev):
                     model.prepare_route(*batches[k % nb])
                 torch.cuda.synchronize()
                 res['bpr_fed_route_ms'] = (time.perf_counter() - t0) / args.steps * 1e3
+                if args.weighted:
+                    model.prepare_pair_negatives(power=0.75)
+                    with torch.cuda.stream(model.stream):
+                        res['bpr_drawn_weighted_route_and_step_ms'] = region_ms(drawn, args.steps, args.warmup,
+                                                                                 args.repeats)
+                    res['bpr_drawn_weighted_loss'] = float(model.read_loss().item())
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for k in range(args.steps):
+                        model.prepare_route(*batches[k % nb][:2])
+                    torch.cuda.synchronize()
+                    res['bpr_drawn_weighted_route_ms'] = (time.perf_counter() - t0) / args.steps * 1e3
+                    users = torch.from_numpy(batches[0][0]).to(dev)              # (world 1: user id = local row)
+                    res['draw_kernels'] = draw_kernels_us(users, model._neg_csr[0], model._neg_csr[1],
+                                                          model._neg_tables[0], model._neg_tables[1], args.n_items,
+                                                          None, dev)
+                    model.prepare_pair_negatives()                               # the uniform route once more: spread
+                    with torch.cuda.stream(model.stream):
+                        res['bpr_drawn_again_route_and_step_ms'] = region_ms(drawn, args.steps, args.warmup,
+                                                                              args.repeats)
             del model, routes
             gc.collect()
             torch.cuda.synchronize()
@@ -200,6 +248,9 @@ def main():
     ap.add_argument('--kernel-only', action='store_true')
     ap.add_argument('--sharded', action='store_true',
                     help="the world-1 ShardedHMF pair step (C2 shape) instead of the single-GPU workloads")
+    ap.add_argument('--weighted', action='store_true',
+                    help="with 'bpr-drawn': also the step drawing by popularity^0.75 (arx_neg_draw_weighted), and the "
+                         "uniform and the weighted draw kernel alone")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     dev = torch.device('cuda:0')

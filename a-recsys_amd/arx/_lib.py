@@ -237,6 +237,11 @@ PROTOTYPES = {
     "arx_gemm_nt_topk_filter_excl": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, f32p, i64, i32, f32p, i32p, i64,
                                             cint, i32p, f32p, i64, i32p, i64, i32p, i32p, vp]),
     "arx_topk_mark_empty": (cint, [f32p, i64, i32p, i64, i64, cint, vp]),
+    "arx_rows_inv_norm": (cint, [f32p, i64, i64, i64, f32p, vp]),
+    "arx_gather_rows_unit": (cint, [f32p, i64, i32p, i64, i64, f32p, i64, vp]),
+    "arx_cos_chunk_finish": (cint, [f32p, i64, i64, i32, i64, f32p, i32p, vp]),
+    "arx_gemm_nt_topk_filter_cos": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, i32p, f32p, i64, i32, f32p, i32p,
+                                           i64, cint, i32p, vp]),
     "arx_topk_merge_shards": (cint, [f32p, i32p, i64, cint, cint, f32p, i32p, vp]),
     "arx_topk_softmax_merge_shards": (cint, [f32p, i32p, f32p, i64, cint, cint, f32p, i32p, f32p, vp]),
     "arx_gemm_nt_eval_parts": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, f32p, f32p, f32p, i64, vp]),

@@ -23,7 +23,7 @@ import torch
 
 from .. import graph as G
 from .. import ops
-from ..topk import logits_too_big
+from ..topk import TopKScan, logits_too_big, similar_scan
 from ..utils.prepare_train import pair_draw_tables
 
 # the full-vocabulary loss a model trained with a sampled loss evaluates with (hmf_model.py:130,144; 'mce' -> 'ce':
@@ -652,6 +652,53 @@ class EmbeddingAttribute(object):
         if ex is None:
             raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
         return (self.u_indices['input'].value, self.batch_size, ex[0], ex[1])
+
+    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536, output_feat=1):
+        """Cosine nearest neighbours of items over the full vocabulary, in the latent space recommend scores against:
+        the rows of _pool_embed('full', output_feat) -- the id row of an id-only model, the mean of the id row and the
+        attribute bags for HET / MIX items; the bias plays no part.  logit_ids: the items asked about, logit indices in
+        [0, V) (recommend's output space), at least one; 1 <= k <= min(1024, V).  Returns int32 [len(ids), k] logit
+        indices on the device ordered by (cosine desc, index asc), and their float32 cosines with return_values;
+        include_self False leaves the query itself out; (-1, -inf) where fewer than k items are left (k = V without
+        the query).  An all-zero latent has cosine 0 with every item, also as a query.
+        Eager, on the runtime's stream: the pool rows are looked up again from the current tables, the inverse norms
+        recomputed (topk.similar_scan); buffers are this method's own, cached per (len(ids), k).  chunk: the width of
+        TopKScan's first chunk.  output_feat 2 / 3 score each token of a bag: there is no item latent to compare."""
+        if output_feat not in (0, 1):
+            raise NotImplementedError("similar_items: output_feat 2 / 3 pool the token SCORES of an item -- there is "
+                                      "no item latent pool to take cosines in")
+        V = self.logit_size
+        ids = logit_ids.cpu().numpy() if isinstance(logit_ids, torch.Tensor) else np.asarray(logit_ids)
+        ids = ids.astype(np.int64).reshape(-1)
+        k = int(k)
+        if not 1 <= k <= min(1024, V):
+            raise ValueError("similar_items: need 1 <= k <= min(1024, %d)" % V)
+        if len(ids) < 1:
+            raise ValueError("similar_items: need at least one query id")
+        if ids.min() < 0 or ids.max() >= V:
+            raise ValueError("similar_items: query ids must be logit indices in [0, %d)" % V)
+        node = self._pool_embed('full', output_feat)
+        node.forward(False)                                 # (the lookup a recommend plan runs: same rows, same buffer)
+        table = node.value
+        B, dev = len(ids), self.rt.device
+        cache = getattr(self, '_similar', None)
+        if cache is None:
+            cache = self._similar = {}
+        key = (B, k, int(chunk), output_feat)
+        st = cache.get(key)
+        if st is None:
+            if len(cache) > 8:
+                cache.clear()
+            st = cache[key] = (TopKScan(B, V, int(table.shape[1]), k, dev, chunk=chunk),
+                               torch.empty(B, dtype=torch.int32, device=dev),
+                               torch.empty((B, k), dtype=torch.float32, device=dev),
+                               torch.empty((B, k), dtype=torch.int32, device=dev))
+            if getattr(self, '_similar_ws', None) is None:
+                self._similar_ws = ops.Workspace(dev)
+        scan, rows, vals, idx = st
+        rows.copy_(torch.from_numpy(ids.astype(np.int32)))
+        similar_scan(scan, table, rows, vals, idx, self._similar_ws, include_self)
+        return (idx.clone(), vals.clone()) if return_values else idx.clone()
 
     def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
         """The items a drawn negative of the pair losses must not hit, per user -- typically the training history:

@@ -42,7 +42,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops as _ops
-from .topk import TopKScan, run_complete
+from .topk import TopKScan, run_complete, similar_scan
 from .utils.prepare_train import pair_draw_tables
 
 
@@ -330,6 +330,49 @@ class HipBackend(object):
             indices[:, :kk].copy_(io)
         if lse is not None:
             lse.copy_(scan.lse)
+
+    sim_chunk = 65536       # first-chunk width of shard_similar's TopKScan (tests narrow it to reach the fused kernel)
+
+    def gather_rows_unit(self, E, rows, out):
+        """out[r] = E[rows[r]] / |E[rows[r]]|; a zero row for rows[r] < 0 and for a zero row (arx_gather_rows_unit)."""
+        self.ops.gather_rows_unit(E, rows, out)
+
+    def shard_similar(self, Q, E, k, self_cols, values, indices):
+        """similar_items' local stage: values / indices [B, k] = every row's k best cosines of the unit rows Q [B, d]
+        with the shard's rows E [V, d], by (cosine desc, local column asc).  self_cols [B] int32 (None: keep them):
+        the local column each row leaves out, anything outside [0, V) for a query of another shard.  The inverse norms
+        of the shard are recomputed here (one read of it), then the streaming top-k with the cosine scale
+        (topk.similar_scan); a shard with fewer than k rows -- or k rows and one left out -- fills the rest with
+        (-inf, -1).  Buffers and GEMM workspace are this stage's own."""
+        ops = self.ops
+        B, V, d = int(Q.shape[0]), int(E.shape[0]), int(Q.shape[1])
+        if getattr(self, 'ws_sim', None) is None:
+            self.ws_sim, self._sim_scans = ops.Workspace(Q.device), {}
+        if B == 0:
+            return
+        if V < k:
+            ops.fill_f32(values, float('-inf'))
+            ops.fill_i32(indices, -1)
+            if V == 0:
+                return
+            kk = V
+        else:
+            kk = k
+        key = (B, V, d, kk, self.sim_chunk)
+        scan = self._sim_scans.get(key)
+        if scan is None:
+            if len(self._sim_scans) > 8:
+                self._sim_scans.clear()
+            scan = self._sim_scans[key] = TopKScan(B, V, d, kk, Q.device, chunk=self.sim_chunk)
+            scan.fused = scan.fused and int(E.shape[1]) == d
+            if kk < k:
+                scan.short = (torch.empty((B, kk), dtype=torch.float32, device=Q.device),
+                              torch.empty((B, kk), dtype=torch.int32, device=Q.device))
+        vo, io = (values, indices) if kk == k else scan.short
+        similar_scan(scan, E, Q, vo, io, self.ws_sim, self_cols is None, self_cols)
+        if kk < k:
+            values[:, :kk].copy_(vo)
+            indices[:, :kk].copy_(io)
 
     def topk_merge_shards(self, v, c, vo, io):
         """[W, B, k] per-shard lists (local columns) -> [B, k] global ids (arx_topk_merge_shards)."""
@@ -1418,6 +1461,82 @@ class ShardedHMF(object):
         be.topk_merge_shards(recv_v, recv_c, vo, io)
         return vo, io
 
+    # ------------------------------------------------------------ similar_items
+    def similar_items(self, items, k, include_self=False, return_values=False):
+        """Cosine nearest neighbours of items over the full item vocabulary of the row-sharded model, in the latent
+        space recommend scores against (E_item; the bias plays no part).  A collective with recommend's calling rules:
+        every rank calls it with the same k and include_self.  items: global ids this rank OWNS (id % world == rank),
+        0 <= len(items) <= B_loc (the count may differ between ranks; an id may come twice).  Returns int32 global item
+        ids [len(items), k] on the device ordered by (cosine desc, id asc) (and their float32 cosines with
+        return_values); include_self False leaves the query itself out; -1 (cosine -inf) where fewer than k items are
+        left.  A zero row has cosine 0 with everything, also as a query.
+
+          gather          this rank's query rows as UNIT rows -> [B_loc, d] (backend.gather_rows_unit; padding: zeros)
+          all_gather      rows [B_loc, d] -> [B, d], item ids [B_loc] -> [B] (padding: -1)
+          (local)         the local column of every query this shard owns (arx_shard_route's keys; none elsewhere)
+          (local)         inverse norms of the shard, recomputed at every call (one read of it: no cache to go stale),
+                          then the top-k of Q_all . E_item[:ni]^T * inv_norm over the shard (backend.shard_similar)
+          all_to_all      value / local-column lists [B, k] -> the ranks that own the queries: [W][B_loc][k]
+          (local)         W-way merge into global ids (arx_topk_merge_shards)
+
+        Eager, joined with the model's stream as recommend is; its buffers are its own, per k."""
+        W, r = self.world, self.rank
+        it = items.cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
+        it = it.astype(np.int64).reshape(-1)
+        k = int(k)
+        if not 1 <= k <= min(1024, self.n_items):
+            raise ValueError("similar_items: need 1 <= k <= min(1024, n_items)")
+        if len(it) > self.B_loc:
+            raise ValueError("similar_items: at most B_loc = %d items per call and rank" % self.B_loc)
+        if len(it) and (it.min() < 0 or it.max() >= self.n_items or np.any(it % W != r)):
+            raise ValueError("similar_items: items must be global ids in [0, %d) owned by rank %d" % (self.n_items, r))
+        with _ops.joined(self._stream if self.use_graphs else None):
+            vo, io = self._similar(it, k, bool(include_self))
+        n = len(it)
+        ids = io[:n].clone()
+        return (ids, vo[:n].clone()) if return_values else ids
+
+    def _similar(self, it, k, include_self):
+        be, W, B_loc, B, d = self.be, self.world, self.B_loc, self.B, self.d
+        dev, f32, i32 = self.device, torch.float32, torch.int32
+        n = len(it)
+        if getattr(self, '_sim_lat', None) is None:     # [B_loc] ids / local rows, [B_loc, d] rows; gathered: [B], [B, d]
+            kl, ql = torch.full((B_loc,), -1, dtype=i32, device=dev), torch.zeros((B_loc, d), dtype=f32, device=dev)
+            self._sim_lat = (kl, ql, torch.full((B_loc,), -1, dtype=i32, device=dev),
+                             torch.empty((B,), dtype=i32, device=dev)) + \
+                ((kl, ql) if W == 1 else (torch.empty((B,), dtype=i32, device=dev),
+                                          torch.empty((B, d), dtype=f32, device=dev)))
+            self._sim_k = {}
+        keys_loc, Q_loc, rows_loc, self_cols, keys_all, Q_all = self._sim_lat
+        bk = self._sim_k.get(k)
+        if bk is None:
+            e = lambda dt, *sh: torch.empty(sh, dtype=dt, device=dev)
+            bk = self._sim_k[k] = (e(f32, B, k), e(i32, B, k), e(f32, W, B_loc, k), e(i32, W, B_loc, k),
+                                   e(f32, B_loc, k), e(i32, B_loc, k))
+        out_v, out_i, recv_v, recv_c, vo, io = bk
+        kh = np.full(B_loc, -1, dtype=np.int32)
+        kh[:n] = it
+        keys_loc.copy_(torch.from_numpy(kh))
+        kh = np.full(B_loc, -1, dtype=np.int32)
+        kh[:n] = it // W
+        rows_loc.copy_(torch.from_numpy(kh))
+        ni = self.ni_loc
+        be.gather_rows_unit(self.E_item[:ni], rows_loc, Q_loc)          # (a padding row, -1: zeros)
+        if W > 1:
+            dist.all_gather_into_tensor(Q_all, Q_loc, group=self.group)
+            dist.all_gather_into_tensor(keys_all, keys_loc, group=self.group)
+        if not include_self:
+            # (ids < 0 and items of other shards: ARX_KEY_NONE, a column of no shard)
+            be.shard_route(keys_all, W, self.rank, self.zero_row, None, self_cols)
+        be.shard_similar(Q_all, self.E_item[:ni], k, None if include_self else self_cols, out_v, out_i)
+        if W == 1:
+            recv_v, recv_c = out_v.view(1, B, k), out_i.view(1, B, k)
+        else:
+            _all_to_all(recv_v.view(B, k), out_v, group=self.group)
+            _all_to_all(recv_c.view(B, k), out_i, group=self.group)
+        be.topk_merge_shards(recv_v, recv_c, vo, io)
+        return vo, io
+
     def _serve_latents(self, u, out):
         """The latents recommend / evaluate score against the item shard, for the users u (global ids this rank owns)
         -> out [len(u), d]: this model's are its user rows."""
@@ -2152,6 +2271,13 @@ class ShardedHMFBags(ShardedHMF):
         raise NotImplementedError("%s.recommend: item latents are bag means -- use item_view().recommend"
                                   % type(self).__name__)
 
+    def similar_items(self, items, k, include_self=False, return_values=False):
+        """ShardedHMF.similar_items over the materialised item latents 1/2 (id row + bag mean): through a serving view
+        (item_view()) this model keeps for the purpose -- it refreshes when the model has stepped or been restored."""
+        if getattr(self, '_sim_view', None) is None:
+            self._sim_view = self.item_view()
+        return self._sim_view.similar_items(items, k, include_self=include_self, return_values=return_values)
+
     def evaluate(self, users, items, loss='warp', return_rows=False):
         """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
         raise NotImplementedError("%s.evaluate: item latents are bag means -- use item_view().evaluate"
@@ -2301,6 +2427,13 @@ class ShardedHMFRepTokens(ShardedHMF):
         raise NotImplementedError("%s.recommend: item latents are bag means -- use item_view().recommend"
                                   % type(self).__name__)
 
+    def similar_items(self, items, k, include_self=False, return_values=False):
+        """ShardedHMF.similar_items over the materialised item latents 1/2 (id row + bag mean): through a serving view
+        (item_view()) this model keeps for the purpose -- it refreshes when the model has stepped or been restored."""
+        if getattr(self, '_sim_view', None) is None:
+            self._sim_view = self.item_view()
+        return self._sim_view.similar_items(items, k, include_self=include_self, return_values=return_values)
+
     def evaluate(self, users, items, loss='warp', return_rows=False):
         """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
         raise NotImplementedError("%s.evaluate: item latents are bag means -- use item_view().evaluate"
@@ -2390,6 +2523,11 @@ class ShardedHetView(ShardedHMF):
         if self._seen != (self.model.steps, self.model.n_restores):
             self._refresh()
         return super()._evaluate(u, it, loss)
+
+    def _similar(self, it, k, include_self):
+        if self._seen != (self.model.steps, self.model.n_restores):
+            self._refresh()
+        return super()._similar(it, k, include_self)
 
     def _no_training(self, *a, **k):
         raise TypeError("ShardedHetView: a view does not train (step, pools and positives belong to the model)")

@@ -255,6 +255,12 @@ class LatentProductModel(object):
         self._plans.pop('recommend_ex', None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
+    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536):
+        """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the item latent space
+        recommend scores against: EmbeddingAttribute.similar_items."""
+        return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
+                                          chunk=chunk)
+
     def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
         """'bpr' / 'bpr-hinge': the items a DRAWN negative must not hit, per user -- typically the training history:
         {user_index: items} or a (ptr, items) CSR pair in item-index space.  After this call a step without

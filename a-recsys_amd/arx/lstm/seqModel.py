@@ -802,6 +802,12 @@ class SeqModel(SeqBatching):
             bk['plans'].pop('recommend_ex', None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
+    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536):
+        """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the output item latents
+        step_recommend scores against (EmbeddingAttribute.similar_items); output_feat 2 / 3: NotImplementedError."""
+        return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
+                                          chunk=chunk, output_feat=self.output_feat)
+
     def step_recommend(self, session, user_input, item_inputs, positions, bucket_id, exclude_seen=False):
         """seqModel.py:326-353 -> [(uid, values[topk_n], indexes[topk_n])]: the top-k softmax
         values / logit indexes at time position positions[i] of sequence i.  Small vocabularies: the full

@@ -1269,6 +1269,52 @@ def topk_mark_empty(values, indices):
          int(values.shape[1]), _stream())
 
 
+def rows_inv_norm(E, out):
+    """out[i] = 1 / |E[i]| (0 for a zero row) of the rows of a 2-D fp32 view (arx.h)."""
+    _chk(E, torch.float32, 'E'); _chk(out, torch.float32, 'out')
+    if E.dim() != 2 or out.dim() != 1 or int(out.shape[0]) < int(E.shape[0]):
+        raise ValueError("rows_inv_norm: E [n, d], out [>= n]")
+    if E.shape[0] == 0:
+        return
+    call("arx_rows_inv_norm", _p(E), _ld(E), int(E.shape[0]), int(E.shape[1]), _p(out), _stream())
+
+
+def gather_rows_unit(E, rows, out):
+    """out[r] = E[rows[r]] / |E[rows[r]]| (a zero row for rows[r] < 0 and for a zero row of E) (arx.h).  The caller
+    keeps rows[r] below E.shape[0]."""
+    _chk(E, torch.float32, 'E'); _chk(rows, torch.int32, 'rows'); _chk(out, torch.float32, 'out')
+    B = int(rows.shape[0])
+    if E.dim() != 2 or out.dim() != 2 or int(out.shape[0]) < B or int(out.shape[1]) != int(E.shape[1]):
+        raise ValueError("gather_rows_unit: E [n, d], rows [B], out [>= B, d]")
+    if B == 0:
+        return
+    call("arx_gather_rows_unit", _p(E), _ld(E), _p(rows), B, int(E.shape[1]), _p(out), _ld(out), _stream())
+
+
+def cos_chunk_finish(logits, col0, col_scale, self_col=None):
+    """logits[r, c] *= col_scale[col0 + c], then -inf at each row's own column self_col[r] - col0 (arx.h)."""
+    _chk(logits, torch.float32, 'logits'); _chk(col_scale, torch.float32, 'col_scale')
+    _chk(self_col, torch.int32, 'self_col')
+    B, n = int(logits.shape[0]), int(logits.shape[1])
+    if int(col_scale.shape[0]) < int(col0) + n or (self_col is not None and int(self_col.shape[0]) < B):
+        raise ValueError("cos_chunk_finish: col_scale needs col0 + ncols entries, self_col one per row")
+    if B == 0 or n == 0:
+        return
+    call("arx_cos_chunk_finish", _p(logits), _ld(logits), B, int(col0), n, _p(col_scale), _p(self_col), _stream())
+
+
+def gemm_nt_topk_filter_cos(A, Bm, col_scale, self_col, thr, col_base, cand_v, cand_i, capp, overflow):
+    """gemm_nt_topk_filter with v = (A . Bm^T) * col_scale[col] and no bias; self_col [M] int32 (or None): the
+    absolute column col_base + col each row drops (arx.h)."""
+    _chk(col_scale, torch.float32, 'col_scale'); _chk(self_col, torch.int32, 'self_col')
+    if int(col_scale.shape[0]) < int(Bm.shape[0]) or (self_col is not None and
+                                                      int(self_col.shape[0]) < int(A.shape[0])):
+        raise ValueError("gemm_nt_topk_filter_cos: col_scale needs an entry per row of Bm, self_col one per row of A")
+    call("arx_gemm_nt_topk_filter_cos", _p(A), _ld(A), int(A.shape[0]), _p(Bm), _ld(Bm), int(Bm.shape[0]),
+         int(A.shape[1]), _p(col_scale), _p(self_col), _p(thr), int(thr.stride(0)), int(col_base), _p(cand_v),
+         _p(cand_i), int(cand_v.stride(0)), int(capp), _p(overflow), _stream())
+
+
 def topk_merge_shards(v, c, vo, io):
     """W-way merge of per-shard top-k lists into global ids (arx.h): v / c [W, B, k] (shard s's lists in block s,
     local columns, -1 = empty) -> vo / io [B, k], id = c * W + s, order (value desc, id asc); -inf / empty -> -1."""

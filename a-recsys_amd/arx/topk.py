@@ -121,16 +121,27 @@ class TopKScan(object):
         finally:
             self.fused = was
 
-    def run(self, latent, pool, bias, ws, values, indices, ex=None):
+    def run(self, latent, pool, bias, ws, values, indices, ex=None, col_scale=None, self_col=None):
         """values / indices [B, k] = the top-k of latent . pool^T + bias (bias may be None) over all V >= k pool rows;
-        ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace."""
+        ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace.
+        col_scale [V] (None: every launch is the one above): the scores are (latent . pool^T) * col_scale[column] --
+        cosines, with unit rows in latent and the pool's inverse row norms (similar_scan) -- and self_col [B] int32
+        (optional) names the column each row leaves out (any value outside [0, V): none); a row with fewer than k
+        columns left ends in (-inf, -1).  No bias, no exclusion lists and no log-sum-exp in that form."""
         V, k = pool.shape[0], self.k
+        cos = col_scale is not None
+        if cos and (self.want_lse or bias is not None or ex is not None):
+            raise ValueError("TopKScan.run: col_scale goes with no bias, no exclusion lists and no log-sum-exp")
+        if self_col is not None and not cos:
+            raise ValueError("TopKScan.run: self_col belongs to the col_scale form")
         run_v, run_i = values, indices
         out_v, out_i = self._ov, self._oi
         if self.fused and V > self.chunk and pool.stride(0) % 4 == 0 and latent.stride(0) % 4 == 0:
             n0 = self.chunk
             lg = self._buf[:, :n0]
             ops.gemm(latent, pool[:n0], lg, ws, transB=True, col_bias=bias[:n0] if bias is not None else None)
+            if cos:
+                ops.cos_chunk_finish(lg, 0, col_scale, self_col)
             capp, cand_v, cand_i, cpos, parts = self._cand_bufs(n0, V)
             lp = None
             if self.want_lse:
@@ -142,7 +153,10 @@ class TopKScan(object):
             ops.topk_chunk(lg, k, 0, run_v, run_i)
             ops.fill_f32(cand_v.view(-1), float('-inf'))
             ops.fill_i32(self.overflow, 0)
-            if ex is not None:
+            if cos:
+                ops.gemm_nt_topk_filter_cos(latent, pool[n0:], col_scale[n0:], self_col, run_v[:, k - 1], n0, cand_v,
+                                            cand_i, capp, self.overflow)
+            elif ex is not None:
                 ops.gemm_nt_topk_filter_excl(latent, pool[n0:], bias[n0:] if bias is not None else None,
                                              run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, ex,
                                              lse_part=lp)
@@ -156,7 +170,7 @@ class TopKScan(object):
             ops.topk_merge(run_v, run_i, self._cv, self._ci, k, out_v, out_i)
             values.copy_(out_v)
             indices.copy_(out_i)
-            if ex is not None:
+            if ex is not None or self_col is not None:
                 ops.topk_mark_empty(values, indices)
             return
         nch = (V + self.chunk - 1) // self.chunk
@@ -171,6 +185,8 @@ class TopKScan(object):
                 lp[:, c0 // self.chunk].copy_(self._lse0)
             if ex is not None:
                 ops.topk_exclude_fill(lg, c0, ex)
+            if cos:
+                ops.cos_chunk_finish(lg, c0, col_scale, self_col)
             if c0 == 0:                              # chunk >= k and V >= k: the first chunk fills all k
                 ops.topk_chunk(lg, k, 0, run_v, run_i)
                 continue
@@ -182,7 +198,7 @@ class TopKScan(object):
         if run_v.data_ptr() != values.data_ptr():
             values.copy_(run_v)
             indices.copy_(run_i)
-        if ex is not None:
+        if ex is not None or self_col is not None:
             ops.topk_mark_empty(values, indices)
         if self.want_lse:
             ops.row_logsumexp(lp, self.lse)
@@ -249,3 +265,35 @@ def run_complete(scan, run, forget=None):
         finally:
             forget()
     return out
+
+
+def similar_scan(scan, table, query_rows, values, indices, ws, include_self, self_cols=None):
+    """Cosine nearest neighbours of table rows over the whole table -- the one place the rules of similar_items live
+    (EmbeddingAttribute.similar_items, arx.dist HipBackend.shard_similar).  scan: a TopKScan(B, V, d, k) without
+    want_lse; table [V, d]; query_rows [B] int32: the rows asked about (< 0: a zero query).  In order: the inverse row
+    norms of the table (one streaming read, recomputed at every call: no cache to go stale), the queries as unit rows
+    (arx_gather_rows_unit), the scan -- once more on the chunked path where the fused candidate lists overflowed.
+    values / indices [B, k]: (cosine desc, row asc); include_self False leaves each query's own row out; (-inf, -1)
+    where fewer than k rows are left.  A zero row has cosine 0 with everything, also as a query.
+    The sharded caller's queries come from their owners as unit rows already: query_rows is then that float32 [B, d]
+    tensor (nothing is gathered here) and self_cols [B] int32 names the LOCAL column each row leaves out (anything
+    outside [0, V): none; ignored with include_self)."""
+    V = int(table.shape[0])
+    inv = getattr(scan, '_inv_norm', None)
+    if inv is None or int(inv.shape[0]) != V:
+        inv = scan._inv_norm = torch.empty(V, dtype=torch.float32, device=table.device)
+    ops.rows_inv_norm(table, inv)
+    if query_rows.dtype == torch.float32:
+        q = query_rows
+    else:
+        q = getattr(scan, '_unit_rows', None)
+        if q is None or tuple(q.shape) != (int(query_rows.shape[0]), int(table.shape[1])):
+            q = scan._unit_rows = torch.empty((int(query_rows.shape[0]), int(table.shape[1])), dtype=torch.float32,
+                                              device=table.device)
+        ops.gather_rows_unit(table, query_rows, q)
+        if self_cols is None:
+            self_cols = query_rows
+    sc = None if include_self else self_cols
+    if sc is None and not include_self:
+        raise ValueError("similar_scan: unit-row queries need self_cols to leave their own rows out")
+    run_complete(scan, lambda: scan.run(q, table, None, ws, values, indices, col_scale=inv, self_col=sc))

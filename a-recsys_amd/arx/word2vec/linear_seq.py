@@ -92,6 +92,7 @@ class LinearSeq(object):
         self.logit_size_test = logit_size_test
         self.loss_function = loss = loss_function
         self.n_input_items = n_input_items
+        self.output_feat = output_feat
         self.n_sampled = n_sampled
         self.batch_size = mb = batch_size
         self.dropout = dropout
@@ -175,6 +176,12 @@ class LinearSeq(object):
         CSR pair in item-index space (EmbeddingAttribute.prepare_recommend_exclusions).  A second call replaces them."""
         self._plans.pop('recommend_ex', None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
+
+    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536):
+        """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the OUTPUT item latents the
+        model scores against (EmbeddingAttribute.similar_items); output_feat 2 / 3: NotImplementedError."""
+        return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
+                                          chunk=chunk, output_feat=self.output_feat)
 
     def _plan(self, key):
         if key not in self._plans:

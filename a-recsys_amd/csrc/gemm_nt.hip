@@ -63,13 +63,16 @@ struct NtFilter {
   // kNtRank (with kNtRelu: warp_eval, embed_attribute.py:620-639 [margin_rank, true_rank]): tsc[row] is t itself, the
   // margin term is relu((v - t) + 1) and cnt_part[row * ldl + part] = #columns of the range with v > t; the row's own
   // target column tcol[row] (a column of this launch, anything else: none) counts as (1, 0)
+  // kNtSelf (with kNtCos: the item-to-item scan) reads tcol too: the row's own ABSOLUTE column col_base + col (anything
+  // outside the launch's columns: none), dropped before it takes a position in the row's list
   const int32_t* tcol; int32_t* cnt_part;
 };
 
 // MODE (FILTER kernels): bit 0 candidate lists (thr), bit 1 lse_part, bit 2 relu_part, bit 3 exclusion lists (with
 // bit 0 only), bit 4 rank counts (with bit 2 only) -- a template parameter, not a run-time switch: every feature is 32
-// registers of per-row state and the plain kernel already holds 246
-constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8, kNtRank = 16;
+// registers of per-row state and the plain kernel already holds 246.  bit 5 cosine (with bit 0 alone, or bit 0 and
+// bit 6): v = acc * col_scale[col], the scale travelling where the bias does; bit 6 the row's self column (with bit 5)
+constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8, kNtRank = 16, kNtCos = 32, kNtSelf = 64;
 
 template <int KT, int MODE = 0>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
@@ -81,6 +84,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   constexpr bool want_excl = (MODE & kNtExcl) != 0, want_rank = (MODE & kNtRank) != 0;
   static_assert(!want_excl || want_topk, "the exclusion lists filter candidates");
   static_assert(!want_rank || (want_relu && !want_topk && !want_lse), "the rank counts ride on the margin sums");
+  constexpr bool want_cos = (MODE & kNtCos) != 0, want_self = (MODE & kNtSelf) != 0;
+  static_assert(!want_cos || (want_topk && !want_lse && !want_relu && !want_excl), "the cosine scale serves the lists");
+  static_assert(!want_self || want_cos, "the self column belongs to the item-to-item scan");
   constexpr int NS = KT / 8;                  // steps of 4 MFMAs
   constexpr int CPR = KT / 4;                 // 16-B chunks per pool row
   constexpr int NLB = kNtBN * CPR / 256;      // DMA pieces per thread per tile
@@ -149,7 +155,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   // kNtExcl: [beg, end) of each row's exclusion list (1 KB; read only by a lane whose logit beat the threshold)
   __shared__ int s_xb[want_excl ? kNtBM : 1], s_xe[want_excl ? kNtBM : 1];
   // kNtRank: the rows' target columns (read per tile by one lane per row, per logit only in a tile that holds one)
-  __shared__ int s_tc[want_rank ? kNtBM : 1];
+  // kNtSelf: the rows' own columns, absolute (read only by a lane whose logit beat the threshold)
+  __shared__ int s_tc[(want_rank || want_self) ? kNtBM : 1];
   float lm[want_lse ? 16 : 1], ls[want_lse ? 16 : 1], rsum[want_relu ? 16 : 1];
   // kNtRank: ONE register per count -- a row's count is the popcount of its half of a ballot (wave-uniform), kept by
   // the lane l31 == e of the half (16 counters spilled at K=128: the margin mode already holds 236 VGPRs).  The margin
@@ -165,6 +172,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
         s_th[threadIdx.x] = row < M ? flt.thr[row * flt.ldthr] : __builtin_inff();
         s_cnt[threadIdx.x] = 0;
       }
+      if (want_self) s_tc[threadIdx.x] = row < M ? flt.tcol[row] : -1;
       if (want_relu && !want_rank) s_tq[threadIdx.x] = row < M ? flt.tsc[row] - 1.f : 0.f;
       if (want_rank) {
         s_tq[threadIdx.x] = row < M ? flt.tsc[row] : 0.f;
@@ -295,7 +303,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
         const float bias = (j == 0) ? bias0 : bias1;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const float v = alpha * (j == 0 ? acc0[e] : acc1[e]) + bias;
+          // kNtCos: `bias` is the column's 1 / norm; + 0.f turns a product -0 (a zero column under a negative dot)
+          // into +0, so a cosine 0 has ONE bit pattern and ties on it break by column like any other
+          const float v = want_cos ? (j == 0 ? acc0[e] : acc1[e]) * bias + 0.f
+                                   : alpha * (j == 0 ? acc0[e] : acc1[e]) + bias;
           if (want_rank) {
             float dz = v - tq[e];
             bool act = dz + 1.f > 0.f, gt = v > tq[e];
@@ -325,6 +336,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
           if (!want_topk) continue;
           bool pred = col < N && v > th[e];
           const int rl = rl0 + (e & 3) + 8 * (e >> 2);
+          // the row's own column (a survivor: rare) leaves BEFORE the ballot, as an excluded one does
+          if (want_self && pred && flt.col_base + (int32_t)col == s_tc[rl]) pred = false;
           if (want_excl && pred) {
             // a survivor (rare): lower_bound of its absolute column in the row's list, BEFORE the ballot, so an
             // excluded column takes no position and the placement stays deterministic
@@ -540,6 +553,36 @@ int arx_gemm_nt_topk_filter_excl(const float* A, int64_t lda, int64_t M, const f
     nt_launch_mode<kNtTopk | kNtLse | kNtExcl>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
   else
     nt_launch_mode<kNtTopk | kNtExcl>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_gemm_nt_topk_filter_cos(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
+                                int64_t K, const float* col_scale, const int32_t* self_col, const float* thr,
+                                int64_t ldthr, int32_t col_base, float* cand_v, int32_t* cand_i, int64_t ldcand, int capp,
+                                int* overflow, void* stream) {
+  ARX_CHECK_ARG(A && Bm && col_scale && thr && cand_v && cand_i && overflow,
+                "arx_gemm_nt_topk_filter_cos: null pointer (only self_col may be NULL)");
+  ARX_CHECK_ARG(M > 0 && N > 0 && capp > 0 && ldcand > 0 && lda >= K && ldb >= K,
+                "arx_gemm_nt_topk_filter_cos: need M > 0, N > 0, capp > 0, ldcand > 0, lda >= K, ldb >= K");
+  ARX_CHECK_ARG(col_base >= 0 && (int64_t)col_base + N <= 0x7fffffff,
+                "arx_gemm_nt_topk_filter_cos: need col_base >= 0 and col_base + N < 2^31");
+  ARX_CHECK_ARG(K == 32 || K == 64 || K == 128, "arx_gemm_nt_topk_filter_cos: K must be 32, 64 or 128");
+  ARX_CHECK_ARG(!((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) && lda % 4 == 0 &&
+                    ldb % 4 == 0,
+                "arx_gemm_nt_topk_filter_cos: operands must be 16-byte aligned");
+  int64_t tpb, ns;
+  nt_split(M, N, &tpb, &ns);
+  ARX_CHECK_ARG(ns * capp <= ldcand, "arx_gemm_nt_topk_filter_cos: candidate rows too short (parts * capp > ldcand)");
+  const int64_t grid = ceil_div(M, (int64_t)kNtBM) * ns;
+  ARX_CHECK_ARG(grid <= 0x7fffffff, "arx_gemm_nt_topk_filter_cos: grid too large");
+  NtFilter f{thr, ldthr, cand_v, cand_i, ldcand, capp, col_base, overflow};
+  f.tcol = self_col;
+  hipStream_t s = as_stream(stream);
+  if (self_col)
+    nt_launch_mode<kNtTopk | kNtCos | kNtSelf>(K, grid, s, M, N, A, lda, Bm, ldb, col_scale, (int)tpb, (int)ns, f);
+  else
+    nt_launch_mode<kNtTopk | kNtCos>(K, grid, s, M, N, A, lda, Bm, ldb, col_scale, (int)tpb, (int)ns, f);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

@@ -1081,6 +1081,37 @@ int arx_gemm_nt_topk_filter_excl(const float* A, int64_t lda, int64_t M, const f
                                  const int32_t* ex_cols, void* stream);
 int arx_topk_mark_empty(const float* values, int64_t ldv, int32_t* indices, int64_t ldi, int64_t B, int k,
                         void* stream);
+/* Item-to-item neighbours (model.similar_items: cosine over the full item vocabulary; opt-in, every call above is
+ * unchanged).  cos(q, j) = (E[q] / |E[q]|) . E[j] * (1 / |E[j]|): the query rows are gathered as unit rows, the pool
+ * keeps its rows and a vector of inverse norms takes the place of the bias -- as a SCALE in the scorer's epilogue, so
+ * no normalised copy of the table exists.  A zero row has inverse norm 0: its cosine with everything is 0, also as a
+ * query.  A product that is -0 is stored as +0 (v = acc * scale + 0), so equal cosines are equal bit patterns and ties
+ * break by column (the lower one first) exactly as in arx_topk.
+ * arx_rows_inv_norm: out[i] = 1 / sqrt(sum_c E[i * ld + c]^2), i < n; 0 for an all-zero row.  f32 accumulation in one
+ * fixed order (deterministic), 1.0f / sqrtf (both correctly rounded: a sum 4^e gives exactly 2^-e).  Any d >= 1,
+ * ld >= d, n >= 0 (0: no launch); float4 reads where d % 4 == 0, ld % 4 == 0 and E is 16-byte aligned.
+ * arx_gather_rows_unit: out[r * ldo + c] = E[rows[r] * ld + c] * inv, r < B, c < d, inv as above from the row itself
+ * (the same summation order: bit-identical to arx_rows_inv_norm's where both take the float4 path or both do not).
+ * rows[r] < 0: a zero row, nothing is read through the index.  rows[r] must be a row of E otherwise.  ldo >= d.
+ * arx_cos_chunk_finish: the materialised chunk [B, ncols] of logits over the columns [col0, col0 + ncols):
+ * logits[r * ld + c] = logits[r * ld + c] * col_scale[col0 + c] + 0, then -inf at c = self_col[r] - col0 where that
+ * falls inside the chunk.  self_col [B] may be NULL; col_scale holds an entry for every column of the chunk.  One
+ * launch; B == 0 or ncols == 0: none.
+ * arx_gemm_nt_topk_filter_cos: arx_gemm_nt_topk_filter (same candidate layout, parts, capp and overflow rules; no bias,
+ * no lse) with v = acc * col_scale[col] + 0; col_scale [N] is indexed by the launch's own columns, as col_bias is.
+ * self_col [M] (may be NULL): a candidate whose ABSOLUTE column col_base + col equals self_col[row] is dropped before
+ * it takes a position, so the lists stay deterministic and in column order; any value outside
+ * [col_base, col_base + N) means "none" (ARX_KEY_NONE, as arx_shard_route's keys_out gives for an item of another
+ * shard, is outside every range: col_base + N < 2^31 is required).  K in {32, 64, 128}, 16-byte aligned operands. */
+int arx_rows_inv_norm(const float* E, int64_t ld, int64_t n, int64_t d, float* out, void* stream);
+int arx_gather_rows_unit(const float* E, int64_t ld, const int32_t* rows, int64_t B, int64_t d, float* out, int64_t ldo,
+                         void* stream);
+int arx_cos_chunk_finish(float* logits, int64_t ld, int64_t B, int32_t col0, int64_t ncols, const float* col_scale,
+                         const int32_t* self_col, void* stream);
+int arx_gemm_nt_topk_filter_cos(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
+                                int64_t K, const float* col_scale, const int32_t* self_col, const float* thr,
+                                int64_t ldthr, int32_t col_base, float* cand_v, int32_t* cand_i, int64_t ldcand, int capp,
+                                int* overflow, void* stream);
 /* Recommend of the row-sharded model (arx.dist.ShardedHMF.recommend; owner of item g = g % W, local column g / W):
  * every shard ranks its own columns, the lists cross by all_to_all and this W-way merge forms the global top-k of the
  * rows in ONE launch.  v / c: [W][B][k] contiguous -- block s holds shard s's lists (as all_to_all delivers them),

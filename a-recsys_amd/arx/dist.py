@@ -78,6 +78,18 @@ def _reduce_scatter(out, inp, group=None):
     dist.reduce_scatter_tensor(out, inp, op=dist.ReduceOp.SUM, group=group)
 
 
+def owner_order(ids, world):
+    """Requests for the rows of global ids `ids` (owner = id % world), ordered by owner -- host only:
+    (perm, slot, send): perm orders the requests by owner (stable: inside an owner's group they keep their order),
+    slot[i] = place of request i in that order (the inverse of perm: its row of the block that comes back),
+    send[g] = number of requests to owner g (int64 [world])."""
+    owner = np.asarray(ids) % world
+    perm = np.argsort(owner, kind='stable')
+    slot = np.empty(len(perm), dtype=np.int32)
+    slot[perm] = np.arange(len(perm), dtype=np.int32)
+    return perm, slot, np.bincount(owner, minlength=world).astype(np.int64)
+
+
 class HipBackend(object):
     """Compute stages on libarx.so (include/arx.h)."""
 
@@ -456,10 +468,17 @@ class ShardedHMF(object):
     kernel -- or a pair loss, 'bpr' / 'bpr-hinge' (exchange='rows' only): no pool, one negative per interaction, fed
     with the batch or drawn on the device (prepare_pair_negatives); _step_body_pair.
 
-    The step of this class and of its two subclasses is ONE body each (_step_body: named segments of kernels between
-    the collectives), run by one driver (_run_step): as captured hipGraph segments on the product backend, kernel by
-    kernel everywhere else (graphs=False, ARX_DIST_EAGER=1, the numpy double of the CPU tests) -- the same launches,
-    padding and exchanges either way.  exchange='logits' is a separate, eager-only step (_step_logits)."""
+    A step is a body (named segments of kernels between the collectives) run by one driver (_run_step): as captured
+    hipGraph segments on the product backend, kernel by kernel everywhere else (graphs=False, ARX_DIST_EAGER=1, the
+    numpy double of the CPU tests) -- the same launches, padding and exchanges either way.  _step_body is the ONE body
+    of the sampled-pool step with exchange='rows', for this class, ShardedW2V and ShardedHMFRepTokens: it scores "the
+    scorer's input" and a subclass overrides what differs -- more blocks of the index vector, feeds and key entries
+    (_step_blocks, _static_feeds, _key_more), the lookups and the K7 pass (_gather, _k7), the input and its gradient
+    (_scorer_io, _input_fwd, _input_bwd), their exchanges (_send_input_rows, _return_input_grads), launches behind the
+    apply segment and the entry of a step that is not a replay (_after_apply, _fresh_step).  The pair step
+    (_step_body_pair) and ShardedHMFBags._step_body have other collectives and bodies of their own; all of them share
+    the router (_route_requests over owner_order), the index feed (_index_feed) and the scorer call (_scorer_loss,
+    _scorer_bwd).  exchange='logits' is a separate, eager-only step (_step_logits)."""
 
     loss_name, pair, n_draws = 'mw', False, 0          # (instances set their own; a serving view keeps these)
 
@@ -784,32 +803,42 @@ class ShardedHMF(object):
                 raise ValueError("prepare_route: negative ids must lie below %d (< 0: a void row)" % self.n_items)
         live = ng >= 0
         req = np.concatenate([it, ng[live]])                                # the requests: positives, live negatives
-        row_of_neg = np.nonzero(live)[0]
-        owner = req % W
-        perm = np.argsort(owner, kind='stable')
-        slot = np.empty(len(req), dtype=np.int32)
-        slot[perm] = np.arange(len(req), dtype=np.int32)                    # request -> its row of the received block
-        pos_slot = slot[:B_loc]
+        route, slot = self._route_requests(req)[:2]                         # request -> its row of the received block
         neg_slot = np.full(B_loc, -1, dtype=np.int32)
-        neg_slot[row_of_neg] = slot[B_loc:]
-        send = np.bincount(owner, minlength=W).astype(np.int64)
-        st = torch.from_numpy(send).to(dev)
+        neg_slot[np.nonzero(live)[0]] = slot[B_loc:]
+        self._alloc_recv(route['R'])
+        route.update(users=users_d, items=torch.from_numpy(np.ascontiguousarray(it)).to(dev),
+                     neg_items=torch.from_numpy(np.ascontiguousarray(ng)).to(dev),
+                     slots=torch.from_numpy(np.concatenate([slot[:B_loc], neg_slot])).to(dev), n_req=int(len(req)),
+                     urows=urows)
+        return route
+
+    def _count_exchange(self, send):
+        """send[g] = what this rank sends to rank g (int64 [world], host) -> what it receives from every rank: one
+        tiny all_to_all."""
+        st = torch.from_numpy(send).to(self.device)
         rt = torch.empty_like(st)
         _all_to_all(rt, st, group=self.group)
-        recv = [int(v) for v in rt.cpu().tolist()]
+        return [int(v) for v in rt.cpu().tolist()]
+
+    def _route_requests(self, req):
+        """The router of every variable-size exchange: the requests req (int32 global item ids, host) are ordered by
+        owner (owner_order), the counts cross, then the ids, and every owner resolves the ids it received to rows of
+        its shard.  Two collectives, in this order.  Returns ({send, recv: the split sizes; R: rows this rank serves;
+        recv_ids, recv_rows: what it serves, as ids and as local rows (device)}, slots (host: request -> its row of
+        the block that comes back), perm (host), the requests in the order they were sent (device))."""
+        W, dev = self.world, self.device
+        perm, slot, send = owner_order(req, W)
+        recv = self._count_exchange(send)
+        send = [int(v) for v in send.tolist()]
         R = int(sum(recv))
-        self._alloc_recv(R)
-        req_d = torch.from_numpy(np.ascontiguousarray(req[perm])).to(dev)
+        ids = torch.from_numpy(np.ascontiguousarray(req[perm])).to(dev)
         recv_ids = torch.zeros((R,), dtype=torch.int32, device=dev)
-        _all_to_all(recv_ids, req_d, recv, [int(v) for v in send.tolist()], group=self.group)
+        _all_to_all(recv_ids, ids, recv, send, group=self.group)
         recv_rows = torch.zeros((R,), dtype=torch.int32, device=dev)
         if R > 0:
             self.be.shard_route(recv_ids, W, self.rank, self.zero_row, recv_rows, None)
-        return {'users': users_d, 'items': torch.from_numpy(np.ascontiguousarray(it)).to(dev),
-                'neg_items': torch.from_numpy(np.ascontiguousarray(ng)).to(dev),
-                'slots': torch.from_numpy(np.concatenate([pos_slot, neg_slot])).to(dev), 'n_req': int(len(req)),
-                'send': [int(v) for v in send.tolist()], 'recv': recv, 'R': R, 'recv_ids': recv_ids,
-                'recv_rows': recv_rows, 'urows': urows}
+        return {'send': send, 'recv': recv, 'R': R, 'recv_ids': recv_ids, 'recv_rows': recv_rows}, slot, perm, ids
 
     def prepare_route(self, users, items, neg_items=None):
         """Data-loader side of a batch (host): orders the interactions by the owner of their
@@ -824,31 +853,15 @@ class ShardedHMF(object):
         W = self.world
         u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
         it = items.cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
-        u = u.astype(np.int32)
-        it = it.astype(np.int32)
-        owner = it % W
-        perm = np.argsort(owner, kind='stable')
-        send = np.bincount(owner, minlength=W).astype(np.int64)
-        st = torch.from_numpy(send).to(self.device)
-        rt = torch.empty_like(st)
-        _all_to_all(rt, st, group=self.group)
-        recv = [int(v) for v in rt.cpu().tolist()]
-        route = {'users': torch.from_numpy(np.ascontiguousarray(u[perm])).to(self.device),
-                 'items': torch.from_numpy(np.ascontiguousarray(it[perm])).to(self.device),
-                 'send': [int(v) for v in send.tolist()], 'recv': recv, 'R': int(sum(recv))}
+        # The ids themselves are routed here too (they are input data, like the owner ordering): every owner learns
+        # which of its rows this batch asks for, and the local row of every id is resolved once.  The step path then
+        # starts at the table lookups.
+        route, _, perm, items_d = self._route_requests(it.astype(np.int32))
         self._alloc_recv(route['R'])
-        # The ids themselves are routed here too (they are input data, like the owner ordering
-        # above): every owner learns which of its rows this batch asks for, and the local row of
-        # every id is resolved once.  The step path then starts at the table lookups.
-        R = route['R']
-        recv_ids = torch.zeros((R,), dtype=torch.int32, device=self.device)
-        _all_to_all(recv_ids, route['items'], recv, route['send'], group=self.group)
-        recv_rows = torch.zeros((R,), dtype=torch.int32, device=self.device)
-        if R > 0:
-            self.be.shard_route(recv_ids, W, self.rank, self.zero_row, recv_rows, None)
+        users_d = torch.from_numpy(np.ascontiguousarray(u.astype(np.int32)[perm])).to(self.device)
         urows = torch.zeros((self.B_loc,), dtype=torch.int32, device=self.device)
-        self.be.shard_route(route['users'], W, self.rank, 0, urows, None)   # all owned: local rows
-        route.update(recv_ids=recv_ids, recv_rows=recv_rows, urows=urows)
+        self.be.shard_route(users_d, W, self.rank, 0, urows, None)          # all owned: local rows
+        route.update(users=users_d, items=items_d, urows=urows)
         return route
 
     # ------------------------------------------------------------------- step
@@ -919,9 +932,7 @@ class ShardedHMF(object):
         be.transpose(self.logitsT, self.logits)
         w_rows.wait()
         dU = arena[:B_loc, :d]
-        self._loss_fused(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], self.urows,
-                         self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
-                         self.t_loc, self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
+        self._scorer_loss(False, self.U_loc, None, self.urows, self.dT_pack[:, d], dU, self.dT_pack[:, :d])
         # ---- backward ----
         w_dt = _all_to_all(arena[B_loc + Sg:B_loc + Sg + R], self.dT_pack, recv, send, group=grp, async_op=True)
         be.transpose(self.dlogits, self.dlogitsT[:S])
@@ -996,14 +1007,8 @@ class ShardedHMF(object):
                 mode, self._graphs = 'capture', {}
             else:
                 mode, self._graphs, self._graph_key = 'eager', {}, None
-            if mode != 'replay' and getattr(self, 'D_tok', None) is not None:
-                # ShardedHMFRepTokens: the dense token-gradient table must be all zero at step entry (the token apply
-                # zeroes the rows it consumes).  A step that died between the gradient pass and that apply would
-                # leave sums behind that the next step counts twice: every step that is NOT a replay (the first
-                # eager one, a re-capture, the step after an exception -- the graphs are dropped below) starts from
-                # a cleared table.
-                self.D_tok.zero_()
-                self.Db_tok.zero_()
+            if mode != 'replay':
+                self._fresh_step()
             body(mode)
         except BaseException:
             self._graphs, self._graph_key, self._warm_key = {}, None, None
@@ -1059,7 +1064,8 @@ class ShardedHMF(object):
             torch.cuda.current_stream(self.device).wait_event(done)
 
     def _step_body(self, route):
-        """The step with every buffer at a fixed address and a fixed size, so that the kernels between two
+        """The ONE body of the sampled-pool step ('mw' / 'mce', exchange='rows') of ShardedHMF, ShardedW2V and
+        ShardedHMFRepTokens, with every buffer at a fixed address and a fixed size, so that the kernels between two
         collectives are ONE hipGraph launch each (5 segments + K7's sort half as a sixth, on a second stream under
         the forward kernels + 4 collectives per step instead of ~35 kernel launches from Python; world 1: ONE graph,
         the sort half a branch of it).  What varies from batch to batch is the index vector [user rows ; received
@@ -1068,112 +1074,75 @@ class ShardedHMF(object):
         of the first segment, and the split sizes of the two all-to-alls, which stay outside the graphs.  The two
         large exchanges (target rows out, target-row gradients back: B_loc x (d+4) floats each) are issued
         asynchronously and waited for only where their result is needed, so that they travel under the scorer and
-        under the two backward GEMMs.  Returns (graph key, body(mode)) for _run_step."""
+        under the two backward GEMMs.  Returns (graph key, body(mode)) for _run_step.
+
+        The body scores "the scorer's input" X and writes its gradient dX; a subclass supplies what differs by
+        overriding (the defaults are the id-only step):
+          _step_blocks, _static_feeds, _key_more   more blocks of the index vector, more feeds, more key entries
+          _gather, _k7                             the lookups of fwd_gather, the fused scatter + Adagrad pass
+          _scorer_io, _input_fwd, _input_bwd       X / dX (U_loc / the arena's user rows), X formed at the head of
+                                                   fwd_score, dX consumed at the tail of bwd_gemms
+          _send_input_rows, _return_input_grads    the exchanges of a model whose input has rows on other ranks
+          _after_apply, _fresh_step                launches behind the apply segment; a step that is not a replay"""
         if self.pair:
             return self._step_body_pair(route)
         be, W = self.be, self.world
-        B, B_loc, S, Sg, d = self.B, self.B_loc, self.S, self.Sg, self.d
-        grp, dev = self.group, self.device
+        B_loc, S, Sg, d = self.B_loc, self.S, self.Sg, self.d
+        grp = self.group
         send, recv, R = route['send'], route['recv'], route['R']
-        if R > self.cap_r:
-            self._alloc_recv(R)
+        feed = self._index_feed(route, self._step_blocks(route))
         cap, cap_r = self.cap, self.cap_r
-        n_idx = B_loc + cap_r
-        idx = route.get('idx')
-        if idx is None or idx.shape[0] != n_idx:
-            idx = torch.full((n_idx,), self.zero_row, dtype=torch.int32, device=dev)
-            idx[:B_loc] = route['urows']
-            if R > 0:
-                idx[B_loc:B_loc + R] = route['recv_rows']
-            route['idx'] = idx
-        if self.g_idx is None or self.g_idx.shape[0] != n_idx:
-            self.g_idx = torch.empty(n_idx, dtype=torch.int32, device=dev)
-        feed = [(idx, self.g_idx)]                     # (a kernel: a device-to-device hipMemcpyAsync costs more)
         feed += self._static_feeds(route, cap_r)       # (subclasses: more per-batch index vectors)
         key = (cap, cap_r, self.g_idx.data_ptr(), self.arena.data_ptr(), self.pos_ptr.data_ptr(),
-               self.pos_items.data_ptr())
+               self.pos_items.data_ptr()) + self._key_more()
         arena, arena_b = self.arena, self.arena_b
-        urows, rrows = self.g_idx[:B_loc], self.g_idx[B_loc:]
+        urows, rrows = self.g_idx[:B_loc], self.g_idx[B_loc:B_loc + (B_loc if W == 1 else cap_r)]
         self.urows = urows
-        ni = self.ni_loc
-        dU = arena[:B_loc, :d]
-        T_in = self.T_pack if W == 1 else self.T_send[:cap_r]              # target rows as gathered
-        dT = arena[B_loc + Sg:B_loc + Sg + B_loc] if W == 1 else self.dT_pack
-
+        base_t = B_loc + Sg
+        X, dX = self._scorer_io()
         # world 1: nothing travels, so nothing is packed twice -- the pool bias goes straight to b_all, the pool
         # gradient and its row sums straight into the K7 arena, the target-bias gradient straight into arena_b
-        het = getattr(self, '_het', False)             # ShardedHMFRepTokens: the owner forms HET rows, token table replicated
-
-        def fwd_gather():      # the step's three lookups, one launch
-            if het:
-                return self._het_gather(urows, T_in, cap, cap_r)
-            if W == 1:
-                be.gather_rows_multi([(self.E_user, None, urows, self.U_loc, None),
-                                      (self.E_item, self.b_item, self.pool_rows, self.I_all, self.b_all),
-                                      (self.E_item, self.b_item, rrows[:B_loc], T_in, 'packed')])
-            else:
-                be.gather_rows_multi([(self.E_user, None, urows, self.U_loc, None),
-                                      (self.E_item, self.b_item, self.pool_rows[:cap], self.I_pack[:cap], 'packed'),
-                                      (self.E_item, self.b_item, rrows, T_in, 'packed')])
-
+        T_in = self.T_pack if W == 1 else self.T_send[:cap_r]              # target rows as gathered
+        dT = arena[base_t:base_t + B_loc] if W == 1 else self.dT_pack
         # default (ARX_SCORER_F32=1: the f32-MFMA logits / loss / GEMM kernels): the scorer on the bf16 matrix pipe --
         # hinge GEMM (act bits instead of logits / dlogits) + the two bit-operand backward products
         fused = self._fused_scorer()
 
+        def fwd_gather():      # the step's lookups, one launch
+            self._gather(urows, rrows, T_in)
+
         def fwd_score():
+            self._input_fwd()
             if W > 1:    # blocks -> pool (slot) order, their bias column -> b_all
                 be.gather_rows_multi([(self.I_gath, d, self.gidx, self.I_all, self.b_all)])
             if not fused:
-                be.gemm(self.U_loc, self.I_all[:, :d], self.logits, transB=True, col_bias=self.b_all)
+                be.gemm(X, self.I_all[:, :d], self.logits, transB=True, col_bias=self.b_all)
 
         def loss():
             # (global mean => gscale = 1/B; the target score and its rank-one gradients are formed by the same
             # kernel, straight from / into the packed rows: bias and dt live in column d)
-            dt = arena_b[B_loc + Sg:B_loc + Sg + B_loc] if W == 1 else dT[:, d]
-            if fused:
-                self.scorer.fwd(self.U_loc, self.I_all[:, :d], self.b_all, self.T_pack[:, :d], self.T_pack[:, d],
-                                urows, self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.t_loc, dt, dU,
-                                dT[:, :d], 1.0 / B)
-                return
-            self._loss_fused(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], urows,
-                             self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
-                             self.t_loc, dt, dU, dT[:, :d], 1.0 / B)
+            dt = arena_b[base_t:base_t + B_loc] if W == 1 else dT[:, d]
+            self._scorer_loss(fused, X, self.I_all[:, :d], urows, dt, dX, dT[:, :d])
 
         def bwd_gemms():
-            if fused:
-                self.scorer.bwd_dU(dU, beta=1.0)
-                if W == 1:
-                    self.scorer.bwd_dI(arena[B_loc:B_loc + S, :d], db=arena_b[B_loc:B_loc + S])
-                    return
-                self.scorer.bwd_dI(self.dI_all[:S, :d], db=self.gb_all)
-                be.copy_strided(self.gb_all, self.dI_all[:S, d])
-                return
-            be.gemm(self.dlogits, self.I_all[:, :d], dU, beta=1.0)
             if W == 1:
-                be.gemm(self.dlogits, self.U_loc, arena[B_loc:B_loc + S, :d], transA=True,
-                        a_rowsum=arena_b[B_loc:B_loc + S])
-                return
-            be.gemm(self.dlogits, self.U_loc, self.dI_all[:S, :d], transA=True, a_rowsum=self.gb_all)
-            be.copy_strided(self.gb_all, self.dI_all[:S, d])
+                self._scorer_bwd(fused, X, self.I_all[:, :d], dX, arena[B_loc:B_loc + S, :d],
+                                 arena_b[B_loc:B_loc + S])
+            else:
+                self._scorer_bwd(fused, X, self.I_all[:, :d], dX, self.dI_all[:S, :d], self.gb_all)
+                be.copy_strided(self.gb_all, self.dI_all[:S, d])
+            self._input_bwd()
 
-        def k7(phase):         # one fused scatter + Adagrad pass over both shards
-            if het:
-                return self._het_k7(phase, urows, rrows[:B_loc] if W == 1 else rrows, cap, cap_r)
-            be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
-                                     (self.E_item[:ni], self.A_item[:ni], self.b_item[:ni], self.Ab_item[:ni])],
-                                    [(0, urows, 0), (1, self.pool_rows[:cap], B_loc),
-                                     (1, rrows[:B_loc] if W == 1 else rrows, B_loc + Sg)],
-                                    arena[:, :d], arena_b, self.lr, phase=phase)
+        def k7(phase):         # one fused scatter + Adagrad pass over all shards
+            self._k7(phase, urows, rrows)
 
         def apply():
             if W > 1:    # the rows of this rank's block out of the summed pool gradient (bias column -> arena_b),
                 #              the bias column of the received target-row gradients
                 be.gather_rows_multi([(self.dI_all, d, self.my_slots[:cap], arena[B_loc:B_loc + cap],
                                        arena_b[B_loc:B_loc + cap])])
-                be.copy_strided(arena[B_loc + Sg:B_loc + Sg + cap_r, d], arena_b[B_loc + Sg:B_loc + Sg + cap_r])
+                be.copy_strided(arena[base_t:base_t + cap_r, d], arena_b[base_t:base_t + cap_r])
             k7(2)
-            if het and W == 1:
-                self._het_tok_apply()                  # (one rank: nothing to sum, the dense step follows at once)
 
         def body(mode):
             seg = lambda name, fn, feeds=None: self._segment(mode, name, fn, feeds)
@@ -1189,6 +1158,7 @@ class ShardedHMF(object):
                 bwd_gemms()
                 self._k7_join(sorted_)
                 apply()
+                self._after_apply(lambda name, fn: fn())     # (one rank: in the same graph, at once)
 
             if W == 1:
                 return seg('step', whole_step, feed)
@@ -1196,26 +1166,121 @@ class ShardedHMF(object):
             sorted_ = self._k7_sorts(mode, k7, True)
             dist.all_gather_into_tensor(self.I_gath[:W * cap], self.I_pack[:cap], group=grp)
             w_rows = _all_to_all(self.T_pack, self.T_send[:R], send, recv, group=grp, async_op=True)
+            self._send_input_rows(route)
             seg('fwd_score', fwd_score)                       # scorer GEMM under the target-row exchange
             w_rows.wait()
             seg('loss', loss)
-            w_dt = _all_to_all(arena[B_loc + Sg:B_loc + Sg + R], self.dT_pack, recv, send, group=grp,
-                               async_op=True)
-            seg('bwd_gemms', bwd_gemms)                       # dU, dI under the gradient exchange
+            w_dt = _all_to_all(arena[base_t:base_t + R], self.dT_pack, recv, send, group=grp, async_op=True)
+            seg('bwd_gemms', bwd_gemms)                       # dX, dI under the gradient exchange
+            w_dx = self._return_input_grads(route)
             # 0.5 MB: summed everywhere, every owner picks the rows of its block (padding -> the zero row)
             dist.all_reduce(self.dI_all[:S], op=dist.ReduceOp.SUM, group=grp)
             w_dt.wait()
+            w_dx.wait()
             self._k7_join(sorted_)
             seg('apply', apply)
-            if het:            # the merged token gradients of all ranks, then the same dense Adagrad step everywhere
-                dist.all_reduce(self.D_tok, op=dist.ReduceOp.SUM, group=grp)
-                dist.all_reduce(self.Db_tok, op=dist.ReduceOp.SUM, group=grp)
-                seg('tok_apply', self._het_tok_apply)
+            self._after_apply(seg)
 
         return key, body
 
+    # ---- what a subclass overrides in _step_body (here: the id-only step) ----
+    def _step_blocks(self, route):
+        """Grows the capacities to this route and returns the (rows, capacity) blocks of the index vector behind the
+        user rows."""
+        if route['R'] > self.cap_r:
+            self._alloc_recv(route['R'])
+        return [(route['recv_rows'], self.cap_r)]
+
     def _static_feeds(self, route, cap_r):
         return []
+
+    def _key_more(self):
+        return ()
+
+    def _gather(self, urows, rrows, T_in, more=()):
+        """The step's lookups in one launch: the user rows, the owned pool block, the requested target rows
+        (+ more sites)."""
+        cap = self.cap
+        pool = (self.E_item, self.b_item, self.pool_rows, self.I_all, self.b_all) if self.world == 1 else \
+            (self.E_item, self.b_item, self.pool_rows[:cap], self.I_pack[:cap], 'packed')
+        self.be.gather_rows_multi([(self.E_user, None, urows, self.U_loc, None), pool,
+                                   (self.E_item, self.b_item, rrows, T_in, 'packed'), *more])
+
+    def _k7(self, phase, urows, rrows, tables=(), sites=()):
+        """One fused scatter + Adagrad pass over the user shard and the item shard (+ more tables and their sites)."""
+        B_loc, d, ni = self.B_loc, self.d, self.ni_loc
+        self.be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
+                                      (self.E_item[:ni], self.A_item[:ni], self.b_item[:ni], self.Ab_item[:ni]),
+                                      *tables],
+                                     [(0, urows, 0), (1, self.pool_rows[:self.cap], B_loc),
+                                      (1, rrows, B_loc + self.Sg), *sites],
+                                     self.arena[:, :d], self.arena_b, self.lr, phase=phase)
+
+    def _scorer_io(self):
+        """(X, dX): what the scorer multiplies with the pool, and where its gradient goes."""
+        return self.U_loc, self.arena[:self.B_loc, :self.d]
+
+    def _input_fwd(self):
+        pass
+
+    def _input_bwd(self):
+        pass
+
+    def _send_input_rows(self, route):
+        """Issued behind the target-row all-to-all; back before fwd_score."""
+
+    def _return_input_grads(self, route):
+        """Issued behind bwd_gemms; returns what the step waits for beside the target-row gradients."""
+        return _Done()
+
+    def _after_apply(self, seg):
+        """Behind the apply segment; seg(name, fn) runs launches as a segment of the step."""
+
+    def _fresh_step(self):
+        """Before the body of a step that is not a replay (the first eager one, a capture, the step after an
+        exception)."""
+
+    # ---- shared by the bodies: the index feed and the scorer call ----
+    def _index_feed(self, route, blocks):
+        """The per-batch index vector [user rows ; the rows of every (rows, capacity) block, padded to its capacity
+        with the shard's zero row], built once per route and set of capacities (kept on the route), and g_idx, the
+        static vector it is copied into by the step's first node.  Returns the feed [(idx, g_idx)]."""
+        B_loc = self.B_loc
+        caps = tuple([c for _, c in blocks])
+        idx = route.get('idx')
+        if idx is None or route['idx_caps'] != caps:
+            idx = torch.full((B_loc + sum(caps),), self.zero_row, dtype=torch.int32, device=self.device)
+            idx[:B_loc] = route['urows']
+            at = B_loc
+            for rows, c in blocks:
+                if rows.shape[0] > 0:
+                    idx[at:at + rows.shape[0]] = rows
+                at += c
+            route['idx'], route['idx_caps'] = idx, caps
+        if self.g_idx is None or self.g_idx.shape[0] != idx.shape[0]:
+            self.g_idx = torch.empty(idx.shape[0], dtype=torch.int32, device=self.device)
+        return [(idx, self.g_idx)]             # (a kernel: a device-to-device hipMemcpyAsync costs more)
+
+    def _scorer_loss(self, fused, X, pool, urows, dt, dX, dT):
+        """Loss, dlogits (fused: act bits), the target score and its rank-one gradients (dt, dX, dT) in one kernel:
+        the bf16-pipe scorer's forward on (X, pool), or the loss kernel over the logits."""
+        d = self.d
+        if fused:
+            self.scorer.fwd(X, pool, self.b_all, self.T_pack[:, :d], self.T_pack[:, d], urows, self.pos_ptr,
+                            self.pos_items, self.item2slot, self.bl, self.t_loc, dt, dX, dT, 1.0 / self.B)
+        else:
+            self._loss_fused(self.logits, X, self.T_pack[:, :d], self.T_pack[:, d], urows, self.pos_ptr,
+                             self.pos_items, self.item2slot, self.bl, self.dlogits, self.t_loc, dt, dX, dT,
+                             1.0 / self.B)
+
+    def _scorer_bwd(self, fused, X, pool, dX, dI, db):
+        """The backward products: dX += dL . pool, dI = dL^T . X and its row sums db (the bias gradient)."""
+        if fused:
+            self.scorer.bwd_dU(dX, beta=1.0)
+            self.scorer.bwd_dI(dI, db=db)
+        else:
+            self.be.gemm(self.dlogits, pool, dX, beta=1.0)
+            self.be.gemm(self.dlogits, X, dI, transA=True, a_rowsum=db)
 
     def _step_body_pair(self, route):
         """The 'bpr' / 'bpr-hinge' step (hmf_model.py:96-107 on the global batch, gscale = 1 / B), a body for the same
@@ -1236,22 +1301,10 @@ class ShardedHMF(object):
         never read by the kernel, and their arena rows carry the padding key: K7 drops them."""
         be, W = self.be, self.world
         B, B_loc, d = self.B, self.B_loc, self.d
-        grp, dev = self.group, self.device
+        grp = self.group
         send, recv, R, n_req = route['send'], route['recv'], route['R'], route['n_req']
-        if R > self.cap_r:
-            self._alloc_recv(R)
+        feed = self._index_feed(route, self._step_blocks(route)) + [(route['slots'], self.g_slots)]
         cap_r = self.cap_r
-        n_idx = B_loc + cap_r
-        idx = route.get('idx')
-        if idx is None or idx.shape[0] != n_idx:
-            idx = torch.full((n_idx,), self.zero_row, dtype=torch.int32, device=dev)
-            idx[:B_loc] = route['urows']
-            if R > 0:
-                idx[B_loc:B_loc + R] = route['recv_rows']
-            route['idx'] = idx
-        if self.g_idx is None or self.g_idx.shape[0] != n_idx:
-            self.g_idx = torch.empty(n_idx, dtype=torch.int32, device=dev)
-        feed = [(idx, self.g_idx), (route['slots'], self.g_slots)]
         key = ('pair', cap_r, self.g_idx.data_ptr(), self.arena.data_ptr(), self.g_slots.data_ptr())
         arena, arena_b = self.arena, self.arena_b
         urows, rrows = self.g_idx[:B_loc], self.g_idx[B_loc:]
@@ -1358,17 +1411,12 @@ class ShardedHMF(object):
                              % (what, self.n_users, r, W, r))
         if len(items) and (items.min() < 0 or items.max() >= self.n_items):
             raise ValueError("%s: item ids must lie in [0, %d)" % (what, self.n_items))
-        owner = items % W
-        order = np.argsort(owner, kind='stable')
+        order, _, send = owner_order(items, W)
         pairs = np.stack([users, items], 1)[order].astype(np.int32).reshape(-1)
         if W == 1:
             recv = pairs
         else:
-            send = np.bincount(owner, minlength=W).astype(np.int64)
-            st = torch.from_numpy(send).to(self.device)
-            rt = torch.empty_like(st)
-            _all_to_all(rt, st, group=self.group)
-            cnt = [int(v) for v in rt.cpu().tolist()]
+            cnt = self._count_exchange(send)
             out = torch.zeros((2 * sum(cnt),), dtype=torch.int32, device=self.device)
             _all_to_all(out, torch.from_numpy(pairs).to(self.device), [2 * c for c in cnt],
                         [2 * int(c) for c in send.tolist()], group=self.group)
@@ -1726,9 +1774,21 @@ class ShardedW2V(ShardedHMF):
     The context rows of a batch live on any ranks, so they are routed like the two rows of a pair step
     (_prepare_route_pair): the n B_loc requests (skip-gram training: the B_loc of t = 0) are ordered by owner, the
     rows come back in that order and every (t, b) knows the SLOT of its row in the received block.  One slot serves one
-    request: an item asked for twice travels twice and K7 merges its gradient rows.  _step_body is ShardedHMF's with
-    one more gather site, one more pair of all-to-alls and the two slot-addressed window kernels
-    (arx_window_slots_fwd / _bwd); K7 is one pass over the three tables.
+    request: an item asked for twice travels twice and K7 merges its gradient rows.  The step IS
+    ShardedHMF._step_body: this class overrides its hooks and adds one more gather site, one more pair of all-to-alls
+    and the two slot-addressed window kernels (arx_window_slots_fwd / _bwd); K7 is one pass over the three tables.
+
+      fwd_gather   + one site: the requested context rows -> the packed send block [cap_c, d]
+      all_to_all   context rows out, in request order (asynchronous, beside the target-row exchange)
+      fwd_score    arx_window_slots_fwd: X = 0.5 U_loc + w sum_t C_pack[slot(t, b)]; then the scorer on X
+      loss, bwd_gemms   as ShardedHMF with X / dX for U_loc / dU; then arx_window_slots_bwd: 0.5 dX into the
+                   arena's user rows, w dX into the n slots of the gradient block
+      all_to_all   context gradient rows back to their owners, into the arena behind the received target rows
+      apply        ONE sparse_adagrad_multi over the three tables: user rows, pool, received targets, received
+                   context rows
+
+    The per-batch vectors -- [user rows ; received target rows (cap_r) ; received context rows (cap_c)], padded with
+    the shard's zero row, and the slots -- are fed by the first node.
 
     loss: 'mw' | 'mce'; exchange: 'rows'; n_input >= 1 (ValueError otherwise).  Out of scope: use_sep_item=False (one
     shared item table), multi-hot or several features per entity, output_feat != 1, dropout, n_input_items = 0."""
@@ -1809,26 +1869,9 @@ class ShardedW2V(ShardedHMF):
         """The requests ctx [n_win][m] (time-major) of this rank, ordered by owner: one count exchange and one id
         exchange resolve them to local rows of the owners' context shards; cslots[t * m + b] = the row of request
         (t, b) in the block that comes back."""
-        W, dev = self.world, self.device
-        req = ctx.reshape(-1).astype(np.int32)
-        owner = req % W
-        perm = np.argsort(owner, kind='stable')
-        slot = np.empty(len(req), dtype=np.int32)
-        slot[perm] = np.arange(len(req), dtype=np.int32)
-        send = np.bincount(owner, minlength=W).astype(np.int64)
-        st = torch.from_numpy(send).to(dev)
-        rt = torch.empty_like(st)
-        _all_to_all(rt, st, group=self.group)
-        recv = [int(v) for v in rt.cpu().tolist()]
-        Rc = int(sum(recv))
-        req_d = torch.from_numpy(np.ascontiguousarray(req[perm])).to(dev)
-        recv_ids = torch.zeros((Rc,), dtype=torch.int32, device=dev)
-        _all_to_all(recv_ids, req_d, recv, [int(v) for v in send.tolist()], group=self.group)
-        rows = torch.zeros((Rc,), dtype=torch.int32, device=dev)
-        if Rc > 0:
-            self.be.shard_route(recv_ids, W, self.rank, self.zero_row, rows, None)
-        return {'cslots': torch.from_numpy(slot).to(dev), 'csend': [int(v) for v in send.tolist()], 'crecv': recv,
-                'Rc': Rc, 'crecv_rows': rows, 'n_win': int(ctx.shape[0]), 'n_req': int(len(req))}
+        r, slot = self._route_requests(ctx.reshape(-1).astype(np.int32))[:2]
+        return {'cslots': torch.from_numpy(slot).to(self.device), 'csend': r['send'], 'crecv': r['recv'],
+                'Rc': r['R'], 'crecv_rows': r['recv_rows'], 'n_win': int(ctx.shape[0]), 'n_req': int(ctx.size)}
 
     def prepare_route(self, users, items, context):
         """ShardedHMF.prepare_route for (users, targets) -- the batch ordered by the target's owner -- with the
@@ -1844,7 +1887,7 @@ class ShardedW2V(ShardedHMF):
         if it.min() < 0 or it.max() >= self.n_items:
             raise ValueError("prepare_route: item ids must lie in [0, %d)" % self.n_items)
         ctx = self._context_array(context, B_loc, "prepare_route")
-        perm = np.argsort(it % self.world, kind='stable')
+        perm = owner_order(it, self.world)[0]
         route = super().prepare_route(u[perm], it[perm])         # (sorted already: its own stable sort keeps the order)
         ctx = ctx[:, perm]
         route['context'] = torch.from_numpy(np.ascontiguousarray(ctx.astype(np.int32))).to(self.device)
@@ -1859,161 +1902,62 @@ class ShardedW2V(ShardedHMF):
         route = users if isinstance(users, dict) else self.prepare_route(users, items, context)
         self._run_step(route)
 
+    # ------------------------------------------- step: what ShardedHMF._step_body takes from this class
+    # World 1: the context rows are gathered straight into the block the window kernel reads and their gradient rows
+    # written straight into the arena.  Arena rows behind the received requests carry the padding key: K7 drops them.
+    def _step_blocks(self, route):
+        if route.get('n_win') != self.n_train:
+            raise ValueError("step: the route asks for %r window rows, a training step of this model for %d"
+                             % (route.get('n_win'), self.n_train))
+        if route['R'] > self.cap_r or route['Rc'] > self.cap_c:
+            self._alloc_recv(route['R'], route['Rc'])
+        return [(route['recv_rows'], self.cap_r), (route['crecv_rows'], self.cap_c)]
+
     def _static_feeds(self, route, cap_r):
         return [(route['cslots'], self.g_cslots)]
 
-    # ------------------------------------------------------------------- step
-    def _step_body(self, route):
-        """ShardedHMF._step_body with the window in front of the scorer:
+    def _key_more(self):
+        return (self.cap_c, self.C_send.data_ptr(), self.g_cslots.data_ptr())
 
-          fwd_gather   + one site: the requested context rows -> the packed send block [cap_c, d]
-          all_to_all   context rows out, in request order (asynchronous, beside the target-row exchange)
-          fwd_score    arx_window_slots_fwd: X = 0.5 U_loc + w sum_t C_pack[slot(t, b)]; then the scorer on X
-          loss, bwd_gemms   as ShardedHMF with X / dX for U_loc / dU; then arx_window_slots_bwd: 0.5 dX into the
-                       arena's user rows, w dX into the n slots of the gradient block
-          all_to_all   context gradient rows back to their owners, into the arena behind the received target rows
-          apply        ONE sparse_adagrad_multi over the three tables: user rows, pool, received targets, received
-                       context rows
+    def _ctx(self):
+        """(rows to look up, the block they are gathered into, their gradient block, its row in the arena): the
+        context requests this rank serves."""
+        B_loc, n_req = self.B_loc, self.n_train * self.B_loc
+        base_c = B_loc + self.Sg + self.cap_r
+        crows = self.g_idx[B_loc + self.cap_r:]
+        if self.world == 1:
+            return crows[:n_req], self.C_pack, self.arena[base_c:base_c + n_req], base_c
+        return crows, self.C_send[:self.cap_c], self.dC_pack, base_c
 
-        The per-batch vectors -- [user rows ; received target rows (cap_r) ; received context rows (cap_c)], padded
-        with the shard's zero row, and the slots -- are fed by the first node.  World 1: ONE graph; the context rows
-        are gathered straight into the block the window kernel reads and their gradient rows written straight into
-        the arena.  Arena rows behind the received requests carry the padding key: K7 drops them."""
-        be, W = self.be, self.world
-        B, B_loc, S, Sg, d = self.B, self.B_loc, self.S, self.Sg, self.d
-        grp, dev = self.group, self.device
-        n_w, n_req = self.n_train, self.n_train * B_loc
-        if route.get('n_win') != n_w:
-            raise ValueError("step: the route asks for %r window rows, a training step of this model for %d"
-                             % (route.get('n_win'), n_w))
-        send, recv, R = route['send'], route['recv'], route['R']
-        csend, crecv, Rc = route['csend'], route['crecv'], route['Rc']
-        if R > self.cap_r or Rc > self.cap_c:
-            self._alloc_recv(R, Rc)
-        cap, cap_r, cap_c = self.cap, self.cap_r, self.cap_c
-        n_idx = B_loc + cap_r + cap_c
-        idx = route.get('idx')
-        if idx is None or idx.shape[0] != n_idx or route.get('idx_cap_r') != cap_r:
-            idx = torch.full((n_idx,), self.zero_row, dtype=torch.int32, device=dev)
-            idx[:B_loc] = route['urows']
-            if R > 0:
-                idx[B_loc:B_loc + R] = route['recv_rows']
-            if Rc > 0:
-                idx[B_loc + cap_r:B_loc + cap_r + Rc] = route['crecv_rows']
-            route['idx'], route['idx_cap_r'] = idx, cap_r
-        if self.g_idx is None or self.g_idx.shape[0] != n_idx:
-            self.g_idx = torch.empty(n_idx, dtype=torch.int32, device=dev)
-        feed = [(idx, self.g_idx)] + self._static_feeds(route, cap_r)
-        key = ('w2v', cap, cap_r, cap_c, self.g_idx.data_ptr(), self.arena.data_ptr(), self.C_send.data_ptr(),
-               self.g_cslots.data_ptr(), self.pos_ptr.data_ptr(), self.pos_items.data_ptr())
-        arena, arena_b = self.arena, self.arena_b
-        urows, rrows, crows = self.g_idx[:B_loc], self.g_idx[B_loc:B_loc + cap_r], self.g_idx[B_loc + cap_r:]
-        if W == 1:
-            rrows, crows = rrows[:B_loc], crows[:n_req]
-        self.urows = urows
+    def _gather(self, urows, rrows, T_in):
+        crows, C_in = self._ctx()[:2]
+        super()._gather(urows, rrows, T_in, [(self.E_ctx, None, crows, C_in, None)])
+
+    def _k7(self, phase, urows, rrows):
         ni = self.ni_loc
-        base_t, base_c = B_loc + Sg, B_loc + Sg + cap_r
-        X, dX, cslots = self.X, self.dX, self.g_cslots
-        w = 0.5 / n_w
-        T_in = self.T_pack if W == 1 else self.T_send[:cap_r]
-        dT = arena[base_t:base_t + B_loc] if W == 1 else self.dT_pack
-        C_in = self.C_pack if W == 1 else self.C_send[:cap_c]
-        dC = arena[base_c:base_c + n_req] if W == 1 else self.dC_pack
+        crows, _, _, base_c = self._ctx()
+        super()._k7(phase, urows, rrows, [(self.E_ctx[:ni], self.A_ctx[:ni], None, None)], [(2, crows, base_c)])
 
-        def fwd_gather():      # the step's four lookups, one launch
-            pool = (self.E_item, self.b_item, self.pool_rows, self.I_all, self.b_all) if W == 1 else \
-                (self.E_item, self.b_item, self.pool_rows[:cap], self.I_pack[:cap], 'packed')
-            be.gather_rows_multi([(self.E_user, None, urows, self.U_loc, None), pool,
-                                  (self.E_item, self.b_item, rrows, T_in, 'packed'),
-                                  (self.E_ctx, None, crows, C_in, None)])
+    def _scorer_io(self):
+        return self.X, self.dX
 
-        fused = self._fused_scorer()
+    def _input_fwd(self):      # arx_window_slots_fwd: X = 0.5 U_loc + w sum_t C_pack[slot(t, b)]
+        n = self.n_train
+        self.be.window_slots_fwd(self.C_pack, self.g_cslots, n, 0.5 / n, self.U_loc, 0.5, self.X)
 
-        def fwd_score():
-            be.window_slots_fwd(self.C_pack, cslots, n_w, w, self.U_loc, 0.5, X)
-            if W > 1:
-                be.gather_rows_multi([(self.I_gath, d, self.gidx, self.I_all, self.b_all)])
-            if not fused:
-                be.gemm(X, self.I_all[:, :d], self.logits, transB=True, col_bias=self.b_all)
+    def _input_bwd(self):      # dX -> 0.5 dX into the user rows of the arena, w dX into the window's slots
+        n, d = self.n_train, self.d
+        self.be.window_slots_bwd(self.dX, self.g_cslots, n, 0.5 / n, 0.5, self.arena[:self.B_loc, :d], False,
+                                 self._ctx()[2][:, :d])
 
-        def loss():
-            dt = arena_b[base_t:base_t + B_loc] if W == 1 else dT[:, d]
-            if fused:
-                self.scorer.fwd(X, self.I_all[:, :d], self.b_all, self.T_pack[:, :d], self.T_pack[:, d], urows,
-                                self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.t_loc, dt, dX, dT[:, :d],
-                                1.0 / B)
-                return
-            self._loss_fused(self.logits, X, self.T_pack[:, :d], self.T_pack[:, d], urows, self.pos_ptr,
-                             self.pos_items, self.item2slot, self.bl, self.dlogits, self.t_loc, dt, dX, dT[:, :d],
-                             1.0 / B)
+    def _send_input_rows(self, route):         # context rows out, in request order
+        _all_to_all(self.C_pack[:self.n_train * self.B_loc], self.C_send[:route['Rc']], route['csend'],
+                    route['crecv'], group=self.group, async_op=True).wait()
 
-        def bwd_gemms():
-            if fused:
-                self.scorer.bwd_dU(dX, beta=1.0)
-                if W == 1:
-                    self.scorer.bwd_dI(arena[B_loc:B_loc + S, :d], db=arena_b[B_loc:B_loc + S])
-                else:
-                    self.scorer.bwd_dI(self.dI_all[:S, :d], db=self.gb_all)
-                    be.copy_strided(self.gb_all, self.dI_all[:S, d])
-            else:
-                be.gemm(self.dlogits, self.I_all[:, :d], dX, beta=1.0)
-                if W == 1:
-                    be.gemm(self.dlogits, X, arena[B_loc:B_loc + S, :d], transA=True,
-                            a_rowsum=arena_b[B_loc:B_loc + S])
-                else:
-                    be.gemm(self.dlogits, X, self.dI_all[:S, :d], transA=True, a_rowsum=self.gb_all)
-                    be.copy_strided(self.gb_all, self.dI_all[:S, d])
-            # dX -> 0.5 dX into the user rows of the arena, w dX into the window's slots
-            be.window_slots_bwd(dX, cslots, n_w, w, 0.5, arena[:B_loc, :d], False, dC[:, :d])
-
-        def k7(phase):         # one fused scatter + Adagrad pass over the three shards
-            be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
-                                     (self.E_item[:ni], self.A_item[:ni], self.b_item[:ni], self.Ab_item[:ni]),
-                                     (self.E_ctx[:ni], self.A_ctx[:ni], None, None)],
-                                    [(0, urows, 0), (1, self.pool_rows[:cap], B_loc), (1, rrows, base_t),
-                                     (2, crows, base_c)], arena[:, :d], arena_b, self.lr, phase=phase)
-
-        def apply():
-            if W > 1:
-                be.gather_rows_multi([(self.dI_all, d, self.my_slots[:cap], arena[B_loc:B_loc + cap],
-                                       arena_b[B_loc:B_loc + cap])])
-                be.copy_strided(arena[base_t:base_t + cap_r, d], arena_b[base_t:base_t + cap_r])
-            k7(2)
-
-        def body(mode):
-            seg = lambda name, fn, feeds=None: self._segment(mode, name, fn, feeds)
-
-            def whole_step():
-                fwd_gather()
-                sorted_ = self._k7_sorts(mode, k7, False)
-                fwd_score()
-                loss()
-                bwd_gemms()
-                self._k7_join(sorted_)
-                apply()
-
-            if W == 1:
-                return seg('step', whole_step, feed)
-            seg('fwd_gather', fwd_gather, feed)
-            sorted_ = self._k7_sorts(mode, k7, True)
-            dist.all_gather_into_tensor(self.I_gath[:W * cap], self.I_pack[:cap], group=grp)
-            w_rows = _all_to_all(self.T_pack, self.T_send[:R], send, recv, group=grp, async_op=True)
-            w_ctx = _all_to_all(self.C_pack[:n_req], self.C_send[:Rc], csend, crecv, group=grp, async_op=True)
-            w_ctx.wait()
-            seg('fwd_score', fwd_score)                       # window + scorer GEMM under the target-row exchange
-            w_rows.wait()
-            seg('loss', loss)
-            w_dt = _all_to_all(arena[base_t:base_t + R], self.dT_pack, recv, send, group=grp, async_op=True)
-            seg('bwd_gemms', bwd_gemms)
-            w_dc = _all_to_all(arena[base_c:base_c + Rc], self.dC_pack[:n_req], crecv, csend, group=grp,
-                               async_op=True)
-            dist.all_reduce(self.dI_all[:S], op=dist.ReduceOp.SUM, group=grp)
-            w_dt.wait()
-            w_dc.wait()
-            self._k7_join(sorted_)
-            seg('apply', apply)
-
-        return key, body
+    def _return_input_grads(self, route):      # context gradient rows back, into the arena behind the target rows
+        base_c = self.B_loc + self.Sg + self.cap_r
+        return _all_to_all(self.arena[base_c:base_c + route['Rc']], self.dC_pack[:self.n_train * self.B_loc],
+                           route['crecv'], route['csend'], group=self.group, async_op=True)
 
     # ---------------------------------------------------------------- serving
     def _serve_latents(self, u, out):
@@ -2194,22 +2138,11 @@ class ShardedHMFBags(ShardedHMF):
                 be.gemm(self.U_loc, self.P_part[:, :d], self.logits, transB=True, col_bias=self.b_all)
 
         def loss():
-            if fused:
-                self.scorer.fwd(self.U_loc, self.P_part[:, :d], self.b_all, self.T_pack[:, :d], self.T_pack[:, d],
-                                urows, self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.t_loc,
-                                self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
-                return
-            self._loss_fused(self.logits, self.U_loc, self.T_pack[:, :d], self.T_pack[:, d], urows,
-                             self.pos_ptr, self.pos_items, self.item2slot, self.bl, self.dlogits,
-                             self.t_loc, self.dT_pack[:, d], dU, self.dT_pack[:, :d], 1.0 / B)
+            self._scorer_loss(fused, self.U_loc, self.P_part[:, :d], urows, self.dT_pack[:, d], dU,
+                              self.dT_pack[:, :d])
 
         def bwd():
-            if fused:
-                self.scorer.bwd_dU(dU, beta=1.0)
-                self.scorer.bwd_dI(gP[:, :d], db=self.gb_all)
-            else:
-                be.gemm(self.dlogits, self.P_part[:, :d], dU, beta=1.0)                    # dU += dL . pool
-                be.gemm(self.dlogits, self.U_loc, gP[:, :d], transA=True, a_rowsum=self.gb_all)
+            self._scorer_bwd(fused, self.U_loc, self.P_part[:, :d], dU, gP[:, :d], self.gb_all)
             be.copy_strided(self.gb_all, gP[:, d])
 
         def k7(phase):
@@ -2307,8 +2240,6 @@ class ShardedHMFRepTokens(ShardedHMF):
     2 x B x (d + 4) x 4 B with B the GLOBAL batch
     (predicted comm / compute 0.35 against 0.57 at N = 8, B_loc = 16384)."""
 
-    _het = True
-
     def __init__(self, n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, bags, n_tokens,
                  backend=None, group=None, tables=None, seed=0, acc0=0.1, graphs=None, loss='mw'):
         super().__init__(n_users, n_items, d, B_loc, S, learning_rate, rank, world, device, backend=backend,
@@ -2366,7 +2297,7 @@ class ShardedHMFRepTokens(ShardedHMF):
         else:          # block row -> pool slot (S: padding) -> item id (padding entity)
             be.take_i32(self.pool_ext, self.my_slots, self.block_ids, self.pad_item)
 
-    # ---- hooks of ShardedHMF._step_body: HET rows and the replicated token table ----
+    # ---- what ShardedHMF._step_body takes from this class: HET rows and the replicated token table ----
     def _static_feeds(self, route, cap_r):
         gid = route.get('gid')
         if gid is None or gid.shape[0] != cap_r:
@@ -2379,10 +2310,10 @@ class ShardedHMFRepTokens(ShardedHMF):
             self.g_gid = torch.empty(cap_r, dtype=torch.int32, device=self.device)
         return [(gid, self.g_gid)]
 
-    def _het_gather(self, urows, T_in, cap, cap_r):
+    def _gather(self, urows, rrows, T_in):
         """users, the owned pool block and the requested target rows in ONE launch (arx_lookup_multi): item rows =
         (id row + bag mean) / 2 with their biases, then the two bias columns of the packed rows."""
-        be, d, W = self.be, self.d, self.world
+        be, d, W, cap, cap_r = self.be, self.d, self.world, self.cap, self.cap_r
         bag = (self.bag_vals, self.bag_starts, self.bag_lens)
         item = (self.E_item, self.b_item, self.lmap, self.E_tok, self.b_tok) + bag
         nt_rows = self.B_loc if W == 1 else cap_r
@@ -2397,9 +2328,9 @@ class ShardedHMFRepTokens(ShardedHMF):
             be.copy_strided(pool_b, self.I_pack[:cap, d])
         be.copy_strided(self.tb_send[:nt_rows], T_in[:nt_rows, d])
 
-    def _het_k7(self, phase, urows, rrows, cap, cap_r):
+    def _k7(self, phase, urows, rrows):
         be, d, B_loc, Sg, ni, W = self.be, self.d, self.B_loc, self.Sg, self.ni_loc, self.world
-        arena, arena_b = self.arena, self.arena_b
+        arena, arena_b, cap, cap_r = self.arena, self.arena_b, self.cap, self.cap_r
         nb = self.S if W == 1 else cap
         nt_rows = B_loc if W == 1 else cap_r
         be.sparse_adagrad_multi([(self.E_user, self.A_user, None, None),
@@ -2411,12 +2342,28 @@ class ShardedHMFRepTokens(ShardedHMF):
                            [(self.block_ids[:nb], B_loc, 0.5), (self.g_gid[:nt_rows], B_loc + Sg, 0.5)],
                            arena[:, :d], arena_b, phase=phase)
 
-    def _het_tok_apply(self):
+    def _tok_apply(self):
         """The same Adagrad step on every replica: rows of the summed gradient table that are not all zero (the rest
         would not move), the table zeroed on the way for the next step's accumulation (arx_adagrad_rows_nonzero)."""
         nt = self.n_tokens
         self.be.adagrad_rows_nonzero(self.E_tok[:nt], self.A_tok[:nt], self.b_tok[:nt], self.Ab_tok[:nt], self.D_tok,
                                      self.Db_tok, self.lr)
+
+    def _after_apply(self, seg):
+        """The merged token gradients of all ranks (one rank: nothing to sum), then the same dense Adagrad step
+        everywhere."""
+        if self.world > 1:
+            dist.all_reduce(self.D_tok, op=dist.ReduceOp.SUM, group=self.group)
+            dist.all_reduce(self.Db_tok, op=dist.ReduceOp.SUM, group=self.group)
+        seg('tok_apply', self._tok_apply)
+
+    def _fresh_step(self):
+        """The dense token-gradient table must be all zero at step entry (the token apply zeroes the rows it
+        consumes).  A step that died between the gradient pass and that apply would leave sums behind that the next
+        step counts twice: every step that is NOT a replay (the first eager one, a re-capture, the step after an
+        exception -- its graphs are dropped) starts from a cleared table."""
+        self.D_tok.zero_()
+        self.Db_tok.zero_()
 
     def item_view(self, chunk_cols=16384):
         """A serving view of this model (ShardedHetView): recommend / evaluate over its materialised item latents."""
@@ -2858,10 +2805,8 @@ class SeqHybridParallel(SeqDataParallel):
         lookups grouped by owner (stable: the order inside a group is the order of the lookups), rows as LOCAL rows
         of their owner."""
         full_rows = np.asarray(full_rows, dtype=np.int64)
-        owner = full_rows % world
-        order = np.argsort(owner, kind='stable')
-        return (order.astype(np.int32), (full_rows[order] // world).astype(np.int32),
-                np.bincount(owner, minlength=world).astype(np.int64))
+        order, _, counts = owner_order(full_rows, world)
+        return order.astype(np.int32), (full_rows[order] // world).astype(np.int32), counts
 
     def _feature(self, f):
         """The map of a feature re-expressed for a striped table: kept on the host (entity -> global row) for the

@@ -369,6 +369,37 @@ def test_hybrid_route_rows_groups_by_owner_stably():
     assert len(order) == 0 and counts.tolist() == [0, 0, 0, 0]
 
 
+@pytest.mark.parametrize("world", [1, 2, 3, 4])
+def test_owner_order_matches_brute_force(world):
+    """arx.dist.owner_order (the host half of every variable-size exchange) against a loop that deals the requests
+    out to their owners one by one: the permutation lists owner 0's requests in request order, then owner 1's, ...;
+    the slots invert it; the counts are the group sizes."""
+    from arx.dist import owner_order
+    rng = np.random.default_rng(world)
+    cases = [np.array([7, 3, 7, 7, 12, 3, 0, 5, 12, 7], dtype=np.int32),        # repeated ids
+             np.zeros(0, dtype=np.int32),                                       # no request at all
+             (rng.integers(0, 50, size=37) * world).astype(np.int32),           # every owner but 0 gets nothing
+             (rng.integers(0, 50, size=41) * world + world - 1).astype(np.int64),   # ... every owner but the last
+             rng.integers(0, 1000, size=129).astype(np.int32)]
+    if world > 2:
+        ids = rng.integers(0, 1000, size=64)
+        cases.append(ids[ids % world != 1].astype(np.int32))                    # a middle owner gets nothing
+    for ids in cases:
+        groups = [[] for _ in range(world)]
+        for i, v in enumerate(ids.tolist()):
+            groups[v % world].append(i)
+        want_perm = [i for g in groups for i in g]
+        want_slot = [0] * len(ids)
+        for place, i in enumerate(want_perm):
+            want_slot[i] = place
+        perm, slot, send = owner_order(ids, world)
+        assert perm.tolist() == want_perm
+        assert slot.tolist() == want_slot and slot.dtype == np.int32
+        assert send.tolist() == [len(g) for g in groups] and send.dtype == np.int64
+        np.testing.assert_array_equal(perm[slot], np.arange(len(ids)))          # the slots invert the permutation
+        np.testing.assert_array_equal(slot[perm], np.arange(len(ids)))
+
+
 def _hybrid_worker(rank, world, port, out_dir):
     for p in (ROOT, os.path.join(ROOT, "a-recsys_amd"), os.path.join(ROOT, "tests")):
         if p not in sys.path:

@@ -107,10 +107,10 @@ class HipBackend(object):
         self.ops.gather_mulhot_mean(E, bias, vals, starts, lens, ids, out, scale=scale, accumulate=accumulate,
                                     bias_out=bias_out)
 
-    def bags_adagrad(self, E, acc, bias, bias_acc, vals, starts, lens, sites, G, Gb, lr, phase=3):
+    def bags_adagrad(self, E, acc, bias, bias_acc, vals, starts, lens, sites, G, Gb, lr, phase=_ops.K7_BOTH):
         """Two-stage multi-hot pass (arx_sparse_adagrad_bags); sites: [(entity ids, row_base, coef)].
         Tokens >= E.shape[0] (rows of other shards, mapped to the padding row) are dropped.
-        phase 1: both sorts (ids only), 2: merge + apply, 3: both."""
+        phase ops.K7_SORT: both sorts (ids only), K7_APPLY: merge + apply, K7_BOTH: both."""
         ops = self.ops
         # one workspace per SHAPE of the pass (counts, row bases, coefficients); the id tensors may be
         # fresh every step (prepare_route): only the pointer arrays are rebuilt then
@@ -232,10 +232,10 @@ class HipBackend(object):
     def sum_scaled(self, x, scale, out):
         self.ops.sum_scaled(x, scale, out)
 
-    def sparse_adagrad_multi(self, tables, sites, G, Gb, lr, phase=3):
+    def sparse_adagrad_multi(self, tables, sites, G, Gb, lr, phase=_ops.K7_BOTH):
         """tables: [(E, acc, bias|None, bias_acc|None)]; sites: [(table, local_rows, row_base)]:
-        one fused pass (arx_sparse_adagrad_cat_multi).  phase 1: keys + sorts + run records (needs the
-        ids only), 2: apply, 3: both."""
+        one fused pass (arx_sparse_adagrad_cat_multi).  phase ops.K7_SORT: keys + sorts + run records (needs the
+        ids only), K7_APPLY: apply, K7_BOTH: both."""
         ops = self.ops
         sites = [(x[0], x[1], x[2], x[3] if len(x) > 3 else 1.0) for x in sites]   # (table, rows, base[, coef])
         key = tuple((t, r.data_ptr(), int(r.shape[0]), b, c) for t, r, b, c in sites)
@@ -268,7 +268,7 @@ class HipBackend(object):
                                              torch.empty(ent.total, dtype=torch.float32, device=G.device))
         ops.sparse_adagrad_cat_multi(ent, G, Gb, lr, kb, sb, cb, self.ws_k7, phase=phase)
 
-    def bags_grad_dense(self, D, Db, vals, starts, lens, sites, G, Gb, phase=3):
+    def bags_grad_dense(self, D, Db, vals, starts, lens, sites, G, Gb, phase=_ops.K7_BOTH):
         """D[t] += sum of the gradient rows of the bags that hold token t (coefficient coef / len), Db likewise: the
         two-stage multi-hot pass in its gradient-descent form (no slots) with a step of -1 onto a gradient table --
         0 - (-1) g = g, the merged sums themselves, bit for bit.  Tokens >= D.shape[0] are dropped."""
@@ -1039,12 +1039,12 @@ class ShardedHMF(object):
             self._graphs[name].replay(feeds)
 
     def _k7_sorts(self, mode, k7, own_graph):
-        """k7(1) -- K7's keys, sorts and run records, which need the ids only -- on the second stream, under the
+        """k7(K7_SORT) -- K7's keys, sorts and run records, which need the ids only -- on the second stream, under the
         forward kernels (the ~70 us chain leaves the critical path): a graph of its own between the segments
         (own_graph), or a branch of the one graph at world 1.  Returns what _k7_join waits for before the apply half.
         A model without a second stream runs it in line."""
         if self._side is None:
-            k7(1)
+            k7(_ops.K7_SORT)
             return None
         main, side = torch.cuda.current_stream(self.device), self._side
         ev = torch.cuda.Event()
@@ -1052,9 +1052,9 @@ class ShardedHMF(object):
         side.wait_event(ev)
         with torch.cuda.stream(side):
             if own_graph:
-                self._segment(mode, 'k7_sorts', lambda: k7(1))
+                self._segment(mode, 'k7_sorts', lambda: k7(_ops.K7_SORT))
             else:
-                k7(1)
+                k7(_ops.K7_SORT)
             done = torch.cuda.Event()
             done.record(side)
         return done
@@ -1142,7 +1142,7 @@ class ShardedHMF(object):
                 be.gather_rows_multi([(self.dI_all, d, self.my_slots[:cap], arena[B_loc:B_loc + cap],
                                        arena_b[B_loc:B_loc + cap])])
                 be.copy_strided(arena[base_t:base_t + cap_r, d], arena_b[base_t:base_t + cap_r])
-            k7(2)
+            k7(_ops.K7_APPLY)
 
         def body(mode):
             seg = lambda name, fn, feeds=None: self._segment(mode, name, fn, feeds)
@@ -1333,7 +1333,7 @@ class ShardedHMF(object):
 
         def apply():
             be.copy_strided(arena[B_loc:B_loc + n_rows, d], arena_b[B_loc:B_loc + n_rows])
-            k7(2)
+            k7(_ops.K7_APPLY)
 
         def body(mode):
             seg = lambda name, fn, feeds=None: self._segment(mode, name, fn, feeds)
@@ -2158,7 +2158,7 @@ class ShardedHMFBags(ShardedHMF):
 
         def apply():
             be.copy_strided(arena[B_loc:, d], arena_b[B_loc:])
-            k7(2)
+            k7(_ops.K7_APPLY)
 
         def body(mode):
             seg = lambda name, fn, feeds=None: self._segment(mode, name, fn, feeds)
@@ -2636,7 +2636,7 @@ class SeqDataParallel(object):
             for _, g, _ in gs:
                 g.key_off = off
                 off += g.cap
-            tables.append((table, gs, gbufs, rows))
+            tables.append(G.TableEntry(table, gs, gbufs, rows))
         st = dict(preds=preds, tables=tables)
         self._plans[id(plan)] = st
         return st
@@ -2680,8 +2680,8 @@ class SeqDataParallel(object):
                         self._all_gather(src_b, ab)
 
     def gathered_tables(self, plan):
-        """plan.tables with the gathered sites in place of the local ones (same tuple layout)."""
-        return [(table, [g for _, g, _ in gs], gbufs, rows) for table, gs, gbufs, rows in self._state(plan)['tables']]
+        """plan.tables with the gathered sites in place of the local ones (the planner's graph.TableEntry)."""
+        return [e._replace(sites=[g for _, g, _ in e.sites]) for e in self._state(plan)['tables']]
 
 
 
@@ -2700,6 +2700,7 @@ class _ShardView(object):
         self.bias = None if t.bias is None else t.bias[:rows]
         self.bias_acc = None if t.bias_acc is None else t.bias_acc[:rows]
         self.sites = []
+        self.aux_first = self.aux_cnt = None     # (Plan._aux_cnt)
 
 
 class SeqHybridParallel(SeqDataParallel):
@@ -2795,9 +2796,7 @@ class SeqHybridParallel(SeqDataParallel):
             t.E, t.acc, t.bias, t.bias_acc = E, acc, bias, bias_acc
             t.shard = dict(V=V, rows=rows, zero_row=rows, count=int(mine.shape[0]))
             t.view = _ShardView(t, rows)
-            for a in ('aux_cnt', 'aux_first'):
-                if hasattr(t, a):
-                    delattr(t, a)
+            t.aux_first = t.aux_cnt = None
 
     @staticmethod
     def route_rows(full_rows, world):
@@ -3315,7 +3314,7 @@ class SeqHybridParallel(SeqDataParallel):
             for _, g, _, _ in out:
                 g.key_off = off
                 off += g.cap
-            tables.append((table.view, out, gbufs, rows))
+            tables.append(G.TableEntry(table.view, out, gbufs, rows))
         # per-step pool gradients: only their squares are needed -> reduce_scatter (see the class docstring)
         steps = []
         for n in preds:
@@ -3396,7 +3395,7 @@ class SeqHybridParallel(SeqDataParallel):
                     self._a2a(ab[:R], rec['send_b'], rc, sc)
 
     def gathered_tables(self, plan):
-        return [(view, [g for _, g, _, _ in gs], gbufs, rows) for view, gs, gbufs, rows in self._state(plan)['tables']]
+        return [e._replace(sites=[g for _, g, _, _ in e.sites]) for e in self._state(plan)['tables']]
 
     # ---- checkpoints (utils/checkpoint.py ShardedSaver) ------------------------------------------------
     def _checkpoint_arrays(self):

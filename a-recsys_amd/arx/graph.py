@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import os
 import weakref
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -21,6 +22,26 @@ import torch
 from . import ops
 
 KEY_NONE = ops.KEY_NONE
+
+# ---- the records of Plan's K7 planner (tuples: bench.py and the tests unpack and slice them by position) ----
+TableEntry = namedtuple('TableEntry', 'table sites bufs total')   # Plan.tables: a table, its SparseSites, their buffers
+Member = namedtuple('Member', 'entry cat bags')            # a table of the fused pass: its live one-hot / multi-hot sites
+# a bag table riding on the fused pass; index: the group member whose lookups it shares (None = virtual)
+Rider = namedtuple('Rider', 'entry live use_bias virtual index')
+FusedPass = namedtuple('FusedPass', 'group rider')         # `what` of a 'multi' job ('bags' / 'cat': the TableEntry)
+# a pass the step ran: kind 'multi' | 'bags' | 'cat', key = its identity for the side branch, n_hot / n_bag = live
+# one-hot contributions / bag tokens (estimates for _plan_early)
+Job = namedtuple('Job', 'kind what key n_hot n_bag')
+# a step's side branch: keys of the jobs it sorted, its end event, the event between the one-hot and the token half of
+# a rider pass (or None), ring = it sorted the NEXT step's lookups
+Branch = namedtuple('Branch', 'keys done mid ring')
+# ---- the K7 chooser's limits (each measured where Plan._choose_fused / _bags_ok / _find_rider use it) ----
+K7_RANK_SORT_MAX = 8192        # contributions the one-launch LDS rank sort takes
+K7_PAD_MAX = 1 << 19           # padded multi-hot entries a fused pass carries before the pads cost more than launches
+K7_PASS_MAX = 1 << 22          # contributions of one fused / lone one-hot pass
+K7_KEY_BITS = 30               # row bits + 2 table bits of the fused sort key
+K7_GROUP_MAX = 4               # tables of a fused pass (3 beside a virtual one)
+K7_SITES_MAX = 8               # one-hot sites, and multi-hot sites, of a pass
 
 
 # --------------------------------------------------------------------------
@@ -41,6 +62,7 @@ class Table(object):
         self.bias = bias
         self.bias_acc = torch.full_like(bias, acc0) if bias is not None else None
         self.sites = []      # SparseSite list (rebuilt per plan)
+        self.aux_first = self.aux_cnt = None     # K7 scratch per row, allocated on first use (Plan._aux_cnt)
 
 
 class DenseParam(object):
@@ -1009,6 +1031,11 @@ class Plan(object):
         self._early_jobs, self._k7_early, self._k7_stream, self._k7_done_keys = [], None, None, None
         self._k7_fork = None
         self._jobs, self._n_passes = [], 0
+        self._rider_cache = {}         # (map, bag index, rows) -> the bag index by table row (_rider_csr)
+        self._multi_cache = {}         # pass key [+ ring slot] -> descriptors, buffers, workspaces of a fused pass
+        self._csc_cache = {}           # (bag index, max_len, rows) -> ops.BagCSC, the static token order
+        self._mid_waited = False       # this step's main chain took the one-hot sort's event between dU and dI
+        self._k7_virtual = False       # the side branch's rider pass has a virtual entity table (where to wait: _execute)
         # ring mode (prepare_next): the K7 sort half of step t + 1 runs as the side branch of step t's graph
         self.ring_req = False          # set by the model for the coming run()
         self._ring = False             # inside a ring execution / capture
@@ -1062,7 +1089,7 @@ class Plan(object):
             widths = set(s.node.shape[1] for s in sites)
             if len(widths) != 1:
                 raise NotImplementedError("a table used by lookups of different output widths")
-            self.tables.append((table, sites, bufs, total))
+            self.tables.append(TableEntry(table, sites, bufs, total))
 
     def _bind(self):
         """Point the lookup nodes at THIS plan's gradient arena.  Lookup nodes can be shared between
@@ -1149,7 +1176,7 @@ class Plan(object):
         # ~50 us after the feed: 367 us/step; issued after the first lookup: 352 us.  With a
         # two-stage bag pass of its own (C3-MIX, ~135 us of sorts) the early start wins (414 vs 423
         # us); one-hot only (C2): no difference.
-        rider = any(j[0] == 'multi' and j[1][1] is not None for j in self._early_jobs)
+        rider = any(j.kind == 'multi' and j.what.rider is not None for j in self._early_jobs)
         early_after = (1 if rider else 0) if self.train else -1
         if early_after == 0:
             self._early_launch()
@@ -1171,10 +1198,10 @@ class Plan(object):
             self._mid_waited = False
             # (measured: with a VIRTUAL entity table -- MIX -- 350 -> 340 us/step; with a real id table -- HET
             # -- 313 -> 315, so there the dependency stays at the apply)
-            mid_at = 'dI' if getattr(self, '_k7_virtual', False) else 'apply'
-            if (self._k7_early is not None and self._k7_early[2] is not None and self._k7_early[2] != 'ring'
-                    and mid_at == 'dI'):
-                def _mid_wait(ev=self._k7_early[2]):
+            mid_at = 'dI' if self._k7_virtual else 'apply'
+            early = self._k7_early
+            if early is not None and early.mid is not None and not early.ring and mid_at == 'dI':
+                def _mid_wait(ev=early.mid):
                     if not self._mid_waited:
                         torch.cuda.current_stream().wait_event(ev)
                         self._mid_waited = True
@@ -1205,187 +1232,196 @@ class Plan(object):
             if not m.fused:
                 m.scatter(1)                               # reset_mask (:217-218)
 
+    # ---- K7: the lookup-gradient scatter + sparse update.  _choose_fused picks the pass shapes (host only),
+    # _join_early takes the side branch back, _dispatch launches; the records are the namedtuples at the top ----
     def _fusable(self, entry):
-        """(one-hot sites, multi-hot sites) of a table that can join the fused K7 pass."""
-        rt = self.rt
-        table, sites, bufs, total = entry
-        live = [s for s in sites if s.node._grad_written]
-        if not live or rt.force_sort_path or rt.cat_mode != 0:
-            return None
-        if any(s.col_off != 0 for s in live):
+        """The Member (live one-hot sites, live multi-hot sites) a table would be in the fused K7 pass, or None."""
+        live = [s for s in entry.sites if s.node._grad_written]
+        if not live or any(s.col_off != 0 for s in live):
             return None
         if any(s.kind == 'window' for s in live):
             return None                   # a context window: many keys per gradient row, the general pass (_apply_one)
         if self._bags_ok(live):
             return None                   # multi-hot table with its own two-stage pass (_bag_pass)
-        return [s for s in live if s.kind == 'cat'], [s for s in live if s.kind != 'cat']
+        return Member(entry, [s for s in live if s.kind == 'cat'], [s for s in live if s.kind != 'cat'])
 
     def _bags_ok(self, live):
         """Multi-hot lookups of one table take the two-stage pass (merge per entity, then per token:
         arx_sparse_adagrad_bags) once their padded expansion is past the one-launch rank sort --
         below that the step is launch-bound and the contribution-level chain has fewer launches."""
-        rt = self.rt
-        if rt.no_bags or rt.force_sort_path or not live or len(live) > 8:
+        if not live or len(live) > K7_SITES_MAX:
             return False
         s0 = live[0]
         return (all(s.kind == 'mulhot' and s.col_off == 0 and s.maps[0] is s0.maps[0]
                     and s.node.arena is s0.node.arena for s in live)
-                and sum(s.cap for s in live) > 8192 and sum(s.cap for s in live) < (1 << 31) - 1)
+                and K7_RANK_SORT_MAX < sum(s.cap for s in live) < (1 << 31) - 1)
+
+    @staticmethod
+    def _uses_bias(table, sites):
+        """This step's backward wrote a bias gradient for one of `sites`: their pass updates the table's bias."""
+        return table.bias is not None and any(s.node.bias_grad_used for s in sites)
+
+    def _slots(self, table, use_bias):
+        """(E, acc, bias, bias_acc) as a K7 wrapper takes them: no bias cells unless the pass updates them, no
+        accumulators under plain SGD (the kernels then do gradient descent)."""
+        sgd = self.rt.optimizer == 'sgd'
+        return (table.E, None if sgd else table.acc, table.bias if use_bias else None,
+                table.bias_acc if (use_bias and not sgd) else None)
 
     def _apply_sparse(self):
         """One K7 pass per table -- except that tables of equal width that read the same
         gradient arena share ONE pass (arx_sparse_adagrad_cat_multi: the sort key carries the
         table index; multi-hot lookups join as pre-expanded segments): the kernel chains are
         launch-bound, and parallel hipGraph branches did not overlap them (measured)."""
-        rt = self.rt
-        fused = []
-        if not rt.no_multi:
-            cand = []
-            for entry in self.tables:
-                f = self._fusable(entry)
-                if f is not None:
-                    cand.append((entry, f[0], f[1]))
-            virt = None
-            if len(cand) == 1 and not cand[0][2]:
-                virt = self._find_rider([cand[0]], {id(cand[0][0])})     # a bag table that can ride on it?
-            if len(cand) >= 2 or virt is not None:
-                e0, c0, m0 = cand[0]
-                n0 = (c0 + m0)[0].node
-                d0 = e0[0].E.shape[1]
-                group = [(e, c, m) for e, c, m in cand
-                         if e[0].E.shape[1] == d0 and all(x.node.arena is n0.arena for x in c + m)
-                         and all(x.node.arena_b is n0.arena_b for x in c + m)]
-                # multi-hot segments are padded to their worst-case capacity: past ~0.5 M entries
-                # the shared sort/apply pays more for the pads than the saved launches (measured:
-                # C3 B=16384 fused 627 us vs 543 us) -- then only the one-hot tables share a pass
-                if sum(x.cap for _, c, m in group for x in c + m) > (1 << 19):
-                    group = [(e, c, m) for e, c, m in group if not m]
-                rows_bits = max(int(e[0].E.shape[0] - 1).bit_length() for e, _, _ in group) if group else 0
-                n_tot = sum(x.cap for _, c, m in group for x in c + m)
-                # below the LDS rank-sort limit a table's own chain is already 3 launches; fusing
-                # would push the union into the 8-launch radix path (measured slower at B=4096)
-                big = any(sum(x.cap for x in c + m) > 8192 for _, c, m in group)
-                # ... unless the UNION still fits the rank sort: then one 3-launch chain serves all
-                # tables (C1, B=64: two chains of 3 launches -> one)
-                if virt is not None and len(group) == 1:
-                    fused = group            # one one-hot table + the entity ids of a bag table (below)
-                elif ((big or (n_tot <= 8192 and not any(m for _, _, m in group))) and 2 <= len(group) <= 4 and sum(len(c) for _, c, _ in group) <= 8
-                        and sum(len(m) for _, _, m in group) <= 8 and rows_bits + 2 <= 30
-                        and n_tot <= (1 << 22)):
-                    fused = group
-        early = self._k7_early
-        self._k7_early = None
+        group, rider = self._choose_fused()
+        ring_done, split_join = self._join_early()
+        self._dispatch(group, rider, ring_done, split_join)
+
+    def _choose_fused(self):
+        """(group, rider) of this step's fused pass: the Members that share it, table 0 first, and the Rider on it
+        or None; ([], None): no fused pass.  Reads the live sites and the table shapes, launches nothing."""
+        cand = [m for m in map(self._fusable, self.tables) if m is not None]
+        lone = len(cand) == 1 and not cand[0].bags
+        if lone:
+            group = cand                 # one one-hot table: a pass of its own kind only if a bag table rides on it
+        elif len(cand) >= 2:
+            n0 = (cand[0].cat + cand[0].bags)[0].node
+            d0 = cand[0].entry.table.E.shape[1]
+            group = [m for m in cand
+                     if m.entry.table.E.shape[1] == d0 and all(x.node.arena is n0.arena for x in m.cat + m.bags)
+                     and all(x.node.arena_b is n0.arena_b for x in m.cat + m.bags)]
+            # multi-hot segments are padded to their worst-case capacity: past ~0.5 M entries
+            # the shared sort/apply pays more for the pads than the saved launches (measured:
+            # C3 B=16384 fused 627 us vs 543 us) -- then only the one-hot tables share a pass
+            if sum(x.cap for m in group for x in m.cat + m.bags) > K7_PAD_MAX:
+                group = [m for m in group if not m.bags]
+            rows_bits = max(int(m.entry.table.E.shape[0] - 1).bit_length() for m in group) if group else 0
+            n_tot = sum(x.cap for m in group for x in m.cat + m.bags)
+            # below the LDS rank-sort limit a table's own chain is already 3 launches; fusing
+            # would push the union into the 8-launch radix path (measured slower at B=4096)
+            big = any(sum(x.cap for x in m.cat + m.bags) > K7_RANK_SORT_MAX for m in group)
+            # ... unless the UNION still fits the rank sort: then one 3-launch chain serves all
+            # tables (C1, B=64: two chains of 3 launches -> one)
+            if not ((big or (n_tot <= K7_RANK_SORT_MAX and not any(m.bags for m in group)))
+                    and 2 <= len(group) <= K7_GROUP_MAX and sum(len(m.cat) for m in group) <= K7_SITES_MAX
+                    and sum(len(m.bags) for m in group) <= K7_SITES_MAX and rows_bits + 2 <= K7_KEY_BITS
+                    and n_tot <= K7_PASS_MAX):
+                return [], None
+        else:
+            return [], None
+        # a multi-hot table looked up with exactly the lookups of one fused one-hot table (HET: an
+        # item's id row and its bag): it rides on the fused pass -- that table goes first (its
+        # keys sort first), the bag needs no entity sort / merge pass of its own.  Without such a
+        # table (MIX: the id token lives in the bag) the entity ids join the pass as a VIRTUAL
+        # table 0: sorted with the others, runs merged, no rows updated.
+        rider = self._find_rider(group)
+        if rider is None:
+            return ([], None) if lone else (group, None)      # (a lone one-hot table keeps its own pass)
+        if not rider.virtual:
+            group = [group[rider.index]] + group[:rider.index] + group[rider.index + 1:]
+        return group, rider
+
+    def _join_early(self):
+        """Take the side branch of this step (_early_launch) back into the main chain.  Returns (ring_done,
+        split_join): events _dispatch still has to wait for -- ring: the branch sorted the NEXT step's lookups, it
+        only rejoins at the end of the step; mid event: the one-hot sort is waited for here (or was, between the
+        backward GEMMs), the token chain before its apply; plain: the whole branch is joined here."""
+        early, self._k7_early = self._k7_early, None
         self._k7_done_keys = None
-        split_join = None
-        ring_done = None
-        if early is not None and early[2] == 'ring':
-            ring_done = early[1]
-            self._k7_done_keys = early[0]           # this step's sort half ran one step ago (slot _ring_par)
-        elif early is not None:
-            if early[2] is not None:
-                if not getattr(self, '_mid_waited', False):
-                    torch.cuda.current_stream().wait_event(early[2])  # the one-hot sort is done ...
-                split_join = early[1]                                 # ... the token chain is joined before its apply
-            else:
-                torch.cuda.current_stream().wait_event(early[1])      # join the sort branch
-            self._k7_done_keys = early[0]
+        if early is None:
+            return None, None
+        self._k7_done_keys = early.keys
+        if early.ring:
+            return early.done, None                 # this step's sort half ran one step ago (slot _ring_par)
+        if early.mid is None:
+            torch.cuda.current_stream().wait_event(early.done)        # join the sort branch
+            return None, None
+        if not self._mid_waited:
+            torch.cuda.current_stream().wait_event(early.mid)         # the one-hot sort is done ...
+        return None, early.done                                       # ... the token chain is joined before its apply
+
+    def _dispatch(self, group, rider, ring_done, split_join):
+        """The fused pass (whole, its apply half, or -- with a rider sorted ahead -- its two apply quarters with
+        the token chain joined between them), then one pass per remaining table, then next step's side branch."""
+        main = torch.cuda.current_stream()
         self._jobs, self._n_passes = [], 0
-        done = set(id(e) for e, _, _ in fused)
-        rider = self._find_rider(fused, done) if fused else None
-        if rider is not None:
-            # a multi-hot table looked up with exactly the lookups of one fused one-hot table (HET: an
-            # item's id row and its bag): it rides on the fused pass -- that table goes first (its
-            # keys sort first), the bag needs no entity sort / merge pass of its own.  Without such a
-            # table (MIX: the id token lives in the bag) the entity ids join the pass as a VIRTUAL
-            # table 0: sorted with the others, runs merged, no rows updated.
-            gi, bag_entry, bag_live = rider
-            if gi is not None:
-                fused = [fused[gi]] + fused[:gi] + fused[gi + 1:]
-            done.add(id(bag_entry))
-        elif len(fused) == 1:
-            fused = []                       # (a lone one-hot table keeps its own pass)
-            done = set()
-        if fused:
-            key = self._multi_key(fused)
-            bag = None
+        done = set(id(m.entry) for m in group)
+        if group:
+            key = self._multi_key(group)
             if rider is not None:
-                use_bias = bag_entry[0].bias is not None and any(x.node.bias_grad_used for x in bag_live)
-                key = key + ('rider', id(bag_entry), use_bias, gi is None)
-                bag = (bag_entry, bag_live, use_bias, gi is None)
-            phase = 2 if (self._k7_done_keys is not None and key in self._k7_done_keys) else 3
-            if self._ring and phase != 2:
+                done.add(id(rider.entry))
+                key = key + ('rider', id(rider.entry), rider.use_bias, rider.virtual)
+            ahead = self._k7_done_keys is not None and key in self._k7_done_keys
+            if self._ring and not ahead:
                 raise RuntimeError("ring mode: the step's K7 pass differs from the one sorted ahead")
-            if phase == 2 and ring_done is not None and bag is not None:
-                self._apply_multi(fused, phase=7, key=key, bag=bag)
-                self._apply_multi(fused, phase=8, key=key, bag=bag)
-            elif phase == 2 and split_join is not None and bag is not None:
-                self._apply_multi(fused, phase=7, key=key, bag=bag)
-                torch.cuda.current_stream().wait_event(split_join)
-                split_join = None
-                self._apply_multi(fused, phase=8, key=key, bag=bag)
+            if ahead and rider is not None and (ring_done is not None or split_join is not None):
+                self._apply_multi(group, phase=ops.K7_APPLY_HOT, key=key, bag=rider)
+                if split_join is not None:
+                    main.wait_event(split_join)
+                self._apply_multi(group, phase=ops.K7_APPLY_TOKENS, key=key, bag=rider)
             else:
                 if split_join is not None:
-                    torch.cuda.current_stream().wait_event(split_join)
-                    split_join = None
-                self._apply_multi(fused, phase=phase, key=key, bag=bag)
+                    main.wait_event(split_join)
+                self._apply_multi(group, phase=ops.K7_APPLY if ahead else ops.K7_BOTH, key=key, bag=rider)
+            split_join = None
             # size estimate for _plan_early: one-hot sites are all live, a multi-hot site's padded
             # capacity (max_len slots per bag) holds about a third of that in live tokens
-            job = ('multi', (fused, bag), key, sum(x.cap for _, c, _m in fused for x in c)
-                   + sum(x.cap for _, _c, m in fused for x in m) // 3)
-            if bag is not None:
-                job = job + (sum(x.cap for x in bag_live) // 6,)
-            self._jobs.append(job)
+            self._jobs.append(Job('multi', FusedPass(group, rider), key,
+                                  sum(x.cap for m in group for x in m.cat) + sum(x.cap for m in group for x in m.bags) // 3,
+                                  sum(x.cap for x in rider.live) // 6 if rider is not None else 0))
             self._n_passes += 1
         if split_join is not None:
-            torch.cuda.current_stream().wait_event(split_join)
+            main.wait_event(split_join)
         for entry in self.tables:            # the tables that are not part of the fused pass: one pass each
             if id(entry) not in done:
                 self._apply_one(entry)
         if ring_done is not None:
-            torch.cuda.current_stream().wait_event(ring_done)      # rejoin the branch (next step's sorts)
+            main.wait_event(ring_done)       # rejoin the branch (next step's sorts)
         self._plan_early(self._jobs, self._n_passes)
 
-    def _find_rider(self, fused, done):
-        """(index in the fused group, table entry, live sites) of a two-stage multi-hot table whose
-        lookups are exactly the lookups of one fused one-hot table: same id tensors, gradient rows,
-        coefficients and arena (arx_sparse_adagrad_cat_multi_bags), or None.  Index None: no such
-        table, but the bag table's lookups read the group's arena and fit the pass as a virtual
-        table (its entity ids only)."""
-        rt = self.rt
-        if rt.no_rider or any(m for _, _, m in fused):
+    def _find_rider(self, fused):
+        """The Rider of the group `fused`: a two-stage multi-hot table whose lookups are exactly the lookups of
+        one fused one-hot table -- same id tensors, gradient rows, coefficients and arena
+        (arx_sparse_adagrad_cat_multi_bags) -- with that table's index; or, without such a table, a bag table whose
+        lookups read the group's arena and fit the pass as a VIRTUAL table (its entity ids only; index None); or
+        None."""
+        if any(m.bags for m in fused):
             return None
         virtual = None
-        n0 = fused[0][1][0].node
+        n0 = fused[0].cat[0].node
+        done = set(id(m.entry) for m in fused)
         for entry in self.tables:
             if id(entry) in done:
                 continue
-            live = [x for x in entry[1] if x.node._grad_written]
+            live = [x for x in entry.sites if x.node._grad_written]
             if not self._bags_ok(live):
                 continue
+            use_bias = self._uses_bias(entry.table, live)
             for gi, (e, c, _m) in enumerate(fused):
-                if len(c) != len(live) or e[0].E.shape[1] != entry[0].E.shape[1]:
+                if len(c) != len(live) or e.table.E.shape[1] != entry.table.E.shape[1]:
                     continue
                 if any(x.maps[0] is not c[0].maps[0] for x in c):
                     continue
-                if self._rider_csr(c[0].maps[0], live[0].maps[1], live[0].maps[2], int(e[0].E.shape[0])) is None:
+                if self._rider_csr(c[0].maps[0], live[0].maps[1], live[0].maps[2], int(e.table.E.shape[0])) is None:
                     continue                    # (entity -> id-table row must be one-to-one)
                 if all(a.ids_node.value.data_ptr() == b.ids_node.value.data_ptr()
                        and a.ids_node.value.shape == b.ids_node.value.shape and a.node.row0 == b.node.row0
                        and a.coef == b.coef and a.node.arena is b.node.arena and a.node.arena_b is b.node.arena_b
                        for a, b in zip(c, live)):
-                    return gi, entry, live
-            if (virtual is None and len(fused) <= 3 and sum(len(c) for _, c, _ in fused) + len(live) <= 8
-                    and entry[0].E.shape[1] == fused[0][0][0].E.shape[1]
+                    return Rider(entry, live, use_bias, False, gi)
+            if (virtual is None and len(fused) <= K7_GROUP_MAX - 1
+                    and sum(len(m.cat) for m in fused) + len(live) <= K7_SITES_MAX
+                    and entry.table.E.shape[1] == fused[0].entry.table.E.shape[1]
                     and all(x.node.arena is n0.arena and x.node.arena_b is n0.arena_b for x in live)
-                    and int(live[0].maps[2].shape[0]).bit_length() + 2 <= 30 and not rt.no_virtual):
-                virtual = (None, entry, live)
+                    and int(live[0].maps[2].shape[0]).bit_length() + 2 <= K7_KEY_BITS):
+                virtual = Rider(entry, live, use_bias, True, None)
         return virtual
 
     def _rider_csr(self, m, starts, lens, rows):
         """The bag index (starts, lens) of a multi-hot feature re-indexed by the ROW of the one-hot
         table whose lookups it shares (m: entity -> row, None = identity): the sorted keys of the
         fused pass are rows.  None unless m is one-to-one.  Built once per (map, bag index)."""
-        cache = self.__dict__.setdefault('_rider_cache', {})
+        cache = self._rider_cache
         k = (0 if m is None else m.data_ptr(), starts.data_ptr(), lens.data_ptr(), rows)
         if k not in cache:
             out = None
@@ -1404,120 +1440,112 @@ class Plan(object):
         return cache[k]
 
     def _multi_key(self, group):
-        return tuple(id(x) for _, c, m in group for x in c + m) + tuple(
-            bool(e[0].bias is not None and any(x.node.bias_grad_used for x in c + m)) for e, c, m in group)
+        return tuple(id(x) for m in group for x in m.cat + m.bags) + tuple(
+            bool(self._uses_bias(m.entry.table, m.cat + m.bags)) for m in group)
 
-    def _apply_multi(self, group, phase=3, key=None, bag=None, slot=None):
-        """phase 1: contributions + sort (ids only), 2: apply, 3: both -- see _early_sort.
-        bag: (table entry, live sites, use_bias) of a multi-hot table riding on table 0 of the group.
+    def _apply_multi(self, group, phase=ops.K7_BOTH, key=None, bag=None, slot=None):
+        """The fused pass of the Members `group`, or one of its halves / quarters (ops.K7_*) -- see _early_sort.
+        bag: the Rider on table 0 of the group.
         slot (ring mode): one of two buffer sets; its sort half reads the NEXT step's id placeholders."""
         rt = self.rt
         if key is None:
             key = self._multi_key(group)
         if slot is None and self._ring:
-            if phase in (1, 5, 6):
+            if ops.k7_is_sort(phase):
                 slot = 1 - self._ring_par        # the branch: the NEXT step's sort half
-            elif phase in (2, 7, 8):
+            elif ops.k7_is_apply(phase):
                 slot = self._ring_par            # this step's apply, from what the previous step's branch left
             else:
                 raise RuntimeError("ring mode runs the two halves of a K7 pass in different steps (phase %d)" % phase)
         ids_of = (lambda x: x.ids_node.value) if slot is None else (lambda x: x.ids_node.next_value())
-        cache = self.__dict__.setdefault('_multi_cache', {})
         ck = key if slot is None else (key, 'slot', slot)
-        ent = cache.get(ck)
+        ent = self._multi_cache.get(ck)
         if ent is None:
             tables, sites, extra, xsites = [], [], [], []
             t_off = 0
-            if bag is not None and bag[3]:
+            if bag is not None and bag.virtual:
                 # virtual table 0: the bag table's entity lookups (key = entity id)
-                n_ent = int(bag[1][0].maps[2].shape[0])
+                n_ent = int(bag.live[0].maps[2].shape[0])
                 vmap = torch.zeros(n_ent, dtype=torch.int32, device=rt.device)    # per-entity map of the grouped K7 path
                 tables.append((None, None, None, None, vmap, n_ent))
-                for x in bag[1]:
+                for x in bag.live:
                     sites.append((0, None, ids_of(x), x.node.row0, x.coef))
                 t_off = 1
             # which tables update their bias is part of the pass key (_multi_key, taken at apply time): the
             # nodes' bias_grad_used flags are only set once the step's backward ran -- a sort branch that builds
             # this entry runs before it
-            n_ids = sum(len(c) + len(m) for _, c, m in group)
+            n_ids = sum(len(m.cat) + len(m.bags) for m in group)
             key_bias = key[n_ids:n_ids + len(group)]
-            for ti, (e, c, m) in enumerate(group, start=t_off):
-                table = e[0]
-                use_bias = bool(key_bias[ti - t_off])
-                sgd = rt.optimizer == 'sgd'          # no slots: the kernels do plain gradient descent
-                tables.append((table.E, None if sgd else table.acc, table.bias if use_bias else None,
-                               table.bias_acc if (use_bias and not sgd) else None, self._aux_cnt(table)))
-                for x in c:
+            for ti, m in enumerate(group, start=t_off):
+                table = m.entry.table
+                tables.append(self._slots(table, bool(key_bias[ti - t_off])) + (self._aux_cnt(table),))
+                for x in m.cat:
                     sites.append((ti, x.maps[0], ids_of(x), x.node.row0, x.coef))
-                for x in m:
+                for x in m.bags:
                     extra.append((ti, x.cap))
                     xsites.append(x)
             args = ops.MultiCatArgs(tables, sites, extra)
-            n = args.total
-            dev = rt.device
+            n, dev = args.total, rt.device
             ent = dict(args=args, xsites=xsites,
                        keys=torch.empty(n, dtype=torch.int32, device=dev),
                        src=torch.empty(n, dtype=torch.int32, device=dev),
                        coef=torch.empty(n, dtype=torch.float32, device=dev),
                        any_bias=any(t[2] is not None for t in tables),
                        ws=ops.Workspace(dev))       # own workspace: the sorted arrays live in it
-            cache[ck] = ent                         # between the two phases
+            self._multi_cache[ck] = ent             # between the two phases
         args = ent['args']
         # timing-only ablations (WRONG results; tools/r06_abl.sh): ARX_ABL_SKIP_SORT leaves the ids-only half out once it
         # ran eagerly (the applies then walk the first batch's lists), ARX_ABL_SKIP_APPLY leaves the apply half out
-        if _ABL_SKIP_SORT and phase in (1, 5, 6) and self.warm >= 1:
+        if _ABL_SKIP_SORT and ops.k7_is_sort(phase) and self.warm >= 1:
             return
-        if _ABL_SKIP_APPLY and phase in (2, 7, 8) and self.warm >= 1:
+        if _ABL_SKIP_APPLY and ops.k7_is_apply(phase) and self.warm >= 1:
             return
-        if phase & 1:
+        if not ops.k7_is_apply(phase):
             for x, off in zip(ent['xsites'], args.extra_off):   # multi-hot lookups: padded slots, the sort drops the pads
                 ops.bag_expand_padded(x.maps[0], x.maps[1], x.maps[2], ids_of(x), x.max_len,
                                       x.node.row0, x.coef, ent['keys'][off:off + x.cap],
                                       ent['src'][off:off + x.cap], ent['coef'][off:off + x.cap])
-        node0 = (group[0][1] + group[0][2])[0].node
-        if bag is not None:
-            bag_entry, bag_live, bag_bias, bag_virtual = bag
-            bt, s0 = bag_entry[0], bag_live[0]
-            if 'bag_ws' not in ent:
-                ent['bag_ws'] = ops.Workspace(rt.device)     # token lists + merged rows, between the phases
-            sgd = rt.optimizer == 'sgd'
-            if bag_virtual:
-                starts_r, lens_r = s0.maps[1], s0.maps[2]
-            else:
-                starts_r, lens_r = self._rider_csr(group[0][1][0].maps[0], s0.maps[1], s0.maps[2],
-                                                   int(group[0][0][0].E.shape[0]))
-            max_len = max(x.max_len for x in bag_live)
-            if 'csc' not in ent:
-                # static token order of the bags (ops.BagCSC: built once per bag index), flags / slots per pass
-                ent['csc'] = None
-                if rt.csc_mode == '1' or (rt.csc_mode != '0' and bag_virtual):
-                    cache = self.__dict__.setdefault('_csc_cache', {})
-                    ck2 = (s0.maps[0].data_ptr(), starts_r.data_ptr(), lens_r.data_ptr(), max_len, int(bt.E.shape[0]))
-                    if ck2 not in cache:
-                        cache[ck2] = ops.BagCSC(s0.maps[0], starts_r, lens_r, max_len, int(bt.E.shape[0]))
-                    if cache[ck2].ok:
-                        ent['csc'] = (cache[ck2],) + cache[ck2].scratch()
-            if ent['csc'] is not None:
-                # the flag bytes are zero between steps because every sort half that marks (phase 1 / 5) is followed
-                # by the sweep that clears (1 / 6); an eager step that raised in between leaves marks behind, which
-                # the next sweep would take for live pairs -- cleared here (never on the replay path: no Python there)
-                if phase in (1, 3, 5):
-                    if ent.get('csc_marked'):
-                        ent['csc'][1].zero_()
-                    ent['csc_marked'] = phase == 5
-                elif phase == 6:
-                    ent['csc_marked'] = False
-            ops.sparse_adagrad_cat_multi_bags(
-                args, node0.arena, node0.arena_b if (ent['any_bias'] or bag_bias) else None, rt.lr,
-                ent['keys'], ent['src'], ent['coef'], ent['ws'], bt.E, None if sgd else bt.acc,
-                bt.bias if bag_bias else None, bt.bias_acc if (bag_bias and not sgd) else None,
-                s0.maps[0], starts_r, lens_r, max_len, ent['bag_ws'],
-                gscale_dev=rt.clip_coef_dev, phase=phase, bag_aux_cnt=self._aux_cnt(bt), csc=ent['csc'],
-                split=rt.rider_split(ent['csc'] is not None, bool(bag_virtual)))
+        node0 = (group[0].cat + group[0].bags)[0].node
+        if bag is None:
+            ops.sparse_adagrad_cat_multi(args, node0.arena, node0.arena_b if ent['any_bias'] else None,
+                                         rt.lr, ent['keys'], ent['src'], ent['coef'], ent['ws'],
+                                         gscale_dev=rt.clip_coef_dev, phase=phase)
             return
-        ops.sparse_adagrad_cat_multi(args, node0.arena, node0.arena_b if ent['any_bias'] else None,
-                                     rt.lr, ent['keys'], ent['src'], ent['coef'], ent['ws'],
-                                     gscale_dev=rt.clip_coef_dev, phase=phase)
+        bt, s0 = bag.entry.table, bag.live[0]
+        if 'bag_ws' not in ent:
+            ent['bag_ws'] = ops.Workspace(rt.device)     # token lists + merged rows, between the phases
+        if bag.virtual:
+            starts_r, lens_r = s0.maps[1], s0.maps[2]
+        else:
+            starts_r, lens_r = self._rider_csr(group[0].cat[0].maps[0], s0.maps[1], s0.maps[2],
+                                               int(group[0].entry.table.E.shape[0]))
+        max_len = max(x.max_len for x in bag.live)
+        if 'csc' not in ent:
+            # static token order of the bags (ops.BagCSC: built once per bag index), flags / slots per pass
+            ent['csc'] = None
+            if rt.csc_mode == '1' or (rt.csc_mode != '0' and bag.virtual):
+                ck2 = (s0.maps[0].data_ptr(), starts_r.data_ptr(), lens_r.data_ptr(), max_len, int(bt.E.shape[0]))
+                if ck2 not in self._csc_cache:
+                    self._csc_cache[ck2] = ops.BagCSC(s0.maps[0], starts_r, lens_r, max_len, int(bt.E.shape[0]))
+                if self._csc_cache[ck2].ok:
+                    ent['csc'] = (self._csc_cache[ck2],) + self._csc_cache[ck2].scratch()
+        if ent['csc'] is not None:
+            # the flag bytes are zero between steps because every sort half that marks (K7_SORT / K7_SORT_HOT) is
+            # followed by the sweep that clears (K7_SORT / K7_SORT_TOKENS); an eager step that raised in between leaves
+            # marks behind, which the next sweep would take for live pairs -- cleared here (never on the replay path:
+            # no Python there)
+            if phase in (ops.K7_SORT, ops.K7_BOTH, ops.K7_SORT_HOT):
+                if ent.get('csc_marked'):
+                    ent['csc'][1].zero_()
+                ent['csc_marked'] = phase == ops.K7_SORT_HOT
+            elif phase == ops.K7_SORT_TOKENS:
+                ent['csc_marked'] = False
+        ops.sparse_adagrad_cat_multi_bags(
+            args, node0.arena, node0.arena_b if (ent['any_bias'] or bag.use_bias) else None, rt.lr,
+            ent['keys'], ent['src'], ent['coef'], ent['ws'], *self._slots(bt, bag.use_bias),
+            s0.maps[0], starts_r, lens_r, max_len, ent['bag_ws'],
+            gscale_dev=rt.clip_coef_dev, phase=phase, bag_aux_cnt=self._aux_cnt(bt), csc=ent['csc'],
+            split=rt.rider_split(ent['csc'] is not None, bool(bag.virtual)))
 
     def _early_sort(self):
         """The K7 contributions and their sort depend on the lookup ids only: run them on a side
@@ -1529,13 +1557,27 @@ class Plan(object):
         jobs = self._early_jobs
         if not jobs or self.rt.dp is not None:
             return                            # (data-parallel: the apply sorts the GATHERED lookups)
-        rt = self.rt
         if self._k7_stream is None:
-            self._k7_stream = torch.cuda.Stream(device=rt.device)
-        main = torch.cuda.current_stream()
+            self._k7_stream = torch.cuda.Stream(device=self.rt.device)
         ev = torch.cuda.Event()
-        ev.record(main)
+        ev.record(torch.cuda.current_stream())
         self._k7_fork = (ev, jobs)
+
+    def _sort_half(self, job, quarters, between=None):
+        """The ids-only half of a Job.  quarters: a fused pass with a rider runs it as its two quarters, and
+        between(rider) is called after the one-hot one."""
+        if job.kind == 'multi' and job.what.rider is not None and quarters:
+            group, rider = job.what
+            self._apply_multi(group, phase=ops.K7_SORT_HOT, key=job.key, bag=rider)
+            if between is not None:
+                between(rider)
+            self._apply_multi(group, phase=ops.K7_SORT_TOKENS, key=job.key, bag=rider)
+        elif job.kind == 'multi':
+            self._apply_multi(job.what.group, phase=ops.K7_SORT, key=job.key, bag=job.what.rider)
+        elif job.kind == 'bags':
+            self._bag_pass(job.what, job.key, phase=ops.K7_SORT)
+        else:
+            self._cat_pass(job.what, job.key, phase=ops.K7_SORT)
 
     def _early_launch(self):
         """Second half of _early_sort: the branch's kernels.  Issued AFTER the main stream's first
@@ -1544,34 +1586,24 @@ class Plan(object):
         step's first gather started ~17 us after the feed instead of right behind it."""
         if self._k7_fork is None:
             return
-        ev, jobs = self._k7_fork
-        self._k7_fork = None
+        (ev, jobs), self._k7_fork = self._k7_fork, None
         self._k7_stream.wait_event(ev)
+        mid = []
+
+        def between(rider):
+            # a bag table rides on the pass: the one-hot apply only needs the one-hot sort --
+            # the token chain behind it may still run while that apply does (quarter phases)
+            self._k7_virtual = bool(rider.virtual)
+            mid.append(torch.cuda.Event())
+            mid[-1].record(self._k7_stream)
         with torch.cuda.stream(self._k7_stream):
-            mid = None
-            for kind, what, key in jobs:
-                if kind == 'multi' and what[1] is not None and len(jobs) == 1:
-                    # a bag table rides on the pass: the one-hot apply only needs the one-hot sort --
-                    # the token chain behind it may still run while that apply does (quarter phases)
-                    self._apply_multi(what[0], phase=5, key=key, bag=what[1])
-                    self._k7_virtual = bool(what[1][3])
-                    mid = torch.cuda.Event()
-                    mid.record(self._k7_stream)
-                    self._apply_multi(what[0], phase=6, key=key, bag=what[1])
-                elif kind == 'multi':
-                    self._apply_multi(what[0], phase=1, key=key, bag=what[1])
-                elif kind == 'bags':
-                    self._bag_pass(what, key, phase=1)
-                else:
-                    self._cat_pass(what, key, phase=1)
+            for job in jobs:
+                self._sort_half(job, quarters=len(jobs) == 1, between=between)
             done = torch.cuda.Event()
             done.record(self._k7_stream)
-        if self._ring:
-            # the branch sorted the NEXT step's lookups (slot 1 - _ring_par): nothing in this step waits for it
-            # but the end of the step (a captured branch has to rejoin its origin)
-            self._k7_early = (set(k for _, _, k in jobs), done, 'ring')
-            return
-        self._k7_early = (set(k for _, _, k in jobs), done, mid)
+        # ring: the branch sorted the NEXT step's lookups (slot 1 - _ring_par): nothing in this step waits for it
+        # but the end of the step (a captured branch has to rejoin its origin)
+        self._k7_early = Branch(set(j.key for j in jobs), done, mid[-1] if mid and not self._ring else None, self._ring)
 
     def _plan_early(self, jobs, n_passes):
         """Which of this execution's passes may be sorted ahead next time: all of them or none
@@ -1588,11 +1620,9 @@ class Plan(object):
         # tiny steps are bound by the host-side cost of a graph launch, and a graph with a second
         # branch costs more to launch (C1, B=64: 75 -> 103 us per step with the branch)
         lo = int(os.environ.get('ARX_K7_EARLY_MIN', '8192'))
-        n_bags = sum(j[3] for j in jobs if j[0] == 'bags') + sum(j[4] for j in jobs if len(j) > 4)
-        n_hot = sum(j[3] for j in jobs if j[0] != 'bags')
-        ok = (jobs and len(jobs) == n_passes and lo <= n_bags + n_hot and n_hot <= cap
-              and n_bags <= cap_bags)
-        self._early_jobs = [j[:3] for j in jobs] if ok else []
+        n_bags, n_hot = sum(j.n_bag for j in jobs), sum(j.n_hot for j in jobs)
+        ok = jobs and len(jobs) == n_passes and lo <= n_bags + n_hot and n_hot <= cap and n_bags <= cap_bags
+        self._early_jobs = list(jobs) if ok else []
 
     def _cat_pass(self, entry, key, phase):
         """One-hot table, its own pass (arx_sparse_adagrad_cat); key = (live sites, use_bias)."""
@@ -1606,22 +1636,15 @@ class Plan(object):
                 [(s.maps[0], None, s.ids_node.value, s.node.row0, s.coef) for s in live_sites])
             bufs['cat_node0'] = live_sites[0].node
             bufs['cat_ws'] = ops.Workspace(rt.device)      # the sorted arrays live here between the phases
-        if getattr(table, 'aux_first', None) is None:
-            table.aux_first = torch.full((table.E.shape[0],), 2 ** 31 - 1, dtype=torch.int32,
-                                         device=rt.device)
-            table.aux_cnt = torch.zeros((table.E.shape[0],), dtype=torch.int32, device=rt.device)
-        node0 = bufs['cat_node0']
-        mode = rt.cat_mode if rt.cat_mode else {3: 0, 1: 0x10, 2: 0x20}[phase]
-        sgd = rt.optimizer == 'sgd'
-        ops.sparse_adagrad_cat(table.E, None if sgd else table.acc, table.bias if use_bias else None,
-                               table.bias_acc if (use_bias and not sgd) else None, bufs['cat_args'],
+        node0, aux_cnt = bufs['cat_node0'], self._aux_cnt(table)
+        ops.sparse_adagrad_cat(*self._slots(table, use_bias), bufs['cat_args'],
                                node0.arena, node0.arena_b if use_bias else None, rt.lr,
-                               table.aux_first, table.aux_cnt, bufs['hot'], bufs['keys'],
+                               table.aux_first, aux_cnt, bufs['hot'], bufs['keys'],
                                bufs['src'], bufs['coef'], bufs['cat_ws'], gscale_dev=rt.clip_coef_dev,
-                               mode=mode)
+                               mode=ops.K7_CAT_MODE[phase])
 
     def _bag_pass(self, entry, key, phase):
-        """Multi-hot table, two-stage pass (arx_sparse_adagrad_bags); key = (live sites, use_bias)."""
+        """Multi-hot table, two-stage pass (arx_sparse_adagrad_bags); key = ('bags', live sites, use_bias)."""
         rt = self.rt
         table, sites, bufs, total = entry
         live_ids, use_bias = key[1], key[2]
@@ -1633,76 +1656,65 @@ class Plan(object):
             bufs['bag_site0'] = live_sites[0]
             bufs['bag_ws'] = ops.Workspace(rt.device)      # sorted arrays + merged rows live here between the phases
         s0 = bufs['bag_site0']
-        sgd = rt.optimizer == 'sgd'
-        ops.sparse_adagrad_bags(table.E, None if sgd else table.acc, table.bias if use_bias else None,
-                                table.bias_acc if (use_bias and not sgd) else None, s0.maps[0], s0.maps[1],
+        ops.sparse_adagrad_bags(*self._slots(table, use_bias), s0.maps[0], s0.maps[1],
                                 s0.maps[2], bufs['bag_args'], s0.node.arena,
                                 s0.node.arena_b if use_bias else None, rt.lr, bufs['bag_ws'],
                                 gscale_dev=rt.clip_coef_dev, phase=phase, aux_cnt=None)
 
     def _apply_one(self, entry):
+        """The pass of a table outside the fused one: the two-stage bag pass, the lone one-hot pass (both sorted
+        ahead when the side branch ran their sort half), or the general sorted pass over explicit triples."""
         rt = self.rt
-        for table, sites, bufs, total in (entry,):
-            live_sites = [s for s in sites if s.node._grad_written]
-            if not live_sites:
-                continue
-            n_live = sum(s.n for s in live_sites)
-            if self._bags_ok(live_sites):
-                use_bias = table.bias is not None and any(s.node.bias_grad_used for s in live_sites)
-                key = ('bags', tuple(id(s) for s in live_sites), use_bias)
-                early = self._k7_done_keys
-                self._bag_pass(entry, key, 2 if (early is not None and key in early) else 3)
-                # live tokens after the per-entity merge: about a third of the padded slots hold a
-                # token, and Zipf-popular batches repeat entities about twice
-                self._jobs.append(('bags', entry, key, sum(s.cap for s in live_sites) // 6))
-                self._n_passes += 1
-                continue
-            if all(s.kind == 'cat' and s.col_off == 0 for s in live_sites) and n_live <= (1 << 22) \
-                    and len(live_sites) <= 8 and not rt.force_sort_path:
-                # one-hot lookups: own pass (optim_cat.hip); sorted ahead when _early_sort ran it
-                use_bias = table.bias is not None and any(s.node.bias_grad_used for s in live_sites)
-                key = (tuple(id(s) for s in live_sites), use_bias)
-                early = self._k7_done_keys
-                self._cat_pass(entry, key, 2 if (early is not None and key in early and not rt.cat_mode) else 3)
-                if not rt.cat_mode:
-                    self._jobs.append(('cat', entry, key, n_live))
-                self._n_passes += 1
-                continue
-            live = False
-            for s in sites:
-                node = s.node
-                if not node._grad_written:
-                    # this lookup received no gradient this step: leave its keys at NONE
-                    ops.fill_i32(bufs['keys'][s.key_off:s.key_off + s.cap], KEY_NONE)
-                    continue
-                live = True
-                ks = bufs['keys'][s.key_off:s.key_off + s.cap]
-                ss = bufs['src'][s.key_off:s.key_off + s.cap]
-                cs = bufs['coef'][s.key_off:s.key_off + s.cap]
-                if s.kind == 'cat':
-                    ops.sparse_site_onehot(s.maps[0], s.ids_node.value, node.row0, s.coef, ks, ss, cs)
-                elif s.kind == 'window':
-                    ops.sparse_site_window(s.maps[0], s.ids_node.value, s.max_len, node.row0, s.coef, ks, ss, cs)
-                else:
-                    ops.bag_expand_padded(s.maps[0], s.maps[1], s.maps[2], s.ids_node.value, s.max_len,
-                                          node.row0, s.coef, ks, ss, cs)
-            if not live:
-                continue
-            node0 = sites[0].node
-            G = node0.arena[:, sites[0].col_off:] if sites[0].col_off else node0.arena
-            use_bias = table.bias is not None and any(s.node.bias_grad_used for s in sites)
-            sgd = rt.optimizer == 'sgd'
-            ops.sparse_adagrad(table.E, None if sgd else table.acc, table.bias if use_bias else None,
-                               table.bias_acc if (use_bias and not sgd) else None, bufs['keys'], bufs['src'],
-                               bufs['coef'], G, node0.arena_b if use_bias else None, rt.lr, rt.ws,
-                               gscale_dev=rt.clip_coef_dev, n=total, aux_cnt=self._aux_cnt(table))
-            self._n_passes += 1           # a pass that is not sorted ahead: no side branch next time
+        table, sites, bufs, total = entry
+        live_sites = [s for s in sites if s.node._grad_written]
+        if not live_sites:
+            return
+        ahead = self._k7_done_keys or ()
+        n_live = sum(s.n for s in live_sites)
+        use_bias = self._uses_bias(table, live_sites)
+        if self._bags_ok(live_sites):
+            key = ('bags', tuple(id(s) for s in live_sites), use_bias)
+            self._bag_pass(entry, key, ops.K7_APPLY if key in ahead else ops.K7_BOTH)
+            # live tokens after the per-entity merge: about a third of the padded slots hold a
+            # token, and Zipf-popular batches repeat entities about twice
+            self._jobs.append(Job('bags', entry, key, 0, sum(s.cap for s in live_sites) // 6))
+            self._n_passes += 1
+            return
+        if all(s.kind == 'cat' and s.col_off == 0 for s in live_sites) and n_live <= K7_PASS_MAX \
+                and len(live_sites) <= K7_SITES_MAX:
+            # one-hot lookups: own pass (optim_cat.hip); sorted ahead when _early_sort ran it
+            key = (tuple(id(s) for s in live_sites), use_bias)
+            self._cat_pass(entry, key, ops.K7_APPLY if key in ahead else ops.K7_BOTH)
+            self._jobs.append(Job('cat', entry, key, n_live, 0))
+            self._n_passes += 1
+            return
+        for s in sites:
+            node = s.node
+            ks = bufs['keys'][s.key_off:s.key_off + s.cap]
+            ss = bufs['src'][s.key_off:s.key_off + s.cap]
+            cs = bufs['coef'][s.key_off:s.key_off + s.cap]
+            if not node._grad_written:
+                ops.fill_i32(ks, KEY_NONE)     # this lookup received no gradient this step: leave its keys at NONE
+            elif s.kind == 'cat':
+                ops.sparse_site_onehot(s.maps[0], s.ids_node.value, node.row0, s.coef, ks, ss, cs)
+            elif s.kind == 'window':
+                ops.sparse_site_window(s.maps[0], s.ids_node.value, s.max_len, node.row0, s.coef, ks, ss, cs)
+            else:
+                ops.bag_expand_padded(s.maps[0], s.maps[1], s.maps[2], s.ids_node.value, s.max_len,
+                                      node.row0, s.coef, ks, ss, cs)
+        node0 = sites[0].node
+        G = node0.arena[:, sites[0].col_off:] if sites[0].col_off else node0.arena
+        use_bias = self._uses_bias(table, sites)
+        ops.sparse_adagrad(*self._slots(table, use_bias), bufs['keys'], bufs['src'],
+                           bufs['coef'], G, node0.arena_b if use_bias else None, rt.lr, rt.ws,
+                           gscale_dev=rt.clip_coef_dev, n=total, aux_cnt=self._aux_cnt(table))
+        self._n_passes += 1           # a pass that is not sorted ahead: no side branch next time
 
     def _aux_cnt(self, table):
-        """Per-row arrival counters of the window apply (zero between launches)."""
-        if getattr(table, 'aux_cnt', None) is None:
-            table.aux_first = torch.full((table.E.shape[0],), 2 ** 31 - 1, dtype=torch.int32,
-                                         device=self.rt.device)
+        """Per-row scratch of a table, allocated once: aux_cnt, the arrival counters of the window apply (zero
+        between launches), and aux_first (INT_MAX between launches) of the lone one-hot pass."""
+        if table.aux_cnt is None:
+            table.aux_first = torch.full((table.E.shape[0],), 2 ** 31 - 1, dtype=torch.int32, device=self.rt.device)
             table.aux_cnt = torch.zeros((table.E.shape[0],), dtype=torch.int32, device=self.rt.device)
         return table.aux_cnt
 
@@ -1712,8 +1724,7 @@ class Plan(object):
         another id placeholder; hipGraph replay on (ring mode is a property of the captured graph)."""
         rt = self.rt
         return bool(self.train and rt.use_graph and rt.dp is None and self.warm >= 1 and self._early_jobs
-                    and all(j[0] == 'multi' for j in self._early_jobs) and len(self._early_jobs) == 1
-                    and not rt.no_multi)
+                    and all(j.kind == 'multi' for j in self._early_jobs) and len(self._early_jobs) == 1)
 
     def ring_ids(self):
         """The id placeholders the K7 sites read (each once)."""
@@ -1736,12 +1747,8 @@ class Plan(object):
         self._ring, par = True, self._ring_par
         try:
             self._ring_par = 1 - par              # (_apply_multi sorts into 1 - _ring_par)
-            for kind, what, key in self._early_jobs:
-                if what[1] is not None:
-                    self._apply_multi(what[0], phase=5, key=key, bag=what[1])
-                    self._apply_multi(what[0], phase=6, key=key, bag=what[1])
-                else:
-                    self._apply_multi(what[0], phase=1, key=key, bag=what[1])
+            for job in self._early_jobs:
+                self._sort_half(job, quarters=True)
         finally:
             self._ring, self._ring_par = False, par
         self._ring_ready = True
@@ -1857,14 +1864,6 @@ class Runtime(object):
         self.feeds_in_graph = True      # captured plans take them in as graph nodes (False: an eager launch per step)
         self._stage = None              # host-fed placeholders: pinned + device slabs (host_feed)
         self.stage_host_feeds = os.environ.get('ARX_STAGE_FEEDS', '1') != '0'
-        # K7 pass selection overrides (attributes, not environment switches: set them on the runtime object to
-        # force a pass shape that the sizes would not pick; all False / 0 in production)
-        self.force_sort_path = False     # every table through arx_sparse_adagrad (explicit triples)
-        self.cat_mode = 0                # 1: atomic-election one-hot pass (arx_sparse_adagrad_cat mode 1)
-        self.no_multi = False            # one K7 pass per table
-        self.no_bags = False             # contribution-level multi-hot pass
-        self.no_rider = False            # the bag table keeps its own two-stage pass
-        self.no_virtual = False          # ... unless an id table shares its lookups
         # round 6: the riding bag table's tokens in their STATIC order (csrc/csc.hip) instead of a sort per step.
         # Measured (profiles/r06_csc_ab.txt, alternating runs on one box): MIX layout (virtual entity table) 250 ->
         # 236 us per step, HET 231 -> 235..239 -- so: ARX_K7_CSC unset = where the entity table is virtual, 1 = every

@@ -818,10 +818,41 @@ class CatSiteArgs(object):
         self._keep = sites
 
 
+# The halves of a K7 pass (include/arx.h: arx_sparse_adagrad_cat_multi_phase, _cat_multi_bags[_csc], _bags).  The
+# two halves of a pass take the same arguments and the same, otherwise untouched, workspace.
+K7_SORT = 1              # key generation + sort(s): needs the lookup ids only (side stream, under the GEMMs)
+K7_APPLY = 2             # apply: needs the gradient arena
+K7_BOTH = 3              # both halves in one call
+# ... each half split again for a pass with a riding bag table, so the token chain can run under the one-hot apply:
+K7_SORT_HOT = 5          # the one-hot keys + sort (+ the bag offsets; static token order: marks the live pairs)
+K7_SORT_TOKENS = 6       # the token chain (needs 5; static token order: sweeps the marks out)
+K7_APPLY_HOT = 7         # the one-hot apply, merged entity rows as its side output (needs 5 and the arena)
+K7_APPLY_TOKENS = 8      # the token apply (needs 6 and 7)
+# the rider's apply form, OR-ed into every phase of a pass (0: the process default ARX_K7_RIDER):
+K7_FORM_SPLIT = 0x100    # `split`: table 0's runs alone, then ONE launch with the token runs and the other tables' runs
+K7_FORM_WIN = 0x200      # `win`: window + finish launches, then the token apply
+# the halves of the lone one-hot pass (arx_sparse_adagrad_cat's `mode`):
+K7_CAT_BOTH = 0          # the whole sorted pass
+K7_CAT_SORT = 0x10       # its first half: contributions + sort (ids only)
+K7_CAT_APPLY = 0x20      # its second half: apply
+K7_CAT_MODE = {K7_BOTH: K7_CAT_BOTH, K7_SORT: K7_CAT_SORT, K7_APPLY: K7_CAT_APPLY}     # pass phase -> `mode`
+
+
+def k7_is_sort(phase):
+    """phase is a sort half (or a part of one): it reads the lookup ids only."""
+    return phase in (K7_SORT, K7_SORT_HOT, K7_SORT_TOKENS)
+
+
+def k7_is_apply(phase):
+    """phase is an apply half (or a part of one): it reads the gradient arena and the sort half's lists."""
+    return phase in (K7_APPLY, K7_APPLY_HOT, K7_APPLY_TOKENS)
+
+
 def sparse_adagrad_cat(E, acc, bias, bias_acc, site_args, G, Gb, lr_dev, aux_first, aux_cnt,
-                       aux_hot, keys_buf, src_buf, coef_buf, ws, gscale_dev=None, mode=0):
+                       aux_hot, keys_buf, src_buf, coef_buf, ws, gscale_dev=None, mode=K7_CAT_BOTH):
     """sites: list of (cat_map|None, _, ids, row_base, coef) packed in CatSiteArgs.
-    mode 0: fused keygen + LDS sort + Adagrad passes (n <= 16384) else atomic election."""
+    mode K7_CAT_BOTH: fused keygen + LDS sort + Adagrad passes (n <= 16384) else atomic election; K7_CAT_SORT /
+    K7_CAT_APPLY: its halves."""
     wsp, wsn = ws.get(_lib.lib.arx_sparse_adagrad_workspace_bytes(site_args.total))
     call("arx_sparse_adagrad_cat", _p(E), _p(acc), _p(bias), _p(bias_acc), int(E.shape[0]),
          int(E.shape[1]), site_args.n, site_args.cat_map, site_args.ids, site_args.count,
@@ -870,8 +901,8 @@ class MultiCatArgs(object):
         self._keep = (tables, sites)
 
 
-def sparse_adagrad_cat_multi(args, G, Gb, lr_dev, keys_buf, src_buf, coef_buf, ws, gscale_dev=None, phase=3):
-    """phase 1: key generation + sort (needs the ids only), phase 2: apply, 3: both.  The two
+def sparse_adagrad_cat_multi(args, G, Gb, lr_dev, keys_buf, src_buf, coef_buf, ws, gscale_dev=None, phase=K7_BOTH):
+    """phase K7_SORT: key generation + sort (needs the ids only), K7_APPLY: apply, K7_BOTH: both.  The two
     halves must use the same workspace object, untouched in between."""
     wsp, wsn = ws.get(_lib.lib.arx_sparse_adagrad_workspace_bytes(args.total))
     call("arx_sparse_adagrad_cat_multi_phase", int(phase), args.nt, args.E, args.acc, args.bias,
@@ -883,11 +914,12 @@ def sparse_adagrad_cat_multi(args, G, Gb, lr_dev, keys_buf, src_buf, coef_buf, w
 
 def sparse_adagrad_cat_multi_bags(args, G, Gb, lr_dev, keys_buf, src_buf, coef_buf, ws, bag_E, bag_acc,
                                   bag_bias, bag_bias_acc, vals, starts, lens, max_len, bag_ws,
-                                  gscale_dev=None, phase=3, bag_aux_cnt=None, csc=None, split=None):
+                                  gscale_dev=None, phase=K7_BOTH, bag_aux_cnt=None, csc=None, split=None):
     """arx_sparse_adagrad_cat_multi with a multi-hot table riding on it: the lookups of one-hot
     table 0 are also the lookups of the bags of table bag_E -- an item's id row and its multi-hot
     attribute (HET layout); starts / lens are indexed by the ROW of table 0 (arx.h).  Same phases as
-    sparse_adagrad_cat_multi; `ws` and `bag_ws` must be the same objects for both halves."""
+    sparse_adagrad_cat_multi, or the quarters K7_SORT_HOT .. K7_APPLY_TOKENS; `ws` and `bag_ws` must be the same
+    objects for all of them."""
     assert args.nx == 0
     n0 = sum(int(args.count[q]) for q in range(args.ns) if int(args.site_table[q]) == 0)
     wsp, wsn = ws.get(_lib.lib.arx_sparse_adagrad_workspace_bytes(args.total))
@@ -895,7 +927,7 @@ def sparse_adagrad_cat_multi_bags(args, G, Gb, lr_dev, keys_buf, src_buf, coef_b
     # csc: (BagCSC, flags, slot_of) -- the table's static token order (no expansion, no token sort in the step)
     cs, flags, slot_of = csc if csc is not None else (None, None, None)
     # split: this pass's apply form (True `split`, False `win`, None: the process default ARX_K7_RIDER) -- arx.h
-    form = 0 if split is None else (0x100 if split else 0x200)
+    form = 0 if split is None else (K7_FORM_SPLIT if split else K7_FORM_WIN)
     call("arx_sparse_adagrad_cat_multi_bags_csc", int(phase) | form, args.nt, args.E, args.acc, args.bias,
          args.bias_acc, args.rows, args.cnt, args.d, args.ns, args.site_table, args.cat_map, args.ids,
          args.count, args.row_base, args.coef, _p(G), _ld(G), _p(Gb), _p(lr_dev), _p(gscale_dev),
@@ -980,9 +1012,9 @@ class BagSiteArgs(object):
 
 
 def sparse_adagrad_bags(E, acc, bias, bias_acc, vals, starts, lens, site_args, G, Gb, lr_dev, ws,
-                        gscale_dev=None, phase=3, aux_cnt=None):
-    """Multi-hot lookups of one table: merge per entity, then per token (arx.h).  phase 1: both
-    sorts (ids only), 2: merge + apply, 3: both; same `ws` for both halves."""
+                        gscale_dev=None, phase=K7_BOTH, aux_cnt=None):
+    """Multi-hot lookups of one table: merge per entity, then per token (arx.h).  phase K7_SORT: both
+    sorts (ids only), K7_APPLY: merge + apply, K7_BOTH: both; same `ws` for both halves."""
     d = int(E.shape[1])
     wsp, wsn = ws.get(_lib.lib.arx_sparse_adagrad_bags_workspace_bytes(site_args.total, site_args.max_len, d))
     call("arx_sparse_adagrad_bags", int(phase), _p(E), _p(acc), _p(bias), _p(bias_acc), int(E.shape[0]), d,

@@ -55,12 +55,9 @@ PROTOTYPES = {
                                   f32, f32p, i64, f32p, i64, i64, vp]),
     "arx_lookup_multi": (cint, [cint] +[C.POINTER(vp)] * 9 + [C.POINTER(i64), cint, C.POINTER(f32), C.POINTER(vp),
                                 C.POINTER(i64), C.POINTER(vp), vp]),
-    "arx_gather_onehot_multi": (cint, [cint, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                       C.POINTER(i64), cint, C.POINTER(f32), C.POINTER(vp), C.POINTER(i64),
-                                       C.POINTER(vp), vp]),
-    "arx_gather_onehot_multi_ld": (cint, [cint, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
-                                          C.POINTER(vp), C.POINTER(i64), cint, C.POINTER(f32), C.POINTER(vp), C.POINTER(i64),
-                                          C.POINTER(vp), C.POINTER(i64), vp]),
+    "arx_gather_onehot_multi": (cint, [cint, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(vp),
+                                       C.POINTER(vp), C.POINTER(i64), cint, C.POINTER(f32), C.POINTER(vp), C.POINTER(i64),
+                                       C.POINTER(vp), C.POINTER(i64), vp]),
     "arx_gather_mulhot_mean_fwd": (cint, [f32p, f32p, i32p, i32p, i32p, i32p, i64, cint, f32, cint,
                                           f32p, i64, f32p, vp]),
     "arx_dot_score_fwd": (cint, [f32p, i64, f32p, i64, f32p, i64, cint, f32p, vp]),
@@ -76,10 +73,8 @@ PROTOTYPES = {
     "arx_gemm_f32_workspace_bytes": (sz, [i64, i64, i64]),
     "arx_gemm_nt_bx6_workspace_bytes": (sz, [i64, i64]),
     "arx_gemm_nt_bx6": (cint, [i64, i64, i64, f32p, i64, f32p, i64, f32p, f32p, i64, vp, sz, vp]),
-    "arx_gemm_f32": (cint, [cint, cint, i64, i64, i64, f32, f32p, i64, f32p, i64, f32, f32p, i64,
-                            f32p, vp, sz, vp]),
-    "arx_gemm_f32_rowsum": (cint, [cint, cint, i64, i64, i64, f32, f32p, i64, f32p, i64, f32, f32p,
-                                   i64, f32p, f32p, vp, sz, vp]),
+    "arx_gemm_f32": (cint, [cint, cint, i64, i64, i64, f32, f32p, i64, f32p, i64, f32, f32p,
+                            i64, f32p, f32p, vp, sz, vp]),
     "arx_gemm_f32_tn_pair_workspace_bytes": (sz, [i64, i64, i64]),
     "arx_gemm_f32_tn_pair": (cint, [i64, i64, i64, i64, f32p, i64, f32p, i64, f32p, i64, i64, f32p, i64, f32p,
                                     vp, sz, vp]),
@@ -119,18 +114,12 @@ PROTOTYPES = {
     "arx_mw_scorer_state_bytes": (sz, [i64, i64, cint]),
     "arx_mw_scorer_state_layout": (cint, [i64, i64, cint, C.POINTER(i64)]),
     "arx_mw_scorer_fwd": (cint, [f32p, i64, f32p, i64, f32p, f32p, i64, f32p, i64, cint, i32p, i32p, i32p, i32p,
-                                 i64, f32, f32p, i64, i64, f32p, f32p, f32p, i64, f32p, i64, f32p, i64, vp, sz, vp]),
-    "arx_mw_scorer_fwd_phases": (cint, [f32p, i64, f32p, i64, f32p, f32p, i64, f32p, i64, cint, i32p, i32p, i32p, i32p,
-                                        i64, f32, f32p, i64, i64, f32p, f32p, f32p, i64, f32p, i64, f32p, i64, vp, sz,
-                                        cint, vp]),
-    "arx_mw_scorer_fwd_seqw": (cint, [f32p, i64, f32p, i64, f32p, f32p, i64, f32p, i64, cint, i32p, i32p, i32p, i32p,
-                                      i64, f32, f32p, f32p, i64, i64, i64, f32p, f32p, f32p, i64, f32p, i64, f32p, i64,
-                                      vp, sz, cint, vp]),
-    "arx_mw_scorer_bwd_di_loss": (cint, [i64, i64, cint, vp, i64, f32, f32p, i64, f32p, f32p, f32p, f32p, f32, f32p,
-                                         f32p, vp, sz, vp]),
+                                 i64, f32, f32p, f32p, i64, i64, i64, f32p, f32p, f32p, i64, f32p, i64, f32p, i64,
+                                 vp, sz, cint, vp]),
     "arx_mw_scorer_bwd_du": (cint, [i64, i64, cint, vp, f32, f32p, i64, vp]),
     "arx_mw_scorer_bwd_di_workspace_bytes": (sz, [i64, i64, cint, i64]),
-    "arx_mw_scorer_bwd_di": (cint, [i64, i64, cint, vp, i64, f32, f32p, i64, f32p, f32p, f32p, vp, sz, vp]),
+    "arx_mw_scorer_bwd_di": (cint, [i64, i64, cint, vp, i64, f32, f32p, i64, f32p, f32p, f32p, f32p, f32, f32p,
+                                    f32p, vp, sz, vp]),
     "arx_gemm_bt_bx6_supported": (cint, [i64, i64, i64]),
     "arx_gemm_bt_bx6": (cint, [i64, i64, i64, f32p, i64, f32p, i64, f32, f32p, i64, vp]),
     "arx_mce_scorer_supported": (cint, [i64, i64, cint]),
@@ -139,53 +128,35 @@ PROTOTYPES = {
                                   i64, f32, f32p, f32p, i64, i64, i64, f32p, f32p, f32p, i64, f32p, i64, f32p, i64,
                                   vp, sz, cint, vp]),
     "arx_mce_scorer_bwd_di_workspace_bytes": (sz, [i64, i64, cint, i64]),
-    "arx_mce_scorer_bwd_di_loss": (cint, [i64, i64, cint, vp, f32p, i64, i64, f32, f32p, i64, f32p, f32p, f32p, f32p, f32,
-                                          f32p, f32p, vp, sz, vp]),
-    "arx_sample_wor_workspace_bytes": (sz, [i64]),
-    "arx_sample_wor_keys_workspace_bytes": (sz, [i64, i64, f32]),
-    "arx_sample_wor": (cint, [f32p, i64, i64, u64, u64, i32p, vp, sz, vp]),
-    "arx_sample_wor_capped": (cint, [f32p, i64, i64, u64, u64, f32, i32p, vp, sz, vp]),
-    "arx_sample_wor_keys": (cint, [f32p, i64, i64, u64, u64, f32, i32p, f32p, vp, sz, vp]),
+    "arx_mce_scorer_bwd_di": (cint, [i64, i64, cint, vp, f32p, i64, i64, f32, f32p, i64, f32p, f32p, f32p, f32p, f32,
+                                     f32p, f32p, vp, sz, vp]),
+    "arx_sample_wor_workspace_bytes": (sz, [i64, i64, f32]),
+    "arx_sample_wor": (cint, [f32p, i64, i64, u64, u64, f32, i32p, f32p, vp, sz, vp]),
     "arx_loss_rs_fwdbwd": (cint, [f32p, i64, i32p, u8p, i64, i32p, i32p, i32p, i32p, i64, cint, cint,
                                   f32, f32, f32p, i64, i64, f32p, f32p, i64, vp]),
     "arx_loss_ce_fwdbwd": (cint, [f32p, i64, i32p, f32, f32p, i64, i64, f32p, f32p, i64, vp]),
     "arx_row_logsumexp": (cint, [f32p, i64, i64, i64, f32p, vp]),
     "arx_loss_warp_eval": (cint, [f32p, i64, i32p, u8p, i64, i64, i64, i64, f32p, i32p, vp]),
     "arx_sparse_adagrad_workspace_bytes": (sz, [i64]),
-    "arx_sparse_adagrad": (cint, [f32p, f32p, f32p, f32p, cint, i32p, i32p, f32p, i64, f32p, i64,
-                                  f32p, f32p, f32p, cint, vp, sz, vp]),
-    "arx_sparse_adagrad_ticket": (cint, [f32p, f32p, f32p, f32p, cint, i32p, i32p, f32p, i64, f32p,
-                                         i64, f32p, f32p, f32p, cint, i32p, vp, sz, vp]),
+    "arx_sparse_adagrad": (cint, [f32p, f32p, f32p, f32p, cint, i32p, i32p, f32p, i64, f32p,
+                                  i64, f32p, f32p, f32p, cint, i32p, vp, sz, vp]),
     "arx_sparse_adagrad_cat": (cint, [f32p, f32p, f32p, f32p, i64, cint, cint, C.POINTER(vp),
                                       C.POINTER(vp), C.POINTER(i64), C.POINTER(i32),
                                       C.POINTER(f32), f32p, i64, f32p, f32p, f32p, i32p, i32p,
                                       i32p, i64, i32p, i32p, f32p, cint, vp, sz, vp]),
-    "arx_sparse_adagrad_cat_multi": (cint, [cint, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+    "arx_sparse_adagrad_cat_multi": (cint, [cint, cint, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                             C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), cint, cint,
                                             C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
                                             C.POINTER(i64), C.POINTER(i32), C.POINTER(f32), f32p, i64,
                                             f32p, f32p, f32p, i32p, i32p, f32p, cint, C.POINTER(i64),
                                             C.POINTER(i32), vp, sz, vp]),
-    "arx_sparse_adagrad_cat_multi_phase": (cint, [cint, cint, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                                  C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), cint, cint,
-                                                  C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
-                                                  C.POINTER(i64), C.POINTER(i32), C.POINTER(f32), f32p, i64,
-                                                  f32p, f32p, f32p, i32p, i32p, f32p, cint, C.POINTER(i64),
-                                                  C.POINTER(i32), vp, sz, vp]),
     "arx_sparse_adagrad_cat_multi_bags": (cint, [cint, cint, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
                                                  C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), cint, cint,
                                                  C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
                                                  C.POINTER(i64), C.POINTER(i32), C.POINTER(f32), f32p, i64,
                                                  f32p, f32p, f32p, i32p, i32p, f32p, vp, sz,
                                                  f32p, f32p, f32p, f32p, i64, i32p, i32p, i32p, cint, i32p,
-                                                 vp, sz, vp]),
-    "arx_sparse_adagrad_cat_multi_bags_csc": (cint, [cint, cint, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
-                                                     C.POINTER(vp), C.POINTER(i64), C.POINTER(vp), cint, cint,
-                                                     C.POINTER(i32), C.POINTER(vp), C.POINTER(vp),
-                                                     C.POINTER(i64), C.POINTER(i32), C.POINTER(f32), f32p, i64,
-                                                     f32p, f32p, f32p, i32p, i32p, f32p, vp, sz,
-                                                     f32p, f32p, f32p, f32p, i64, i32p, i32p, i32p, cint, i32p,
-                                                     vp, sz, i32p, i32p, vp, i32p, i64, vp]),
+                                                 vp, sz, i32p, i32p, vp, i32p, i64, vp]),
     "arx_sparse_adagrad_bags_workspace_bytes": (sz, [i64, cint, cint]),
     "arx_sparse_adagrad_bags": (cint, [cint, f32p, f32p, f32p, f32p, i64, cint, i32p, i32p, i32p, i64, cint,
                                        cint, C.POINTER(vp), C.POINTER(i64), C.POINTER(i32), C.POINTER(f32),
@@ -251,8 +222,7 @@ PROTOTYPES = {
                                      i32p, i32p, i64, i32p, i32p, i64, f32p, i32p, vp]),
     "arx_eval_merge_shards": (cint, [cint, f32p, i32p, f32p, i64, cint, f32p, i32p, vp]),
     "arx_lstm_fwd": (cint, [f32p, f32p, f32p, i64, i64, cint, cint, f32, f32p, f32p, f32p, vp]),
-    "arx_lstm_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, i64, i64, cint, cint, f32p, vp]),
-    "arx_lstm_bwd_wxt": (cint, [f32p, f32p, f32p, f32p, f32p, i64, i64, cint, cint, f32p, f32p, vp]),
+    "arx_lstm_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, i64, i64, cint, cint, f32p, f32p, vp]),
     "arx_seq_weights": (cint, [f32p, i64, i64, f32p, vp]),
     "arx_capture_begin": (cint, [vp]),
     "arx_capture_end": (cint, [vp, C.POINTER(vp)]),
@@ -291,7 +261,7 @@ _NO_CHECK = ("arx_last_error", "arx_version", "arx_csr_expand_workspace_bytes",
              "arx_col_sum_workspace_bytes",
              "arx_gemm_f32_workspace_bytes", "arx_gemm_f32_tn_pair_workspace_bytes",
              "arx_sparse_adagrad_workspace_bytes",
-             "arx_sample_wor_workspace_bytes", "arx_sample_wor_keys_workspace_bytes",
+             "arx_sample_wor_workspace_bytes",
              "arx_gemm_nt_bx6_workspace_bytes", "arx_reduce_scratch_bytes", "arx_mw_scorer_supported",
              "arx_mw_scorer_state_bytes", "arx_mw_scorer_bwd_di_workspace_bytes", "arx_mce_scorer_supported",
              "arx_mce_scorer_state_bytes", "arx_mce_scorer_bwd_di_workspace_bytes", "arx_gemm_bt_bx6_supported")

@@ -3650,7 +3650,7 @@ def bench_run(args, world, rank, local_rank, init_pg=True):
         route_ms.append((time.time() - t_r) * 1e3)
     # Shared negative pool: ONE draw of S items without replacement with p ~ count^0.5 over ALL items
     # (prepare_train.py:7-35 sample_items over item_frequency, run_hmf.py:62 power = 0.5): every rank
-    # races its own shard on device (arx_sample_wor_keys), the ranks exchange their S best (key, id)
+    # races its own shard on device (arx_sample_wor), the ranks exchange their S best (key, id)
     # pairs (8 KB each) and keep the S smallest keys of the union (draw_global_pool) -- inside the
     # timed region, every n_resample steps.  Setup: global interaction counts of the owned items (one
     # reduce_scatter).

@@ -47,9 +47,6 @@ K7_SITES_MAX = 8               # one-hot sites, and multi-hot sites, of a pass
 # --------------------------------------------------------------------------
 # parameters
 # --------------------------------------------------------------------------
-_ABL_SKIP_SORT = bool(os.environ.get('ARX_ABL_SKIP_SORT'))
-_ABL_SKIP_APPLY = bool(os.environ.get('ARX_ABL_SKIP_APPLY'))
-
 class Table(object):
     """One attribute embedding table [Vf,d] (+ optional bias [Vf]) with its
     Adagrad accumulators (TF initial_accumulator_value = 0.1)."""
@@ -768,7 +765,7 @@ def _bl_forward_gemm_fused(self, bl, rw, uid, ptr, items, i2s):
         if dt.data_ptr() != te.bias_grad.data_ptr():
             raise RuntimeError("target-score gradient is expected to alias the bias gradient rows")
     # the scalar the step reports, gscale * sum_r row_w_r * loss_r, comes out of the backward's reduce launch
-    # (arx_mw_scorer_bwd_di_loss) whenever that launch exists, i.e. the pool trains
+    # (arx_mw_scorer_bwd_di) whenever that launch exists, i.e. the pool trains
     sink = self.loss_sink
     self.loss_in_scorer = sink is not None and bool(pool.train_tables)
     # the sequence model's example weights, normalised over time by the scorer's first launch (SeqWeights.forward
@@ -1494,12 +1491,6 @@ class Plan(object):
                        ws=ops.Workspace(dev))       # own workspace: the sorted arrays live in it
             self._multi_cache[ck] = ent             # between the two phases
         args = ent['args']
-        # timing-only ablations (WRONG results; tools/r06_abl.sh): ARX_ABL_SKIP_SORT leaves the ids-only half out once it
-        # ran eagerly (the applies then walk the first batch's lists), ARX_ABL_SKIP_APPLY leaves the apply half out
-        if _ABL_SKIP_SORT and ops.k7_is_sort(phase) and self.warm >= 1:
-            return
-        if _ABL_SKIP_APPLY and ops.k7_is_apply(phase) and self.warm >= 1:
-            return
         if not ops.k7_is_apply(phase):
             for x, off in zip(ent['xsites'], args.extra_off):   # multi-hot lookups: padded slots, the sort drops the pads
                 ops.bag_expand_padded(x.maps[0], x.maps[1], x.maps[2], ids_of(x), x.max_len,

@@ -235,7 +235,7 @@ class SeqWeights(G.Node):
 
     def forward(self, train):
         if train and self.folded_into is not None:
-            self.alloc_value()        # written by arx_mw_scorer_fwd_seqw (graph._bl_forward_gemm_fused)
+            self.alloc_value()        # written by arx_mw_scorer_fwd (graph._bl_forward_gemm_fused)
             return
         ops.seq_weights(self.inputs[0].value, self.L, self.B, self.alloc_value())
 

@@ -328,7 +328,7 @@ class GatherSet(object):
 
 
 def gather_onehot_multi(gs):
-    call("arx_gather_onehot_multi_ld", gs.n, gs.E, gs.bias, gs.ldbi, gs.cat_map, gs.ids, gs.cnt, gs.d, gs.scale, gs.out,
+    call("arx_gather_onehot_multi", gs.n, gs.E, gs.bias, gs.ldbi, gs.cat_map, gs.ids, gs.cnt, gs.d, gs.scale, gs.out,
          gs.ldo, gs.bias_out, gs.ldb, _stream())
 
 
@@ -482,7 +482,7 @@ def gemm(A, B, C, ws, transA=False, transB=False, alpha=1.0, beta=0.0, col_bias=
             and a_rowsum is None and M >= 4096):
         return gemm_nt_bx6(A, B, C, col_bias)
     wsp, wsn = ws.get(_lib.lib.arx_gemm_f32_workspace_bytes(M, N, K))
-    call("arx_gemm_f32_rowsum", int(bool(transA)), int(bool(transB)), M, N, K, float(alpha), _p(A),
+    call("arx_gemm_f32", int(bool(transA)), int(bool(transB)), M, N, K, float(alpha), _p(A),
          _ld(A), _p(B), _ld(B), float(beta), _p(C), _ld(C), _p(col_bias), _p(a_rowsum), wsp, wsn,
          _stream())
     return C
@@ -640,9 +640,9 @@ class MwScorer(object):
 
     def fwd(self, U, P, pbias, T, tbias, user_ids, pos_ptr, pos_items, item2slot, batch_loss, tscore_out, dtscore,
             dU, dT, gscale, row_w=None, mask_rows=0, phases=7, seq_w=None, seq_rows=0):
-        """phases: 1 pool planes + hit lists, 2 hinge GEMM, 4 row kernel (arx_mw_scorer_fwd_phases).  seq_w (the
+        """phases: 1 pool planes + hit lists, 2 hinge GEMM, 4 row kernel (arx_mw_scorer_fwd).  seq_w (the
         sequence model's raw example weights, [L * seq_rows]): row_w is WRITTEN by phase 1 (normalised over time)."""
-        call("arx_mw_scorer_fwd_seqw", _p(U), _ld(U), _p(P), _ld(P), _p(pbias), _p(T), _ld(T), _p(tbias),
+        call("arx_mw_scorer_fwd", _p(U), _ld(U), _p(P), _ld(P), _p(pbias), _p(T), _ld(T), _p(tbias),
              int(tbias.stride(0)) if tbias is not None else 1, self.d, _p(user_ids), _p(pos_ptr), _p(pos_items),
              _p(item2slot), int(mask_rows), float(gscale), _p(row_w), _p(seq_w), int(seq_rows), self.B, self.S,
              _p(batch_loss), _p(tscore_out), _p(dtscore), int(dtscore.stride(0)) if dtscore is not None else 1,
@@ -662,7 +662,7 @@ class MwScorer(object):
             wsp, wsn = self.ws.get(_lib.lib.arx_mw_scorer_bwd_di_workspace_bytes(self.B, self.S, self.d,
                                                                                  int(step_rows)))
         bl, gs, rw, out = loss if loss is not None else (None, 0.0, None, None)
-        call("arx_mw_scorer_bwd_di_loss", self.B, self.S, self.d, _p(self.state), int(step_rows), float(beta), _p(dI),
+        call("arx_mw_scorer_bwd_di", self.B, self.S, self.d, _p(self.state), int(step_rows), float(beta), _p(dI),
              _ld(dI), _p(db), _p(dI_steps), _p(db_steps), _p(bl), float(gs), _p(rw), _p(out), wsp, wsn, _stream())
 
 
@@ -720,7 +720,7 @@ class MceScorer(object):
     def bwd_dI(self, dI, db=None, beta=0.0, step_rows=0, dI_steps=None, db_steps=None, loss=None):
         wsp, wsn = self.ws.get(_lib.lib.arx_mce_scorer_bwd_di_workspace_bytes(self.B, self.S, self.d, int(step_rows)))
         bl, gs, rw, out = loss if loss is not None else (None, 0.0, None, None)
-        call("arx_mce_scorer_bwd_di_loss", self.B, self.S, self.d, _p(self.state), _p(self._pbias), self._mask_rows,
+        call("arx_mce_scorer_bwd_di", self.B, self.S, self.d, _p(self.state), _p(self._pbias), self._mask_rows,
              int(step_rows),
              float(beta), _p(dI), _ld(dI), _p(db), _p(dI_steps), _p(db_steps), _p(bl), float(gs), _p(rw), _p(out),
              wsp, wsn, _stream())
@@ -743,11 +743,11 @@ def item_frequency(item_ids, n_items, counts, weights=None, total=0, power=0.5):
 
 def sample_wor(weights, S, seed, counter, out, ws, key_cap=0.0, out_keys=None):
     """Weighted sampling without replacement on device (exponential race); out: int32 [S].
-    key_cap > 0: pre-filter for very large item sets (arx_sample_wor_capped).  out_keys (float32
-    [S]): the race keys of the drawn items, ascending (arx_sample_wor_keys)."""
+    key_cap > 0: pre-filter for very large item sets.  out_keys (float32 [S]): the race keys of
+    the drawn items, ascending (arx_sample_wor)."""
     n = int(weights.shape[0])
-    wsp, wsn = ws.get(_lib.lib.arx_sample_wor_keys_workspace_bytes(n, int(S), float(key_cap)))
-    call("arx_sample_wor_keys", _p(weights), n, int(S), int(seed) & (2 ** 64 - 1),
+    wsp, wsn = ws.get(_lib.lib.arx_sample_wor_workspace_bytes(n, int(S), float(key_cap)))
+    call("arx_sample_wor", _p(weights), n, int(S), int(seed) & (2 ** 64 - 1),
          int(counter) & (2 ** 64 - 1), float(key_cap), _p(out), _p(out_keys), wsp, wsn, _stream())
     return out
 
@@ -797,7 +797,7 @@ def sparse_adagrad(E, acc, bias, bias_acc, keys, src, coef, G, Gb, lr_dev, ws, g
     """aux_cnt (int32[table rows], zeros): enables the one-launch apply (ticket)."""
     n = int(keys.shape[0]) if n is None else int(n)
     wsp, wsn = ws.get(_lib.lib.arx_sparse_adagrad_workspace_bytes(n))
-    call("arx_sparse_adagrad_ticket", _p(E), _p(acc), _p(bias), _p(bias_acc), int(E.shape[1]),
+    call("arx_sparse_adagrad", _p(E), _p(acc), _p(bias), _p(bias_acc), int(E.shape[1]),
          _p(keys), _p(src), _p(coef), n, _p(G), _ld(G), _p(Gb), _p(lr_dev), _p(gscale_dev),
          key_bits_for(E.shape[0]), _p(aux_cnt), wsp, wsn, _stream())
 
@@ -818,7 +818,7 @@ class CatSiteArgs(object):
         self._keep = sites
 
 
-# The halves of a K7 pass (include/arx.h: arx_sparse_adagrad_cat_multi_phase, _cat_multi_bags[_csc], _bags).  The
+# The halves of a K7 pass (include/arx.h: arx_sparse_adagrad_cat_multi, _cat_multi_bags, _bags).  The
 # two halves of a pass take the same arguments and the same, otherwise untouched, workspace.
 K7_SORT = 1              # key generation + sort(s): needs the lookup ids only (side stream, under the GEMMs)
 K7_APPLY = 2             # apply: needs the gradient arena
@@ -905,7 +905,7 @@ def sparse_adagrad_cat_multi(args, G, Gb, lr_dev, keys_buf, src_buf, coef_buf, w
     """phase K7_SORT: key generation + sort (needs the ids only), K7_APPLY: apply, K7_BOTH: both.  The two
     halves must use the same workspace object, untouched in between."""
     wsp, wsn = ws.get(_lib.lib.arx_sparse_adagrad_workspace_bytes(args.total))
-    call("arx_sparse_adagrad_cat_multi_phase", int(phase), args.nt, args.E, args.acc, args.bias,
+    call("arx_sparse_adagrad_cat_multi", int(phase), args.nt, args.E, args.acc, args.bias,
          args.bias_acc, args.rows, args.cnt, args.d, args.ns, args.site_table, args.cat_map, args.ids,
          args.count, args.row_base, args.coef, _p(G), _ld(G), _p(Gb), _p(lr_dev), _p(gscale_dev),
          _p(keys_buf), _p(src_buf), _p(coef_buf), args.nx, args.extra_n, args.extra_table, wsp, wsn,
@@ -928,7 +928,7 @@ def sparse_adagrad_cat_multi_bags(args, G, Gb, lr_dev, keys_buf, src_buf, coef_b
     cs, flags, slot_of = csc if csc is not None else (None, None, None)
     # split: this pass's apply form (True `split`, False `win`, None: the process default ARX_K7_RIDER) -- arx.h
     form = 0 if split is None else (K7_FORM_SPLIT if split else K7_FORM_WIN)
-    call("arx_sparse_adagrad_cat_multi_bags_csc", int(phase) | form, args.nt, args.E, args.acc, args.bias,
+    call("arx_sparse_adagrad_cat_multi_bags", int(phase) | form, args.nt, args.E, args.acc, args.bias,
          args.bias_acc, args.rows, args.cnt, args.d, args.ns, args.site_table, args.cat_map, args.ids,
          args.count, args.row_base, args.coef, _p(G), _ld(G), _p(Gb), _p(lr_dev), _p(gscale_dev),
          _p(keys_buf), _p(src_buf), _p(coef_buf), wsp, wsn, _p(bag_E), _p(bag_acc), _p(bag_bias),
@@ -940,7 +940,7 @@ def sparse_adagrad_cat_multi_bags(args, G, Gb, lr_dev, keys_buf, src_buf, coef_b
 
 class BagCSC(object):
     """The STATIC token-major order of a multi-hot table's bags (csrc/csc.hip; arx.h,
-    arx_sparse_adagrad_cat_multi_bags_csc): built once per (bag index, max_len) on the host from the
+    arx_sparse_adagrad_cat_multi_bags): built once per (bag index, max_len) on the host from the
     feature CSR of attributes/attribute.py (embed_attribute.py:265-318 uploads it once and never
     changes it).  Pairs are enumerated by (entity, position in bag) and ordered by token with a stable
     sort -- the order the per-step stable radix sort of the expanded bags produced, so the token
@@ -1454,7 +1454,7 @@ def lstm_fwd(x, W, b, L, B, din, h, forget_bias, hs, cs, gates):
 
 def lstm_bwd(W, hs, cs, gates, dhs, L, B, din, h, dz, wxt=None):
     """dz of the whole unrolled cell; wxt (optional, [4h, din]) receives W[:din]^T on the way."""
-    call("arx_lstm_bwd_wxt", _p(W), _p(hs), _p(cs), _p(gates), _p(dhs), int(L), int(B), int(din),
+    call("arx_lstm_bwd", _p(W), _p(hs), _p(cs), _p(gates), _p(dhs), int(L), int(B), int(din),
          int(h), _p(dz), _p(wxt), _stream())
 
 

@@ -106,7 +106,7 @@ class DeviceSampler(object):
         self.seed = int(seed)
         self.counter = 0
         # large populations: keys that cannot be among the n smallest are dropped before the sort
-        # (arx_sample_wor_capped); the draw is the un-capped one.  The cap depends on n: _cap_for
+        # (arx_sample_wor); the draw is the un-capped one.  The cap depends on n: _cap_for
         self._caps = {}
         self._npos = None
 

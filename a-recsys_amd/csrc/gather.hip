@@ -881,18 +881,10 @@ int arx_gather_onehot_packed_fwd(const float* E, const float* bias, const int32_
   return ARX_OK;
 }
 
-int arx_gather_onehot_multi(int nsites, const float* const* E, const float* const* bias,
+int arx_gather_onehot_multi(int nsites, const float* const* E, const float* const* bias, const int64_t* ldbi,
                             const int32_t* const* cat_map, const int32_t* const* ids,
                             const int64_t* n, int d, const float* scale, float* const* out,
-                            const int64_t* ldo, float* const* bias_out, void* stream) {
-  return arx_gather_onehot_multi_ld(nsites, E, bias, nullptr, cat_map, ids, n, d, scale, out, ldo, bias_out, nullptr,
-                                    stream);
-}
-
-int arx_gather_onehot_multi_ld(int nsites, const float* const* E, const float* const* bias, const int64_t* ldbi,
-                               const int32_t* const* cat_map, const int32_t* const* ids,
-                               const int64_t* n, int d, const float* scale, float* const* out,
-                               const int64_t* ldo, float* const* bias_out, const int64_t* ldb, void* stream) {
+                            const int64_t* ldo, float* const* bias_out, const int64_t* ldb, void* stream) {
   ARX_CHECK_ARG(nsites >= 1 && nsites <= kMaxSites, "arx_gather_onehot_multi: 1..8 sites");
   ARX_CHECK_ARG(E && ids && n && out && ldo && scale, "arx_gather_onehot_multi: null pointer");
   int rc = check_d("arx_gather_onehot_multi", d);

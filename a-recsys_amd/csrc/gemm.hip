@@ -415,10 +415,10 @@ size_t arx_gemm_f32_workspace_bytes(int64_t M, int64_t N, int64_t K) {
   return need;
 }
 
-int arx_gemm_f32_rowsum(int transA, int transB, int64_t M, int64_t N, int64_t K, float alpha,
-                        const float* A, int64_t lda, const float* B, int64_t ldb, float beta,
-                        float* C, int64_t ldc, const float* col_bias, float* a_rowsum,
-                        void* workspace, size_t workspace_bytes, void* stream) {
+int arx_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, float alpha,
+                 const float* A, int64_t lda, const float* B, int64_t ldb, float beta,
+                 float* C, int64_t ldc, const float* col_bias, float* a_rowsum,
+                 void* workspace, size_t workspace_bytes, void* stream) {
   ARX_CHECK_ARG(M >= 0 && N >= 0 && K >= 0, "arx_gemm_f32: negative dimension");
   if (M == 0 || N == 0) return ARX_OK;
   ARX_CHECK_ARG(A && B && C, "arx_gemm_f32: null pointer");
@@ -558,14 +558,6 @@ int arx_gemm_f32_tn_pair(int64_t M, int64_t N1, int64_t N2, int64_t K, const flo
   launch_splitk_reduce(part, sp, M, N, 1.f, 0.f, Ct, ldct, nullptr, rsp, a_rowsum, s, /*tr=*/1);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
-}
-
-int arx_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, float alpha,
-                 const float* A, int64_t lda, const float* B, int64_t ldb, float beta, float* C,
-                 int64_t ldc, const float* col_bias, void* workspace, size_t workspace_bytes,
-                 void* stream) {
-  return arx_gemm_f32_rowsum(transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc,
-                             col_bias, nullptr, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -741,14 +741,8 @@ int arx_lstm_fwd(const float* x, const float* W, const float* b, int64_t L, int6
 }
 
 int arx_lstm_bwd(const float* W, const float* hs, const float* cs, const float* gates,
-                 const float* dhs, int64_t L, int64_t B, int din, int h, float* dz,
+                 const float* dhs, int64_t L, int64_t B, int din, int h, float* dz, float* wxt,
                  void* stream) {
-  return arx_lstm_bwd_wxt(W, hs, cs, gates, dhs, L, B, din, h, dz, nullptr, stream);
-}
-
-int arx_lstm_bwd_wxt(const float* W, const float* hs, const float* cs, const float* gates,
-                     const float* dhs, int64_t L, int64_t B, int din, int h, float* dz, float* wxt,
-                     void* stream) {
   (void)hs;
   ARX_CHECK_ARG(W && cs && gates && dhs && dz, "arx_lstm_bwd: null pointer");
   ARX_CHECK_ARG(L >= 0 && B >= 0 && din > 0 && h > 0, "arx_lstm_bwd: bad size");

@@ -1466,10 +1466,6 @@ int csc_token_sort(const BagWs& w, char* base, const CatSites& st, int64_t n_i, 
   float* scoef_t = reinterpret_cast<float*>(bt + w.wt.off_scoef);
   int32_t* count_t = reinterpret_cast<int32_t*>(bt + w.wt.off_count);
   void* lb = base + w.off_csc_lb;
-  // timing-only ablation (WRONG results): ARX_ABL_CSC_SKIP=1 -- after the first call only the marks go out (the token
-  // apply walks the first batch's list): what the step would cost if the apply read the flags itself
-  static const bool abl_skip = getenv("ARX_ABL_CSC_SKIP") != nullptr;
-  static int abl_calls = 0;
   if (part == 0) {
     MarkSites ms = {};
     ms.rows = st.rows[0];
@@ -1482,11 +1478,8 @@ int csc_token_sort(const BagWs& w, char* base, const CatSites& st, int64_t n_i, 
       ++ms.n;
     }
     for (int q = ms.n; q < kMaxSites; ++q) ms.offs[q + 1] = ms.offs[ms.n];
-    const bool skip = abl_skip && abl_calls++ >= 1;
-    return launch_csc_mark(ms, *bag.csc, bag.starts, bag.lens, bag.max_len, count_t, skip ? 0 : 512, lb,
-                           skip ? 0 : 1024, s);
+    return launch_csc_mark(ms, *bag.csc, bag.starts, bag.lens, bag.max_len, count_t, 512, lb, 1024, s);
   }
-  if (abl_skip && abl_calls > 1) return ARX_OK;
   int kbt = 1;
   while ((1ll << kbt) < bag.rows && kbt < 30) ++kbt;
   int rc = launch_csc_compact(*bag.csc, sk_t, ssrc_t, scoef_t, n_t, count_t + 2, lb, s);
@@ -1751,17 +1744,8 @@ size_t arx_sparse_adagrad_workspace_bytes(int64_t n) {
 int arx_sparse_adagrad(float* E, float* acc, float* bias, float* bias_acc, int d,
                        const int32_t* keys, const int32_t* src, const float* coef, int64_t n,
                        const float* G, int64_t ldg, const float* Gb, const float* lr_dev,
-                       const float* gscale_dev, int key_bits, void* workspace,
-                       size_t workspace_bytes, void* stream) {
-  return arx_sparse_adagrad_ticket(E, acc, bias, bias_acc, d, keys, src, coef, n, G, ldg, Gb, lr_dev,
-                                   gscale_dev, key_bits, nullptr, workspace, workspace_bytes, stream);
-}
-
-int arx_sparse_adagrad_ticket(float* E, float* acc, float* bias, float* bias_acc, int d,
-                              const int32_t* keys, const int32_t* src, const float* coef, int64_t n,
-                              const float* G, int64_t ldg, const float* Gb, const float* lr_dev,
-                              const float* gscale_dev, int key_bits, int32_t* aux_cnt,
-                              void* workspace, size_t workspace_bytes, void* stream) {
+                       const float* gscale_dev, int key_bits, int32_t* aux_cnt,
+                       void* workspace, size_t workspace_bytes, void* stream) {
   ARX_CHECK_ARG(E && keys && G && lr_dev, "arx_sparse_adagrad: null pointer");
   ARX_CHECK_ARG(acc ? (bias == nullptr) == (bias_acc == nullptr) : bias_acc == nullptr,
                 "arx_sparse_adagrad: bias and bias_acc go together (acc == NULL: gradient descent, no slots)");

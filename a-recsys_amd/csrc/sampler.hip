@@ -241,12 +241,8 @@ extern "C" {
 // capped draws of up to kCompactCap / 8 items: survivor list + its count
 static bool compact_path(int64_t S, float key_cap) { return key_cap > 0.f && S * 8 <= kCompactCap; }
 
-size_t arx_sample_wor_keys_workspace_bytes(int64_t n, int64_t S, float key_cap) {
+size_t arx_sample_wor_workspace_bytes(int64_t n, int64_t S, float key_cap) {
   if (compact_path(S, key_cap)) return (size_t)kCompactCap * 8 + 256;
-  return arx_sample_wor_workspace_bytes(n);
-}
-
-size_t arx_sample_wor_workspace_bytes(int64_t n) {
   const size_t ni = align256((size_t)(n > 0 ? n : 1) * 4);
   // raw keys, 2 x (keys, src, coef) ping-pong, histograms, live count
   return ni * 7 + radix_sort_hist_bytes() + 256;
@@ -274,18 +270,6 @@ int arx_item_frequency(const int32_t* item_ids, int64_t n, int64_t n_items, int6
   return ARX_OK;
 }
 
-int arx_sample_wor(const float* weights, int64_t n, int64_t S, uint64_t seed, uint64_t counter,
-                   int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream) {
-  return arx_sample_wor_capped(weights, n, S, seed, counter, 0.f, out_idx, workspace, workspace_bytes, stream);
-}
-
-int arx_sample_wor_capped(const float* weights, int64_t n, int64_t S, uint64_t seed, uint64_t counter,
-                          float key_cap, int32_t* out_idx, void* workspace, size_t workspace_bytes,
-                          void* stream) {
-  return arx_sample_wor_keys(weights, n, S, seed, counter, key_cap, out_idx, nullptr, workspace, workspace_bytes,
-                             stream);
-}
-
 int arx_merge_keyed_take(const float* keys, const int32_t* ids, int64_t m, int64_t S, int32_t* out, void* stream) {
   ARX_CHECK_ARG(keys && ids && out, "arx_merge_keyed_take: null pointer");
   ARX_CHECK_ARG(m > 0 && m <= kCompactCap && S > 0 && S <= m, "arx_merge_keyed_take: need 0 < S <= m <= 16384");
@@ -297,12 +281,12 @@ int arx_merge_keyed_take(const float* keys, const int32_t* ids, int64_t m, int64
   return ARX_OK;
 }
 
-int arx_sample_wor_keys(const float* weights, int64_t n, int64_t S, uint64_t seed, uint64_t counter,
-                        float key_cap, int32_t* out_idx, float* out_keys, void* workspace,
-                        size_t workspace_bytes, void* stream) {
+int arx_sample_wor(const float* weights, int64_t n, int64_t S, uint64_t seed, uint64_t counter,
+                   float key_cap, int32_t* out_idx, float* out_keys, void* workspace,
+                   size_t workspace_bytes, void* stream) {
   ARX_CHECK_ARG(weights && out_idx, "arx_sample_wor: null pointer");
   ARX_CHECK_ARG(n > 0 && n < (int64_t)0x7fffffff && S > 0 && S <= n, "arx_sample_wor: need 0 < S <= n < 2^31");
-  const size_t need = arx_sample_wor_keys_workspace_bytes(n, S, key_cap);
+  const size_t need = arx_sample_wor_workspace_bytes(n, S, key_cap);
   if (!workspace || workspace_bytes < need) {
     set_error("arx_sample_wor: workspace too small (%zu < %zu)", workspace_bytes, need);
     return ARX_EWORKSPACE;

@@ -16,14 +16,14 @@
 // loader waves (global_load_lds_dwordx4: no staging registers) three stages ahead in a four-slot ring, the hinge
 // epilogue of tile j - 1 interleaved with the MFMAs of tile j, the target score formed by the half waves of k_sc_prep
 // that list a row's positives (round 4: in the forward kernel's prologue), and every operand plane produced by the
-// kernel that has the data in registers anyway (k_sc_prep: pool rows in both layouts; k_sc_rows: g U transposed) --
+// kernel that has the data in registers anyway (k_sc_prep: pool rows in both layouts; k_sc_rows_g: g U transposed) --
 // no split launches.
 //
 // Round 5, k_sc_hinge 28.2 -> 24.4 us (0.38 -> 0.42 of 2500 / 6; the C4 shape 56.4 -> 49.9): its start is bound by the
 // bytes 256 workgroups ask for at once.  The T rows and the dot moved to k_sc_prep (+1.7 us there at the C3 shape, 0
 // at C4's), the pieces of U are made chunk by chunk between the MFMAs of tile 0 instead of in front of them, loads are
 // issued in cache-line order, and the two column splits of a row block run on ONE XCD (blockIdx mapping).  Measured
-// on the way, with UNTRACED builds timed by rocprofv3 (tools/r05_sc_ab.sh) -- the cycle stamps of tools/sc_trace.py
+// on the way, with UNTRACED builds timed by rocprofv3 around tools/scorerbench.py -- the cycle stamps of tools/sc_trace.py
 // slow the stamped kernel by 8 us and mis-attribute it (a traced build made the bias re-reads look like a third of the
 // loop): no MFMA 9.6 us, no LDS-DMA -2.3, no barriers -0.8, no re-initialising writes +-0, the bias through
 // v_readlane instead of LDS +0.6, U pre-split by k_sc_prep 24.3 but +3 us in k_sc_prep.  The part runs this kernel at
@@ -31,11 +31,9 @@
 // waves: +-0.  k_sc_prep by role (blocks of the others returning at once): pool planes 5.0 us, hit lists + target scores
 // 8.7 (a chain of four dependent loads per row), together 10.1.
 //
-// Launches of a step:  k_sc_prep -> k_sc_hinge -> k_sc_rows          (arx_mw_scorer_fwd)
+// Launches of a step:  k_sc_prep -> k_sc_hinge -> k_sc_rows_g        (arx_mw_scorer_fwd)
 //                      k_sc_bits (dU += g (act . P))                 (arx_mw_scorer_bwd_du)
 //                      k_sc_bits (slices of act^T . (g U)) -> k_sc_tn_reduce   (arx_mw_scorer_bwd_di)
-#include <stdlib.h>
-
 #include "common.h"
 #include "posmask.h"
 
@@ -57,7 +55,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 #ifndef SC_TRACE_CHUNKS
 #define SC_TRACE_CHUNKS 0            // 1: a stamp after every chunk (perturbs: each stamp drains the LDS counter)
 #endif
-#if defined(SC_TRACE) || defined(SC_TRACE_ROWS)
+#ifdef SC_TRACE
 __device__ unsigned long long g_sc_trace[4096];
 #define SC_T(ev_)                                                                                        \
   if (blockIdx.x == (gridDim.x > 5 ? 5 : 0) && threadIdx.x == 0 && tcount < 4096)                        \
@@ -70,11 +68,6 @@ __device__ unsigned long long g_sc_trace[4096];
 #define SC_TREAL(ev_)
 #define SC_T(ev_)
 #define SC_TDECL
-#endif
-#ifdef SC_TRACE_ROWS                  // the same stamps in k_sc_rows (phases of one wave of workgroup 5)
-#define SC_TR(ev_) SC_T(ev_)
-#else
-#define SC_TR(ev_)
 #endif
 constexpr int kScHits = 8;            // pool slots of a row's positives kept in the hit list (more: the row kernel walks)
 constexpr int kScSlots = 4;           // LDS ring: the stage being read + three in flight
@@ -708,7 +701,7 @@ __global__ __launch_bounds__(512) void k_sc_hinge(int64_t B, int64_t S, int CW, 
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// k_sc_rows: workgroup = 32 batch rows (8 waves x 4 rows).  Per row: the column splits' partial sums in fixed
+// k_sc_rows_g: workgroup = 32 batch rows (8 waves x 4 rows).  Per row: the column splits' partial sums in fixed
 // order, the user's positives that sit in the pool taken out again (their logit recomputed from the row's latent
 // and the pool row, the act bit cleared), loss = log(1 + s), g = gscale * w / (1 + s), dt = -g * cnt and the
 // rank-one terms dT = dt U, dU = dt T.  Per workgroup: g U as TRANSPOSED bf16 planes UgT [3][d][Bp] (the dI
@@ -742,179 +735,15 @@ struct ScRows {
   const float* pool_bad;           // [S / 32]: NaN where a block of pool rows / biases holds a non-finite value
 };
 
-__global__ __launch_bounds__(512) void k_sc_rows(ScRows a, PosMask pm, int64_t mask_rows, int64_t B, int64_t S) {
-  __shared__ float tile[32 * 129];              // g U of the block's rows, f32 [32][d + 1]
-  __shared__ uint32_t sbits[32 * 64];           // final act words of the rows [32][S / 32]
-  __shared__ float sg[32];
-#ifdef SC_TRACE_ROWS
-  SC_TDECL
-  SC_TREAL(120)
-#endif
-  SC_TR(10)
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wv = tid >> 6;
-  const int64_t r0 = (int64_t)blockIdx.x * 32;
-  const int nwords = (int)(S >> 5);
-  const int ld = a.d + 1;
-  const bool colok = lane * 4 < a.d;
-  // non-finite inputs poison the loss like an f32 chain would (the hinge itself drops a NaN logit: v > 0 is false)
-  const float pbad = sc_wsum(lane < (int)(S >> 5) ? a.pool_bad[lane] : 0.f);
-  constexpr int RPW = 4;                          // rows per wave, all loads of the four rows issued up front
-  float4 u[RPW], tr[RPW];
-  float s[RPW], c[RPW], t[RPW];
-  int nh[RPW];
-  uint32_t w0[RPW];
-#pragma unroll
-  for (int q = 0; q < RPW; ++q) {
-    const int64_t r = r0 + wv * RPW + q;
-    const bool live = r < B;
-    u[q] = make_float4(0.f, 0.f, 0.f, 0.f);
-    tr[q] = u[q];
-    s[q] = c[q] = t[q] = 0.f;
-    nh[q] = 0;
-    w0[q] = 0u;
-    if (live) {
-      for (int p = 0; p < a.nsplit; ++p) {                    // fixed order: bit-reproducible
-        s[q] += a.rs_part[(int64_t)p * B + r];
-        c[q] += a.cnt_part[(int64_t)p * B + r];
-      }
-      t[q] = a.tscore[r];
-      if (colok) {
-        u[q] = *reinterpret_cast<const float4*>(a.U + r * a.ldu + lane * 4);
-        tr[q] = *reinterpret_cast<const float4*>(a.T + r * a.ldt + lane * 4);
-      }
-      nh[q] = a.nhit[r];
-      if (lane < nwords) w0[q] = a.bits[(int64_t)lane * a.ldbits + r];
-    }
-  }
-  SC_TR(16)
-#pragma unroll
-  for (int q = 0; q < RPW; ++q) {
-    const int rl = wv * RPW + q;
-    const int64_t r = r0 + rl;
-    const bool live = r < B;
-    uint32_t myw = w0[q];
-    float sq = s[q], cq = c[q];
-    const float4 uq = u[q], tq = tr[q];
-    if (live && nh[q] != 0) {
-      // the row's bit words live in the lanes (word w in lane w; S <= 2048): a slot the positives name twice is
-      // taken out once, and the write-back is one store per changed word
-      auto take_out = [&](int jj) {                   // jj wave-uniform
-        const uint32_t w = __shfl(myw, jj >> 5, 64);
-        if (!((w >> (jj & 31)) & 1u)) return;         // hinge not active there (or already taken out)
-        float4 pr = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (colok) pr = *reinterpret_cast<const float4*>(a.P + (int64_t)jj * a.ldp + lane * 4);
-        const float x = sc_wsum(uq.x * pr.x + uq.y * pr.y + uq.z * pr.z + uq.w * pr.w) + (a.pb ? a.pb[jj] : 0.f);
-        const float v = x - t[q] + 1.f;
-        sq -= v > 0.f ? v : 0.f;
-        cq -= 1.f;
-        if (lane == (jj >> 5)) myw &= ~(1u << (jj & 31));
-      };
-      if (nh[q] > 0) {
-        const int myhit = lane < nh[q] ? a.hits[r * kScHits + lane] : 0;
-        for (int k = 0; k < nh[q]; ++k) take_out(__shfl(myhit, k, 64));
-      } else {                                        // long list: walk the positives here
-        const int usr = pm.user_ids[r % mask_rows];
-        const int beg = pm.pos_ptr[usr], end = pm.pos_ptr[usr + 1];
-        for (int p0 = beg; p0 < end; p0 += 64) {
-          const int p = p0 + lane;
-          int j = -1;
-          if (p < end) {
-            j = pos_slot(pm, pm.pos_items[p]);
-            if (j < 0 || j >= S) j = -1;
-          }
-          unsigned long long hm = __ballot(j >= 0);
-          while (hm) {
-            const int src = __builtin_ctzll(hm);
-            hm &= hm - 1;
-            take_out(__shfl(j, src, 64));
-          }
-        }
-      }
-      if (lane < nwords && myw != w0[q]) a.bits[(int64_t)lane * a.ldbits + r] = myw;
-    }
-    sq = fmaxf(sq, 0.f) + (pbad + sc_wsum(((uq.x + uq.y) + (uq.z + uq.w) + (tq.x + tq.y) + (tq.z + tq.w)) * 0.f) + t[q] * 0.f);
-    const float g = live ? a.gscale * (a.row_w ? a.row_w[r] : 1.f) / (1.f + sq) : 0.f;
-    const float dt = -g * cq;
-    if (lane == 0) {
-      sg[rl] = g;
-      if (live) {
-        if (a.batch_loss) a.batch_loss[r] = logf(1.f + sq);
-        if (a.dtscore) a.dtscore[r * a.dts_stride] = dt;
-      }
-      a.g_out[r] = g;                                 // (rows past B inside the padded length: 0)
-    }
-    if (lane < nwords) sbits[rl * 64 + lane] = myw;
-    if (colok) {
-      if (live) {
-        if (a.dT) *reinterpret_cast<float4*>(a.dT + r * a.lddt + lane * 4) = make_float4(dt * uq.x, dt * uq.y, dt * uq.z, dt * uq.w);
-        if (a.dU) *reinterpret_cast<float4*>(a.dU + r * a.lddu + lane * 4) = make_float4(dt * tq.x, dt * tq.y, dt * tq.z, dt * tq.w);
-      }
-      float* tp = tile + rl * ld + lane * 4;
-      tp[0] = g * uq.x; tp[1] = g * uq.y; tp[2] = g * uq.z; tp[3] = g * uq.w;
-    }
-  }
-  SC_TR(11)
-  __syncthreads();
-  SC_TR(15)
-  // g U -> transposed planes, 32 consecutive k (= batch rows) per column n
-  sc_emit_planes_t(tile, ld, 32, a.d, a.UgT, (int64_t)a.d * a.ldug, a.ldug, r0, tid, 512);
-  SC_TR(12)
-  // act bits transposed: a 32 x 32 bit block is 32 ballots -- lane l of a half-wave holds row l's word of one word
-  // column, ballot k collects bit k of the 32 rows = the transposed word of column 32 c + k (the low half of the
-  // ballot for the word column of lanes 0..31, the high half for the one of lanes 32..63).  Then the block's
-  // bias-gradient partial per column from that word (the per-column loop over 32 LDS words it replaces took 9.7 k
-  // cycles of the workgroup's 28 k)
-  uint32_t* tw = reinterpret_cast<uint32_t*>(tile);            // (the f32 tile is dead: planes emitted above)
-  __syncthreads();
-  for (int c0 = wv * 2; c0 < nwords; c0 += 16) {
-    const int c = c0 + (lane >> 5);
-    const uint32_t w = c < nwords ? sbits[(lane & 31) * 64 + c] : 0u;
-    uint32_t mine = 0u;                                        // lane 32 h + k ends up with ballot k's half h
-#pragma unroll
-    for (int k = 0; k < 32; ++k) {
-      const unsigned long long bal = __ballot((w >> k) & 1u);
-      // (s_nop: a v_writelane that reads an SGPR a VALU compare has just written needs wait states the compiler
-      // cannot insert inside inline asm -- without them the lanes got garbage; probed on gfx950)
-      asm volatile("s_nop 4\n\tv_writelane_b32 %0, %1, %3\n\tv_writelane_b32 %0, %2, %4"
-                   : "+v"(mine) : "s"((uint32_t)bal), "s"((uint32_t)(bal >> 32)), "n"(k), "n"(32 + k));
-    }
-    if (c < nwords) tw[c * 32 + (lane & 31)] = mine;
-  }
-  SC_TR(14)
-  __syncthreads();
-  // (g of the 32 rows read from LDS as broadcasts, four at a time: kept in 32 registers the kernel went from 88 to
-  // 115 VGPRs and the radix scatter that runs beside it in the step no longer fitted on the SIMDs -- 13 -> 32 us)
-  for (int col = tid; col < S; col += 512) {
-    const uint32_t word = tw[col];
-    float db = 0.f;
-#pragma unroll 1
-    for (int r4 = 0; r4 < 32; r4 += 4) {
-      const float4 g4 = *reinterpret_cast<const float4*>(&sg[r4]);
-      db += ((word >> r4) & 1u) ? g4.x : 0.f;
-      db += ((word >> (r4 + 1)) & 1u) ? g4.y : 0.f;
-      db += ((word >> (r4 + 2)) & 1u) ? g4.z : 0.f;
-      db += ((word >> (r4 + 3)) & 1u) ? g4.w : 0.f;
-    }
-    a.bitsT[(int64_t)blockIdx.x * a.ldbt + col] = word;
-    a.dbp[(int64_t)blockIdx.x * S + col] = db;
-  }
-  SC_TR(13)
-#ifdef SC_TRACE_ROWS
-  SC_TREAL(121)
-#endif
-}
-
 // ------------------------------------------------------------------------------------------------------------
-// k_sc_rows_g (round 6): k_sc_rows with the row phase laid out for the width the scorer family has -- d = 64 / 128 is
+// The row phase (round 6) is laid out for the width the scorer family has -- d = 64 / 128 is
 // LPR = 16 / 32 lanes of 16 bytes, so a wave serves 64 / LPR rows AT ONCE (one sub-group per row) instead of four
 // rows one after the other with 48 / 32 idle lanes: one load instruction per operand for all of the wave's rows, 16-
 // / 32-lane reductions (the upper steps of the 64-lane xor tree added exact zeros: same bits), the row's S / 32
 // activity words spread over the sub-group's lanes (word w in lane w % LPR, slot w / LPR).  Measured on the C4 shape
 // (51 200 rows, d = 64; cycle stamps of one wave, tools/sc_trace.py): the four-rows-in-a-row phase was 6 300 of the
-// workgroup's 23 200 cycles behind an 8 900-cycle first load; k_sc_rows was the largest kernel of the C4 step (71.8 us).
-// Results bit-identical to k_sc_rows (ARX_SC_ROWS_OLD=1 selects it: the A/B of DESIGN.md section 6).
+// workgroup's 23 200 cycles behind an 8 900-cycle first load; that kernel was the largest of the C4 step (71.8 us).
+// Its results were bit-identical; the A/B that retired it is recorded in DESIGN.md section 6.
 // ------------------------------------------------------------------------------------------------------------
 template <int LPR>
 __global__ __launch_bounds__(512) void k_sc_rows_g(ScRows a, PosMask pm, int64_t mask_rows, int64_t B, int64_t S) {
@@ -1048,7 +877,7 @@ __global__ __launch_bounds__(512) void k_sc_rows_g(ScRows a, PosMask pm, int64_t
   __syncthreads();
   // g U -> transposed planes, 32 consecutive k (= batch rows) per column n
   sc_emit_planes_t(tile, ld, 32, a.d, a.UgT, (int64_t)a.d * a.ldug, a.ldug, r0, tid, 512);
-  // act bits transposed + the block's bias-gradient partials: as in k_sc_rows
+  // act bits transposed + the block's bias-gradient partials
   uint32_t* tw = reinterpret_cast<uint32_t*>(tile);            // (the f32 tile is dead: planes emitted above)
   __syncthreads();
   for (int c0 = wv * 2; c0 < nwords; c0 += 16) {
@@ -1289,7 +1118,7 @@ __global__ __launch_bounds__(256) void k_sc_tn_reduce(const float* __restrict__ 
     // the step's scalar loss, gscale * sum_r row_w[r] * loss[r] over the row kernel's batch_loss, in a fixed order
     // (thread t takes float4s t, t + 256, ..., eight pairs of loads in flight; the 256 sub-sums meet in a fixed
     // tree) -- was a launch of its own (mean / weighted dot) between the forward and the backward kernels.
-    // (Block sums out of the row kernel would be less to read, but ANY code added to k_sc_rows -- one store --
+    // (Block sums out of the row kernel would be less to read, but ANY code added to the row kernel -- one store --
     // cost a register, 88 -> 89 = one allocation granule, and ~6 us of the C3 step: measured.)
     __shared__ float sls[256];
     const int64_t n4 = lrows >> 2;
@@ -1901,7 +1730,7 @@ using namespace arx;
 
 extern "C" {
 
-#if defined(SC_TRACE) || defined(SC_TRACE_ROWS)
+#ifdef SC_TRACE
 int arx_sc_trace_read(void* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_sc_trace), sizeof(g_sc_trace)); }
 #endif
 
@@ -1929,30 +1758,17 @@ int arx_mw_scorer_state_layout(int64_t B, int64_t S, int d, int64_t* out) {
   return ARX_OK;
 }
 
-int arx_mw_scorer_fwd_phases(const float* U, int64_t ldu, const float* P, int64_t ldp, const float* pbias,
-                             const float* T, int64_t ldt, const float* tbias, int64_t tb_stride, int d,
-                             const int32_t* user_ids, const int32_t* pos_ptr, const int32_t* pos_items,
-                             const int32_t* item2slot, int64_t mask_rows, float gscale, const float* row_w, int64_t B,
-                             int64_t S, float* batch_loss, float* tscore_out, float* dtscore, int64_t dtscore_stride,
-                             float* dU, int64_t lddu, float* dT, int64_t lddt, void* state, size_t state_bytes,
-                             int phases, void* stream) {
-  return arx_mw_scorer_fwd_seqw(U, ldu, P, ldp, pbias, T, ldt, tbias, tb_stride, d, user_ids, pos_ptr, pos_items,
-                                item2slot, mask_rows, gscale, const_cast<float*>(row_w), nullptr, 0, B, S, batch_loss,
-                                tscore_out, dtscore, dtscore_stride, dU, lddu, dT, lddt, state, state_bytes, phases,
-                                stream);
-}
-
-int arx_mw_scorer_fwd_seqw(const float* U, int64_t ldu, const float* P, int64_t ldp, const float* pbias,
-                           const float* T, int64_t ldt, const float* tbias, int64_t tb_stride, int d,
-                           const int32_t* user_ids, const int32_t* pos_ptr, const int32_t* pos_items,
-                           const int32_t* item2slot, int64_t mask_rows, float gscale, float* row_w,
-                           const float* seq_w, int64_t seq_rows, int64_t B, int64_t S, float* batch_loss,
-                           float* tscore_out, float* dtscore, int64_t dtscore_stride, float* dU, int64_t lddu,
-                           float* dT, int64_t lddt, void* state, size_t state_bytes, int phases, void* stream) {
+int arx_mw_scorer_fwd(const float* U, int64_t ldu, const float* P, int64_t ldp, const float* pbias,
+                      const float* T, int64_t ldt, const float* tbias, int64_t tb_stride, int d,
+                      const int32_t* user_ids, const int32_t* pos_ptr, const int32_t* pos_items,
+                      const int32_t* item2slot, int64_t mask_rows, float gscale, float* row_w,
+                      const float* seq_w, int64_t seq_rows, int64_t B, int64_t S, float* batch_loss,
+                      float* tscore_out, float* dtscore, int64_t dtscore_stride, float* dU, int64_t lddu,
+                      float* dT, int64_t lddt, void* state, size_t state_bytes, int phases, void* stream) {
   ARX_CHECK_ARG(U && P && T && user_ids && pos_ptr && pos_items && item2slot && state,
                 "arx_mw_scorer_fwd: null pointer");
   ARX_CHECK_ARG(!seq_w || (row_w && seq_rows > 0 && B % seq_rows == 0),
-                "arx_mw_scorer_fwd_seqw: sequence weights need row_w [B] to write and seq_rows dividing B");
+                "arx_mw_scorer_fwd: sequence weights need row_w [B] to write and seq_rows dividing B");
   ScLayout L;
   const bool ok = sc_layout(B, S, d, &L) && ldu % 4 == 0 && ldp % 4 == 0 && ldt % 4 == 0 && ldu >= d && ldp >= d &&
                   ldt >= d && (!dU || (lddu % 4 == 0 && lddu >= d)) && (!dT || (lddt % 4 == 0 && lddt >= d)) &&
@@ -2001,24 +1817,11 @@ int arx_mw_scorer_fwd_seqw(const float* U, int64_t ldu, const float* P, int64_t 
              P, ldp, pbias, d, gscale, row_w, batch_loss, reinterpret_cast<float*>(st + L.g), dtscore,
              dtscore_stride > 0 ? dtscore_stride : 1, dU, lddu, dT, lddt, reinterpret_cast<uint16_t*>(st + L.UgT), L.ldug,
              reinterpret_cast<float*>(st + L.dbp), hits, nhit, reinterpret_cast<const float*>(st + L.pbad)};
-    static const bool rows_old = getenv("ARX_SC_ROWS_OLD") != nullptr;     // (A/B: the four-rows-in-a-row kernel)
-    if (!rows_old && d == 64) k_sc_rows_g<16><<<(int)L.nblk, 512, 0, s>>>(a, pm, mrows, B, S);
-    else if (!rows_old && d == 128) k_sc_rows_g<32><<<(int)L.nblk, 512, 0, s>>>(a, pm, mrows, B, S);
-    else k_sc_rows<<<(int)L.nblk, 512, 0, s>>>(a, pm, mrows, B, S);
+    if (d == 64) k_sc_rows_g<16><<<(int)L.nblk, 512, 0, s>>>(a, pm, mrows, B, S);
+    else k_sc_rows_g<32><<<(int)L.nblk, 512, 0, s>>>(a, pm, mrows, B, S);                // (sc_layout: d is 64 or 128)
     ARX_CHECK_LAUNCH();
   }
   return ARX_OK;
-}
-
-int arx_mw_scorer_fwd(const float* U, int64_t ldu, const float* P, int64_t ldp, const float* pbias, const float* T,
-                      int64_t ldt, const float* tbias, int64_t tb_stride, int d, const int32_t* user_ids,
-                      const int32_t* pos_ptr, const int32_t* pos_items, const int32_t* item2slot, int64_t mask_rows,
-                      float gscale, const float* row_w, int64_t B, int64_t S, float* batch_loss, float* tscore_out,
-                      float* dtscore, int64_t dtscore_stride, float* dU, int64_t lddu, float* dT, int64_t lddt,
-                      void* state, size_t state_bytes, void* stream) {
-  return arx_mw_scorer_fwd_phases(U, ldu, P, ldp, pbias, T, ldt, tbias, tb_stride, d, user_ids, pos_ptr, pos_items,
-                                  item2slot, mask_rows, gscale, row_w, B, S, batch_loss, tscore_out, dtscore,
-                                  dtscore_stride, dU, lddu, dT, lddt, state, state_bytes, 7, stream);
 }
 
 /* dU[m, :] = beta dU[m, :] + g[m] * sum_s act[m][s] P[s, :]   (embed_attribute.py:171 backward, latent side) */
@@ -2056,21 +1859,14 @@ size_t arx_mw_scorer_bwd_di_workspace_bytes(int64_t B, int64_t S, int d, int64_t
  * rows, step_rows % 128 == 0): the products of the single steps are kept as well -- dI_steps [L][S][d] (may alias
  * the workspace's slices: pass NULL to use the workspace) and db_steps [L][S] -- for TF-1.0's per-unrolled-step
  * clip norm (seqModel.py:179-180). */
-int arx_mw_scorer_bwd_di(int64_t B, int64_t S, int d, const void* state, int64_t step_rows, float beta, float* dI,
-                         int64_t lddi, float* db, float* dI_steps, float* db_steps, void* workspace,
-                         size_t workspace_bytes, void* stream) {
-  return arx_mw_scorer_bwd_di_loss(B, S, d, state, step_rows, beta, dI, lddi, db, dI_steps, db_steps, nullptr, 0.f,
-                                   nullptr, nullptr, workspace, workspace_bytes, stream);
-}
-
-int arx_mw_scorer_bwd_di_loss(int64_t B, int64_t S, int d, const void* state, int64_t step_rows, float beta,
-                              float* dI, int64_t lddi, float* db, float* dI_steps, float* db_steps,
-                              const float* batch_loss, float gscale, const float* row_w, float* loss_out,
-                              void* workspace, size_t workspace_bytes, void* stream) {
+int arx_mw_scorer_bwd_di(int64_t B, int64_t S, int d, const void* state, int64_t step_rows, float beta,
+                         float* dI, int64_t lddi, float* db, float* dI_steps, float* db_steps,
+                         const float* batch_loss, float gscale, const float* row_w, float* loss_out,
+                         void* workspace, size_t workspace_bytes, void* stream) {
   ScLayout L;
   ARX_CHECK_ARG(!loss_out || (batch_loss && (reinterpret_cast<uintptr_t>(batch_loss) & 15) == 0 &&
                               (reinterpret_cast<uintptr_t>(row_w) & 15) == 0),
-                "arx_mw_scorer_bwd_di_loss: loss_out needs batch_loss (and row_w) 16-byte aligned");
+                "arx_mw_scorer_bwd_di: loss_out needs batch_loss (and row_w) 16-byte aligned");
   ARX_CHECK_ARG(state && dI && sc_layout(B, S, d, &L), "arx_mw_scorer_bwd_di: bad argument / shape");
   ARX_CHECK_ARG(lddi % 4 == 0 && lddi >= d && (reinterpret_cast<uintptr_t>(dI) & 15) == 0,
                 "arx_mw_scorer_bwd_di: dI rows must be 16-byte aligned");
@@ -2277,15 +2073,15 @@ size_t arx_mce_scorer_bwd_di_workspace_bytes(int64_t B, int64_t S, int d, int64_
 }
 
 /* dI[s, :] = beta dI[s, :] + sum_r w_rs U[r, :], db[s] = sum_r w_rs with w_rs = coef_r m_rs exp(x_rs - t_r), recomputed
- * tile by tile; arguments as arx_mw_scorer_bwd_di_loss (step_rows > 0: B % step_rows == 0, step_rows % 128 == 0). */
-int arx_mce_scorer_bwd_di_loss(int64_t B, int64_t S, int d, const void* state, const float* pbias, int64_t mask_rows,
-                               int64_t step_rows, float beta, float* dI, int64_t lddi, float* db, float* dI_steps, float* db_steps,
-                               const float* batch_loss, float gscale, const float* row_w, float* loss_out,
-                               void* workspace, size_t workspace_bytes, void* stream) {
+ * tile by tile; arguments as arx_mw_scorer_bwd_di (step_rows > 0: B % step_rows == 0, step_rows % 128 == 0). */
+int arx_mce_scorer_bwd_di(int64_t B, int64_t S, int d, const void* state, const float* pbias, int64_t mask_rows,
+                          int64_t step_rows, float beta, float* dI, int64_t lddi, float* db, float* dI_steps, float* db_steps,
+                          const float* batch_loss, float gscale, const float* row_w, float* loss_out,
+                          void* workspace, size_t workspace_bytes, void* stream) {
   McLayout L;
   ARX_CHECK_ARG(!loss_out || (batch_loss && (reinterpret_cast<uintptr_t>(batch_loss) & 15) == 0 &&
                               (reinterpret_cast<uintptr_t>(row_w) & 15) == 0),
-                "arx_mce_scorer_bwd_di_loss: loss_out needs batch_loss (and row_w) 16-byte aligned");
+                "arx_mce_scorer_bwd_di: loss_out needs batch_loss (and row_w) 16-byte aligned");
   ARX_CHECK_ARG(state && dI && mc_layout(B, S, d, &L), "arx_mce_scorer_bwd_di: bad argument / shape");
   ARX_CHECK_ARG(lddi % 4 == 0 && lddi >= d && (reinterpret_cast<uintptr_t>(dI) & 15) == 0,
                 "arx_mce_scorer_bwd_di: dI rows must be 16-byte aligned");

@@ -342,7 +342,7 @@ extern "C" {
 
 const char* arx_last_error(void) { return g_err; }
 
-int arx_version(void) { return 100; }
+int arx_version(void) { return 101; }
 
 int arx_device_info(int* cu, int* wave, int* lds_bytes, char* arch, int arch_len) {
   int dev = 0;

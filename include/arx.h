@@ -212,21 +212,17 @@ int arx_lookup_multi(int nsites, const float* const* E_id, const float* const* b
 
 /* nsites one-hot lookups of equal width d in ONE launch (site s: out[s][r, 0:d] = scale[s] *
  * E[s][cat_map[s] ? cat_map[s][ids[s][r]] : ids[s][r], :], bias_out[s][r] likewise; r < n[s]).
- * The lookups of a step (user ids, target items, sampled pool, input items) are independent. */
-int arx_gather_onehot_multi(int nsites, const float* const* E, const float* const* bias,
-                            const int32_t* const* cat_map, const int32_t* const* ids,
-                            const int64_t* n, int d, const float* scale, float* const* out,
-                            const int64_t* ldo, float* const* bias_out, void* stream);
-/* ... with a stride for every site's bias output, bias_out[s][r * ldb[s]], and bias input,
- * bias[s][row * ldbi[s]] (NULL: 1 everywhere).  bias_out[s] = out[s] + d with ldb[s] = ldo[s] gives
+ * The lookups of a step (user ids, target items, sampled pool, input items) are independent.
+ * Every site's bias output has a stride, bias_out[s][r * ldb[s]], and so has its bias input,
+ * bias[s][row * ldbi[s]] (ldb / ldbi NULL: 1 everywhere).  bias_out[s] = out[s] + d with ldb[s] = ldo[s] gives
  * the packed rows of arx_gather_onehot_packed_fwd: the sharded step's three lookups (own user rows;
  * pool block and requested target rows, packed for the exchanges) are one launch.  bias[s] = E[s] + d0
  * with ldbi[s] = d reads column d0 of a table of PACKED rows (d = its full row width): reordering
  * received packed rows and splitting off their bias column is one launch too. */
-int arx_gather_onehot_multi_ld(int nsites, const float* const* E, const float* const* bias, const int64_t* ldbi,
-                               const int32_t* const* cat_map, const int32_t* const* ids,
-                               const int64_t* n, int d, const float* scale, float* const* out,
-                               const int64_t* ldo, float* const* bias_out, const int64_t* ldb, void* stream);
+int arx_gather_onehot_multi(int nsites, const float* const* E, const float* const* bias, const int64_t* ldbi,
+                            const int32_t* const* cat_map, const int32_t* const* ids,
+                            const int64_t* n, int d, const float* scale, float* const* out,
+                            const int64_t* ldo, float* const* bias_out, const int64_t* ldb, void* stream);
 
 /* ---- a5: multi-hot gather + segment-mean (K1) ---------------------------
  * embed_attribute.py:382-407 with mulhot_index.py:48-67 fused in:
@@ -325,16 +321,16 @@ int arx_neg_draw_weighted(const int32_t* users, int64_t B, int64_t n_users, cons
  *   C[M,N] = alpha * op(A)[M,K] . op(B)[K,N] + beta * C + col_bias[n]
  * transA=0: A stored [M,K] (lda>=K); transA=1: A stored [K,M] (lda>=M).
  * transB=0: B stored [K,N] (ldb>=N); transB=1: B stored [N,K] (ldb>=K).
- * col_bias nullable.  Split-K (deterministic, workspace partials) is chosen
+ * col_bias nullable.  Additionally a_rowsum[m] = sum_k op(A)[m,k] (nullable).  With
+ * op(A) = dlogits^T this is the item-bias gradient (embed_attribute.py:171 `+ bias`
+ * back-propagated), produced by the dI GEMM for free instead of a separate pass.
+ * Split-K (deterministic, workspace partials) is chosen
  * internally; workspace >= arx_gemm_f32_workspace_bytes(M,N,K). */
 size_t arx_gemm_f32_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int arx_gemm_f32(int transA, int transB, int64_t M, int64_t N, int64_t K, float alpha,
                  const float* A, int64_t lda, const float* B, int64_t ldb, float beta,
-                 float* C, int64_t ldc, const float* col_bias,
+                 float* C, int64_t ldc, const float* col_bias, float* a_rowsum,
                  void* workspace, size_t workspace_bytes, void* stream);
-/* Same, and additionally a_rowsum[m] = sum_k op(A)[m,k] (nullable).  With
- * op(A) = dlogits^T this is the item-bias gradient (embed_attribute.py:171 `+ bias`
- * back-propagated), produced by the dI GEMM for free instead of a separate pass. */
 /* EXPERIMENT (off unless ARX_GEMM_BX6=1 in arx.ops): the same C = A . B^T + col_bias
  * (embed_attribute.py:171 matmul(user, item^T) + bias), f32 in / f32 out, on the bf16 matrix pipe: every
  * f32 operand is split exactly into three bf16 pieces and six of the nine piece products (the other three are
@@ -355,10 +351,6 @@ int arx_gemm_nt_bx6(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda
 int arx_gemm_bt_bx6_supported(int64_t M, int64_t N, int64_t K);
 int arx_gemm_bt_bx6(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* Bt, int64_t ldb,
                     float beta, float* C, int64_t ldc, void* stream);
-int arx_gemm_f32_rowsum(int transA, int transB, int64_t M, int64_t N, int64_t K, float alpha,
-                        const float* A, int64_t lda, const float* B, int64_t ldb, float beta,
-                        float* C, int64_t ldc, const float* col_bias, float* a_rowsum,
-                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* Per-time-step TN products for the LSTM path (seqModel.py:480-493 scores every
  * step against the same pool): for t in [0,steps): C_steps[t] = A_t^T . B_t with
@@ -440,41 +432,36 @@ int arx_item_frequency(const int32_t* item_ids, int64_t n, int64_t n_items, int6
  * of S sequential weighted draws without replacement.  weights [n] need not be normalised;
  * entries <= 0 are never drawn.  out_idx [S]: item positions in draw order (-1 if fewer than S
  * positive weights).  Deterministic in (seed, counter); NOT numpy's random stream.
- * workspace >= arx_sample_wor_workspace_bytes(n). */
-size_t arx_sample_wor_workspace_bytes(int64_t n);
-int arx_sample_wor(const float* weights, int64_t n, int64_t S, uint64_t seed, uint64_t counter,
-                   int32_t* out_idx, void* workspace, size_t workspace_bytes, void* stream);
-/* The same draw with a pre-filter for very large item sets: keys above key_cap (> 0) are dropped
- * before the sort.  With key_cap = c * S / sum(weights) about c * S items survive (key_i < t with
- * probability 1 - exp(-w_i t)), so for c = 8 the S smallest keys are all below the cap except with
+ *
+ * key_cap > 0 is a pre-filter for very large item sets: keys above key_cap are dropped before the
+ * sort (key_cap <= 0: no cap).  With key_cap = c * S / sum(weights) about c * S items survive (key_i < t
+ * with probability 1 - exp(-w_i t)), so for c = 8 the S smallest keys are all below the cap except with
  * probability < exp(-3S) and the result is the un-capped one -- while the sort's later passes
  * handle ~8 S entries instead of n (100 M-item shard: ~5 ms -> ~0.3 ms per redraw).  Entries of
  * out_idx are -1 if fewer than S keys survive.
  * Draws of S <= 2048 items with a cap never store the n keys: the survivors are appended to a list
  * of 16384 entries and sorted by one workgroup (same keys, same (key, item) order: the same draw; the
- * workspace is arx_sample_wor_keys_workspace_bytes(n, S, key_cap) = 128 KB instead of 28 n bytes).  A
- * cap that lets MORE than 16384 keys through (8 S expected survivors is the contract) yields -1 in
- * every entry. */
-int arx_sample_wor_capped(const float* weights, int64_t n, int64_t S, uint64_t seed, uint64_t counter,
-                          float key_cap, int32_t* out_idx, void* workspace, size_t workspace_bytes,
-                          void* stream);
-size_t arx_sample_wor_keys_workspace_bytes(int64_t n, int64_t S, float key_cap);
+ * workspace is 128 KB instead of 28 n bytes).  A cap that lets MORE than 16384 keys through (8 S
+ * expected survivors is the contract) yields -1 in every entry.
+ *
+ * out_keys [S] (NULL: not wanted): the race keys of the drawn items, ascending; +inf where out_idx is
+ * -1.  For ONE draw over an item set that is sharded over several ranks (the reference draws
+ * its S negatives from one distribution, prepare_train.py:7-17): every rank races its own shard
+ * -- weights on a common scale, independent seeds --, the ranks exchange their S smallest (key, id)
+ * pairs and keep the S smallest of the union: the S smallest keys of the whole item set, i.e. exactly
+ * the single-process draw (arx.dist.draw_global_pool).
+ *
+ * workspace >= arx_sample_wor_workspace_bytes(n, S, key_cap). */
+size_t arx_sample_wor_workspace_bytes(int64_t n, int64_t S, float key_cap);
+int arx_sample_wor(const float* weights, int64_t n, int64_t S, uint64_t seed, uint64_t counter,
+                   float key_cap, int32_t* out_idx, float* out_keys, void* workspace,
+                   size_t workspace_bytes, void* stream);
 /* The S smallest of m (key, id) pairs in (key, position) order: out[r] = id of the pair of rank r.  Merges the
  * ranks' race lists of ONE negative-pool draw over an item set whose weights are sharded (utils/prepare_train.py:7-17
  * draws the pool from one distribution; arx.dist.draw_global_pool all-gathers every rank's S smallest (key, id) pairs
  * rank-major: ties go to the lower rank, then to the earlier entry -- a stable order, identical on every rank).
  * keys: non-negative floats or +inf.  m <= 16384, 0 < S <= m.  One launch. */
 int arx_merge_keyed_take(const float* keys, const int32_t* ids, int64_t m, int64_t S, int32_t* out, void* stream);
-
-/* ... and the race keys of the drawn items (out_keys [S], ascending; +inf where out_idx is -1; NULL:
- * not wanted).  For ONE draw over an item set that is sharded over several ranks (the reference draws
- * its S negatives from one distribution, prepare_train.py:7-17): every rank races its own shard
- * -- weights on a common scale, independent seeds --, the ranks exchange their S smallest (key, id)
- * pairs and keep the S smallest of the union: the S smallest keys of the whole item set, i.e. exactly
- * the single-process draw (arx.dist.draw_global_pool). */
-int arx_sample_wor_keys(const float* weights, int64_t n, int64_t S, uint64_t seed, uint64_t counter,
-                        float key_cap, int32_t* out_idx, float* out_keys, void* workspace,
-                        size_t workspace_bytes, void* stream);
 
 /* rs / rs-sig / rs-sig2 / bbpr losses (embed_attribute.py:551-603 _compute_rs_loss) over full
  * logits [B, V], forward + backward fused.  kind: 0 rs, 1 rs-sig, 2 rs-sig2, 3 bbpr;
@@ -539,7 +526,7 @@ int arx_eval_finish(int mode, const float* acc0, const float* acc1, const float*
  * products (the other three are below 2^-26 of the product) are accumulated in f32 with the small terms in
  * their own accumulator; where one operand is the 0/1 hinge-activity matrix (exact in ONE piece) three do.
  *
- * arx_mw_scorer_fwd (three launches):
+ * arx_mw_scorer_fwd (three launches, phases = 7):
  *   t_r = U_r . T_r + tbias_r;   x = U . P^T + pbias  (not stored);
  *   act[r, s] = mask[r, s] and (x[r, s] - t_r + 1 > 0), one bit per logit, kept in `state`;
  *   loss_r = log(1 + sum_s act * (x - t + 1));  g_r = gscale * row_w_r / (1 + sum);  dt_r = -g_r * #act
@@ -548,12 +535,24 @@ int arx_eval_finish(int mode, const float* acc0, const float* acc1, const float*
  * dU = dt * T and dT = dt * U (rank-one terms of the target score, WRITTEN; nullable).  `state` keeps what the
  * backward products read: the act bits in both orientations, g, the bf16 planes of P (both layouts) and of
  * g * U, the bias-gradient partials.
+ *   phases picks the launches -- bit 0 the pool planes, the positives' hit lists and (since round 5) the target
+ *   scores t_r = U_r . T_r + tb_r, written to the state and to tscore_out (needs U and T: no longer ahead of the
+ *   lookups), bit 1 the hinge GEMM (act bits, partial sums; reads the target scores bit 0 left), bit 2 the row
+ *   kernel (loss, g, rank-one terms, the g U planes); in this order on one stream.
+ *   seq_w (nullable; the sequence model, seqModel.py:561-567): with seq_w [B] (time-major, B = L * seq_rows) the
+ *   row weights are formed on the way -- row_w[t * seq_rows + b] = seq_w[t * seq_rows + b] / (sum_t seq_w[t *
+ *   seq_rows + b] + 1e-12) is WRITTEN to row_w by the launch of phase bit 0 and read by the row kernel (the
+ *   arithmetic of arx_seq_weights).  seq_w == NULL (seq_rows 0): row_w is an input (nullable).
  * arx_mw_scorer_bwd_du:  dU[r, :] = beta dU[r, :] + g_r sum_s act[r, s] P[s, :]
  * arx_mw_scorer_bwd_di:  dI[s, :] = beta dI[s, :] + sum_r act[r, s] g_r U[r, :],  db[s] = sum_r act[r, s] g_r;
  *   step_rows > 0 (the sequence model: B = L * step_rows time-major rows, step_rows % 128 == 0): the products of
  *   the single time steps are kept too -- dI_steps [L][S][d] (NULL: they live in the workspace only) and
  *   db_steps [L][S] -- because TF-1.0's clip_by_global_norm squares one dense gradient per unrolled step
  *   (seqModel.py:179-180).
+ *   loss_out (nullable): *loss_out = gscale * sum_r row_w[r] * batch_loss[r] over the B row losses the forward
+ *   wrote (row_w NULL: ones) -- hmf_model.py:140 reduce_mean with gscale = 1 / B; seqModel.py:571-604 with row_w
+ *   the normalised example weights -- added up in a fixed order by one more block of the reduce launch.  loss_out
+ *   NULL: no sum is formed (batch_loss, gscale and row_w may be NULL / 0 then).
  * Shapes: d in {64, 128}, S % 128 == 0, 128 <= S <= 2048, any B >= 1; U / P / T / dU / dT / dI rows 16-byte
  * aligned (ld % 4 == 0).  arx_mw_scorer_supported tells; callers take the unfused path (arx_gemm_f32 +
  * arx_loss_mw_fused_pos) otherwise.  `state`: arx_mw_scorer_state_bytes(B, S, d) bytes, 256-byte aligned,
@@ -564,48 +563,20 @@ int arx_eval_finish(int mode, const float* acc0, const float* acc1, const float*
 int arx_mw_scorer_supported(int64_t B, int64_t S, int d);
 size_t arx_mw_scorer_state_bytes(int64_t B, int64_t S, int d);
 int arx_mw_scorer_state_layout(int64_t B, int64_t S, int d, int64_t* out);
-int arx_mw_scorer_fwd(const float* U, int64_t ldu, const float* P, int64_t ldp, const float* pbias, const float* T,
-                      int64_t ldt, const float* tbias, int64_t tb_stride, int d, const int32_t* user_ids,
-                      const int32_t* pos_ptr, const int32_t* pos_items, const int32_t* item2slot, int64_t mask_rows,
-                      float gscale, const float* row_w, int64_t B, int64_t S, float* batch_loss, float* tscore_out,
-                      float* dtscore, int64_t dtscore_stride, float* dU, int64_t lddu, float* dT, int64_t lddt,
-                      void* state, size_t state_bytes, void* stream);
-/* the same in parts -- phases: bit 0 the pool planes, the positives' hit lists and (since round 5) the target scores
- * t_r = U_r . T_r + tb_r, written to the state and to tscore_out (needs U and T: no longer ahead of the lookups),
- * bit 1 the hinge GEMM (act bits, partial sums; reads the target scores bit 0 left), bit 2 the row kernel (loss, g,
- * rank-one terms, the g U planes); in this order on one stream.  arx_mw_scorer_fwd == phases 7. */
-int arx_mw_scorer_fwd_phases(const float* U, int64_t ldu, const float* P, int64_t ldp, const float* pbias,
-                             const float* T, int64_t ldt, const float* tbias, int64_t tb_stride, int d,
-                             const int32_t* user_ids, const int32_t* pos_ptr, const int32_t* pos_items,
-                             const int32_t* item2slot, int64_t mask_rows, float gscale, const float* row_w, int64_t B,
-                             int64_t S, float* batch_loss, float* tscore_out, float* dtscore, int64_t dtscore_stride,
-                             float* dU, int64_t lddu, float* dT, int64_t lddt, void* state, size_t state_bytes,
-                             int phases, void* stream);
-/* arx_mw_scorer_fwd_phases for the sequence model (seqModel.py:561-567): with seq_w [B] (time-major, B = L *
- * seq_rows) the row weights are formed on the way -- row_w[t * seq_rows + b] = seq_w[t * seq_rows + b] /
- * (sum_t seq_w[t * seq_rows + b] + 1e-12) is WRITTEN to row_w by the launch of phase bit 0 and read by the row
- * kernel (the arithmetic of arx_seq_weights).  seq_w == NULL: row_w is an input (nullable), as above. */
-int arx_mw_scorer_fwd_seqw(const float* U, int64_t ldu, const float* P, int64_t ldp, const float* pbias,
-                           const float* T, int64_t ldt, const float* tbias, int64_t tb_stride, int d,
-                           const int32_t* user_ids, const int32_t* pos_ptr, const int32_t* pos_items,
-                           const int32_t* item2slot, int64_t mask_rows, float gscale, float* row_w,
-                           const float* seq_w, int64_t seq_rows, int64_t B, int64_t S, float* batch_loss,
-                           float* tscore_out, float* dtscore, int64_t dtscore_stride, float* dU, int64_t lddu,
-                           float* dT, int64_t lddt, void* state, size_t state_bytes, int phases, void* stream);
+int arx_mw_scorer_fwd(const float* U, int64_t ldu, const float* P, int64_t ldp, const float* pbias,
+                      const float* T, int64_t ldt, const float* tbias, int64_t tb_stride, int d,
+                      const int32_t* user_ids, const int32_t* pos_ptr, const int32_t* pos_items,
+                      const int32_t* item2slot, int64_t mask_rows, float gscale, float* row_w,
+                      const float* seq_w, int64_t seq_rows, int64_t B, int64_t S, float* batch_loss,
+                      float* tscore_out, float* dtscore, int64_t dtscore_stride, float* dU, int64_t lddu,
+                      float* dT, int64_t lddt, void* state, size_t state_bytes, int phases, void* stream);
 int arx_mw_scorer_bwd_du(int64_t B, int64_t S, int d, const void* state, float beta, float* dU, int64_t lddu,
                          void* stream);
 size_t arx_mw_scorer_bwd_di_workspace_bytes(int64_t B, int64_t S, int d, int64_t step_rows);
-int arx_mw_scorer_bwd_di(int64_t B, int64_t S, int d, const void* state, int64_t step_rows, float beta, float* dI,
-                         int64_t lddi, float* db, float* dI_steps, float* db_steps, void* workspace,
-                         size_t workspace_bytes, void* stream);
-/* The same, and *loss_out = gscale * sum_r row_w[r] * batch_loss[r] over the B row losses the forward wrote (row_w
- * NULL: ones) -- hmf_model.py:140 reduce_mean with gscale = 1 / B; seqModel.py:571-604 with row_w the normalised
- * example weights -- added up in a fixed order by one more block of the reduce launch.  loss_out NULL:
- * arx_mw_scorer_bwd_di. */
-int arx_mw_scorer_bwd_di_loss(int64_t B, int64_t S, int d, const void* state, int64_t step_rows, float beta,
-                              float* dI, int64_t lddi, float* db, float* dI_steps, float* db_steps,
-                              const float* batch_loss, float gscale, const float* row_w, float* loss_out,
-                              void* workspace, size_t workspace_bytes, void* stream);
+int arx_mw_scorer_bwd_di(int64_t B, int64_t S, int d, const void* state, int64_t step_rows, float beta,
+                         float* dI, int64_t lddi, float* db, float* dI_steps, float* db_steps,
+                         const float* batch_loss, float gscale, const float* row_w, float* loss_out,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* Sampled softmax ('mce').  BUILD-DEFINED: the reference accepts loss 'mce'
  * (embed_attribute.py:527 assert, :717 feed guard, run_hmf.py:31,100, lstm/run.py:447) but its
@@ -643,13 +614,13 @@ int arx_loss_mce_fused_pos(const float* logits, int64_t ldl, const float* U, int
  * materialising entry point's max shift does not), backward weight w_rs = coef_r m_rs e_rs, coef_r = gscale row_w_r /
  * (1 + s_r), dt_r = -coef_r s_r.  The weight tile is recomputed where it is used and consumed out of the MFMA
  * accumulators (six-term f32-exact x, e split into three exact bf16 pieces, six-term products):
- *   arx_mce_scorer_fwd (phases bit 0: k_sc_prep as in arx_mw_scorer_fwd_seqw, whose walk of the positives chain
+ *   arx_mce_scorer_fwd (phases bit 0: k_sc_prep as in arx_mw_scorer_fwd, whose walk of the positives chain
  *     leaves the masked pairs as one bit row per USER row -- mask_rows must be B (or 0) or a multiple of 128 that
  *     divides B; bit 1: one pass over U . P^T that leaves s_r AND O_r = sum_s m e_rs P_s; bit 2: the
  *     row kernel): batch_loss, tscore_out, dtscore = dt, dT = dt U, dU = coef O + dt T (WRITTEN: the latent-side
  *     product is complete, there is no bwd_du), and in `state` the planes of U and coef U, coef, -t.
- *   arx_mce_scorer_bwd_di_loss: dI[s, :] = beta dI[s, :] + sum_r w_rs U[r, :], db[s] = sum_r w_rs; pbias = the pool
- *     bias and mask_rows the mask_rows the forward was given; step_rows / dI_steps / db_steps / loss_out as in arx_mw_scorer_bwd_di_loss.
+ *   arx_mce_scorer_bwd_di: dI[s, :] = beta dI[s, :] + sum_r w_rs U[r, :], db[s] = sum_r w_rs; pbias = the pool
+ *     bias and mask_rows the mask_rows the forward was given; step_rows / dI_steps / db_steps / loss_out as in arx_mw_scorer_bwd_di.
  * Shapes: d in {64, 128} (128: round 6), S % 128 == 0, 128 <= S <= 2048, B >= 1, rows 16-byte aligned; arx_mce_scorer_supported tells,
  * callers take arx_gemm_f32 + arx_loss_mce_fused_pos otherwise.  `state`: arx_mce_scorer_state_bytes bytes, 256-byte
  * aligned, zeroed once, private to one (model, stream). */
@@ -663,10 +634,10 @@ int arx_mce_scorer_fwd(const float* U, int64_t ldu, const float* P, int64_t ldp,
                        int64_t lddu, float* dT, int64_t lddt, void* state, size_t state_bytes, int phases,
                        void* stream);
 size_t arx_mce_scorer_bwd_di_workspace_bytes(int64_t B, int64_t S, int d, int64_t step_rows);
-int arx_mce_scorer_bwd_di_loss(int64_t B, int64_t S, int d, const void* state, const float* pbias, int64_t mask_rows,
-                               int64_t step_rows, float beta, float* dI, int64_t lddi, float* db, float* dI_steps, float* db_steps,
-                               const float* batch_loss, float gscale, const float* row_w, float* loss_out,
-                               void* workspace, size_t workspace_bytes, void* stream);
+int arx_mce_scorer_bwd_di(int64_t B, int64_t S, int d, const void* state, const float* pbias, int64_t mask_rows,
+                          int64_t step_rows, float beta, float* dI, int64_t lddi, float* db, float* dI_steps, float* db_steps,
+                          const float* batch_loss, float gscale, const float* row_w, float* loss_out,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 int arx_loss_warp_fwdbwd_pos(const float* logits, int64_t ldl, const int32_t* target,
                              const int32_t* user_ids, const int32_t* pos_ptr,
@@ -702,23 +673,16 @@ int arx_loss_warp_eval(const float* logits, int64_t ldl, const int32_t* target,
  * acc == NULL (then bias_acc == NULL too): plain gradient descent, E[row] -= lr * g -- the
  * GradientDescentOptimizer branch of seqModel.py:175-176; the same holds for arx_sparse_adagrad_cat
  * (sorted pass), arx_sparse_adagrad_cat_multi (acc[t] == NULL) and arx_adagrad_dense.
- * key_bits: number of significant key bits (0 => 31) to shorten the sort. */
+ * key_bits: number of significant key bits (0 => 31) to shorten the sort.
+ * aux_cnt (nullable): a per-table-row ticket counter (caller-owned int32[table rows],
+ * zero-initialised once, left clean): long runs of duplicates are then completed by
+ * their last-arriving piece inside the same launch instead of a second pass. */
 size_t arx_sparse_adagrad_workspace_bytes(int64_t n);
 int arx_sparse_adagrad(float* E, float* acc, float* bias, float* bias_acc, int d,
                        const int32_t* keys, const int32_t* src, const float* coef, int64_t n,
-                       const float* G, int64_t ldg, const float* Gb,
-                       const float* lr_dev, const float* gscale_dev, int key_bits,
+                       const float* G, int64_t ldg, const float* Gb, const float* lr_dev,
+                       const float* gscale_dev, int key_bits, int32_t* aux_cnt,
                        void* workspace, size_t workspace_bytes, void* stream);
-
-/* Same with a per-table-row ticket counter (aux_cnt: caller-owned int32[table rows],
- * zero-initialised once, left clean): long runs of duplicates are then completed by
- * their last-arriving piece inside the same launch instead of a second pass.
- * aux_cnt == NULL behaves exactly like arx_sparse_adagrad. */
-int arx_sparse_adagrad_ticket(float* E, float* acc, float* bias, float* bias_acc, int d,
-                              const int32_t* keys, const int32_t* src, const float* coef, int64_t n,
-                              const float* G, int64_t ldg, const float* Gb, const float* lr_dev,
-                              const float* gscale_dev, int key_bits, int32_t* aux_cnt,
-                              void* workspace, size_t workspace_bytes, void* stream);
 
 /* Fast path of the above for one-hot lookups with few contributions (id-only batches:
  * n = sum(site_n) <= ~64 k).  The lookup sites are described directly -- site s
@@ -758,36 +722,24 @@ int arx_sparse_adagrad_cat(float* E, float* acc, float* bias, float* bias_acc, i
  * e occupies extra_n[e] entries starting at sum(site_n) + sum(extra_n[:e]), table-local token
  * keys, padded with ARX_KEY_NONE) and names the table of each segment in extra_table[e].
  * ntables <= 4, nsites <= 8, nextra <= 8, rows + table bits <= 30.
+ * The pass runs in two halves: phase 1 = key generation + sort (depends on the lookup ids only --
+ * it can run on a side stream under the forward/backward GEMMs), phase 2 = apply (needs G);
+ * phase 3 = both.  Both halves take the same arguments and the same, otherwise untouched,
  * workspace >= arx_sparse_adagrad_workspace_bytes(sum(site_n) + sum(extra_n)). */
-int arx_sparse_adagrad_cat_multi(int ntables, float* const* E, float* const* acc, float* const* bias,
-                                 float* const* bias_acc, const int64_t* table_rows,
-                                 int32_t* const* aux_cnt, int d, int nsites,
-                                 const int32_t* site_table, const int32_t* const* site_cat_map,
+int arx_sparse_adagrad_cat_multi(int phase, int ntables, float* const* E, float* const* acc,
+                                 float* const* bias, float* const* bias_acc,
+                                 const int64_t* table_rows, int32_t* const* aux_cnt, int d,
+                                 int nsites, const int32_t* site_table,
+                                 const int32_t* const* site_cat_map,
                                  const int32_t* const* site_ids, const int64_t* site_n,
-                                 const int32_t* site_row_base, const float* site_coef, const float* G,
-                                 int64_t ldg, const float* Gb, const float* lr_dev,
+                                 const int32_t* site_row_base, const float* site_coef,
+                                 const float* G, int64_t ldg, const float* Gb, const float* lr_dev,
                                  const float* gscale_dev, int32_t* keys_buf, int32_t* src_buf,
                                  float* coef_buf, int nextra, const int64_t* extra_n,
                                  const int32_t* extra_table, void* workspace,
                                  size_t workspace_bytes, void* stream);
-/* The same pass in two halves: phase 1 = key generation + sort (depends on the lookup ids only --
- * it can run on a side stream under the forward/backward GEMMs), phase 2 = apply (needs G);
- * phase 3 = both.  Both halves take the same arguments and the same, otherwise untouched,
- * workspace. */
-int arx_sparse_adagrad_cat_multi_phase(int phase, int ntables, float* const* E, float* const* acc,
-                                       float* const* bias, float* const* bias_acc,
-                                       const int64_t* table_rows, int32_t* const* aux_cnt, int d,
-                                       int nsites, const int32_t* site_table,
-                                       const int32_t* const* site_cat_map,
-                                       const int32_t* const* site_ids, const int64_t* site_n,
-                                       const int32_t* site_row_base, const float* site_coef,
-                                       const float* G, int64_t ldg, const float* Gb, const float* lr_dev,
-                                       const float* gscale_dev, int32_t* keys_buf, int32_t* src_buf,
-                                       float* coef_buf, int nextra, const int64_t* extra_n,
-                                       const int32_t* extra_table, void* workspace,
-                                       size_t workspace_bytes, void* stream);
 
-/* arx_sparse_adagrad_cat_multi_phase with a MULTI-HOT table riding on the pass (HET layout,
+/* arx_sparse_adagrad_cat_multi with a MULTI-HOT table riding on the pass (HET layout,
  * attributes/comb_attribute.py:151-176: an item has an id feature AND a multi-hot attribute, both looked
  * up with the same item ids and fed by the same gradient rows -- embed_attribute.py:383-400).  The
  * lookups of one-hot table 0 (site_table == 0) are also the entity lookups of the bags of table
@@ -808,7 +760,25 @@ int arx_sparse_adagrad_cat_multi_phase(int phase, int ntables, float* const* E, 
  * sorted order as well and the two apply phases cut the work by data flow: phase 7 = the runs of table 0 alone
  * (Adagrad on its rows + the merged rows), phase 8 = ONE launch with the token runs over the merged rows and the runs
  * of the other one-hot tables.  `win` (the default) measured 1-3 us/step faster at C3.
- * bag_workspace >= arx_sparse_adagrad_bags_workspace_bytes(lookups of table 0, max_len, d). */
+ * bag_workspace >= arx_sparse_adagrad_bags_workspace_bytes(lookups of table 0, max_len, d).
+ *
+ * csc_* (csc_qpos nullable): the riding table's STATIC token order (csc.hip).  The bag index
+ * (attributes/attribute.py: the feature CSR built once by _init_attributes, embed_attribute.py:265-318) never
+ * changes, so the token-major order of its (token, entity) pairs is built ONCE per table by the caller:
+ *   csc_qpos  int32[len(vals)]  CSR position p = starts[r] + j -> place q of the pair in the order sorted by
+ *                               (token, p); -1 for tokens outside [0, bag_rows) and for positions past max_len;
+ *   csc_qte   int32[2 * csc_nq] {token row, row of table 0} of every place;
+ *   csc_flags uint8[F + F / 16], F = csc_nq rounded up to 256: one flag byte per place, then one coarse byte per
+ *             16 places; ZERO on entry of phase 5 and zero again on return of phase 6 (1 and 3 hold both);
+ *   csc_slot_of int32[table_rows[0]] scratch (row of the merged gradients of an entity of the step).
+ * The step then neither expands nor sorts: phase 5 also marks the live pairs from the lookups of table 0, phase 6
+ * sweeps the flags out in place order (= the token-sorted list, entries of a token in (entity, position) order --
+ * for a standard CSR the order the stable sort produced: same bits) and extracts the run records -- 3 launches for
+ * 8 (the marks belong to phase 5 because phase 7 reads csc_slot_of and only waits for phase 5).  Used when
+ * csc_qpos != NULL, d >= 32 and lookups * max_len > 8192; otherwise (and with csc_qpos == NULL, the other csc_*
+ * then NULL / 0) the pass expands and sorts the bags as described above: same results bit for bit.
+ * phase: the phase number, optionally | 0x100 (this pass applies in the `split` form) or | 0x200 (`win`), whatever
+ * ARX_K7_RIDER says -- the same bits in every phase of a pass. */
 int arx_sparse_adagrad_cat_multi_bags(int phase, int ntables, float* const* E, float* const* acc,
                                       float* const* bias, float* const* bias_acc,
                                       const int64_t* table_rows, int32_t* const* aux_cnt, int d,
@@ -822,41 +792,9 @@ int arx_sparse_adagrad_cat_multi_bags(int phase, int ntables, float* const* E, f
                                       float* bag_E, float* bag_acc, float* bag_bias, float* bag_bias_acc,
                                       int64_t bag_rows, const int32_t* vals, const int32_t* starts,
                                       const int32_t* lens, int max_len, int32_t* bag_aux_cnt,
-                                      void* bag_workspace, size_t bag_workspace_bytes, void* stream);
-
-
-/* arx_sparse_adagrad_cat_multi_bags with the riding table's STATIC token order (csc.hip).  The bag index
- * (attributes/attribute.py: the feature CSR built once by _init_attributes, embed_attribute.py:265-318) never
- * changes, so the token-major order of its (token, entity) pairs is built ONCE per table by the caller:
- *   csc_qpos  int32[len(vals)]  CSR position p = starts[r] + j -> place q of the pair in the order sorted by
- *                               (token, p); -1 for tokens outside [0, bag_rows) and for positions past max_len;
- *   csc_qte   int32[2 * csc_nq] {token row, row of table 0} of every place;
- *   csc_flags uint8[F + F / 16], F = csc_nq rounded up to 256: one flag byte per place, then one coarse byte per
- *             16 places; ZERO on entry of phase 5 and zero again on return of phase 6 (1 and 3 hold both);
- *   csc_slot_of int32[table_rows[0]] scratch (row of the merged gradients of an entity of the step).
- * The step then neither expands nor sorts: phase 5 also marks the live pairs from the lookups of table 0, phase 6
- * sweeps the flags out in place order (= the token-sorted list, entries of a token in (entity, position) order --
- * for a standard CSR the order the stable sort produced: same bits) and extracts the run records -- 3 launches for
- * 8 (the marks belong to phase 5 because phase 7 reads csc_slot_of and only waits for phase 5).  Used when csc_qpos != NULL, d >= 32 and lookups * max_len > 8192; otherwise
- * (and with csc_qpos == NULL) identical to arx_sparse_adagrad_cat_multi_bags.
- * phase: the phase number, optionally | 0x100 (this pass applies in the `split` form) or | 0x200 (`win`), whatever
- * ARX_K7_RIDER says -- the same bits in every phase of a pass. */
-int arx_sparse_adagrad_cat_multi_bags_csc(int phase, int ntables, float* const* E, float* const* acc,
-                                          float* const* bias, float* const* bias_acc,
-                                          const int64_t* table_rows, int32_t* const* aux_cnt, int d,
-                                          int nsites, const int32_t* site_table,
-                                          const int32_t* const* site_cat_map,
-                                          const int32_t* const* site_ids, const int64_t* site_n,
-                                          const int32_t* site_row_base, const float* site_coef,
-                                          const float* G, int64_t ldg, const float* Gb, const float* lr_dev,
-                                          const float* gscale_dev, int32_t* keys_buf, int32_t* src_buf,
-                                          float* coef_buf, void* workspace, size_t workspace_bytes,
-                                          float* bag_E, float* bag_acc, float* bag_bias, float* bag_bias_acc,
-                                          int64_t bag_rows, const int32_t* vals, const int32_t* starts,
-                                          const int32_t* lens, int max_len, int32_t* bag_aux_cnt,
-                                          void* bag_workspace, size_t bag_workspace_bytes,
-                                          const int32_t* csc_qpos, const int32_t* csc_qte, uint8_t* csc_flags,
-                                          int32_t* csc_slot_of, int64_t csc_nq, void* stream);
+                                      void* bag_workspace, size_t bag_workspace_bytes,
+                                      const int32_t* csc_qpos, const int32_t* csc_qte, uint8_t* csc_flags,
+                                      int32_t* csc_slot_of, int64_t csc_nq, void* stream);
 
 /* Multi-hot lookups of ONE table (embed_attribute.py:397-406: embedding_lookup of the bag
  * tokens + unsorted_segment_sum / length; hmf_model.py:146-151 one Adagrad apply per variable),
@@ -1185,15 +1123,11 @@ int arx_lstm_fwd(const float* x, const float* W, const float* b, int64_t L, int6
 /* dhs: [L,B,h] upstream gradient of every output.  Produces dz [L,B,4h]
  * (pre-activation gate gradients, BPTT through h and c).  dx, dW and db are
  * then plain GEMMs / a column sum over dz that the caller issues
- * (arx_gemm_f32 with W_x^T, [x;h_prev]^T . dz, arx_col_sum). */
+ * (arx_gemm_f32 with W_x^T, [x;h_prev]^T . dz, arx_col_sum).  wxt [4h, din] (may be NULL) =
+ * W[0:din, :]^T, the B operand of dx = dz . W_x^T, is written on the way. */
 int arx_lstm_bwd(const float* W, const float* hs, const float* cs, const float* gates,
-                 const float* dhs, int64_t L, int64_t B, int din, int h, float* dz,
+                 const float* dhs, int64_t L, int64_t B, int din, int h, float* dz, float* wxt,
                  void* stream);
-/* The same, and wxt [4h, din] = W[0:din, :]^T (the B operand of dx = dz . W_x^T) written on the way
- * (wxt may be NULL). */
-int arx_lstm_bwd_wxt(const float* W, const float* hs, const float* cs, const float* gates,
-                     const float* dhs, int64_t L, int64_t B, int din, int h, float* dz, float* wxt,
-                     void* stream);
 
 /* *out = scale * sum_i x[i]*y[i] (single workgroup, fixed order): the weighted
  * sum of sequence_loss (seqModel.py:561-563,596). */

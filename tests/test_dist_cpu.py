@@ -307,7 +307,7 @@ def _pool_worker(rank, world, port, out_dir):
 
     class Shard(object):
         """Stand-in for DeviceSampler.sample_with_keys on this rank's rows (id % world == rank): the
-        exponential race arx_sample_wor_keys runs on device, here in numpy."""
+        exponential race arx_sample_wor runs on device, here in numpy."""
         def __init__(self):
             self.draw = 0
 

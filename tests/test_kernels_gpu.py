@@ -130,7 +130,7 @@ def test_gather_onehot_multi(dev, d, sizes):
 
 @pytest.mark.parametrize("d,sizes", [(128, [300, 77, 1030]), (64, [5, 0, 9])])
 def test_gather_onehot_multi_packed_sites(dev, d, sizes):
-    """arx_gather_onehot_multi_ld: sites whose bias goes to column d of their packed out rows ('packed'),
+    """arx_gather_onehot_multi: sites whose bias goes to column d of their packed out rows ('packed'),
     and a site that reorders PACKED rows and splits off their bias column (bias = column d of the table
     itself) -- the sharded step's fused lookups (arx.dist.ShardedHMF._step_body)."""
     from arx import ops
@@ -1443,7 +1443,7 @@ def test_mw_scorer(dev, B, S, d, mask_rows, maxpos):
     (user of row r = users[r % mask_rows]: the sequence model's time-major rows); then the two backward products
     and the bias gradient out of the bits, incl. the per-time-step products (step_rows).  maxpos = 100: positives
     lists longer than the 32 entries a half wave of k_sc_prep lists per round (round 5), most of them past the
-    kScHits = 8 pool slots a hit list holds (those rows walk their lists in k_sc_rows); B = 515: a ragged last
+    kScHits = 8 pool slots a hit list holds (those rows walk their lists in k_sc_rows_g); B = 515: a ragged last
     8-row hit-list block and 128-row tile."""
     from arx import ops
     import torch
@@ -1550,7 +1550,7 @@ def test_mw_scorer(dev, B, S, d, mask_rows, maxpos):
             np.testing.assert_allclose(dbs[k].cpu().numpy(), dl_dev[rows].sum(0), rtol=RTOL, atol=3e-8)
         np.testing.assert_allclose(dI2.cpu().numpy(), dl_dev.T @ U.astype(np.float64), rtol=RTOL, atol=3e-8)
     if mask_rows:
-        # the sequence model's example weights formed by the first launch (arx_mw_scorer_fwd_seqw): the arithmetic
+        # the sequence model's example weights formed by the first launch (arx_mw_scorer_fwd): the arithmetic
         # of arx_seq_weights bit for bit, and g / the scalar loss follow from them
         L = B // mask_rows
         w_raw = _t(dev, (rng.random(B) * (rng.random(B) > 0.2)).astype(np.float32))
@@ -1575,7 +1575,7 @@ def test_mw_scorer(dev, B, S, d, mask_rows, maxpos):
 @pytest.mark.parametrize("d", [64, 128])
 def test_mce_scorer(dev, B, S, mask_rows, maxpos, bias, d):
     """The build-defined sampled softmax 'mce' on the fused family (csrc/scorer.hip k_mc_flow / k_mc_rows:
-    arx_mce_scorer_fwd / _bwd_di_loss, d = 64 and -- round 6 -- d = 128) against the oracle's logits -> compute_loss('mce') ->
+    arx_mce_scorer_fwd / _bwd_di, d = 64 and -- round 6 -- d = 128) against the oracle's logits -> compute_loss('mce') ->
     compute_loss_bwd chain in f64: loss, target score, dt, dT = dt U, the COMPLETE latent gradient dU = dl . P + dt T
     out of the forward, then dI = beta dI + dl^T . U, db, the step's scalar loss and the per-time-step products.  No
     [B, S] array exists on the device; the positives of the row's user are masked pairs (maxpos = 400: rows with
@@ -1657,7 +1657,7 @@ def test_mce_scorer(dev, B, S, mask_rows, maxpos, bias, d):
             np.testing.assert_allclose(dbs[k].cpu().numpy(), dl[rows].sum(0), rtol=2e-5, atol=1e-12)
         err = np.abs(dI2.cpu().numpy() - dl.T @ U64)
         assert np.all(err <= 2e-6 * scale_i + 1e-12)
-        # the sequence model's example weights formed by the first launch, as in arx_mw_scorer_fwd_seqw
+        # the sequence model's example weights formed by the first launch, as in arx_mw_scorer_fwd
         w_raw = _t(dev, (rng.random(B) * (rng.random(B) > 0.2)).astype(np.float32))
         wn_ref = torch.empty(B, dtype=f32, device=dev)
         ops.seq_weights(w_raw, L, mask_rows, wn_ref)

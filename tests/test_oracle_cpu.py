@@ -743,10 +743,11 @@ def test_abi_argument_validation_without_gpu():
     assert lib.arx_mw_scorer_state_bytes(16384, 1024, 128) > 16384 * 1024 // 8       # at least the activity bits
     # a workspace that is too small is refused before any launch
     need = lib.arx_sparse_adagrad_workspace_bytes(4096)
-    # (pointers are only compared with NULL before the workspace check: small integers stand in for them)
-    rc = lib.arx_sparse_adagrad(1, 1, None, None, 64, 1, 1, 1, 4096, 1, 64, None, 1, None, 12, 1, need - 1, None)
+    # (pointers are only compared with NULL before the workspace check: small integers stand in for them; aux_cnt,
+    # behind key_bits = 12, is NULL: no ticket counters)
+    rc = lib.arx_sparse_adagrad(1, 1, None, None, 64, 1, 1, 1, 4096, 1, 64, None, 1, None, 12, None, 1, need - 1, None)
     assert rc == EWS, (rc, err())
     assert "workspace" in err()
-    assert lib.arx_sparse_adagrad(1, 1, None, None, 62, 1, 1, 1, 4096, 1, 64, None, 1, None, 12, 1, need, None) == EUNS
+    assert lib.arx_sparse_adagrad(1, 1, None, None, 62, 1, 1, 1, 4096, 1, 64, None, 1, None, 12, None, 1, need, None) == EUNS
     assert "d=62" in err()
-    assert lib.arx_sparse_adagrad(1, 1, None, None, 64, 1, 1, 1, 0, 1, 64, None, 1, None, 12, None, 0, None) == 0   # n = 0: nothing to do
+    assert lib.arx_sparse_adagrad(1, 1, None, None, 64, 1, 1, 1, 0, 1, 64, None, 1, None, 12, None, None, 0, None) == 0   # n = 0

@@ -129,7 +129,7 @@ def test_item_frequency_on_device_matches_reference_helper(dev):
 
 
 def test_capped_race_equals_uncapped(dev):
-    """arx_sample_wor_capped: dropping the keys above 8 S / sum(w) before the sort does not change the
+    """arx_sample_wor: dropping the keys above 8 S / sum(w) before the sort does not change the
     draw (the S smallest keys are below the cap), for skewed weights over 3 M items."""
     import torch
     from arx import ops

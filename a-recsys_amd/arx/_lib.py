@@ -1,4 +1,4 @@
-"""ctypes binding of libarx.so (include/arx.h).
+"""ctypes binding of libarx.so (include/arx.h and the extension header it includes, include/arx_tags.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -234,6 +234,13 @@ PROTOTYPES = {
     "arx_graph_destroy": (cint, [vp]),
 }
 
+# include/arx_tags.h (recommend within item tags), one-to-one as above
+TAGS_PROTOTYPES = {
+    "arx_topk_tags_fill": (cint, [f32p, i64, i64, i32, i64, i32p, i32p, i32p, i64, vp]),
+    "arx_gemm_nt_topk_filter_tags": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, f32p, i64, i32, f32p, i32p, i64,
+                                            cint, i32p, f32p, i64, i32p, i64, i32p, i32p, i32p, i32p, i32p, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -245,7 +252,7 @@ def _load():
             "libarx.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` (or `make -C a-recsys_amd/csrc`).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in PROTOTYPES.items():
+    for name, (res, args) in list(PROTOTYPES.items()) + list(TAGS_PROTOTYPES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -23,7 +23,7 @@ import torch
 
 from .. import graph as G
 from .. import ops
-from ..topk import TopKScan, logits_too_big, similar_scan
+from ..topk import TopKScan, logits_too_big, similar_scan, tag_words
 from ..utils.prepare_train import pair_draw_tables
 
 # the full-vocabulary loss a model trained with a sampled loss evaluates with (hmf_model.py:130,144; 'mce' -> 'ce':
@@ -77,6 +77,40 @@ def exclusion_csr(item_sets, n_keys, item2logit):
     if len(cols) == 0:
         cols = np.zeros(1, dtype=np.int64)          # (a valid device pointer; every list is empty)
     return out_ptr.astype(np.int32), cols.astype(np.int32)
+
+
+def item_tag_words(tags, item2logit, n_logits):
+    """One 32-bit tag word per LOGIT column, as int32 bit patterns [n_logits], for the recommend path within item tags
+    (arx_tags.h arx_topk_tags_fill).  tags, per ITEM index: an integer array [n_items] of words in [0, 2^32), or
+    {item_index: iterable of bit numbers 0..31}.  Items go through item2logit (a numpy array, -1 where an item has no
+    logit): an item without a logit is skipped, a column without an item gets 0; where two items share a column their
+    words are OR-ed."""
+    item2logit = np.asarray(item2logit)
+    if isinstance(tags, dict):
+        items = np.fromiter(tags.keys(), dtype=np.int64, count=len(tags))
+        words = np.zeros(len(tags), dtype=np.uint64)
+        for j, bits in enumerate(tags.values()):
+            for b in bits:
+                if isinstance(b, (bool, np.bool_)) or not isinstance(b, (int, np.integer)) or not 0 <= int(b) <= 31:
+                    raise ValueError("item tags: bit numbers must be integers in 0..31, got %r" % (b,))
+                words[j] |= np.uint64(1 << int(b))
+        if len(items) and items.min() < 0:
+            raise ValueError("item tags: negative item index")
+    else:
+        words = tags.cpu().numpy() if isinstance(tags, torch.Tensor) else np.asarray(tags)
+        if words.ndim != 1 or words.dtype == np.bool_ or not np.issubdtype(words.dtype, np.integer):
+            raise ValueError("item tags: an integer array [n_items] or a {item_index: bit numbers} dict")
+        if len(words) and (words.min() < 0 or words.max() >= 2 ** 32):
+            raise ValueError("item tags: words must lie in [0, 2^32)")
+        items = np.arange(len(words), dtype=np.int64)
+        words = words.astype(np.uint64)
+    ok = items < len(item2logit)
+    items, words = items[ok], words[ok]
+    cols = item2logit[items].astype(np.int64)
+    ok = (cols >= 0) & (cols < n_logits)
+    out = np.zeros(n_logits, dtype=np.uint32)
+    np.bitwise_or.at(out, cols[ok], words[ok].astype(np.uint32))
+    return out.view(np.int32)
 
 
 class FeatureList(list):
@@ -652,6 +686,37 @@ class EmbeddingAttribute(object):
         if ex is None:
             raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
         return (self.u_indices['input'].value, self.batch_size, ex[0], ex[1])
+
+    def prepare_item_tags(self, tags):
+        """The items' tag words for recommend(tags_any=, tags_all=): an integer array [n_items] of 32-bit words, or
+        {item_index: bit numbers 0..31} (item_tag_words).  Mapped to logit columns through item_ind2logit_ind and
+        uploaded once as int32 bit patterns [V]; a second call replaces the words in place."""
+        if self._item2logit_np is None:
+            raise ValueError("item tags need item_ind2logit_ind")
+        words = item_tag_words(tags, self._item2logit_np, self.logit_size)
+        dev = getattr(self, '_tags_dev', None)
+        if dev is None:
+            # the per-row request words are placeholders, fed per call: a captured plan replays with new words
+            self._tags_any = G.IdsInput(self.rt, self.batch_size, 'tags_any')
+            self._tags_all = G.IdsInput(self.rt, self.batch_size, 'tags_all')
+            self._tags_dev = self.rt.upload(words, torch.int32)
+        else:
+            dev.copy_(torch.from_numpy(words))
+
+    def tag_args(self):
+        """(col_tags, want_any, want_all, want_rows) of the recommend rows: row r is eligible by the words
+        [r % batch_size] of the two placeholders (ops.topk_tags_fill, ops.gemm_nt_topk_filter_tags)."""
+        dev = getattr(self, '_tags_dev', None)
+        if dev is None:
+            raise ValueError("tags_any / tags_all need prepare_item_tags() first")
+        return (dev, self._tags_any.value, self._tags_all.value, self.batch_size)
+
+    def feed_tag_words(self, tags_any, tags_all, what='recommend'):
+        """Check and feed the request words of one recommend call (topk.tag_words: ValueError before any feed)."""
+        self.tag_args()
+        wa, wl = tag_words(tags_any, tags_all, self.batch_size, what)
+        self._tags_any.feed(wa)
+        self._tags_all.feed(wl)
 
     def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536, output_feat=1):
         """Cosine nearest neighbours of items over the full vocabulary, in the latent space recommend scores against:

@@ -42,7 +42,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops as _ops
-from .topk import TopKScan, run_complete, similar_scan
+from .topk import TopKScan, run_complete, similar_scan, tag_words
 from .utils.prepare_train import pair_draw_tables
 
 
@@ -302,14 +302,15 @@ class HipBackend(object):
         self.ops.het_rows_range(E_id, bias_id, E_tok, bias_tok, vals, starts, lens, n_items, world, rank, c0, c1, out,
                                 bias_out=bias_out, all_owners=all_owners, scale=scale, block_rows=block_rows)
 
-    def shard_topk(self, U, E, bias, k, ex, values, indices, lse=None):
+    def shard_topk(self, U, E, bias, k, ex, values, indices, lse=None, tags=None):
         """Recommend's local stage: values / indices [B, k] = every row's k best of U . E^T + bias over the shard's
         rows, by (value desc, local column asc); ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols of local
         columns) or None.  The streaming top-k of StreamTopK (topk.TopKScan: fused filter GEMM, the chunked path
         after an overflow or for shapes the fused kernel does not take); a shard with fewer than k rows fills the rest
         with (-inf, -1).  lse [B] (optional): the log-sum-exp of every row's logits over ALL the shard's rows, excluded
-        ones included (TopKScan's want_lse); -inf for a shard without rows.  Buffers and GEMM workspace are this
-        stage's own (captured step graphs keep theirs)."""
+        ones included (TopKScan's want_lse); -inf for a shard without rows.  tags (optional): (col_tags [V] int32 of
+        the shard's rows, want_any, want_all, want_rows) -- only the rows eligible by their tag words enter a result
+        (TopKScan.run).  Buffers and GEMM workspace are this stage's own (captured step graphs keep theirs)."""
         ops = self.ops
         B, V, d = int(U.shape[0]), int(E.shape[0]), int(U.shape[1])
         if getattr(self, 'ws_rec', None) is None:
@@ -336,7 +337,7 @@ class HipBackend(object):
                               torch.empty((B, kk), dtype=torch.int32, device=U.device))
         vo, io = (values, indices) if kk == k else scan.short
         # (a candidate segment too short: this rank once more, chunked)
-        run_complete(scan, lambda: scan.run(U, E, bias, self.ws_rec, vo, io, ex))
+        run_complete(scan, lambda: scan.run(U, E, bias, self.ws_rec, vo, io, ex, tags=tags))
         if kk < k:
             values[:, :kk].copy_(vo)
             indices[:, :kk].copy_(io)
@@ -1437,13 +1438,29 @@ class ShardedHMF(object):
         return (torch.from_numpy(ptr.astype(np.int32)).to(self.device),
                 torch.from_numpy(cols.astype(np.int32)).to(self.device))
 
-    def recommend(self, users, k, exclude_seen=False, return_values=False):
+    def prepare_item_tags(self, tags):
+        """The items' 32-bit tag words for recommend(tags_any=, tags_all=): the FULL integer array [n_items] of words
+        in [0, 2^32), the same on every rank.  Each rank keeps its stripe tags[rank::world] on the device as int32 bit
+        patterns; not a collective.  A second call replaces the words.  (Serving metadata, like the exclusion lists:
+        checkpoints do not store them.)"""
+        t = tags.cpu().numpy() if isinstance(tags, torch.Tensor) else np.asarray(tags)
+        if t.ndim != 1 or len(t) != self.n_items or t.dtype == np.bool_ or not np.issubdtype(t.dtype, np.integer):
+            raise ValueError("item tags: an integer array of n_items = %d words" % self.n_items)
+        if len(t) and (t.min() < 0 or t.max() >= 2 ** 32):
+            raise ValueError("item tags: words must lie in [0, 2^32)")
+        mine = np.ascontiguousarray(t[self.rank::self.world].astype(np.uint32)).view(np.int32)
+        self._rec_tags = torch.from_numpy(mine).to(self.device)
+
+    def recommend(self, users, k, exclude_seen=False, return_values=False, tags_any=None, tags_all=None):
         """Full-vocabulary top-k (run_hmf.py:340-409: top_k(logits, top_N) per user) of the row-sharded model.  A
-        collective: every rank calls it with the same k and exclude_seen.  users: global ids this rank owns,
+        collective: every rank calls it with the same k and exclude_seen, and all with or all without tags.  users: global ids this rank owns,
         0 <= len(users) <= B_loc (the count may differ between ranks).  Returns int32 global item ids
         [len(users), k] on the device, ordered by (score desc, id asc) -- tf.nn.top_k's rule -- (and their float32
         scores with return_values); -1 (score -inf) where a user has fewer than k eligible items.  exclude_seen:
-        leave out each user's items of prepare_recommend_exclusions (ValueError without it).
+        leave out each user's items of prepare_recommend_exclusions (ValueError without it).  tags_any / tags_all
+        (an int: one word for every user, or one int per user): only the items whose tag word of prepare_item_tags
+        has a bit of `any` (0: no constraint) and every bit of `all`; the words travel with the user keys (two more
+        all_gathers); composes with exclude_seen.
 
           gather          this rank's user rows -> [B_loc, d] (padding rows: zeros, key -1)
           all_gather      latents [B_loc, d] -> [B, d], user ids [B_loc] -> [B]
@@ -1466,13 +1483,21 @@ class ShardedHMF(object):
             raise ValueError("recommend: users must be global ids in [0, %d) owned by rank %d" % (self.n_users, r))
         if exclude_seen and getattr(self, '_rec_ex', None) is None:
             raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
+        words = None
+        if tags_any is not None or tags_all is not None:
+            if getattr(self, '_rec_tags', None) is None:
+                raise ValueError("tags_any / tags_all need prepare_item_tags() first")
+            words = tag_words(tags_any, tags_all, len(u))
         with _ops.joined(self._stream if self.use_graphs else None):
-            vo, io = self._recommend(u, k, exclude_seen)
+            if words is None:
+                vo, io = self._recommend(u, k, exclude_seen)
+            else:
+                vo, io = self._recommend(u, k, exclude_seen, tags=words)
         n = len(u)
         ids = io[:n].clone()
         return (ids, vo[:n].clone()) if return_values else ids
 
-    def _recommend(self, u, k, exclude_seen):
+    def _recommend(self, u, k, exclude_seen, tags=None):
         be, W, B_loc, B, d = self.be, self.world, self.B_loc, self.B, self.d
         dev, f32, i32 = self.device, torch.float32, torch.int32
         n = len(u)
@@ -1500,7 +1525,25 @@ class ShardedHMF(object):
             dist.all_gather_into_tensor(keys_all, keys_loc, group=self.group)
         ex = (keys_all, B, self._rec_ex[0], self._rec_ex[1]) if exclude_seen else None
         ni = self.ni_loc
-        be.shard_topk(U_all, self.E_item[:ni], self.b_item[:ni], k, ex, out_v, out_i)
+        if tags is not None:
+            # the request words of this rank's users (padding rows: no constraint) -> every rank, like the keys;
+            # `tags=` goes to the backend only here, so one that does not know the argument serves the plain calls
+            if getattr(self, '_rec_words', None) is None:
+                z = lambda m: torch.zeros((m,), dtype=i32, device=dev)
+                loc = (z(B_loc), z(B_loc))
+                self._rec_words = loc + (loc if W == 1 else (z(B), z(B)))
+            any_loc, all_loc, any_all, all_all = self._rec_words
+            for dst, w in ((any_loc, tags[0]), (all_loc, tags[1])):
+                h = np.zeros(B_loc, dtype=np.int32)
+                h[:n] = w
+                dst.copy_(torch.from_numpy(h))
+            if W > 1:
+                dist.all_gather_into_tensor(any_all, any_loc, group=self.group)
+                dist.all_gather_into_tensor(all_all, all_loc, group=self.group)
+            be.shard_topk(U_all, self.E_item[:ni], self.b_item[:ni], k, ex, out_v, out_i,
+                          tags=(self._rec_tags[:ni], any_all, all_all, B))
+        else:
+            be.shard_topk(U_all, self.E_item[:ni], self.b_item[:ni], k, ex, out_v, out_i)
         if W == 1:
             recv_v, recv_c = out_v.view(1, B, k), out_i.view(1, B, k)
         else:
@@ -1981,12 +2024,13 @@ class ShardedW2V(ShardedHMF):
             super()._serve_latents(u, base)
             be.window_slots_fwd(block, r['cslots'], n, 0.5 / n, base, 0.5, out)
 
-    def recommend(self, users, context, k, exclude_seen=False, return_values=False):
+    def recommend(self, users, context, k, exclude_seen=False, return_values=False, tags_any=None, tags_all=None):
         """ShardedHMF.recommend over x_test of (users, context): context is [n_input][len(users)], time-major."""
         u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
         self._serve_ctx = self._context_array(context, int(u.size), "recommend")
         try:
-            return super().recommend(users, k, exclude_seen=exclude_seen, return_values=return_values)
+            return super().recommend(users, k, exclude_seen=exclude_seen, return_values=return_values,
+                                     tags_any=tags_any, tags_all=tags_all)
         finally:
             self._serve_ctx = None
 
@@ -2461,10 +2505,10 @@ class ShardedHetView(ShardedHMF):
         self._seen = (m.steps, m.n_restores)
         self.n_refresh += 1
 
-    def _recommend(self, u, k, exclude_seen):
+    def _recommend(self, u, k, exclude_seen, tags=None):
         if self._seen != (self.model.steps, self.model.n_restores):
             self._refresh()
-        return super()._recommend(u, k, exclude_seen)
+        return super()._recommend(u, k, exclude_seen, tags=tags)
 
     def _evaluate(self, u, it, loss):
         if self._seen != (self.model.steps, self.model.n_restores):

@@ -16,7 +16,8 @@ import torch
 from .. import graph as G
 from .. import ops
 from ..attributes import embed_attribute
-from ..topk import StreamTopK, TopK, TopKScan, excluding_twin, recommend_node, run_complete  # noqa: F401 (re-exported)
+from ..topk import (StreamTopK, TopK, TopKScan, excluding_twin, recommend_key, recommend_node,  # noqa: F401
+                    run_complete)                                                            # (re-exported)
 from ..utils.checkpoint import Saver
 
 
@@ -255,6 +256,19 @@ class LatentProductModel(object):
         self._plans.pop('recommend_ex', None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
+    def prepare_item_tags(self, tags):
+        """The items' 32-bit tag words for recommend(tags_any=, tags_all=): an integer array [n_items] or
+        {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces the words
+        (the captured plans that read them are dropped)."""
+        for key in ('recommend_tags', 'recommend_ex_tags'):
+            self._plans.pop(key, None)
+        self.att_emb.prepare_item_tags(tags)
+
+    def _recommend_node(self, key):
+        return {'recommend': self.topk, 'recommend_ex': getattr(self, 'topk_ex', None),
+                'recommend_tags': getattr(self, 'topk_tags', None),
+                'recommend_ex_tags': getattr(self, 'topk_ex_tags', None)}[key]
+
     def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536):
         """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the item latent space
         recommend scores against: EmbeddingAttribute.similar_items."""
@@ -295,6 +309,17 @@ class LatentProductModel(object):
             if getattr(self, 'topk_ex', None) is None:
                 self.topk_ex = excluding_twin(rt, self.topk, m.exclusion_args)
             p = G.Plan(rt, [self.topk_ex], False, [])
+        elif key == 'recommend_tags':
+            m.tag_args()                       # (raises before anything is built when no tags were prepared)
+            if getattr(self, 'topk_tags', None) is None:
+                self.topk_tags = excluding_twin(rt, self.topk, tag_args=m.tag_args)
+            p = G.Plan(rt, [self.topk_tags], False, [])
+        elif key == 'recommend_ex_tags':
+            m.exclusion_args()
+            m.tag_args()
+            if getattr(self, 'topk_ex_tags', None) is None:
+                self.topk_ex_tags = excluding_twin(rt, self.topk, m.exclusion_args, m.tag_args)
+            p = G.Plan(rt, [self.topk_ex_tags], False, [])
         elif key == 'warp_eval':
             p = G.Plan(rt, [self.batch_loss], False, [m.mask['warp_eval']])
         else:
@@ -378,17 +403,23 @@ class LatentProductModel(object):
 
     def step_async(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
                    item_sampled_id2idx=None, forward_only=False, recommend=False,
-                   recommend_new=False, loss=None, run_op=None, run_meta=None, exclude_seen=False):
+                   recommend_new=False, loss=None, run_op=None, run_meta=None, exclude_seen=False,
+                   tags_any=None, tags_all=None):
         """step() without the device->host read of the result: returns the MeanLoss
         node (call .read() for the device scalar) / the top-k index tensor.  recommend with the streaming top-k
         (StreamTopK, fused form): the result is complete only if `self.topk.overflowed()` is False afterwards
         (one device -> host read; step() checks it and re-runs the request on the chunked path).
         exclude_seen (with recommend): leave out each user's items of prepare_recommend_exclusions -- node
-        self.topk_ex, plan 'recommend_ex'; a user with fewer than top_N eligible items gets -1 tails."""
+        self.topk_ex, plan 'recommend_ex'; a user with fewer than top_N eligible items gets -1 tails.
+        tags_any / tags_all (with recommend; an int or one int per row): only the items eligible by their tag words
+        of prepare_item_tags -- plans 'recommend_tags' / 'recommend_ex_tags'; both None: the calls above."""
         if loss is None:
             loss = self.loss_function
         if exclude_seen and recommend:
             self.att_emb.exclusion_args()      # ValueError before any feed when nothing was prepared
+        tagged = recommend and (tags_any is not None or tags_all is not None)
+        if tagged:
+            self.att_emb.feed_tag_words(tags_any, tags_all)       # ValueError before any other feed
         # pair losses: a step without negatives draws them inside its plan (prepare_pair_negatives)
         pair = self.loss_function in ('bpr', 'bpr-hinge') and not recommend
         draw = pair and (neg_item_input is None or len(neg_item_input) == 0)
@@ -402,6 +433,10 @@ class LatentProductModel(object):
             if draw:
                 self.rt.drop_feed(self.att_emb.i_indices['neg'].value)    # (a queued older feed must not overwrite the draw)
             self.batch_loss.draw = self.att_emb.neg_draw if draw else None
+        if tagged:
+            key = recommend_key(exclude_seen, True)
+            self._plan(key).run()
+            return self._recommend_node(key).indices
         if recommend and exclude_seen:
             self._plan('recommend_ex').run()
             return self.topk_ex.indices
@@ -425,22 +460,26 @@ class LatentProductModel(object):
 
     def step(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
-             loss=None, run_op=None, run_meta=None, exclude_seen=False):
+             loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None):
         """hmf_model.py:162-228.  Returns: train -> mean loss (float); forward_only ->
         loss_eval (float); recommend -> int32 [mb, top_N]; warp_eval -> [loss, rank].
         'bpr' / 'bpr-hinge': neg_item_input (list, array or device tensor) holds one negative item per row; None or
         empty draws them on the device (prepare_pair_negatives first, else ValueError).  self.pos_score /
         neg_score / auc .read() give the last step's scores (hmf_model.py:104-107).
         recommend with exclude_seen=True: the top_N logit indices without each user's items of
-        prepare_recommend_exclusions (ValueError if none were prepared); -1 where a user has fewer eligible items."""
+        prepare_recommend_exclusions (ValueError if none were prepared); -1 where a user has fewer eligible items.
+        recommend with tags_any / tags_all (an int: one 32-bit word for every row, or one int per row): only the items
+        whose tag word of prepare_item_tags has a bit of `any` (0: no constraint) and every bit of `all`; composes
+        with exclude_seen.  ValueError without prepare_item_tags, for words outside [0, 2^32) or a wrong length."""
         run = lambda: self.step_async(session, user_input, item_input, neg_item_input, item_sampled,
                                       item_sampled_id2idx, forward_only, recommend, recommend_new, loss,
-                                      run_op, run_meta, exclude_seen=exclude_seen)
+                                      run_op, run_meta, exclude_seen=exclude_seen, tags_any=tags_any,
+                                      tags_all=tags_all)
         if recommend:
             # (a candidate list of the fused top-k too short for this batch: the request once more, chunked)
-            key = 'recommend_ex' if exclude_seen else 'recommend'
-            self._plan(key)                    # builds topk_ex / raises as the step would
-            node = self.topk_ex if exclude_seen else self.topk
+            key = recommend_key(exclude_seen, tags_any is not None or tags_all is not None)
+            self._plan(key)                    # builds the twin node / raises as the step would
+            node = self._recommend_node(key)
             return run_complete(node, run, lambda: self._plans.pop(key, None)).cpu().numpy()
         out = run()
         if isinstance(out, list):

@@ -23,7 +23,7 @@ from .. import graph as G
 from .. import ops
 from ..attributes.embed_attribute import Dropout, ZeroEmbed
 from ..hmf.hmf_model import _Op, _Var
-from ..topk import StreamTopK, excluding_twin, logits_too_big, run_complete
+from ..topk import StreamTopK, excluding_twin, logits_too_big, recommend_key, run_complete
 from ..utils.checkpoint import Saver
 from .batching import SeqBatching
 
@@ -271,20 +271,26 @@ class TopKSoftmax(G.Node):
     the softmax values of the k winners are exp(v - lse).
     exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
     the row logsumexp is taken over ALL the columns first, then each row's excluded columns are set to -inf IN the
-    logits and the select runs; winners of value -inf get index -1 (softmax value exp(-inf) = 0)."""
+    logits and the select runs; winners of value -inf get index -1 (softmax value exp(-inf) = 0).
+    tags (optional): a callable giving (col_tags, want_any, want_all, want_rows) (EmbeddingAttribute.tag_args): the
+    columns ineligible by their tag words are set to -inf the same way, after the logsumexp."""
 
-    def __init__(self, rt, logits, k, exclude=None):
+    def __init__(self, rt, logits, k, exclude=None, tags=None):
         super().__init__(rt, (logits.shape[0], k), (logits,))
         self.k = k
         self.exclude = exclude
+        self.tags = tags
         self.indices = torch.empty((logits.shape[0], k), dtype=torch.int32, device=rt.device)
         self.lse = torch.empty((logits.shape[0],), dtype=torch.float32, device=rt.device)
 
     def forward(self, train):
         x = self.inputs[0].value
-        if self.exclude is not None:
+        if self.exclude is not None or self.tags is not None:
             ops.row_logsumexp(x, self.lse)
-            ops.topk_exclude_fill(x, 0, self.exclude())
+            if self.exclude is not None:
+                ops.topk_exclude_fill(x, 0, self.exclude())
+            if self.tags is not None:
+                ops.topk_tags_fill(x, 0, self.tags())
             ops.topk(x, self.k, self.alloc_value(), self.indices)
             ops.topk_mark_empty(self.value, self.indices)
             return
@@ -519,6 +525,11 @@ class SeqModel(SeqBatching):
                     bk['recommend_ex'] = excluding_twin(self.rt, bk.get('recommend_stream', bk['recommend']),
                                                         m.exclusion_args)
                 bk['plans'][key] = G.Plan(self.rt, [bk['recommend_ex']], False, [])
+            elif key in ('recommend_tags', 'recommend_ex_tags'):
+                if key not in bk:               # (rows as above: the two request words are want_*[r % mb])
+                    bk[key] = excluding_twin(self.rt, bk.get('recommend_stream', bk['recommend']),
+                                             m.exclusion_args if key == 'recommend_ex_tags' else None, m.tag_args)
+                bk['plans'][key] = G.Plan(self.rt, [bk[key]], False, [])
             else:
                 bk['plans'][key] = G.Plan(self.rt, [bk['eval']], False, m.eval_masks(self.loss, bk['eval'].inputs[0]))
         return bk['plans'][key]
@@ -802,26 +813,43 @@ class SeqModel(SeqBatching):
             bk['plans'].pop('recommend_ex', None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
+    def prepare_item_tags(self, tags):
+        """The items' 32-bit tag words for step_recommend(tags_any=, tags_all=): an integer array [n_items] or
+        {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces them."""
+        for bk in self._bk.values():
+            for key in ('recommend_tags', 'recommend_ex_tags'):
+                bk['plans'].pop(key, None)
+        self.att_emb.prepare_item_tags(tags)
+
     def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536):
         """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the output item latents
         step_recommend scores against (EmbeddingAttribute.similar_items); output_feat 2 / 3: NotImplementedError."""
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
                                           chunk=chunk, output_feat=self.output_feat)
 
-    def step_recommend(self, session, user_input, item_inputs, positions, bucket_id, exclude_seen=False):
+    def step_recommend(self, session, user_input, item_inputs, positions, bucket_id, exclude_seen=False,
+                       tags_any=None, tags_all=None):
         """seqModel.py:326-353 -> [(uid, values[topk_n], indexes[topk_n])]: the top-k softmax
         values / logit indexes at time position positions[i] of sequence i.  Small vocabularies: the full
         [L*mb, V] logits are materialised; past ARX_STREAM_TOPK_BYTES (1 GB) the mb rows asked for are gathered
         and the fused full-vocabulary top-k + log-sum-exp of topk.StreamTopK runs on them (round 5).
         exclude_seen: leave out user_input[i]'s items of prepare_recommend_exclusions (plan 'recommend_ex'); the
         softmax normaliser stays over the full vocabulary, so a winner's value equals the non-excluding one; where
-        a user has fewer than topk_n eligible items the tail has index -1 and value 0.  Under
-        arx.dist.SeqHybridParallel the call is that wrapper's collective of the same name."""
+        a user has fewer than topk_n eligible items the tail has index -1 and value 0.
+        tags_any / tags_all (an int or one int per sequence): only the items eligible by their tag words of
+        prepare_item_tags (plans 'recommend_tags' / 'recommend_ex_tags'), the normaliser again over the full
+        vocabulary; composes with exclude_seen.  Under arx.dist.SeqHybridParallel the call is that wrapper's
+        collective of the same name (which takes no tags: NotImplementedError)."""
         dp = self.rt.dp
+        tagged = tags_any is not None or tags_all is not None
         if dp is not None and hasattr(dp, 'step_recommend'):
+            if tagged:
+                raise NotImplementedError("step_recommend with item tags under SeqHybridParallel")
             return dp.step_recommend(session, user_input, item_inputs, positions, bucket_id, exclude_seen)
         if exclude_seen:
             self.att_emb.exclusion_args()      # ValueError before any feed when nothing was prepared
+        if tagged:
+            self.att_emb.feed_tag_words(tags_any, tags_all, 'step_recommend')
         L = self.buckets[bucket_id]
         m, B = self.att_emb, self.batch_size
         it = item_inputs
@@ -831,16 +859,16 @@ class SeqModel(SeqBatching):
         m.add_input({}, user_input, None, forward_only=True, recommend=True, loss=self.loss)
         bk = self._bucket(bucket_id)
         users = user_input.cpu().numpy() if isinstance(user_input, torch.Tensor) else user_input
-        key = 'recommend_ex' if exclude_seen else 'recommend'
+        key = recommend_key(exclude_seen, tagged)
         if 'recommend_stream' in bk:
             bk['rec_rows'].feed(np.asarray([int(pos) * B + i for i, pos in enumerate(positions)], dtype=np.int32))
             self._plan(bucket_id, key)
-            node = bk['recommend_ex' if exclude_seen else 'recommend_stream']
+            node = bk['recommend_stream' if key == 'recommend' else key]
             run_complete(node, lambda: self._plan(bucket_id, key).run(), lambda: bk['plans'].pop(key, None))
             vals, idx, lse = node.value.cpu().numpy(), node.indices.cpu().numpy(), node.lse.cpu().numpy()
             return [(users[i], np.exp(vals[i] - lse[i]), idx[i]) for i in range(len(positions))]
         self._plan(bucket_id, key).run()
-        node = bk['recommend_ex' if exclude_seen else 'recommend']
+        node = bk[key]
         vals = node.value.cpu().numpy()
         idx = node.indices.cpu().numpy()
         lse = node.lse.cpu().numpy()

@@ -1295,6 +1295,37 @@ def topk_exclude_fill(logits, col0, ex):
          _p(keys), int(key_rows), _p(ptr), _p(cols), _stream())
 
 
+def topk_tags_fill(logits, col0, tags):
+    """logits[r, c - col0] = -inf where column c in [col0, col0 + logits.shape[1]) is ineligible for row r (arx_tags.h).
+    tags: (col_tags [V] int32 bit patterns by ABSOLUTE column, want_any, want_all, want_rows) -- row r's two words
+    are want_*[r % want_rows]."""
+    if logits.numel() == 0:
+        return
+    col_tags, want_any, want_all, want_rows = tags
+    if int(col0) + int(logits.shape[1]) > int(col_tags.shape[0]):
+        raise ValueError("topk_tags_fill: columns [%d, %d) past the %d tag words"
+                         % (col0, int(col0) + int(logits.shape[1]), int(col_tags.shape[0])))
+    call("arx_topk_tags_fill", _p(logits), _ld(logits), int(logits.shape[0]), int(col0), int(logits.shape[1]),
+         _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _stream())
+
+
+def gemm_nt_topk_filter_tags(A, Bm, col_bias, thr, col_base, cand_v, cand_i, capp, overflow, tags, ex=None,
+                             lse_part=None):
+    """gemm_nt_topk_filter_excl whose candidates also skip the columns ineligible by their tag words (arx_tags.h).  tags:
+    (col_tags, want_any, want_all, want_rows) with col_tags ALREADY sliced to this launch's columns (like col_bias);
+    ex: exclusion lists or None."""
+    col_tags, want_any, want_all, want_rows = tags
+    if int(col_tags.shape[0]) < int(Bm.shape[0]):
+        raise ValueError("gemm_nt_topk_filter_tags: %d tag words for %d columns"
+                         % (int(col_tags.shape[0]), int(Bm.shape[0])))
+    keys, key_rows, ptr, cols = ex if ex is not None else (None, 0, None, None)
+    call("arx_gemm_nt_topk_filter_tags", _p(A), _ld(A), int(A.shape[0]), _p(Bm), _ld(Bm), int(Bm.shape[0]),
+         int(A.shape[1]), _p(col_bias), _p(thr), int(thr.stride(0)), int(col_base), _p(cand_v), _p(cand_i),
+         int(cand_v.stride(0)), int(capp), _p(overflow), _p(lse_part),
+         int(lse_part.stride(0)) if lse_part is not None else 0, _p(keys), int(key_rows), _p(ptr), _p(cols),
+         _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _stream())
+
+
 def topk_mark_empty(values, indices):
     """indices = -1 where values == -inf (a row with fewer eligible columns than k)."""
     call("arx_topk_mark_empty", _p(values), _ld(values), _p(indices), _ld(indices), int(values.shape[0]),

@@ -1,12 +1,17 @@
 """Full-vocabulary top-k: the nodes (TopK, StreamTopK on TopKScan) and the serving rules every model shares --
 when the [rows, V] logits are too big to materialise (ARX_STREAM_TOPK_BYTES), which node recommends, the excluding
 twin of a node, and the chunked re-run after the fused candidate lists overflowed.  Depends on graph and ops only.
+Item tags (recommend within "only this category / in stock / this market"): every logit column carries one 32-bit tag
+word, every request row two words (any, all); column c is eligible for row r iff
+(any[r] == 0 or tags[c] & any[r]) and tags[c] & all[r] == all[r] -- the nodes take tags= beside exclude=, the rule
+itself lives in the kernels (arx_tags.h: arx_topk_tags_fill, arx_gemm_nt_topk_filter_tags).
 """
 from __future__ import annotations
 
 import contextlib
 import os
 
+import numpy as np
 import torch
 
 from . import graph as G
@@ -35,20 +40,26 @@ class TopK(G.Node):
     """hmf_model.py:154 tf.nn.top_k(logits, top_N_items, sorted=True).
     exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
     each row's excluded columns are set to -inf IN the logits before the select (nothing after this node may read
-    them), and winners of value -inf (rows with fewer than k eligible columns) get index -1."""
+    them), and winners of value -inf (rows with fewer than k eligible columns) get index -1.
+    tags (optional): a callable giving (col_tags, want_any, want_all, want_rows) (EmbeddingAttribute.tag_args), or
+    that tuple: the columns ineligible for a row by their tag words are set to -inf the same way; a column must pass
+    both."""
 
-    def __init__(self, rt, logits, k, exclude=None):
+    def __init__(self, rt, logits, k, exclude=None, tags=None):
         super().__init__(rt, (logits.shape[0], k), (logits,))
         self.k = k
         self.exclude = exclude
+        self.tags = tags
         self.indices = torch.empty((logits.shape[0], k), dtype=torch.int32, device=rt.device)
 
     def forward(self, train):
         x = self.inputs[0].value
         if self.exclude is not None:
             ops.topk_exclude_fill(x, 0, self.exclude())
+        if self.tags is not None:
+            ops.topk_tags_fill(x, 0, self.tags() if callable(self.tags) else self.tags)
         ops.topk(x, self.k, self.alloc_value(), self.indices)
-        if self.exclude is not None:
+        if self.exclude is not None or self.tags is not None:
             ops.topk_mark_empty(self.value, self.indices)
 
 
@@ -121,15 +132,24 @@ class TopKScan(object):
         finally:
             self.fused = was
 
-    def run(self, latent, pool, bias, ws, values, indices, ex=None, col_scale=None, self_col=None):
+    def run(self, latent, pool, bias, ws, values, indices, ex=None, col_scale=None, self_col=None, tags=None):
         """values / indices [B, k] = the top-k of latent . pool^T + bias (bias may be None) over all V >= k pool rows;
         ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace.
         col_scale [V] (None: every launch is the one above): the scores are (latent . pool^T) * col_scale[column] --
         cosines, with unit rows in latent and the pool's inverse row norms (similar_scan) -- and self_col [B] int32
         (optional) names the column each row leaves out (any value outside [0, V): none); a row with fewer than k
-        columns left ends in (-inf, -1).  No bias, no exclusion lists and no log-sum-exp in that form."""
+        columns left ends in (-inf, -1).  No bias, no exclusion lists and no log-sum-exp in that form.
+        tags: (col_tags [V] int32, want_any, want_all, want_rows) or None -- only the columns eligible for a row by
+        their tag words enter its result (composes with ex; the log-sum-exp stays over ALL the columns).  A tag too
+        rare to give k eligible columns in the first chunk leaves the threshold at -inf: the fused lists may then
+        overflow, and run_complete re-runs the request on the chunked path."""
         V, k = pool.shape[0], self.k
         cos = col_scale is not None
+        if cos and tags is not None:
+            raise ValueError("TopKScan.run: col_scale (the cosine form) takes no item tags")
+        if tags is not None and int(tags[0].shape[0]) != V:
+            raise ValueError("TopKScan.run: %d tag words for %d pool rows" % (int(tags[0].shape[0]), V))
+        empties = ex is not None or self_col is not None or tags is not None
         if cos and (self.want_lse or bias is not None or ex is not None):
             raise ValueError("TopKScan.run: col_scale goes with no bias, no exclusion lists and no log-sum-exp")
         if self_col is not None and not cos:
@@ -150,12 +170,18 @@ class TopKScan(object):
                 lp[:, parts].copy_(self._lse0)
             if ex is not None:
                 ops.topk_exclude_fill(lg, 0, ex)                # threshold = the k-th best ELIGIBLE column
+            if tags is not None:
+                ops.topk_tags_fill(lg, 0, tags)
             ops.topk_chunk(lg, k, 0, run_v, run_i)
             ops.fill_f32(cand_v.view(-1), float('-inf'))
             ops.fill_i32(self.overflow, 0)
             if cos:
                 ops.gemm_nt_topk_filter_cos(latent, pool[n0:], col_scale[n0:], self_col, run_v[:, k - 1], n0, cand_v,
                                             cand_i, capp, self.overflow)
+            elif tags is not None:
+                ops.gemm_nt_topk_filter_tags(latent, pool[n0:], bias[n0:] if bias is not None else None,
+                                             run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow,
+                                             (tags[0][n0:],) + tuple(tags[1:]), ex=ex, lse_part=lp)
             elif ex is not None:
                 ops.gemm_nt_topk_filter_excl(latent, pool[n0:], bias[n0:] if bias is not None else None,
                                              run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, ex,
@@ -170,7 +196,7 @@ class TopKScan(object):
             ops.topk_merge(run_v, run_i, self._cv, self._ci, k, out_v, out_i)
             values.copy_(out_v)
             indices.copy_(out_i)
-            if ex is not None or self_col is not None:
+            if empties:
                 ops.topk_mark_empty(values, indices)
             return
         nch = (V + self.chunk - 1) // self.chunk
@@ -185,6 +211,8 @@ class TopKScan(object):
                 lp[:, c0 // self.chunk].copy_(self._lse0)
             if ex is not None:
                 ops.topk_exclude_fill(lg, c0, ex)
+            if tags is not None:
+                ops.topk_tags_fill(lg, c0, tags)
             if cos:
                 ops.cos_chunk_finish(lg, c0, col_scale, self_col)
             if c0 == 0:                              # chunk >= k and V >= k: the first chunk fills all k
@@ -198,7 +226,7 @@ class TopKScan(object):
         if run_v.data_ptr() != values.data_ptr():
             values.copy_(run_v)
             indices.copy_(run_i)
-        if ex is not None or self_col is not None:
+        if empties:
             ops.topk_mark_empty(values, indices)
         if self.want_lse:
             ops.row_logsumexp(lp, self.lse)
@@ -217,20 +245,24 @@ class StreamTopK(G.Node, TopKScan):
     exclude (optional): a callable giving (row_keys, key_rows, ex_ptr, ex_cols) (EmbeddingAttribute.exclusion_args):
     each row's excluded columns never enter the result (the first chunk and every chunked-path chunk are filled with
     -inf at them, the fused GEMM's candidates skip them); winners of value -inf get index -1.  The log-sum-exp
-    (want_lse) stays over ALL the columns.  share: another StreamTopK over the same shapes whose logits chunk buffer
+    (want_lse) stays over ALL the columns.  tags (optional): a callable giving (col_tags, want_any, want_all,
+    want_rows) (EmbeddingAttribute.tag_args), or that tuple: the columns ineligible for a row by their tag words never enter its
+    result either (the same two places: -inf fills and the fused GEMM's survivor test).  share: another StreamTopK over the same shapes whose logits chunk buffer
     this one re-uses (plans run one after the other on one stream).  The algorithm and its buffers: TopKScan."""
 
-    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None):
+    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None, tags=None):
         G.Node.__init__(self, rt, (latent.shape[0], k), (latent, pool))
         TopKScan.__init__(self, latent.shape[0], pool.shape[0], latent.shape[1], k, rt.device, chunk=chunk,
                           want_lse=want_lse, share=share)
         self.exclude = exclude
+        self.tags = tags
         self.fused = self.fused and pool.shape[1] == latent.shape[1]
 
     def forward(self, train):
         latent, pool = self.inputs
         ex = self.exclude() if self.exclude is not None else None
-        self.run(latent.value, pool.value, pool.bias_value, self.rt.ws, self.alloc_value(), self.indices, ex)
+        tags = self.tags() if callable(self.tags) else self.tags
+        self.run(latent.value, pool.value, pool.bias_value, self.rt.ws, self.alloc_value(), self.indices, ex, tags=tags)
 
 
 def recommend_node(rt, logits, k, rows):
@@ -242,13 +274,45 @@ def recommend_node(rt, logits, k, rows):
     return TopK(rt, logits, k)
 
 
-def excluding_twin(rt, node, exclusion_args):
-    """The excluding twin of a recommend node (the plain node and its plan stay as they are); a streaming twin
-    shares the plain node's chunk buffer."""
+def excluding_twin(rt, node, exclusion_args=None, tag_args=None):
+    """The twin of a recommend node that leaves columns out -- by the exclusion lists, by the item tags, or by both
+    (the plain node and its plan stay as they are); a streaming twin shares the plain node's chunk buffer."""
+    if exclusion_args is None and tag_args is None:
+        raise ValueError("excluding_twin: exclusion lists, item tags or both")
     if isinstance(node, StreamTopK):
         return StreamTopK(rt, node.inputs[0], node.inputs[1], node.k, chunk=node.chunk, want_lse=node.want_lse,
-                          exclude=exclusion_args, share=node)
-    return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args)
+                          exclude=exclusion_args, share=node, tags=tag_args)
+    if tag_args is None:
+        return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args)
+    return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args, tags=tag_args)
+
+
+def recommend_key(exclude_seen, tagged):
+    """The plan of a recommend call: 'recommend', 'recommend_ex', 'recommend_tags' or 'recommend_ex_tags'."""
+    return 'recommend' + ('_ex' if exclude_seen else '') + ('_tags' if tagged else '')
+
+
+def tag_words(tags_any, tags_all, rows, what='recommend'):
+    """The two request words per row as int32 BIT PATTERNS [rows] (what the device placeholders hold).  Each of
+    tags_any / tags_all: None (0: no constraint), an int (one word for every row) or a length-`rows` integer array;
+    ValueError for a word outside [0, 2^32), a non-integer or a wrong length."""
+    out = []
+    for name, w in (('tags_any', tags_any), ('tags_all', tags_all)):
+        if isinstance(w, torch.Tensor):
+            w = w.cpu().numpy()
+        a = np.asarray(0 if w is None else w)
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            if a.dtype != object or not all(isinstance(x, (int, np.integer)) for x in a.reshape(-1)):
+                raise ValueError("%s: %s must hold integers (32-bit tag words)" % (what, name))
+        if a.ndim > 1 or (a.ndim == 1 and len(a) != rows):
+            raise ValueError("%s: %s must be one word or %d words, one per row" % (what, name, rows))
+        flat = a.reshape(-1)
+        if len(flat) and (min(flat) < 0 or max(flat) >= 2 ** 32):      # (one word for no rows is checked too)
+            raise ValueError("%s: %s words must lie in [0, 2^32)" % (what, name))
+        if a.ndim == 0:
+            a = np.full(rows, a.item(), dtype=object if a.dtype == object else a.dtype)
+        out.append(np.ascontiguousarray(a.astype(np.uint32)).view(np.int32))
+    return out[0], out[1]
 
 
 def run_complete(scan, run, forget=None):

@@ -25,7 +25,7 @@ from .. import ops
 from ..attributes import embed_attribute
 from ..attributes.embed_attribute import Dropout
 from ..hmf.hmf_model import _Op, _Var
-from ..topk import excluding_twin, recommend_node, run_complete
+from ..topk import excluding_twin, recommend_key, recommend_node, run_complete
 from ..utils.checkpoint import Saver
 
 
@@ -177,6 +177,13 @@ class LinearSeq(object):
         self._plans.pop('recommend_ex', None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
+    def prepare_item_tags(self, tags):
+        """The items' 32-bit tag words for step(recommend=True, tags_any=, tags_all=): an integer array [n_items] or
+        {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces them."""
+        for key in ('recommend_tags', 'recommend_ex_tags'):
+            self._plans.pop(key, None)
+        self.att_emb.prepare_item_tags(tags)
+
     def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536):
         """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the OUTPUT item latents the
         model scores against (EmbeddingAttribute.similar_items); output_feat 2 / 3: NotImplementedError."""
@@ -195,26 +202,37 @@ class LinearSeq(object):
                 if getattr(self, 'topk_ex', None) is None:      # on first use
                     self.topk_ex = excluding_twin(rt, self.topk, m.exclusion_args)
                 self._plans[key] = G.Plan(rt, [self.topk_ex], False, [])
+            elif key == 'recommend_tags':
+                if getattr(self, 'topk_tags', None) is None:
+                    self.topk_tags = excluding_twin(rt, self.topk, tag_args=m.tag_args)
+                self._plans[key] = G.Plan(rt, [self.topk_tags], False, [])
+            elif key == 'recommend_ex_tags':
+                if getattr(self, 'topk_ex_tags', None) is None:
+                    self.topk_ex_tags = excluding_twin(rt, self.topk, m.exclusion_args, m.tag_args)
+                self._plans[key] = G.Plan(rt, [self.topk_ex_tags], False, [])
             else:
                 self._plans[key] = G.Plan(rt, [self.topk], False, [])
         return self._plans[key]
 
     def _recommend(self, key):
-        """Run the 'recommend' / 'recommend_ex' plan; a streaming top-k whose fused candidate lists overflowed runs
+        """Run the 'recommend' / 'recommend_ex' / 'recommend_tags' / 'recommend_ex_tags' plan; a streaming top-k whose fused candidate lists overflowed runs
         once more on the chunked path (as LatentProductModel.step)."""
         self._plan(key)
-        node = self.topk_ex if key == 'recommend_ex' else self.topk
+        node = {'recommend': self.topk, 'recommend_ex': getattr(self, 'topk_ex', None),
+                'recommend_tags': getattr(self, 'topk_tags', None),
+                'recommend_ex_tags': getattr(self, 'topk_ex_tags', None)}[key]
         # (the placeholders still hold this request's ids in the second run)
         run_complete(node, lambda: self._plan(key).run(), lambda: self._plans.pop(key, None))
         return node.indices.cpu().numpy()
 
     def step(self, session, user_input, item_input=None, item_output=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
-             loss=None, run_op=None, run_meta=None, exclude_seen=False):
+             loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None):
         """linear_seq.py:67-121.  item_input: [n_input][mb] context items (time-major);
         item_output: [mb] target items.  Returns the mean loss (train / forward_only) or the
         top-N logit indices [mb, top_N] (recommend; exclude_seen=True: without each user's items of
-        prepare_recommend_exclusions, -1 where a user has fewer eligible items).
+        prepare_recommend_exclusions, -1 where a user has fewer eligible items; tags_any / tags_all -- an int or one
+        int per row: only the items eligible by their tag words of prepare_item_tags, composing with exclude_seen).
         'mw' / 'mce': item_sampled (n_sampled item ids) stages a new pool -- the first training step needs one,
         later steps keep it until the next is given (run_w2v.py:315-317); item_sampled_id2idx is the host twin of
         the pool's item -> slot map.  forward_only evaluates 'mw' with the full-vocabulary 'warp' loss and 'mce'
@@ -225,6 +243,9 @@ class LinearSeq(object):
             raise NotImplementedError("indices_test is never built by the reference (linear_seq.py:98)")
         if recommend and exclude_seen:
             m.exclusion_args()                 # ValueError before any feed when nothing was prepared
+        tagged = recommend and (tags_any is not None or tags_all is not None)
+        if tagged:
+            m.feed_tag_words(tags_any, tags_all)                  # ValueError before any other feed
         if sampled and not (recommend or forward_only) and item_sampled is None and m._old_pool is None:
             raise ValueError("the first %r training step needs item_sampled (the pool of n_sampled items)"
                              % self.loss_function)
@@ -243,7 +264,7 @@ class LinearSeq(object):
         for op in update_sampled:              # stage the pool (embed_attribute.py:320-348)
             op()
         if recommend:
-            return self._recommend('recommend_ex' if exclude_seen else 'recommend')
+            return self._recommend(recommend_key(exclude_seen, tagged))
         if forward_only:
             self._plan('eval').run()
             return float(self.loss_test.read().item())

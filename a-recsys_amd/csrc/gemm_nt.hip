@@ -66,13 +66,20 @@ struct NtFilter {
   // kNtSelf (with kNtCos: the item-to-item scan) reads tcol too: the row's own ABSOLUTE column col_base + col (anything
   // outside the launch's columns: none), dropped before it takes a position in the row's list
   const int32_t* tcol; int32_t* cnt_part;
+  // kNtTags (the recommend path within item tags): column c of this launch carries the 32 tag bits col_tags[c], row r
+  // the two words want_any / want_all [r % want_rows]; c is eligible for r iff
+  // (any == 0 || (tags & any) != 0) && (tags & all) == all -- a zero word is no constraint
+  const int32_t* col_tags; const int32_t* want_any; const int32_t* want_all; int64_t want_rows;
 };
 
 // MODE (FILTER kernels): bit 0 candidate lists (thr), bit 1 lse_part, bit 2 relu_part, bit 3 exclusion lists (with
 // bit 0 only), bit 4 rank counts (with bit 2 only) -- a template parameter, not a run-time switch: every feature is 32
 // registers of per-row state and the plain kernel already holds 246.  bit 5 cosine (with bit 0 alone, or bit 0 and
-// bit 6): v = acc * col_scale[col], the scale travelling where the bias does; bit 6 the row's self column (with bit 5)
-constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8, kNtRank = 16, kNtCos = 32, kNtSelf = 64;
+// bit 6): v = acc * col_scale[col], the scale travelling where the bias does; bit 6 the row's self column (with bit 5);
+// bit 7 item tags (with bit 0, optionally bits 1 and 3): the eligibility test of NtFilter::col_tags on a survivor -- the
+// column's tag word is loaded from global memory THERE, not carried per lane beside the bias: two more registers per
+// lane for every tile would not fit under the 256 the two workgroups per CU leave (the plain filter holds 246)
+constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8, kNtRank = 16, kNtCos = 32, kNtSelf = 64, kNtTags = 128;
 
 template <int KT, int MODE = 0>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
@@ -87,6 +94,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   constexpr bool want_cos = (MODE & kNtCos) != 0, want_self = (MODE & kNtSelf) != 0;
   static_assert(!want_cos || (want_topk && !want_lse && !want_relu && !want_excl), "the cosine scale serves the lists");
   static_assert(!want_self || want_cos, "the self column belongs to the item-to-item scan");
+  constexpr bool want_tags = (MODE & kNtTags) != 0;
+  static_assert(!want_tags || (want_topk && !want_relu && !want_cos), "the item tags filter the recommend candidates");
   constexpr int NS = KT / 8;                  // steps of 4 MFMAs
   constexpr int CPR = KT / 4;                 // 16-B chunks per pool row
   constexpr int NLB = kNtBN * CPR / 256;      // DMA pieces per thread per tile
@@ -154,6 +163,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   __shared__ int s_cnt[want_topk ? kNtBM : 1];
   // kNtExcl: [beg, end) of each row's exclusion list (1 KB; read only by a lane whose logit beat the threshold)
   __shared__ int s_xb[want_excl ? kNtBM : 1], s_xe[want_excl ? kNtBM : 1];
+  // kNtTags: each row's two request words (1 KB; read only by a lane whose logit beat the threshold)
+  __shared__ uint32_t s_wa[want_tags ? kNtBM : 1], s_wl[want_tags ? kNtBM : 1];
   // kNtRank: the rows' target columns (read per tile by one lane per row, per logit only in a tile that holds one)
   // kNtSelf: the rows' own columns, absolute (read only by a lane whose logit beat the threshold)
   __shared__ int s_tc[(want_rank || want_self) ? kNtBM : 1];
@@ -205,6 +216,11 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
         }
         s_xb[threadIdx.x] = xb;
         s_xe[threadIdx.x] = xe;
+      }
+      if (want_tags) {
+        const int64_t wr = row < M ? row % flt.want_rows : 0;
+        s_wa[threadIdx.x] = row < M ? (uint32_t)flt.want_any[wr] : 0u;
+        s_wl[threadIdx.x] = row < M ? (uint32_t)flt.want_all[wr] : 0u;
       }
     }
 #pragma unroll
@@ -338,6 +354,15 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
           const int rl = rl0 + (e & 3) + 8 * (e >> 2);
           // the row's own column (a survivor: rare) leaves BEFORE the ballot, as an excluded one does
           if (want_self && pred && flt.col_base + (int32_t)col == s_tc[rl]) pred = false;
+          if (want_tags && pred) {
+            // a survivor (rare): its column's tag word comes from global memory here, BEFORE the ballot, so an
+            // ineligible column takes no position; a row of two zero words loads nothing
+            const uint32_t wa = s_wa[rl], wl = s_wl[rl];
+            if ((wa | wl) != 0u) {
+              const uint32_t tg = (uint32_t)flt.col_tags[col];
+              if ((wa != 0u && (tg & wa) == 0u) || (tg & wl) != wl) pred = false;
+            }
+          }
           if (want_excl && pred) {
             // a survivor (rare): lower_bound of its absolute column in the row's list, BEFORE the ballot, so an
             // excluded column takes no position and the placement stays deterministic
@@ -553,6 +578,54 @@ int arx_gemm_nt_topk_filter_excl(const float* A, int64_t lda, int64_t M, const f
     nt_launch_mode<kNtTopk | kNtLse | kNtExcl>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
   else
     nt_launch_mode<kNtTopk | kNtExcl>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_gemm_nt_topk_filter_tags(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
+                                 int64_t K, const float* col_bias, const float* thr, int64_t ldthr, int32_t col_base,
+                                 float* cand_v, int32_t* cand_i, int64_t ldcand, int capp, int* overflow, float* lse_part,
+                                 int64_t ldl, const int32_t* row_keys, int64_t key_rows, const int32_t* ex_ptr,
+                                 const int32_t* ex_cols, const int32_t* col_tags, const int32_t* want_any,
+                                 const int32_t* want_all, int64_t want_rows, void* stream) {
+  ARX_CHECK_ARG(A && Bm && thr && cand_v && cand_i && overflow,
+                "arx_gemm_nt_topk_filter_tags: null pointer (col_bias, lse_part and the exclusion lists may be NULL)");
+  ARX_CHECK_ARG(M > 0 && N > 0 && capp > 0 && ldcand > 0 && lda >= K && ldb >= K,
+                "arx_gemm_nt_topk_filter_tags: need M > 0, N > 0, capp > 0, ldcand > 0, lda >= K, ldb >= K");
+  ARX_CHECK_ARG(col_tags && want_any && want_all && want_rows > 0,
+                "arx_gemm_nt_topk_filter_tags: need col_tags, want_any, want_all and want_rows > 0");
+  const bool excl = row_keys || ex_ptr || ex_cols;
+  ARX_CHECK_ARG(!excl || (row_keys && ex_ptr && ex_cols && key_rows > 0),
+                "arx_gemm_nt_topk_filter_tags: row_keys, ex_ptr, ex_cols go together (all NULL: no lists), key_rows > 0");
+  ARX_CHECK_ARG(col_base >= 0 && (int64_t)col_base + N <= 0x7fffffff,
+                "arx_gemm_nt_topk_filter_tags: need col_base >= 0 and col_base + N < 2^31");
+  ARX_CHECK_ARG(K == 32 || K == 64 || K == 128, "arx_gemm_nt_topk_filter_tags: K must be 32, 64 or 128");
+  ARX_CHECK_ARG(!((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) && lda % 4 == 0 &&
+                    ldb % 4 == 0,
+                "arx_gemm_nt_topk_filter_tags: operands must be 16-byte aligned");
+  int64_t tpb, ns;
+  nt_split(M, N, &tpb, &ns);
+  ARX_CHECK_ARG(ns * capp <= ldcand,
+                "arx_gemm_nt_topk_filter_tags: candidate rows too short (parts * capp > ldcand)");
+  const int64_t grid = ceil_div(M, (int64_t)kNtBM) * ns;
+  ARX_CHECK_ARG(grid <= 0x7fffffff, "arx_gemm_nt_topk_filter_tags: grid too large");
+  ARX_CHECK_ARG(!lse_part || ldl >= ns, "arx_gemm_nt_topk_filter_tags: lse_part rows too short (ldl < parts)");
+  NtFilter f{thr,      ldthr,   cand_v,   cand_i,   ldcand,   capp,   col_base, overflow, lse_part,
+             ldl,      nullptr, nullptr,  row_keys, key_rows, ex_ptr, ex_cols};
+  f.col_tags = col_tags;
+  f.want_any = want_any;
+  f.want_all = want_all;
+  f.want_rows = want_rows;
+  hipStream_t s = as_stream(stream);
+  const int itpb = (int)tpb, ins = (int)ns;
+  if (excl && lse_part)
+    nt_launch_mode<kNtTopk | kNtTags | kNtExcl | kNtLse>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, itpb, ins, f);
+  else if (excl)
+    nt_launch_mode<kNtTopk | kNtTags | kNtExcl>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, itpb, ins, f);
+  else if (lse_part)
+    nt_launch_mode<kNtTopk | kNtTags | kNtLse>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, itpb, ins, f);
+  else
+    nt_launch_mode<kNtTopk | kNtTags>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, itpb, ins, f);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

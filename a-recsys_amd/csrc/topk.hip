@@ -237,6 +237,25 @@ __global__ __launch_bounds__(64 * kExRowsPerBlock) void k_topk_exclude_fill(
   }
 }
 
+// Item tags (recommend within "only this category / in stock / this market"): absolute column c carries 32 tag bits
+// col_tags[c], row r the two words want_any / want_all [r % want_rows]; c is eligible for r iff
+// (any == 0 || (tags & any) != 0) && (tags & all) == all.  One workgroup per row strides over [col0, col0 + ncols) and
+// writes -inf at the ineligible columns (the logits themselves are never read); a row of two zero words returns.
+__global__ __launch_bounds__(256) void k_topk_tags_fill(float* __restrict__ logits, int64_t ld, int32_t col0,
+                                                        int64_t ncols, const int32_t* __restrict__ col_tags,
+                                                        const int32_t* __restrict__ want_any,
+                                                        const int32_t* __restrict__ want_all, int64_t want_rows) {
+  const int64_t r = blockIdx.x;
+  const uint32_t wa = (uint32_t)want_any[r % want_rows], wl = (uint32_t)want_all[r % want_rows];
+  if ((wa | wl) == 0u) return;
+  float* row = logits + r * ld;
+  const int32_t* tg = col_tags + col0;
+  for (int64_t c = threadIdx.x; c < ncols; c += 256) {
+    const uint32_t t = (uint32_t)tg[c];
+    if ((wa != 0u && (t & wa) == 0u) || (t & wl) != wl) row[c] = -__builtin_inff();
+  }
+}
+
 // a winner whose value is -inf is no item (a row with fewer eligible columns than k): index -1
 __global__ void k_topk_mark_empty(const float* __restrict__ values, int64_t ldv, int32_t* __restrict__ indices,
                                   int64_t ldi, int64_t B, int k) {
@@ -420,6 +439,21 @@ int arx_topk_exclude_fill(float* logits, int64_t ld, int64_t B, int32_t col0, in
   if (B == 0 || ncols == 0) return ARX_OK;
   k_topk_exclude_fill<<<(int)ceil_div(B, (int64_t)kExRowsPerBlock), 64 * kExRowsPerBlock, 0, as_stream(stream)>>>(
       logits, ld, B, col0, ncols, row_keys, key_rows, ex_ptr, ex_cols);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_topk_tags_fill(float* logits, int64_t ld, int64_t M, int32_t col0, int64_t ncols, const int32_t* col_tags,
+                       const int32_t* want_any, const int32_t* want_all, int64_t want_rows, void* stream) {
+  ARX_CHECK_ARG(logits && col_tags && want_any && want_all, "arx_topk_tags_fill: null pointer");
+  ARX_CHECK_ARG(M >= 0 && ncols >= 0 && col0 >= 0 && want_rows > 0,
+                "arx_topk_tags_fill: need M >= 0, ncols >= 0, col0 >= 0, want_rows > 0");
+  ARX_CHECK_ARG((int64_t)col0 + ncols <= 0x7fffffff, "arx_topk_tags_fill: need col0 + ncols < 2^31");
+  ARX_CHECK_ARG(M <= 1 || ld >= ncols, "arx_topk_tags_fill: ld < ncols");
+  ARX_CHECK_ARG(M <= 0x7fffffff, "arx_topk_tags_fill: too many rows");
+  if (M == 0 || ncols == 0) return ARX_OK;
+  k_topk_tags_fill<<<(int)M, 256, 0, as_stream(stream)>>>(logits, ld, col0, ncols, col_tags, want_any, want_all,
+                                                          want_rows);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

@@ -1166,4 +1166,7 @@ int arx_graph_feeds_destroy(void* feeds);
 #ifdef __cplusplus
 }
 #endif
+/* Extensions of the ABI live in headers of their own, one per feature, bound by tables of their own in arx/_lib.py:
+ * recommend within item tags (arx_topk_tags_fill, arx_gemm_nt_topk_filter_tags). */
+#include "arx_tags.h"
 #endif /* ARX_H_ */

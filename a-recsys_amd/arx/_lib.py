@@ -1,4 +1,5 @@
-"""ctypes binding of libarx.so (include/arx.h and the extension header it includes, include/arx_tags.h).
+"""ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h and
+include/arx_slate.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -241,6 +242,12 @@ TAGS_PROTOTYPES = {
                                             cint, i32p, f32p, i64, i32p, i64, i32p, i32p, i32p, i32p, i32p, i64, vp]),
 }
 
+# include/arx_slate.h (score_items: a per-row candidate slate), one-to-one as above
+SLATE_PROTOTYPES = {
+    "arx_slate_scores": (cint, [f32p, i64, i64, f32p, i64, f32p, i64, cint, i32p, i64, i64, f32p, i64, vp]),
+    "arx_slate_merge_shards": (cint, [f32p, i64, i64, cint, f32p, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -252,7 +259,8 @@ def _load():
             "libarx.so not found at %s -- build it with `python -c 'import __graft_entry__ as g; "
             "g.build()'` (or `make -C a-recsys_amd/csrc`).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(PROTOTYPES.items()) + list(TAGS_PROTOTYPES.items()):
+    for name, (res, args) in (list(PROTOTYPES.items()) + list(TAGS_PROTOTYPES.items())
+                              + list(SLATE_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

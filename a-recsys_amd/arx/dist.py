@@ -42,6 +42,7 @@ import torch
 import torch.distributed as dist
 
 from . import ops as _ops
+from . import slate as _slate
 from .topk import TopKScan, run_complete, similar_scan, tag_words
 from .utils.prepare_train import pair_draw_tables
 
@@ -390,6 +391,19 @@ class HipBackend(object):
     def topk_merge_shards(self, v, c, vo, io):
         """[W, B, k] per-shard lists (local columns) -> [B, k] global ids (arx_topk_merge_shards)."""
         self.ops.topk_merge_shards(v, c, vo, io)
+
+    def slate_scores(self, U, E, bias, local_cols, out):
+        """score_items' local stage: out[r, j] = U[r] . E[c] + bias[c] for c = local_cols[r, j] in [0, rows of E),
+        -inf (nothing read) for a slot of another shard or an empty one (arx_slate_scores)."""
+        self.ops.slate_scores(U, E, bias, local_cols, out)
+
+    def slate_merge_shards(self, parts, out):
+        """[W, B, C] per-shard scores (-inf where the shard does not own the slot) -> [B, C] (arx_slate_merge_shards)."""
+        self.ops.slate_merge_shards(parts, out)
+
+    def slate_order(self, scores, cand, k, values, pos, ids):
+        """The k best slots of every row by (score desc, slot asc) and their candidate ids (arx.slate.slate_order)."""
+        _slate.slate_order(scores, cand, k, values, pos, ids)
 
     def shard_eval(self, U, E, bias, t, tcol, loss, ex, part, cnt):
         """Evaluation's local stage: per row of U [B, d], this shard's partial over the V rows of E (+ bias) -- 'ce':
@@ -1628,6 +1642,82 @@ class ShardedHMF(object):
         be.topk_merge_shards(recv_v, recv_c, vo, io)
         return vo, io
 
+    # -------------------------------------------------------------- score_items
+    def score_items(self, users, candidates, k=None):
+        """What the model thinks of THESE items for THIS user: every user against a slate of its own (re-ranking
+        another retriever's candidates, an editorial slate, sampled-negative evaluation).  A collective with
+        recommend's calling rules: every rank calls it with the same C and k.  users: global ids this rank owns,
+        0 <= len(users) <= B_loc (the count may differ between ranks); candidates: [len(users), C] GLOBAL item ids,
+        -1 an empty slot.  k None: float32 [len(users), C] scores on the device, -inf at empty slots.
+        1 <= k <= min(1024, C): (ids int32 [len(users), k], values float32) by (score desc, slot asc) -- duplicates
+        and ties keep slate order --, (-1, -inf) where a user has fewer than k live slots.  Build-defined.
+
+          gather          this rank's latents (_serve_latents) -> [B_loc, d]; padding rows zero, their slots -1
+          all_gather      latents -> [B, d]; candidates [B_loc, C] -> [B, C]
+          (local)         arx_shard_route: global id -> local column or ARX_KEY_NONE; arx_slate_scores over
+                          E_item[:ni] / b_item[:ni] (a slot of another shard: -inf, nothing read)
+          all_to_all      partial scores [B, C] -> the rows' owners: [W][B_loc][C]
+          (local)         arx_slate_merge_shards; with k, slate_order over the owner's [B_loc, C] and its own GLOBAL
+                          candidate ids
+
+        Eager, joined with the caller's stream on both sides as recommend is; its buffers are its own, per (C, k)."""
+        W, r = self.world, self.rank
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        u = u.astype(np.int64).reshape(-1)
+        if len(u) > self.B_loc:
+            raise ValueError("score_items: at most B_loc = %d users per call and rank" % self.B_loc)
+        if len(u) and (u.min() < 0 or u.max() >= self.n_users or np.any(u % W != r)):
+            raise ValueError("score_items: users must be global ids in [0, %d) owned by rank %d" % (self.n_users, r))
+        cand = _slate.check_slate(candidates, len(u), self.n_items)
+        k = _slate.check_k(k, int(cand.shape[1]))
+        with _ops.joined(self._stream if self.use_graphs else None):
+            sc, vo, io = self._score_items(u, cand, k)
+        n = len(u)
+        if k is None:
+            return sc[:n].clone()
+        return io[:n].clone(), vo[:n].clone()
+
+    def _score_items(self, u, cand, k):
+        be, W, B_loc, B, d = self.be, self.world, self.B_loc, self.B, self.d
+        dev, f32, i32 = self.device, torch.float32, torch.int32
+        n, C = len(u), int(cand.shape[1])
+        if getattr(self, '_sl_lat', None) is None:       # [B_loc, d] latents; gathered: [B, d]
+            ul = torch.zeros((B_loc, d), dtype=f32, device=dev)
+            self._sl_lat = (ul, ul if W == 1 else torch.empty((B, d), dtype=f32, device=dev))
+            self._sl_k = {}
+        U_loc, U_all = self._sl_lat
+        bk = self._sl_k.get((C, k))
+        if bk is None:
+            if len(self._sl_k) >= 8:
+                self._sl_k.clear()
+            e = lambda dt, *sh: torch.empty(sh, dtype=dt, device=dev)
+            cl = e(i32, B_loc, C)
+            bk = self._sl_k[(C, k)] = (cl, cl if W == 1 else e(i32, B, C), e(i32, B, C), e(f32, B, C),
+                                       e(f32, W, B_loc, C), e(f32, B_loc, C)) + \
+                ((e(f32, B_loc, k), e(i32, B_loc, k), e(i32, B_loc, k)) if k is not None else (None, None, None))
+        cand_loc, cand_all, cols, part, recv, merged, vo, pos, io = bk
+        ch = np.full((B_loc, C), -1, dtype=np.int32)
+        ch[:n] = cand
+        cand_loc.copy_(torch.from_numpy(ch))
+        self._serve_latents(u, U_loc[:n])
+        if n < B_loc:
+            be.fill_zero(U_loc[n:])
+        if W > 1:
+            dist.all_gather_into_tensor(U_all, U_loc, group=self.group)
+            dist.all_gather_into_tensor(cand_all, cand_loc, group=self.group)
+        # (ids < 0 and items of other shards: ARX_KEY_NONE, a column of no shard)
+        be.shard_route(cand_all.view(-1), W, self.rank, self.zero_row, None, cols.view(-1))
+        ni = self.ni_loc
+        be.slate_scores(U_all, self.E_item[:ni], self.b_item[:ni], cols, part)
+        if W == 1:
+            recv = part.view(1, B, C)
+        else:
+            _all_to_all(recv.view(B, C), part, group=self.group)
+        be.slate_merge_shards(recv, merged)
+        if k is not None:
+            be.slate_order(merged, cand_loc, k, vo, pos, io)
+        return merged, vo, io
+
     def _serve_latents(self, u, out):
         """The latents recommend / evaluate score against the item shard, for the users u (global ids this rank owns)
         -> out [len(u), d]: this model's are its user rows."""
@@ -2034,6 +2124,15 @@ class ShardedW2V(ShardedHMF):
         finally:
             self._serve_ctx = None
 
+    def score_items(self, users, context, candidates, k=None):
+        """ShardedHMF.score_items over x_test of (users, context): context is [n_input][len(users)], time-major."""
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        self._serve_ctx = self._context_array(context, int(u.size), "score_items")
+        try:
+            return super().score_items(users, candidates, k=k)
+        finally:
+            self._serve_ctx = None
+
     def evaluate(self, users, context, items, loss='warp', return_rows=False):
         """ShardedHMF.evaluate over x_test of (users, context): context is [n_input][len(users)], time-major."""
         u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
@@ -2255,6 +2354,11 @@ class ShardedHMFBags(ShardedHMF):
             self._sim_view = self.item_view()
         return self._sim_view.similar_items(items, k, include_self=include_self, return_values=return_values)
 
+    def score_items(self, users, candidates, k=None):
+        """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
+        raise NotImplementedError("%s.score_items: item latents are bag means -- use item_view().score_items"
+                                  % type(self).__name__)
+
     def evaluate(self, users, items, loss='warp', return_rows=False):
         """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
         raise NotImplementedError("%s.evaluate: item latents are bag means -- use item_view().evaluate"
@@ -2425,6 +2529,11 @@ class ShardedHMFRepTokens(ShardedHMF):
             self._sim_view = self.item_view()
         return self._sim_view.similar_items(items, k, include_self=include_self, return_values=return_values)
 
+    def score_items(self, users, candidates, k=None):
+        """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
+        raise NotImplementedError("%s.score_items: item latents are bag means -- use item_view().score_items"
+                                  % type(self).__name__)
+
     def evaluate(self, users, items, loss='warp', return_rows=False):
         """Not on the training class: the item latents are bag means -- item_view() materialises them per shard."""
         raise NotImplementedError("%s.evaluate: item latents are bag means -- use item_view().evaluate"
@@ -2519,6 +2628,11 @@ class ShardedHetView(ShardedHMF):
         if self._seen != (self.model.steps, self.model.n_restores):
             self._refresh()
         return super()._similar(it, k, include_self)
+
+    def _score_items(self, u, cand, k):
+        if self._seen != (self.model.steps, self.model.n_restores):
+            self._refresh()
+        return super()._score_items(u, cand, k)
 
     def _no_training(self, *a, **k):
         raise TypeError("ShardedHetView: a view does not train (step, pools and positives belong to the model)")

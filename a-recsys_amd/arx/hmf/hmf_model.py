@@ -15,6 +15,7 @@ import torch
 
 from .. import graph as G
 from .. import ops
+from .. import slate
 from ..attributes import embed_attribute
 from ..topk import (StreamTopK, TopK, TopKScan, excluding_twin, recommend_key, recommend_node,  # noqa: F401
                     run_complete)                                                            # (re-exported)
@@ -274,6 +275,18 @@ class LatentProductModel(object):
         recommend scores against: EmbeddingAttribute.similar_items."""
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
                                           chunk=chunk)
+
+    def score_items(self, user_input, candidates, k=None):
+        """What the model thinks of THESE items for THIS user: row r of one full batch of users (the rules of
+        step(recommend=True)) against its own slate candidates[r] -- [batch_size, C] logit indices, the space
+        recommend returns and similar_items takes; -1 marks an empty slot.  The latent and the item pool are
+        recommend's, dropout off.  k None: float32 [mb, C] scores on the device, -inf at empty slots.
+        1 <= k <= min(1024, C): (ids int32 [mb, k], values float32 [mb, k]) by (score desc, slot asc) -- duplicates
+        and ties keep slate order --, (-1, -inf) where a row has fewer than k live slots (an item switched off by a
+        -inf bias is not live, as in recommend).  ValueError for any other k or a malformed slate.  Build-defined
+        (arx.slate): one plan per (C, k), at most eight kept."""
+        return slate.score_items(self, lambda: self._feed(user_input, None, True, self.loss_function, None, None, True),
+                                 candidates, k)
 
     def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
         """'bpr' / 'bpr-hinge': the items a DRAWN negative must not hit, per user -- typically the training history:

@@ -1478,6 +1478,35 @@ def topk(logits, k, values, indices):
          _p(values), _p(indices), _stream())
 
 
+def slate_scores(U, P, pbias, cand, scores):
+    """scores[r, j] = U[r] . P[cand[r, j]] + pbias[cand[r, j]] where 0 <= cand[r, j] < P.shape[0], else -inf and
+    nothing read (arx_slate.h).  U [B, d], P [V, d], pbias [V] or None, cand [B, C] int32, scores [B, C]; 2-D
+    arguments may be strided views."""
+    _chk(U, torch.float32, 'U'); _chk(P, torch.float32, 'P'); _chk(pbias, torch.float32, 'pbias')
+    _chk(cand, torch.int32, 'cand'); _chk(scores, torch.float32, 'scores')
+    if U.dim() != 2 or P.dim() != 2 or cand.dim() != 2 or scores.dim() != 2 or U.shape[1] != P.shape[1] \
+            or cand.shape[0] != U.shape[0] or tuple(scores.shape) != tuple(cand.shape):
+        raise ValueError("slate_scores: U [B, d], P [V, d], cand and scores [B, C]")
+    if pbias is not None and (pbias.dim() != 1 or int(pbias.shape[0]) < int(P.shape[0])):
+        raise ValueError("slate_scores: pbias needs one entry per pool row")
+    if cand.numel() == 0:
+        return
+    call("arx_slate_scores", _p(U), _ld(U), int(U.shape[0]), _p(P), _ld(P), _p(pbias), int(P.shape[0]),
+         int(U.shape[1]), _p(cand), _ld(cand), int(cand.shape[1]), _p(scores), _ld(scores), _stream())
+
+
+def slate_merge_shards(parts, out):
+    """out[r, j] = max over s of parts[s, r, j] (arx_slate.h): parts [W, B, C] contiguous, every live slot owned by
+    one shard and -inf in the others; out [B, C] may be a strided view."""
+    _chk(parts, torch.float32, 'parts'); _chk(out, torch.float32, 'out')
+    if parts.dim() != 3 or not parts.is_contiguous() or out.dim() != 2 or tuple(out.shape) != tuple(parts.shape[1:]):
+        raise ValueError("slate_merge_shards: parts [W, B, C] contiguous, out [B, C]")
+    if out.numel() == 0:
+        return
+    call("arx_slate_merge_shards", _p(parts), int(parts.shape[1]), int(parts.shape[2]), int(parts.shape[0]), _p(out),
+         _ld(out), _stream())
+
+
 def lstm_fwd(x, W, b, L, B, din, h, forget_bias, hs, cs, gates):
     call("arx_lstm_fwd", _p(x), _p(W), _p(b), int(L), int(B), int(din), int(h), float(forget_bias),
          _p(hs), _p(cs), _p(gates), _stream())

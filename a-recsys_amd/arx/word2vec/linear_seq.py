@@ -22,6 +22,7 @@ import torch
 
 from .. import graph as G
 from .. import ops
+from .. import slate
 from ..attributes import embed_attribute
 from ..attributes.embed_attribute import Dropout
 from ..hmf.hmf_model import _Op, _Var
@@ -189,6 +190,17 @@ class LinearSeq(object):
         model scores against (EmbeddingAttribute.similar_items); output_feat 2 / 3: NotImplementedError."""
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
                                           chunk=chunk, output_feat=self.output_feat)
+
+    def score_items(self, user_input, item_input, candidates, k=None):
+        """Row r of one full batch (user_input and the [n_input][mb] context item_input, the rules of
+        step(recommend=True)) against its own slate candidates[r]: [batch_size, C] logit indices, -1 an empty slot.
+        The latent is recommend's x_test of the full window, the pool the OUTPUT item latents; dropout off.
+        k None: float32 [mb, C] on the device (-inf at empty slots); 1 <= k <= min(1024, C): (ids, values)
+        [mb, k] by (score desc, slot asc), (-1, -inf) past the live slots (LatentProductModel.score_items;
+        arx.slate).  output_feat 2 / 3: NotImplementedError."""
+        def feed():
+            self.att_emb.add_input({}, user_input, item_input, recommend=True, loss=self.loss_function)
+        return slate.score_items(self, feed, candidates, k)
 
     def _plan(self, key):
         if key not in self._plans:

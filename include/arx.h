@@ -1169,4 +1169,5 @@ int arx_graph_feeds_destroy(void* feeds);
 /* Extensions of the ABI live in headers of their own, one per feature, bound by tables of their own in arx/_lib.py:
  * recommend within item tags (arx_topk_tags_fill, arx_gemm_nt_topk_filter_tags). */
 #include "arx_tags.h"
+#include "arx_slate.h"
 #endif /* ARX_H_ */

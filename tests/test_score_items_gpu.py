@@ -1,7 +1,14 @@
 """score_items on the GPU: arx_slate_scores / arx_slate_merge_shards through arx.ops (exact on dyadic data, strided
-views, the second trip of the unit loop, bit-reproducibility, the float32 dot bound, the shard merge), the ordering of
-arx.slate.slate_order, and the model methods -- LatentProductModel / LinearSeq (eager, captured, replayed),
-ShardedHMF and ShardedHetView at world 1 -- against the float64 oracle of tests/slate_oracle.py."""
+views, bit-reproducibility, the float32 dot bound, the shard merge), the ordering of arx.slate.slate_order, and the
+model methods -- LatentProductModel / LinearSeq (eager, captured, replayed), ShardedHMF and ShardedHetView at world
+1 -- against the float64 oracle of tests/slate_oracle.py.
+
+What this file does NOT reach: every entry of SHAPES ends at passes = 1 in arx_slate_scores (the largest,
+(2, 5000, 700, 128), is 1250 units on 16 * cu * 4 waves), so there the unit loop takes one trip and a run is one pass
+of the slot loop.  The 70000-row case below does stride the unit loop and plans passes = 8, but with one lane per
+pair and C = 3: one run per row, which ends in its first pass.  The unit loop past two trips at d = 128 with two runs
+per row and eight passes per run, the passes = 4 and 2 branches of the planner and the merge past its grid cap are in
+tests/test_grid_stride_gpu.py (shapes from tests/grid_trips.py)."""
 import numpy as np
 import pytest
 

@@ -1,5 +1,5 @@
-"""ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h and
-include/arx_slate.h).
+"""ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
+include/arx_slate.h and include/arx_diverse.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -248,6 +248,13 @@ SLATE_PROTOTYPES = {
     "arx_slate_merge_shards": (cint, [f32p, i64, i64, cint, f32p, i64, vp]),
 }
 
+# include/arx_diverse.h (score_items(diversify=): the greedy MMR re-rank of a slate), one-to-one as above
+DIVERSE_PROTOTYPES = {
+    "arx_slate_mmr_supported": (cint, [i64, cint]),
+    "arx_slate_mmr": (cint, [f32p, i64, i64, cint, i32p, i64, f32p, i64, i64, i64, f32p, i32p, i32p, cint, i32p, i64,
+                             f32p, i64, i32p, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -260,7 +267,7 @@ def _load():
             "g.build()'` (or `make -C a-recsys_amd/csrc`).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(TAGS_PROTOTYPES.items())
-                              + list(SLATE_PROTOTYPES.items())):
+                              + list(SLATE_PROTOTYPES.items()) + list(DIVERSE_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -279,7 +286,8 @@ _NO_CHECK = ("arx_last_error", "arx_version", "arx_csr_expand_workspace_bytes",
              "arx_sample_wor_workspace_bytes",
              "arx_gemm_nt_bx6_workspace_bytes", "arx_reduce_scratch_bytes", "arx_mw_scorer_supported",
              "arx_mw_scorer_state_bytes", "arx_mw_scorer_bwd_di_workspace_bytes", "arx_mce_scorer_supported",
-             "arx_mce_scorer_state_bytes", "arx_mce_scorer_bwd_di_workspace_bytes", "arx_gemm_bt_bx6_supported")
+             "arx_mce_scorer_state_bytes", "arx_mce_scorer_bwd_di_workspace_bytes", "arx_gemm_bt_bx6_supported",
+             "arx_slate_mmr_supported")
 
 
 def call(name, *args):

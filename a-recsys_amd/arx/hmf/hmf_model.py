@@ -276,7 +276,14 @@ class LatentProductModel(object):
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
                                           chunk=chunk)
 
-    def score_items(self, user_input, candidates, k=None):
+    def prepare_item_groups(self, groups):
+        """The items' groups (category / brand / seller) for score_items(max_per_group=): an integer array [n_items] or
+        {item_index: group} in item-index space, a negative id for 'no group'.  Mapped through item_ind2logit_ind to
+        one int32 per logit column, -1 for a column without an item (arx.slate.item_group_ids).  A second call
+        replaces the array (the capped plans are dropped)."""
+        slate.prepare_item_groups(self, groups)
+
+    def score_items(self, user_input, candidates, k=None, diversify=None, max_per_group=None):
         """What the model thinks of THESE items for THIS user: row r of one full batch of users (the rules of
         step(recommend=True)) against its own slate candidates[r] -- [batch_size, C] logit indices, the space
         recommend returns and similar_items takes; -1 marks an empty slot.  The latent and the item pool are
@@ -284,9 +291,20 @@ class LatentProductModel(object):
         1 <= k <= min(1024, C): (ids int32 [mb, k], values float32 [mb, k]) by (score desc, slot asc) -- duplicates
         and ties keep slate order --, (-1, -inf) where a row has fewer than k live slots (an item switched off by a
         -inf bias is not live, as in recommend).  ValueError for any other k or a malformed slate.  Build-defined
-        (arx.slate): one plan per (C, k), at most eight kept."""
+        (arx.slate): one plan per (C, k), at most eight kept.
+        diversify = lambda in [0, 1] (a scalar or one per row): "the best k, but spread out" -- a greedy MMR re-rank on
+        the device (arx_diverse.h).  Pick t maximises lambda * rel - (1 - lambda) * (largest cosine between the item's
+        latent and those of picks 0 .. t - 1), rel the score scaled to [0, 1] over the row's live slots; ties go to
+        the higher score, then the lower slot.  max_per_group = m >= 1 (a scalar or one per row): at most m picks of
+        one group, after prepare_item_groups(); alone it means lambda = 1, the best k by score under the cap.  With
+        either, k is required and (ids, values) -- values the model's scores -- come in SELECTION order, (-1, -inf)
+        once no slot qualifies.  ValueError for a lambda outside [0, 1], a cap below 1 or without groups, and a (C, d)
+        outside arx_slate_mmr_supported (C <= 512, d <= 128, C * d <= 32768).  The usual composition: over-fetch with a
+        model built with top_N_items = C, then re-rank to k (the -1 tails of recommend are empty slots already):
+            cands = model.step(None, users, None, recommend=True)
+            ids, values = model.score_items(users, cands, k, diversify=0.7)"""
         return slate.score_items(self, lambda: self._feed(user_input, None, True, self.loss_function, None, None, True),
-                                 candidates, k)
+                                 candidates, k, diversify, max_per_group)
 
     def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
         """'bpr' / 'bpr-hinge': the items a DRAWN negative must not hit, per user -- typically the training history:

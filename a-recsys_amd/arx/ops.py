@@ -1507,6 +1507,39 @@ def slate_merge_shards(parts, out):
          _ld(out), _stream())
 
 
+def slate_mmr_supported(C, d):
+    """True iff arx_slate_mmr takes a slate of C slots over rows of d floats (arx_diverse.h: the one owner of the
+    rule)."""
+    return bool(call("arx_slate_mmr_supported", int(C), int(d)))
+
+
+def slate_mmr(P, cand, scores, lam, groups, max_per_group, k, ids, values, pos):
+    """The greedy MMR re-rank of a scored slate (arx_diverse.h): k picks per row of cand / scores [B, C] by
+    lam[r] * rel - (1 - lam[r]) * (largest cosine with a pick so far), cosines between the rows of P [V, d]; with groups
+    [V] int32 and max_per_group [B] int32 at most that many picks per group (both None: no cap).  ids / pos int32 and
+    values float32 [B, k] receive the picks in selection order, (-1, -inf, -1) past the last one.  lam [B] float32 on
+    the device, every entry in [0, 1].  2-D arguments may be strided views."""
+    _chk(P, torch.float32, 'P'); _chk(cand, torch.int32, 'cand'); _chk(scores, torch.float32, 'scores')
+    _chk(lam, torch.float32, 'lam'); _chk(groups, torch.int32, 'groups')
+    _chk(max_per_group, torch.int32, 'max_per_group'); _chk(ids, torch.int32, 'ids')
+    _chk(values, torch.float32, 'values'); _chk(pos, torch.int32, 'pos')
+    if P.dim() != 2 or cand.dim() != 2 or tuple(scores.shape) != tuple(cand.shape):
+        raise ValueError("slate_mmr: P [V, d], cand and scores [B, C]")
+    B, C, k = int(cand.shape[0]), int(cand.shape[1]), int(k)
+    if any(t.dim() != 2 or tuple(t.shape) != (B, k) for t in (ids, values, pos)):
+        raise ValueError("slate_mmr: ids, values and pos [B, k]")
+    if lam.dim() != 1 or int(lam.shape[0]) < B or not lam.is_contiguous():
+        raise ValueError("slate_mmr: lam needs one contiguous entry per row")
+    if (groups is None) != (max_per_group is None):
+        raise ValueError("slate_mmr: groups and max_per_group go together")
+    if groups is not None and (groups.dim() != 1 or int(groups.shape[0]) < int(P.shape[0]) or max_per_group.dim() != 1
+                               or int(max_per_group.shape[0]) < B):
+        raise ValueError("slate_mmr: groups needs one entry per pool row, max_per_group one per row")
+    call("arx_slate_mmr", _p(P), _ld(P), int(P.shape[0]), int(P.shape[1]), _p(cand), _ld(cand), _p(scores),
+         _ld(scores), B, C, _p(lam), _p(groups), _p(max_per_group), k, _p(ids), _ld(ids), _p(values), _ld(values),
+         _p(pos), _ld(pos), _stream())
+
+
 def lstm_fwd(x, W, b, L, B, din, h, forget_bias, hs, cs, gates):
     call("arx_lstm_fwd", _p(x), _p(W), _p(b), int(L), int(B), int(din), int(h), float(forget_bias),
          _p(hs), _p(cs), _p(gates), _stream())

@@ -191,16 +191,27 @@ class LinearSeq(object):
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
                                           chunk=chunk, output_feat=self.output_feat)
 
-    def score_items(self, user_input, item_input, candidates, k=None):
+    def prepare_item_groups(self, groups):
+        """The items' groups for score_items(max_per_group=): an integer array [n_items] or {item_index: group} in
+        item-index space, mapped to one int32 per logit column (arx.slate.item_group_ids).  A second call replaces
+        them."""
+        slate.prepare_item_groups(self, groups)
+
+    def score_items(self, user_input, item_input, candidates, k=None, diversify=None, max_per_group=None):
         """Row r of one full batch (user_input and the [n_input][mb] context item_input, the rules of
         step(recommend=True)) against its own slate candidates[r]: [batch_size, C] logit indices, -1 an empty slot.
         The latent is recommend's x_test of the full window, the pool the OUTPUT item latents; dropout off.
         k None: float32 [mb, C] on the device (-inf at empty slots); 1 <= k <= min(1024, C): (ids, values)
         [mb, k] by (score desc, slot asc), (-1, -inf) past the live slots (LatentProductModel.score_items;
-        arx.slate).  output_feat 2 / 3: NotImplementedError."""
+        arx.slate).  output_feat 2 / 3: NotImplementedError.
+        diversify (lambda in [0, 1]) and / or max_per_group (after prepare_item_groups()): k is required and (ids,
+        values) come in the selection order of the greedy MMR re-rank, cosines between the OUTPUT item latents
+        (LatentProductModel.score_items states the rule):
+            cands = model.step(None, users, context, recommend=True)
+            ids, values = model.score_items(users, context, cands, k, diversify=0.7)"""
         def feed():
             self.att_emb.add_input({}, user_input, item_input, recommend=True, loss=self.loss_function)
-        return slate.score_items(self, feed, candidates, k)
+        return slate.score_items(self, feed, candidates, k, diversify, max_per_group)
 
     def _plan(self, key):
         if key not in self._plans:

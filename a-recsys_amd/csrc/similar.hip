@@ -9,40 +9,10 @@
 // the two kernels that need a row's norm agree bit for bit.  1.0f / sqrtf(s): both correctly rounded in this build (no
 // fast-math), so s = 4^e gives exactly 2^-e.
 #include "common.h"
+#include "sim_norm.h"
 
 namespace arx {
 namespace {
-
-__host__ __device__ inline int sim_group(int d, bool vec) {
-  const int q = vec ? d / 4 : d;
-  int l = 1;
-  while (l < q && l < 64) l <<= 1;
-  return l;
-}
-
-// sum of squares of `row` over the calling group (every lane of the wave calls it; ok == false: contributes nothing);
-// every lane of the group returns the same sum
-template <bool VEC>
-__device__ __forceinline__ float sim_row_sq(const float* __restrict__ row, int d, int L, int li, bool ok) {
-  float s = 0.f;
-  if (ok) {
-    if (VEC) {
-      for (int c = li * 4; c < d; c += L * 4) {
-        const float4 x = *reinterpret_cast<const float4*>(row + c);
-        s += x.x * x.x;
-        s += x.y * x.y;
-        s += x.z * x.z;
-        s += x.w * x.w;
-      }
-    } else {
-      for (int c = li; c < d; c += L) s += row[c] * row[c];
-    }
-  }
-  for (int o = 1; o < L; o <<= 1) s += __shfl_xor(s, o, 64);
-  return s;
-}
-
-__device__ __forceinline__ float sim_inv(float s) { return s > 0.f ? 1.0f / sqrtf(s) : 0.f; }
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void k_rows_inv_norm(const float* __restrict__ E, int64_t ld, int64_t n, int d, int L,

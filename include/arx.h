@@ -1170,4 +1170,5 @@ int arx_graph_feeds_destroy(void* feeds);
  * recommend within item tags (arx_topk_tags_fill, arx_gemm_nt_topk_filter_tags). */
 #include "arx_tags.h"
 #include "arx_slate.h"
+#include "arx_diverse.h"
 #endif /* ARX_H_ */

@@ -1,5 +1,5 @@
 """ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
-include/arx_slate.h and include/arx_diverse.h).
+include/arx_slate.h, include/arx_diverse.h and include/arx_sample.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -255,6 +255,15 @@ DIVERSE_PROTOTYPES = {
                              f32p, i64, i32p, i64, vp]),
 }
 
+# include/arx_sample.h (the sampled recommend: Gumbel keys), one-to-one as above
+SAMPLE_PROTOTYPES = {
+    "arx_topk_gumbel_add": (cint, [f32p, i64, i64, i32, i64, f32p, i64, i32p, vp]),
+    "arx_topk_gumbel_strip": (cint, [f32p, i64, i32p, i64, i64, cint, f32p, i64, i32p, vp]),
+    "arx_gemm_nt_topk_filter_sample": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, f32p, i64, i32, f32p, i32p,
+                                              i64, cint, i32p, f32p, i64, i32p, i64, i32p, i32p, i32p, i32p, i32p, i64,
+                                              f32p, i64, i32p, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -267,7 +276,8 @@ def _load():
             "g.build()'` (or `make -C a-recsys_amd/csrc`).  There is no CPU fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(TAGS_PROTOTYPES.items())
-                              + list(SLATE_PROTOTYPES.items()) + list(DIVERSE_PROTOTYPES.items())):
+                              + list(SLATE_PROTOTYPES.items()) + list(DIVERSE_PROTOTYPES.items())
+                              + list(SAMPLE_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -23,7 +23,7 @@ import torch
 
 from .. import graph as G
 from .. import ops
-from ..topk import TopKScan, logits_too_big, similar_scan, tag_words
+from ..topk import TopKScan, logits_too_big, sample_params, similar_scan, tag_words
 from ..utils.prepare_train import pair_draw_tables
 
 # the full-vocabulary loss a model trained with a sampled loss evaluates with (hmf_model.py:130,144; 'mce' -> 'ce':
@@ -717,6 +717,34 @@ class EmbeddingAttribute(object):
         wa, wl = tag_words(tags_any, tags_all, self.batch_size, what)
         self._tags_any.feed(wa)
         self._tags_all.feed(wl)
+
+    def sample_args(self):
+        """(tau, tau_rows, seed_words) of the sampled recommend: row r draws at temperature [r % batch_size] of the
+        placeholder and with the noise row r % batch_size (ops.topk_gumbel_add, ops.gemm_nt_topk_filter_sample).  The
+        placeholders are made at first use and fed per call: a captured plan replays with a new temperature and seed."""
+        if getattr(self, '_sample_tau', None) is None:
+            self._sample_tau = G.FloatInput(self.rt, (self.batch_size,), 'sample_tau')
+            self._sample_seed = G.IdsInput(self.rt, 2, 'sample_seed')
+        return (self._sample_tau.value, self.batch_size, self._sample_seed.value)
+
+    sample_draws = 0                 # sampled calls that took their seed from this counter (sample_seed=None)
+
+    def next_sample_seed(self, temperature, seed):
+        """The seed of one sampled call: an int as given (the counter stays), None: the draw counter, which starts at 0
+        and goes up by one -- after the checks of topk.sample_params: a refused call does not move it."""
+        sample_params(temperature, 0 if seed is None else seed, self.batch_size)
+        if seed is not None:
+            return seed
+        seed, self.sample_draws = self.sample_draws, self.sample_draws + 1
+        return seed
+
+    def feed_sample(self, temperature, seed):
+        """Check and feed the temperatures and the seed of one sampled recommend call (topk.sample_params: ValueError
+        before any feed)."""
+        tau, words = sample_params(temperature, self.next_sample_seed(temperature, seed), self.batch_size)
+        self.sample_args()
+        self._sample_tau.feed(tau)
+        self._sample_seed.feed(words)
 
     def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536, output_feat=1):
         """Cosine nearest neighbours of items over the full vocabulary, in the latent space recommend scores against:

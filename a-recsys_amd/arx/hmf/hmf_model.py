@@ -254,18 +254,21 @@ class LatentProductModel(object):
         """The items recommend(exclude_seen=True) leaves out per user -- typically the training history:
         {user_index: items} or a (ptr, items) CSR pair in item-index space (EmbeddingAttribute.
         prepare_recommend_exclusions).  A second call replaces the lists (the captured plan is dropped)."""
-        self._plans.pop('recommend_ex', None)
+        for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample'):
+            self._plans.pop(key, None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
     def prepare_item_tags(self, tags):
         """The items' 32-bit tag words for recommend(tags_any=, tags_all=): an integer array [n_items] or
         {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces the words
         (the captured plans that read them are dropped)."""
-        for key in ('recommend_tags', 'recommend_ex_tags'):
+        for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample'):
             self._plans.pop(key, None)
         self.att_emb.prepare_item_tags(tags)
 
     def _recommend_node(self, key):
+        if key.endswith('_sample'):
+            return getattr(self, '_sample_nodes', {}).get(key)
         return {'recommend': self.topk, 'recommend_ex': getattr(self, 'topk_ex', None),
                 'recommend_tags': getattr(self, 'topk_tags', None),
                 'recommend_ex_tags': getattr(self, 'topk_ex_tags', None)}[key]
@@ -353,6 +356,18 @@ class LatentProductModel(object):
             p = G.Plan(rt, [self.topk_ex_tags], False, [])
         elif key == 'warp_eval':
             p = G.Plan(rt, [self.batch_loss], False, [m.mask['warp_eval']])
+        elif key.startswith('recommend') and key.endswith('_sample'):
+            # the sampled twins (topk.recommend_key): the same filters, the keys of m.sample_args
+            ex, tg = '_ex' in key, '_tags' in key
+            if ex:
+                m.exclusion_args()
+            if tg:
+                m.tag_args()
+            nodes = self.__dict__.setdefault('_sample_nodes', {})
+            if key not in nodes:
+                nodes[key] = excluding_twin(rt, self.topk, m.exclusion_args if ex else None,
+                                            m.tag_args if tg else None, sample_args=m.sample_args)
+            p = G.Plan(rt, [nodes[key]], False, [])
         else:
             raise KeyError(key)
         self._plans[key] = p
@@ -435,7 +450,7 @@ class LatentProductModel(object):
     def step_async(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
                    item_sampled_id2idx=None, forward_only=False, recommend=False,
                    recommend_new=False, loss=None, run_op=None, run_meta=None, exclude_seen=False,
-                   tags_any=None, tags_all=None):
+                   tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None):
         """step() without the device->host read of the result: returns the MeanLoss
         node (call .read() for the device scalar) / the top-k index tensor.  recommend with the streaming top-k
         (StreamTopK, fused form): the result is complete only if `self.topk.overflowed()` is False afterwards
@@ -443,7 +458,9 @@ class LatentProductModel(object):
         exclude_seen (with recommend): leave out each user's items of prepare_recommend_exclusions -- node
         self.topk_ex, plan 'recommend_ex'; a user with fewer than top_N eligible items gets -1 tails.
         tags_any / tags_all (with recommend; an int or one int per row): only the items eligible by their tag words
-        of prepare_item_tags -- plans 'recommend_tags' / 'recommend_ex_tags'; both None: the calls above."""
+        of prepare_item_tags -- plans 'recommend_tags' / 'recommend_ex_tags'; both None: the calls above.
+        sample_temperature / sample_seed (with recommend): the sampled recommend of step() -- the plans ending in
+        '_sample'; None: the calls above."""
         if loss is None:
             loss = self.loss_function
         if exclude_seen and recommend:
@@ -451,6 +468,9 @@ class LatentProductModel(object):
         tagged = recommend and (tags_any is not None or tags_all is not None)
         if tagged:
             self.att_emb.feed_tag_words(tags_any, tags_all)       # ValueError before any other feed
+        sampled = recommend and sample_temperature is not None
+        if sampled:
+            self.att_emb.feed_sample(sample_temperature, sample_seed)
         # pair losses: a step without negatives draws them inside its plan (prepare_pair_negatives)
         pair = self.loss_function in ('bpr', 'bpr-hinge') and not recommend
         draw = pair and (neg_item_input is None or len(neg_item_input) == 0)
@@ -464,8 +484,8 @@ class LatentProductModel(object):
             if draw:
                 self.rt.drop_feed(self.att_emb.i_indices['neg'].value)    # (a queued older feed must not overwrite the draw)
             self.batch_loss.draw = self.att_emb.neg_draw if draw else None
-        if tagged:
-            key = recommend_key(exclude_seen, True)
+        if tagged or sampled:
+            key = recommend_key(exclude_seen, tagged, sampled)
             self._plan(key).run()
             return self._recommend_node(key).indices
         if recommend and exclude_seen:
@@ -491,7 +511,8 @@ class LatentProductModel(object):
 
     def step(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
-             loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None):
+             loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None,
+             sample_temperature=None, sample_seed=None):
         """hmf_model.py:162-228.  Returns: train -> mean loss (float); forward_only ->
         loss_eval (float); recommend -> int32 [mb, top_N]; warp_eval -> [loss, rank].
         'bpr' / 'bpr-hinge': neg_item_input (list, array or device tensor) holds one negative item per row; None or
@@ -501,14 +522,25 @@ class LatentProductModel(object):
         prepare_recommend_exclusions (ValueError if none were prepared); -1 where a user has fewer eligible items.
         recommend with tags_any / tags_all (an int: one 32-bit word for every row, or one int per row): only the items
         whose tag word of prepare_item_tags has a bit of `any` (0: no constraint) and every bit of `all`; composes
-        with exclude_seen.  ValueError without prepare_item_tags, for words outside [0, 2^32) or a wrong length."""
+        with exclude_seen.  ValueError without prepare_item_tags, for words outside [0, 2^32) or a wrong length.
+        recommend with sample_temperature (a number >= 0 or one per row; None: the deterministic call, untouched): top_N
+        DISTINCT items drawn with probability proportional to exp(score / temperature), one after the other without
+        replacement, returned in SELECTION order (the first id is the first draw); a row of temperature 0 is its plain
+        top-k.  sample_seed: an int in [0, 2^63) -- the same seed gives the same items, on every path; None takes the
+        model's draw counter (att_emb.sample_draws: starts at 0, one up per such call).  Composes with exclude_seen
+        and the tags."""
+        sampled = recommend and sample_temperature is not None
+        if sampled:
+            # resolved once here: the chunked re-run after a candidate overflow must draw the same sample
+            sample_seed = self.att_emb.next_sample_seed(sample_temperature, sample_seed)
         run = lambda: self.step_async(session, user_input, item_input, neg_item_input, item_sampled,
                                       item_sampled_id2idx, forward_only, recommend, recommend_new, loss,
                                       run_op, run_meta, exclude_seen=exclude_seen, tags_any=tags_any,
-                                      tags_all=tags_all)
+                                      tags_all=tags_all, sample_temperature=sample_temperature,
+                                      sample_seed=sample_seed)
         if recommend:
             # (a candidate list of the fused top-k too short for this batch: the request once more, chunked)
-            key = recommend_key(exclude_seen, tags_any is not None or tags_all is not None)
+            key = recommend_key(exclude_seen, tags_any is not None or tags_all is not None, sampled)
             self._plan(key)                    # builds the twin node / raises as the step would
             node = self._recommend_node(key)
             return run_complete(node, run, lambda: self._plans.pop(key, None)).cpu().numpy()

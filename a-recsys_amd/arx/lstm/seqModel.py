@@ -273,26 +273,36 @@ class TopKSoftmax(G.Node):
     the row logsumexp is taken over ALL the columns first, then each row's excluded columns are set to -inf IN the
     logits and the select runs; winners of value -inf get index -1 (softmax value exp(-inf) = 0).
     tags (optional): a callable giving (col_tags, want_any, want_all, want_rows) (EmbeddingAttribute.tag_args): the
-    columns ineligible by their tag words are set to -inf the same way, after the logsumexp."""
+    columns ineligible by their tag words are set to -inf the same way, after the logsumexp.
+    sample (optional): a callable giving (tau, tau_rows, seed_words) (EmbeddingAttribute.sample_args), or that tuple:
+    the sampled recommend (arx.topk) -- after the logsumexp and the fills the logits become Gumbel keys, the select draws, and
+    the winners' values are turned back into logits: exp(v - lse) is the item's softmax value at temperature 1."""
 
-    def __init__(self, rt, logits, k, exclude=None, tags=None):
+    def __init__(self, rt, logits, k, exclude=None, tags=None, sample=None):
         super().__init__(rt, (logits.shape[0], k), (logits,))
         self.k = k
         self.exclude = exclude
         self.tags = tags
+        self.sample = sample
         self.indices = torch.empty((logits.shape[0], k), dtype=torch.int32, device=rt.device)
         self.lse = torch.empty((logits.shape[0],), dtype=torch.float32, device=rt.device)
 
     def forward(self, train):
         x = self.inputs[0].value
-        if self.exclude is not None or self.tags is not None:
+        if self.exclude is not None or self.tags is not None or self.sample is not None:
             ops.row_logsumexp(x, self.lse)
             if self.exclude is not None:
                 ops.topk_exclude_fill(x, 0, self.exclude())
             if self.tags is not None:
                 ops.topk_tags_fill(x, 0, self.tags())
+            sample = self.sample() if callable(self.sample) else self.sample
+            if sample is not None:
+                ops.topk_gumbel_add(x, 0, sample)
             ops.topk(x, self.k, self.alloc_value(), self.indices)
-            ops.topk_mark_empty(self.value, self.indices)
+            if self.exclude is not None or self.tags is not None:
+                ops.topk_mark_empty(self.value, self.indices)
+            if sample is not None:
+                ops.topk_gumbel_strip(self.value, self.indices, sample)
             return
         ops.topk(x, self.k, self.alloc_value(), self.indices)
         ops.row_logsumexp(x, self.lse)
@@ -529,6 +539,12 @@ class SeqModel(SeqBatching):
                 if key not in bk:               # (rows as above: the two request words are want_*[r % mb])
                     bk[key] = excluding_twin(self.rt, bk.get('recommend_stream', bk['recommend']),
                                              m.exclusion_args if key == 'recommend_ex_tags' else None, m.tag_args)
+                bk['plans'][key] = G.Plan(self.rt, [bk[key]], False, [])
+            elif key.endswith('_sample'):
+                if key not in bk:               # the sampled twins: temperature and noise row of row r are [r % mb]
+                    bk[key] = excluding_twin(self.rt, bk.get('recommend_stream', bk['recommend']),
+                                             m.exclusion_args if '_ex' in key else None,
+                                             m.tag_args if '_tags' in key else None, sample_args=m.sample_args)
                 bk['plans'][key] = G.Plan(self.rt, [bk[key]], False, [])
             else:
                 bk['plans'][key] = G.Plan(self.rt, [bk['eval']], False, m.eval_masks(self.loss, bk['eval'].inputs[0]))
@@ -810,14 +826,15 @@ class SeqModel(SeqBatching):
         """The items step_recommend(exclude_seen=True) leaves out per user: {user_index: items} or a (ptr, items) CSR
         pair in item-index space (EmbeddingAttribute.prepare_recommend_exclusions).  A second call replaces them."""
         for bk in self._bk.values():
-            bk['plans'].pop('recommend_ex', None)
+            for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample'):
+                bk['plans'].pop(key, None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
     def prepare_item_tags(self, tags):
         """The items' 32-bit tag words for step_recommend(tags_any=, tags_all=): an integer array [n_items] or
         {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces them."""
         for bk in self._bk.values():
-            for key in ('recommend_tags', 'recommend_ex_tags'):
+            for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample'):
                 bk['plans'].pop(key, None)
         self.att_emb.prepare_item_tags(tags)
 
@@ -828,7 +845,7 @@ class SeqModel(SeqBatching):
                                           chunk=chunk, output_feat=self.output_feat)
 
     def step_recommend(self, session, user_input, item_inputs, positions, bucket_id, exclude_seen=False,
-                       tags_any=None, tags_all=None):
+                       tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None):
         """seqModel.py:326-353 -> [(uid, values[topk_n], indexes[topk_n])]: the top-k softmax
         values / logit indexes at time position positions[i] of sequence i.  Small vocabularies: the full
         [L*mb, V] logits are materialised; past ARX_STREAM_TOPK_BYTES (1 GB) the mb rows asked for are gathered
@@ -839,17 +856,26 @@ class SeqModel(SeqBatching):
         tags_any / tags_all (an int or one int per sequence): only the items eligible by their tag words of
         prepare_item_tags (plans 'recommend_tags' / 'recommend_ex_tags'), the normaliser again over the full
         vocabulary; composes with exclude_seen.  Under arx.dist.SeqHybridParallel the call is that wrapper's
-        collective of the same name (which takes no tags: NotImplementedError)."""
+        collective of the same name (which takes no tags and no sample: NotImplementedError).
+        sample_temperature (a number >= 0 or one per sequence; None: the call above) / sample_seed: topk_n distinct
+        items DRAWN with probability proportional to exp(logit / temperature), in selection order
+        (LatentProductModel.step states the rules); a value is still exp(logit - lse) with lse over the full
+        vocabulary: the item's softmax probability at temperature 1, whatever the temperature was."""
         dp = self.rt.dp
         tagged = tags_any is not None or tags_all is not None
+        drawn = sample_temperature is not None
         if dp is not None and hasattr(dp, 'step_recommend'):
             if tagged:
                 raise NotImplementedError("step_recommend with item tags under SeqHybridParallel")
+            if drawn:
+                raise NotImplementedError("step_recommend with sample_temperature under SeqHybridParallel")
             return dp.step_recommend(session, user_input, item_inputs, positions, bucket_id, exclude_seen)
         if exclude_seen:
             self.att_emb.exclusion_args()      # ValueError before any feed when nothing was prepared
         if tagged:
             self.att_emb.feed_tag_words(tags_any, tags_all, 'step_recommend')
+        if drawn:
+            self.att_emb.feed_sample(sample_temperature, sample_seed)   # (fed once: a chunked re-run draws the same)
         L = self.buckets[bucket_id]
         m, B = self.att_emb, self.batch_size
         it = item_inputs
@@ -859,7 +885,7 @@ class SeqModel(SeqBatching):
         m.add_input({}, user_input, None, forward_only=True, recommend=True, loss=self.loss)
         bk = self._bucket(bucket_id)
         users = user_input.cpu().numpy() if isinstance(user_input, torch.Tensor) else user_input
-        key = recommend_key(exclude_seen, tagged)
+        key = recommend_key(exclude_seen, tagged, drawn)
         if 'recommend_stream' in bk:
             bk['rec_rows'].feed(np.asarray([int(pos) * B + i for i, pos in enumerate(positions)], dtype=np.int32))
             self._plan(bucket_id, key)

@@ -1326,6 +1326,42 @@ def gemm_nt_topk_filter_tags(A, Bm, col_bias, thr, col_base, cand_v, cand_i, cap
          _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _stream())
 
 
+def topk_gumbel_add(logits, col0, sample):
+    """logits[r, c] = fmaf(tau[r % tau_rows], g(r % tau_rows, col0 + c), logits[r, c]) in place: the logits become the
+    keys of the sampled recommend (arx_sample.h).  sample: (tau float32 [tau_rows], tau_rows, seed_words int32 [2])."""
+    if logits.numel() == 0:
+        return
+    tau, tau_rows, seed_words = sample
+    call("arx_topk_gumbel_add", _p(logits), _ld(logits), int(logits.shape[0]), int(col0), int(logits.shape[1]),
+         _p(tau), int(tau_rows), _p(seed_words), _stream())
+
+
+def topk_gumbel_strip(values, indices, sample):
+    """values = fmaf(-tau, g(r % tau_rows, index), key): the winners' keys back into scores; -inf at index -1
+    (arx_sample.h)."""
+    tau, tau_rows, seed_words = sample
+    call("arx_topk_gumbel_strip", _p(values), _ld(values), _p(indices), _ld(indices), int(values.shape[0]),
+         int(values.shape[1]), _p(tau), int(tau_rows), _p(seed_words), _stream())
+
+
+def gemm_nt_topk_filter_sample(A, Bm, col_bias, thr, col_base, cand_v, cand_i, capp, overflow, sample, tags=None,
+                               ex=None, lse_part=None):
+    """gemm_nt_topk_filter_tags on the KEYS fmaf(tau, g, logit): thr and cand_v are keys, lse_part stays over the
+    logits (arx_sample.h).  sample: (tau, tau_rows, seed_words); tags: (col_tags ALREADY sliced to this launch's
+    columns, want_any, want_all, want_rows) or None; ex: exclusion lists or None."""
+    tau, tau_rows, seed_words = sample
+    col_tags, want_any, want_all, want_rows = tags if tags is not None else (None, None, None, 0)
+    if tags is not None and int(col_tags.shape[0]) < int(Bm.shape[0]):
+        raise ValueError("gemm_nt_topk_filter_sample: %d tag words for %d columns"
+                         % (int(col_tags.shape[0]), int(Bm.shape[0])))
+    keys, key_rows, ptr, cols = ex if ex is not None else (None, 0, None, None)
+    call("arx_gemm_nt_topk_filter_sample", _p(A), _ld(A), int(A.shape[0]), _p(Bm), _ld(Bm), int(Bm.shape[0]),
+         int(A.shape[1]), _p(col_bias), _p(thr), int(thr.stride(0)), int(col_base), _p(cand_v), _p(cand_i),
+         int(cand_v.stride(0)), int(capp), _p(overflow), _p(lse_part),
+         int(lse_part.stride(0)) if lse_part is not None else 0, _p(keys), int(key_rows), _p(ptr), _p(cols),
+         _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _p(tau), int(tau_rows), _p(seed_words), _stream())
+
+
 def topk_mark_empty(values, indices):
     """indices = -1 where values == -inf (a row with fewer eligible columns than k)."""
     call("arx_topk_mark_empty", _p(values), _ld(values), _p(indices), _ld(indices), int(values.shape[0]),

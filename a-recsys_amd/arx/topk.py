@@ -5,6 +5,12 @@ Item tags (recommend within "only this category / in stock / this market"): ever
 word, every request row two words (any, all); column c is eligible for row r iff
 (any[r] == 0 or tags[c] & any[r]) and tags[c] & all[r] == all[r] -- the nodes take tags= beside exclude=, the rule
 itself lives in the kernels (arx_tags.h: arx_topk_tags_fill, arx_gemm_nt_topk_filter_tags).
+Sampled recommend: the nodes take sample= beside tags= -- (tau [tau_rows] float32, tau_rows, seed_words int32 [2]) on
+the device, or a callable giving it -- and return k DISTINCT columns drawn with probability proportional to
+exp(score / tau), one after the other without replacement (Plackett-Luce), in SELECTION order: the top-k of the keys
+fmaf(tau, g, score), g the Gumbel noise of arx_sample.h, a pure function of (seed, row % tau_rows, column), so the dense,
+the chunked and the fused path draw the same sample.  The values are the winners' SCORES again (arx_topk_gumbel_strip),
+not monotone along a row.  What a temperature and a seed may be: sample_params.
 """
 from __future__ import annotations
 
@@ -43,13 +49,17 @@ class TopK(G.Node):
     them), and winners of value -inf (rows with fewer than k eligible columns) get index -1.
     tags (optional): a callable giving (col_tags, want_any, want_all, want_rows) (EmbeddingAttribute.tag_args), or
     that tuple: the columns ineligible for a row by their tag words are set to -inf the same way; a column must pass
-    both."""
+    both.
+    sample (optional): a callable giving (tau, tau_rows, seed_words) (EmbeddingAttribute.sample_args), or that tuple:
+    the eligible logits become Gumbel keys before the select (k draws without replacement from softmax(logits / tau),
+    in selection order) and the winners' values are turned back into logits after it."""
 
-    def __init__(self, rt, logits, k, exclude=None, tags=None):
+    def __init__(self, rt, logits, k, exclude=None, tags=None, sample=None):
         super().__init__(rt, (logits.shape[0], k), (logits,))
         self.k = k
         self.exclude = exclude
         self.tags = tags
+        self.sample = sample
         self.indices = torch.empty((logits.shape[0], k), dtype=torch.int32, device=rt.device)
 
     def forward(self, train):
@@ -58,9 +68,14 @@ class TopK(G.Node):
             ops.topk_exclude_fill(x, 0, self.exclude())
         if self.tags is not None:
             ops.topk_tags_fill(x, 0, self.tags() if callable(self.tags) else self.tags)
+        sample = self.sample() if callable(self.sample) else self.sample
+        if sample is not None:
+            ops.topk_gumbel_add(x, 0, sample)
         ops.topk(x, self.k, self.alloc_value(), self.indices)
         if self.exclude is not None or self.tags is not None:
             ops.topk_mark_empty(self.value, self.indices)
+        if sample is not None:
+            ops.topk_gumbel_strip(self.value, self.indices, sample)
 
 
 class TopKScan(object):
@@ -132,7 +147,8 @@ class TopKScan(object):
         finally:
             self.fused = was
 
-    def run(self, latent, pool, bias, ws, values, indices, ex=None, col_scale=None, self_col=None, tags=None):
+    def run(self, latent, pool, bias, ws, values, indices, ex=None, col_scale=None, self_col=None, tags=None,
+            sample=None):
         """values / indices [B, k] = the top-k of latent . pool^T + bias (bias may be None) over all V >= k pool rows;
         ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace.
         col_scale [V] (None: every launch is the one above): the scores are (latent . pool^T) * col_scale[column] --
@@ -142,9 +158,15 @@ class TopKScan(object):
         tags: (col_tags [V] int32, want_any, want_all, want_rows) or None -- only the columns eligible for a row by
         their tag words enter its result (composes with ex; the log-sum-exp stays over ALL the columns).  A tag too
         rare to give k eligible columns in the first chunk leaves the threshold at -inf: the fused lists may then
-        overflow, and run_complete re-runs the request on the chunked path."""
+        overflow, and run_complete re-runs the request on the chunked path.
+        sample: (tau [tau_rows], tau_rows, seed_words) or None -- the sampled recommend: per chunk the order is GEMM,
+        log-sum-exp, exclusion fill, tags fill, gumbel_add, select; the fused rest goes through
+        gemm_nt_topk_filter_sample (threshold and candidates are keys); after the merge and mark_empty, gumbel_strip
+        turns the winners' keys back into scores.  Not with col_scale."""
         V, k = pool.shape[0], self.k
         cos = col_scale is not None
+        if cos and sample is not None:
+            raise ValueError("TopKScan.run: col_scale (the cosine form) takes no sample")
         if cos and tags is not None:
             raise ValueError("TopKScan.run: col_scale (the cosine form) takes no item tags")
         if tags is not None and int(tags[0].shape[0]) != V:
@@ -172,12 +194,19 @@ class TopKScan(object):
                 ops.topk_exclude_fill(lg, 0, ex)                # threshold = the k-th best ELIGIBLE column
             if tags is not None:
                 ops.topk_tags_fill(lg, 0, tags)
+            if sample is not None:
+                ops.topk_gumbel_add(lg, 0, sample)              # threshold = the k-th best KEY
             ops.topk_chunk(lg, k, 0, run_v, run_i)
             ops.fill_f32(cand_v.view(-1), float('-inf'))
             ops.fill_i32(self.overflow, 0)
             if cos:
                 ops.gemm_nt_topk_filter_cos(latent, pool[n0:], col_scale[n0:], self_col, run_v[:, k - 1], n0, cand_v,
                                             cand_i, capp, self.overflow)
+            elif sample is not None:
+                ops.gemm_nt_topk_filter_sample(latent, pool[n0:], bias[n0:] if bias is not None else None,
+                                               run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow, sample,
+                                               tags=(tags[0][n0:],) + tuple(tags[1:]) if tags is not None else None,
+                                               ex=ex, lse_part=lp)
             elif tags is not None:
                 ops.gemm_nt_topk_filter_tags(latent, pool[n0:], bias[n0:] if bias is not None else None,
                                              run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow,
@@ -198,6 +227,8 @@ class TopKScan(object):
             indices.copy_(out_i)
             if empties:
                 ops.topk_mark_empty(values, indices)
+            if sample is not None:
+                ops.topk_gumbel_strip(values, indices, sample)
             return
         nch = (V + self.chunk - 1) // self.chunk
         lp = self._lse_buf(nch) if self.want_lse else None
@@ -213,6 +244,8 @@ class TopKScan(object):
                 ops.topk_exclude_fill(lg, c0, ex)
             if tags is not None:
                 ops.topk_tags_fill(lg, c0, tags)
+            if sample is not None:
+                ops.topk_gumbel_add(lg, c0, sample)
             if cos:
                 ops.cos_chunk_finish(lg, c0, col_scale, self_col)
             if c0 == 0:                              # chunk >= k and V >= k: the first chunk fills all k
@@ -228,6 +261,8 @@ class TopKScan(object):
             indices.copy_(run_i)
         if empties:
             ops.topk_mark_empty(values, indices)
+        if sample is not None:
+            ops.topk_gumbel_strip(values, indices, sample)
         if self.want_lse:
             ops.row_logsumexp(lp, self.lse)
 
@@ -248,21 +283,27 @@ class StreamTopK(G.Node, TopKScan):
     (want_lse) stays over ALL the columns.  tags (optional): a callable giving (col_tags, want_any, want_all,
     want_rows) (EmbeddingAttribute.tag_args), or that tuple: the columns ineligible for a row by their tag words never enter its
     result either (the same two places: -inf fills and the fused GEMM's survivor test).  share: another StreamTopK over the same shapes whose logits chunk buffer
-    this one re-uses (plans run one after the other on one stream).  The algorithm and its buffers: TopKScan."""
+    this one re-uses (plans run one after the other on one stream).  sample (optional): a callable giving (tau,
+    tau_rows, seed_words) (EmbeddingAttribute.sample_args), or that tuple: the sampled recommend (TopKScan.run).
+    The algorithm and its buffers: TopKScan."""
 
-    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None, tags=None):
+    def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None, tags=None,
+                 sample=None):
         G.Node.__init__(self, rt, (latent.shape[0], k), (latent, pool))
         TopKScan.__init__(self, latent.shape[0], pool.shape[0], latent.shape[1], k, rt.device, chunk=chunk,
                           want_lse=want_lse, share=share)
         self.exclude = exclude
         self.tags = tags
+        self.sample = sample
         self.fused = self.fused and pool.shape[1] == latent.shape[1]
 
     def forward(self, train):
         latent, pool = self.inputs
         ex = self.exclude() if self.exclude is not None else None
         tags = self.tags() if callable(self.tags) else self.tags
-        self.run(latent.value, pool.value, pool.bias_value, self.rt.ws, self.alloc_value(), self.indices, ex, tags=tags)
+        sample = self.sample() if callable(self.sample) else self.sample
+        self.run(latent.value, pool.value, pool.bias_value, self.rt.ws, self.alloc_value(), self.indices, ex, tags=tags,
+                 sample=sample)
 
 
 def recommend_node(rt, logits, k, rows):
@@ -274,22 +315,52 @@ def recommend_node(rt, logits, k, rows):
     return TopK(rt, logits, k)
 
 
-def excluding_twin(rt, node, exclusion_args=None, tag_args=None):
+def excluding_twin(rt, node, exclusion_args=None, tag_args=None, sample_args=None):
     """The twin of a recommend node that leaves columns out -- by the exclusion lists, by the item tags, or by both
-    (the plain node and its plan stay as they are); a streaming twin shares the plain node's chunk buffer."""
-    if exclusion_args is None and tag_args is None:
+    (the plain node and its plan stay as they are); a streaming twin shares the plain node's chunk buffer.
+    sample_args: the SAMPLED twin (alone, or on top of either filter)."""
+    if exclusion_args is None and tag_args is None and sample_args is None:
         raise ValueError("excluding_twin: exclusion lists, item tags or both")
     if isinstance(node, StreamTopK):
+        more = {} if sample_args is None else {'sample': sample_args}
         return StreamTopK(rt, node.inputs[0], node.inputs[1], node.k, chunk=node.chunk, want_lse=node.want_lse,
-                          exclude=exclusion_args, share=node, tags=tag_args)
+                          exclude=exclusion_args, share=node, tags=tag_args, **more)
+    if sample_args is not None:
+        return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args, tags=tag_args, sample=sample_args)
     if tag_args is None:
         return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args)
     return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args, tags=tag_args)
 
 
-def recommend_key(exclude_seen, tagged):
-    """The plan of a recommend call: 'recommend', 'recommend_ex', 'recommend_tags' or 'recommend_ex_tags'."""
-    return 'recommend' + ('_ex' if exclude_seen else '') + ('_tags' if tagged else '')
+def recommend_key(exclude_seen, tagged, sampled=False):
+    """The plan of a recommend call: 'recommend', 'recommend_ex', 'recommend_tags' or 'recommend_ex_tags'; the sampled
+    twins end in '_sample'."""
+    return 'recommend' + ('_ex' if exclude_seen else '') + ('_tags' if tagged else '') + ('_sample' if sampled else '')
+
+
+def sample_params(temperature, seed, rows):
+    """The temperatures and the seed of one sampled recommend call as what the device placeholders hold: float32
+    [rows] and the two int32 seed words (low, high).  temperature: one number for every row or one per row, finite
+    and >= 0 (0: that row is the plain top-k); seed: an int in [0, 2^63).  ValueError for a negative, NaN or infinite
+    temperature, a bool, a non-number, a wrong length, or a seed outside the range."""
+    t = temperature.cpu().numpy() if isinstance(temperature, torch.Tensor) else temperature
+    a = np.asarray(t)
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise ValueError("sample_temperature must be a number or %d numbers, one per row" % rows)
+    if a.ndim > 1 or (a.ndim == 1 and len(a) != rows):
+        raise ValueError("sample_temperature must be one number or %d numbers, one per row" % rows)
+    a = a.astype(np.float64)
+    if not np.all(np.isfinite(a)) or np.any(a < 0):
+        raise ValueError("sample_temperature must be finite and >= 0")
+    with np.errstate(over='ignore'):
+        tau = np.ascontiguousarray(np.broadcast_to(a, (rows,)).astype(np.float32))
+    if not np.all(np.isfinite(tau)):
+        raise ValueError("sample_temperature must be finite in float32")
+    if isinstance(seed, (bool, np.bool_)) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 63:
+        raise ValueError("sample_seed must be an int in [0, 2^63)")
+    seed = int(seed)
+    words = np.array([seed & 0xffffffff, seed >> 32], dtype=np.uint32).view(np.int32)
+    return tau, words
 
 
 def tag_words(tags_any, tags_all, rows, what='recommend'):

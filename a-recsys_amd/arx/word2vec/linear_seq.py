@@ -175,13 +175,14 @@ class LinearSeq(object):
     def prepare_recommend_exclusions(self, item_sets):
         """The items step(recommend=True, exclude_seen=True) leaves out per user: {user_index: items} or a (ptr, items)
         CSR pair in item-index space (EmbeddingAttribute.prepare_recommend_exclusions).  A second call replaces them."""
-        self._plans.pop('recommend_ex', None)
+        for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample'):
+            self._plans.pop(key, None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
     def prepare_item_tags(self, tags):
         """The items' 32-bit tag words for step(recommend=True, tags_any=, tags_all=): an integer array [n_items] or
         {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces them."""
-        for key in ('recommend_tags', 'recommend_ex_tags'):
+        for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample'):
             self._plans.pop(key, None)
         self.att_emb.prepare_item_tags(tags)
 
@@ -233,6 +234,12 @@ class LinearSeq(object):
                 if getattr(self, 'topk_ex_tags', None) is None:
                     self.topk_ex_tags = excluding_twin(rt, self.topk, m.exclusion_args, m.tag_args)
                 self._plans[key] = G.Plan(rt, [self.topk_ex_tags], False, [])
+            elif key.endswith('_sample'):                       # the sampled twins (topk.recommend_key)
+                nodes = self.__dict__.setdefault('_sample_nodes', {})
+                if key not in nodes:
+                    nodes[key] = excluding_twin(rt, self.topk, m.exclusion_args if '_ex' in key else None,
+                                                m.tag_args if '_tags' in key else None, sample_args=m.sample_args)
+                self._plans[key] = G.Plan(rt, [nodes[key]], False, [])
             else:
                 self._plans[key] = G.Plan(rt, [self.topk], False, [])
         return self._plans[key]
@@ -241,7 +248,8 @@ class LinearSeq(object):
         """Run the 'recommend' / 'recommend_ex' / 'recommend_tags' / 'recommend_ex_tags' plan; a streaming top-k whose fused candidate lists overflowed runs
         once more on the chunked path (as LatentProductModel.step)."""
         self._plan(key)
-        node = {'recommend': self.topk, 'recommend_ex': getattr(self, 'topk_ex', None),
+        node = self._sample_nodes[key] if key.endswith('_sample') else \
+               {'recommend': self.topk, 'recommend_ex': getattr(self, 'topk_ex', None),
                 'recommend_tags': getattr(self, 'topk_tags', None),
                 'recommend_ex_tags': getattr(self, 'topk_ex_tags', None)}[key]
         # (the placeholders still hold this request's ids in the second run)
@@ -250,12 +258,15 @@ class LinearSeq(object):
 
     def step(self, session, user_input, item_input=None, item_output=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
-             loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None):
+             loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None,
+             sample_temperature=None, sample_seed=None):
         """linear_seq.py:67-121.  item_input: [n_input][mb] context items (time-major);
         item_output: [mb] target items.  Returns the mean loss (train / forward_only) or the
         top-N logit indices [mb, top_N] (recommend; exclude_seen=True: without each user's items of
         prepare_recommend_exclusions, -1 where a user has fewer eligible items; tags_any / tags_all -- an int or one
-        int per row: only the items eligible by their tag words of prepare_item_tags, composing with exclude_seen).
+        int per row: only the items eligible by their tag words of prepare_item_tags, composing with exclude_seen;
+        sample_temperature / sample_seed: top_N distinct items DRAWN with probability proportional to
+        exp(score / temperature), in selection order -- LatentProductModel.step states the rules).
         'mw' / 'mce': item_sampled (n_sampled item ids) stages a new pool -- the first training step needs one,
         later steps keep it until the next is given (run_w2v.py:315-317); item_sampled_id2idx is the host twin of
         the pool's item -> slot map.  forward_only evaluates 'mw' with the full-vocabulary 'warp' loss and 'mce'
@@ -269,6 +280,9 @@ class LinearSeq(object):
         tagged = recommend and (tags_any is not None or tags_all is not None)
         if tagged:
             m.feed_tag_words(tags_any, tags_all)                  # ValueError before any other feed
+        drawn = recommend and sample_temperature is not None
+        if drawn:
+            m.feed_sample(sample_temperature, sample_seed)        # (fed once: the chunked re-run draws the same sample)
         if sampled and not (recommend or forward_only) and item_sampled is None and m._old_pool is None:
             raise ValueError("the first %r training step needs item_sampled (the pool of n_sampled items)"
                              % self.loss_function)
@@ -287,7 +301,7 @@ class LinearSeq(object):
         for op in update_sampled:              # stage the pool (embed_attribute.py:320-348)
             op()
         if recommend:
-            return self._recommend(recommend_key(exclude_seen, tagged))
+            return self._recommend(recommend_key(exclude_seen, tagged, drawn))
         if forward_only:
             self._plan('eval').run()
             return float(self.loss_test.read().item())

@@ -20,6 +20,7 @@
 //     again on the ds_read_b128 side: 16 B chunk c of pool row r lives at slot c ^ swz(r);
 //   * 64 KB of LDS and ~200 VGPRs => two workgroups per CU.
 #include "common.h"
+#include "gumbel.h"
 
 namespace arx {
 
@@ -70,6 +71,9 @@ struct NtFilter {
   // the two words want_any / want_all [r % want_rows]; c is eligible for r iff
   // (any == 0 || (tags & any) != 0) && (tags & all) == all -- a zero word is no constraint
   const int32_t* col_tags; const int32_t* want_any; const int32_t* want_all; int64_t want_rows;
+  // kNtGumbel (the sampled recommend, gumbel.h): row r competes with the KEYS fmaf(tau, g, v), tau = tau[r % tau_rows],
+  // g the noise of (seed_words, r % tau_rows, col_base + col); thr and cand_v are keys, lse_part stays over v
+  const float* tau; int64_t tau_rows; const int32_t* seed_words;
 };
 
 // MODE (FILTER kernels): bit 0 candidate lists (thr), bit 1 lse_part, bit 2 relu_part, bit 3 exclusion lists (with
@@ -79,7 +83,12 @@ struct NtFilter {
 // bit 7 item tags (with bit 0, optionally bits 1 and 3): the eligibility test of NtFilter::col_tags on a survivor -- the
 // column's tag word is loaded from global memory THERE, not carried per lane beside the bias: two more registers per
 // lane for every tile would not fit under the 256 the two workgroups per CU leave (the plain filter holds 246)
+// bit 8 Gumbel keys (with bit 0, optionally bits 1, 3 and 7): every logit's hash and a logarithm-free upper bound of
+// its key (gumbel_upper) are computed; the two accurate logarithms only where a lane of the wave may pass.  The row's
+// (tau, b0, b1, thr) come from LDS per logit (one 16-byte read, two addresses per wave): 48 more registers would not
+// fit, and the 16 of the thresholds are given back
 constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8, kNtRank = 16, kNtCos = 32, kNtSelf = 64, kNtTags = 128;
+constexpr int kNtGumbel = 256;
 
 template <int KT, int MODE = 0>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
@@ -96,6 +105,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   static_assert(!want_self || want_cos, "the self column belongs to the item-to-item scan");
   constexpr bool want_tags = (MODE & kNtTags) != 0;
   static_assert(!want_tags || (want_topk && !want_relu && !want_cos), "the item tags filter the recommend candidates");
+  constexpr bool want_gumbel = (MODE & kNtGumbel) != 0;
+  static_assert(!want_gumbel || (want_topk && !want_relu && !want_cos), "the Gumbel keys rank the recommend candidates");
   constexpr int NS = KT / 8;                  // steps of 4 MFMAs
   constexpr int CPR = KT / 4;                 // 16-B chunks per pool row
   constexpr int NLB = kNtBN * CPR / 256;      // DMA pieces per thread per tile
@@ -165,6 +176,9 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   __shared__ int s_xb[want_excl ? kNtBM : 1], s_xe[want_excl ? kNtBM : 1];
   // kNtTags: each row's two request words (1 KB; read only by a lane whose logit beat the threshold)
   __shared__ uint32_t s_wa[want_tags ? kNtBM : 1], s_wl[want_tags ? kNtBM : 1];
+  // kNtGumbel: each row's (tau, b0, b1, thr) (2 KB; read per logit, 16 bytes at two addresses per wave -- the
+  // threshold too: th[] below then holds no registers in this mode)
+  __shared__ uint4 s_gm[want_gumbel ? kNtBM : 1];
   // kNtRank: the rows' target columns (read per tile by one lane per row, per logit only in a tile that holds one)
   // kNtSelf: the rows' own columns, absolute (read only by a lane whose logit beat the threshold)
   __shared__ int s_tc[(want_rank || want_self) ? kNtBM : 1];
@@ -221,6 +235,12 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
         const int64_t wr = row < M ? row % flt.want_rows : 0;
         s_wa[threadIdx.x] = row < M ? (uint32_t)flt.want_any[wr] : 0u;
         s_wl[threadIdx.x] = row < M ? (uint32_t)flt.want_all[wr] : 0u;
+      }
+      if (want_gumbel) {
+        const int64_t nr = row < M ? row % flt.tau_rows : 0;
+        const GumbelRow gr = gumbel_row(flt.seed_words, nr);
+        s_gm[threadIdx.x] = make_uint4(__float_as_uint(row < M ? flt.tau[nr] : 0.f), gr.b0, gr.b1,
+                                       __float_as_uint(row < M ? flt.thr[row * flt.ldthr] : __builtin_inff()));
       }
     }
 #pragma unroll
@@ -352,6 +372,21 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
           if (!want_topk) continue;
           bool pred = col < N && v > th[e];
           const int rl = rl0 + (e & 3) + 8 * (e >> 2);
+          float key = v;
+          if (want_gumbel) {
+            // g <= gumbel_upper and fmaf is monotone in g (tau >= 0): a logit whose bound fails cannot pass, and the
+            // logarithms run only in a wave where some lane's bound passes (tau == 0: key == v bit for bit)
+            const uint4 gm = s_gm[rl];
+            const float tau = __uint_as_float(gm.x);
+            const uint32_t x = gumbel_bits(gm.y, gm.z, (uint32_t)flt.col_base + (uint32_t)col);
+            const float thk = __uint_as_float(gm.w);
+            pred = col < N && fmaf(tau, gumbel_upper(x), v) > thk;
+            if (__ballot(pred) == 0ull) continue;
+            if (pred) {
+              key = fmaf(tau, gumbel_of_bits(x), v);
+              pred = key > thk;
+            }
+          }
           // the row's own column (a survivor: rare) leaves BEFORE the ballot, as an excluded one does
           if (want_self && pred && flt.col_base + (int32_t)col == s_tc[rl]) pred = false;
           if (want_tags && pred) {
@@ -387,7 +422,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
           if (pred) {
             if (pos < flt.capp) {
               const int64_t at = (rbase + (e & 3) + 8 * (e >> 2)) * flt.ldcand + (int64_t)part * flt.capp + pos;
-              flt.cand_v[at] = v;
+              flt.cand_v[at] = key;
               flt.cand_i[at] = flt.col_base + (int32_t)col;
             } else {
               ovf = true;
@@ -510,6 +545,20 @@ static void nt_launch_mode(int64_t K, int64_t grid, hipStream_t s, int64_t M, in
     k_gemm_nt_areg<32, MODE><<<(int)grid, 256, 0, s>>>(M, N, A, lda, Bm, ldb, 1.f, nullptr, 0, col_bias, tpb, ns, f);
 }
 
+template <int MODE>
+static void nt_launch_sample(bool excl, bool tags, int64_t K, int64_t grid, hipStream_t s, int64_t M, int64_t N,
+                             const float* A, int64_t lda, const float* Bm, int64_t ldb, const float* col_bias, int tpb,
+                             int ns, const NtFilter& f) {
+  if (excl && tags)
+    nt_launch_mode<MODE | kNtTags | kNtExcl>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, tpb, ns, f);
+  else if (tags)
+    nt_launch_mode<MODE | kNtTags>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, tpb, ns, f);
+  else if (excl)
+    nt_launch_mode<MODE | kNtExcl>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, tpb, ns, f);
+  else
+    nt_launch_mode<MODE>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, tpb, ns, f);
+}
+
 }  // namespace arx
 
 using namespace arx;
@@ -626,6 +675,59 @@ int arx_gemm_nt_topk_filter_tags(const float* A, int64_t lda, int64_t M, const f
     nt_launch_mode<kNtTopk | kNtTags | kNtLse>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, itpb, ins, f);
   else
     nt_launch_mode<kNtTopk | kNtTags>(K, grid, s, M, N, A, lda, Bm, ldb, col_bias, itpb, ins, f);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_gemm_nt_topk_filter_sample(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
+                                   int64_t K, const float* col_bias, const float* thr, int64_t ldthr, int32_t col_base,
+                                   float* cand_v, int32_t* cand_i, int64_t ldcand, int capp, int* overflow,
+                                   float* lse_part, int64_t ldl, const int32_t* row_keys, int64_t key_rows,
+                                   const int32_t* ex_ptr, const int32_t* ex_cols, const int32_t* col_tags,
+                                   const int32_t* want_any, const int32_t* want_all, int64_t want_rows, const float* tau,
+                                   int64_t tau_rows, const int32_t* seed_words, void* stream) {
+  ARX_CHECK_ARG(A && Bm && thr && cand_v && cand_i && overflow && tau && seed_words,
+                "arx_gemm_nt_topk_filter_sample: null pointer (col_bias, lse_part, the exclusion lists and the tag "
+                "arrays may be NULL)");
+  ARX_CHECK_ARG(M > 0 && N > 0 && capp > 0 && ldcand > 0 && lda >= K && ldb >= K && tau_rows > 0,
+                "arx_gemm_nt_topk_filter_sample: need M > 0, N > 0, capp > 0, ldcand > 0, lda >= K, ldb >= K, "
+                "tau_rows > 0");
+  const bool tags = col_tags || want_any || want_all;
+  ARX_CHECK_ARG(!tags || (col_tags && want_any && want_all && want_rows > 0),
+                "arx_gemm_nt_topk_filter_sample: col_tags, want_any, want_all go together (all NULL: no tags), "
+                "want_rows > 0");
+  const bool excl = row_keys || ex_ptr || ex_cols;
+  ARX_CHECK_ARG(!excl || (row_keys && ex_ptr && ex_cols && key_rows > 0),
+                "arx_gemm_nt_topk_filter_sample: row_keys, ex_ptr, ex_cols go together (all NULL: no lists), "
+                "key_rows > 0");
+  ARX_CHECK_ARG(col_base >= 0 && (int64_t)col_base + N <= 0x7fffffff,
+                "arx_gemm_nt_topk_filter_sample: need col_base >= 0 and col_base + N < 2^31");
+  ARX_CHECK_ARG(K == 32 || K == 64 || K == 128, "arx_gemm_nt_topk_filter_sample: K must be 32, 64 or 128");
+  ARX_CHECK_ARG(!((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) && lda % 4 == 0 &&
+                    ldb % 4 == 0,
+                "arx_gemm_nt_topk_filter_sample: operands must be 16-byte aligned");
+  int64_t tpb, ns;
+  nt_split(M, N, &tpb, &ns);
+  ARX_CHECK_ARG(ns * capp <= ldcand,
+                "arx_gemm_nt_topk_filter_sample: candidate rows too short (parts * capp > ldcand)");
+  const int64_t grid = ceil_div(M, (int64_t)kNtBM) * ns;
+  ARX_CHECK_ARG(grid <= 0x7fffffff, "arx_gemm_nt_topk_filter_sample: grid too large");
+  ARX_CHECK_ARG(!lse_part || ldl >= ns, "arx_gemm_nt_topk_filter_sample: lse_part rows too short (ldl < parts)");
+  NtFilter f{thr,      ldthr,   cand_v,   cand_i,   ldcand,   capp,   col_base, overflow, lse_part,
+             ldl,      nullptr, nullptr,  row_keys, key_rows, ex_ptr, ex_cols};
+  f.col_tags = col_tags;
+  f.want_any = want_any;
+  f.want_all = want_all;
+  f.want_rows = want_rows;
+  f.tau = tau;
+  f.tau_rows = tau_rows;
+  f.seed_words = seed_words;
+  hipStream_t s = as_stream(stream);
+  if (lse_part)
+    nt_launch_sample<kNtTopk | kNtGumbel | kNtLse>(excl, tags, K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb,
+                                                   (int)ns, f);
+  else
+    nt_launch_sample<kNtTopk | kNtGumbel>(excl, tags, K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

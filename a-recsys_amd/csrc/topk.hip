@@ -13,6 +13,7 @@
 // Recommend of the row-sharded model: arx_topk_merge_shards folds the W shards' lists into global ids in one launch;
 // arx_topk_softmax_merge_shards does it for lists of logit ids and turns the winners' values into softmax values.
 #include "common.h"
+#include "gumbel.h"
 
 namespace arx {
 
@@ -256,6 +257,41 @@ __global__ __launch_bounds__(256) void k_topk_tags_fill(float* __restrict__ logi
   }
 }
 
+// The sampled recommend (arx_sample.h): key = fmaf(tau, g(row % tau_rows, column), logit) in place, g the Gumbel noise
+// of gumbel.h.  One workgroup per row strides over [col0, col0 + ncols); a row of tau == 0 returns (its keys ARE its
+// logits); a -inf logit stays -inf (g is finite).
+__global__ __launch_bounds__(256) void k_topk_gumbel_add(float* __restrict__ logits, int64_t ld, int32_t col0,
+                                                         int64_t ncols, const float* __restrict__ tau, int64_t tau_rows,
+                                                         const int32_t* __restrict__ seed_words) {
+  const int64_t r = blockIdx.x, nr = r % tau_rows;
+  const float t = tau[nr];
+  if (t == 0.f) return;
+  const GumbelRow gr = gumbel_row(seed_words, nr);
+  float* row = logits + r * ld;
+  for (int64_t c = threadIdx.x; c < ncols; c += 256)
+    row[c] = fmaf(t, gumbel_of_bits(gumbel_bits(gr.b0, gr.b1, (uint32_t)col0 + (uint32_t)c)), row[c]);
+}
+
+// the winners' keys back into the model's scores: value = fmaf(-tau, g(row % tau_rows, index), key); index -1: -inf
+__global__ void k_topk_gumbel_strip(float* __restrict__ values, int64_t ldv, const int32_t* __restrict__ indices,
+                                    int64_t ldi, int64_t B, int k, const float* __restrict__ tau, int64_t tau_rows,
+                                    const int32_t* __restrict__ seed_words) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= B * k) return;
+  const int64_t r = i / k, nr = r % tau_rows;
+  const int j = (int)(i % k);
+  const int32_t c = indices[r * ldi + j];
+  float* v = values + r * ldv + j;
+  if (c < 0) {
+    *v = -__builtin_inff();
+    return;
+  }
+  const float t = tau[nr];
+  if (t == 0.f) return;
+  const GumbelRow gr = gumbel_row(seed_words, nr);
+  *v = fmaf(-t, gumbel_of_bits(gumbel_bits(gr.b0, gr.b1, (uint32_t)c)), *v);
+}
+
 // a winner whose value is -inf is no item (a row with fewer eligible columns than k): index -1
 __global__ void k_topk_mark_empty(const float* __restrict__ values, int64_t ldv, int32_t* __restrict__ indices,
                                   int64_t ldi, int64_t B, int k) {
@@ -454,6 +490,33 @@ int arx_topk_tags_fill(float* logits, int64_t ld, int64_t M, int32_t col0, int64
   if (M == 0 || ncols == 0) return ARX_OK;
   k_topk_tags_fill<<<(int)M, 256, 0, as_stream(stream)>>>(logits, ld, col0, ncols, col_tags, want_any, want_all,
                                                           want_rows);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_topk_gumbel_add(float* logits, int64_t ld, int64_t M, int32_t col0, int64_t ncols, const float* tau,
+                        int64_t tau_rows, const int32_t* seed_words, void* stream) {
+  ARX_CHECK_ARG(logits && tau && seed_words, "arx_topk_gumbel_add: null pointer");
+  ARX_CHECK_ARG(M >= 0 && ncols >= 0 && col0 >= 0 && tau_rows > 0,
+                "arx_topk_gumbel_add: need M >= 0, ncols >= 0, col0 >= 0, tau_rows > 0");
+  ARX_CHECK_ARG((int64_t)col0 + ncols <= 0x7fffffff, "arx_topk_gumbel_add: need col0 + ncols < 2^31");
+  ARX_CHECK_ARG(M <= 1 || ld >= ncols, "arx_topk_gumbel_add: ld < ncols");
+  ARX_CHECK_ARG(M <= 0x7fffffff, "arx_topk_gumbel_add: too many rows");
+  if (M == 0 || ncols == 0) return ARX_OK;
+  k_topk_gumbel_add<<<(int)M, 256, 0, as_stream(stream)>>>(logits, ld, col0, ncols, tau, tau_rows, seed_words);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_topk_gumbel_strip(float* values, int64_t ldv, const int32_t* indices, int64_t ldi, int64_t B, int k,
+                          const float* tau, int64_t tau_rows, const int32_t* seed_words, void* stream) {
+  ARX_CHECK_ARG(values && indices && tau && seed_words, "arx_topk_gumbel_strip: null pointer");
+  ARX_CHECK_ARG(B >= 0 && k > 0 && tau_rows > 0 && (B <= 1 || (ldv >= k && ldi >= k)),
+                "arx_topk_gumbel_strip: need B >= 0, k > 0, tau_rows > 0, ldv >= k, ldi >= k");
+  ARX_CHECK_ARG(ceil_div(B * k, (int64_t)256) <= 0x7fffffff, "arx_topk_gumbel_strip: too many entries");
+  if (B == 0) return ARX_OK;
+  k_topk_gumbel_strip<<<(int)ceil_div(B * k, (int64_t)256), 256, 0, as_stream(stream)>>>(values, ldv, indices, ldi, B, k,
+                                                                                       tau, tau_rows, seed_words);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

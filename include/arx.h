@@ -1171,4 +1171,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_tags.h"
 #include "arx_slate.h"
 #include "arx_diverse.h"
+#include "arx_sample.h"
 #endif /* ARX_H_ */

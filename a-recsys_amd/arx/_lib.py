@@ -1,5 +1,5 @@
 """ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
-include/arx_slate.h, include/arx_diverse.h and include/arx_sample.h).
+include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h and include/arx_slate_sample.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -264,6 +264,13 @@ SAMPLE_PROTOTYPES = {
                                               f32p, i64, i32p, vp]),
 }
 
+# include/arx_slate_sample.h (score_items(sample_temperature=): a sampled slate with propensities), one-to-one as above
+SLATE_SAMPLE_PROTOTYPES = {
+    "arx_slate_sample_supported": (cint, [i64]),
+    "arx_slate_sample": (cint, [i32p, i64, f32p, i64, i64, i64, f32p, i64, i32p, cint, i32p, i64, f32p, i64, i32p, i64,
+                                f32p, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -277,7 +284,7 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(TAGS_PROTOTYPES.items())
                               + list(SLATE_PROTOTYPES.items()) + list(DIVERSE_PROTOTYPES.items())
-                              + list(SAMPLE_PROTOTYPES.items())):
+                              + list(SAMPLE_PROTOTYPES.items()) + list(SLATE_SAMPLE_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:
@@ -297,7 +304,7 @@ _NO_CHECK = ("arx_last_error", "arx_version", "arx_csr_expand_workspace_bytes",
              "arx_gemm_nt_bx6_workspace_bytes", "arx_reduce_scratch_bytes", "arx_mw_scorer_supported",
              "arx_mw_scorer_state_bytes", "arx_mw_scorer_bwd_di_workspace_bytes", "arx_mce_scorer_supported",
              "arx_mce_scorer_state_bytes", "arx_mce_scorer_bwd_di_workspace_bytes", "arx_gemm_bt_bx6_supported",
-             "arx_slate_mmr_supported")
+             "arx_slate_mmr_supported", "arx_slate_sample_supported")
 
 
 def call(name, *args):

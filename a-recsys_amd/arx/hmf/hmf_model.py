@@ -286,7 +286,8 @@ class LatentProductModel(object):
         replaces the array (the capped plans are dropped)."""
         slate.prepare_item_groups(self, groups)
 
-    def score_items(self, user_input, candidates, k=None, diversify=None, max_per_group=None):
+    def score_items(self, user_input, candidates, k=None, diversify=None, max_per_group=None, sample_temperature=None,
+                    sample_seed=None, return_logprob=False):
         """What the model thinks of THESE items for THIS user: row r of one full batch of users (the rules of
         step(recommend=True)) against its own slate candidates[r] -- [batch_size, C] logit indices, the space
         recommend returns and similar_items takes; -1 marks an empty slot.  The latent and the item pool are
@@ -305,9 +306,27 @@ class LatentProductModel(object):
         outside arx_slate_mmr_supported (C <= 512, d <= 128, C * d <= 32768).  The usual composition: over-fetch with a
         model built with top_N_items = C, then re-rank to k (the -1 tails of recommend are empty slots already):
             cands = model.step(None, users, None, recommend=True)
-            ids, values = model.score_items(users, cands, k, diversify=0.7)"""
+            ids, values = model.score_items(users, cands, k, diversify=0.7)
+        sample_temperature = tau (a number >= 0 or one per row; None: the calls above, untouched): "explore among the
+        best C, and log how likely the draw was" -- k is required and (ids, values) are k DISTINCT items drawn with
+        probability proportional to exp(score / tau), one after the other without replacement (Plackett-Luce), in
+        SELECTION order; values are the model's scores, not monotone along a row.  An item that fills several slots
+        competes once (its lowest slot), -1 and -inf slots never; tau = 0 rows are the plain order; (-1, -inf) past the
+        last distinct live item.  The noise is the sampled recommend's, a function of (seed, row, item): the draw is
+        that call's draw restricted to the slate and does not depend on the slate's order.  sample_seed: an int in
+        [0, 2^63) -- the same seed gives the same draw; None takes the model's draw counter (att_emb.sample_draws, shared
+        with recommend: starts at 0, one up per such call).  return_logprob=True: (ids, values, logprob), logprob
+        float32 [mb, k] the log-probability of each draw given the draws before it (arx_slate_sample.h) -- the row sum
+        is the log-propensity of the returned list; 0 on a tau = 0 row and in the (-1, -inf) columns.  ValueError for
+        a temperature without k or together with diversify / max_per_group, a seed or return_logprob without a
+        temperature, a bad temperature or seed (topk.sample_params) and a C outside arx_slate_sample_supported
+        (C <= 1024).  One more plan per (C, k); the temperature and the seed are fed per call:
+            cands = model.step(None, users, None, recommend=True)
+            ids, values, logp = model.score_items(users, cands, k, sample_temperature=0.5, sample_seed=s,
+                                                  return_logprob=True)"""
         return slate.score_items(self, lambda: self._feed(user_input, None, True, self.loss_function, None, None, True),
-                                 candidates, k, diversify, max_per_group)
+                                 candidates, k, diversify, max_per_group, sample_temperature, sample_seed,
+                                 return_logprob)
 
     def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
         """'bpr' / 'bpr-hinge': the items a DRAWN negative must not hit, per user -- typically the training history:

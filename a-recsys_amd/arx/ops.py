@@ -1576,6 +1576,35 @@ def slate_mmr(P, cand, scores, lam, groups, max_per_group, k, ids, values, pos):
          _p(pos), _ld(pos), _stream())
 
 
+def slate_sample_supported(C):
+    """True iff arx_slate_sample takes a slate of C slots (arx_slate_sample.h: the one owner of the rule)."""
+    return bool(call("arx_slate_sample_supported", int(C)))
+
+
+def slate_sample(cand, scores, sample, k, ids, values, pos, logp=None):
+    """k draws without replacement from softmax(scores / tau) over each row's distinct live candidates, in selection
+    order, with their log-probabilities (arx_slate_sample.h).  cand int32 / scores float32 [B, C]; sample: (tau float32
+    [tau_rows], tau_rows, seed_words int32 [2]) on the device, as ops.topk_gumbel_add takes it; ids / pos int32 and
+    values float32 [B, k] receive the picks, (-1, -inf, -1) past the last competitor; logp float32 [B, k] or None: the
+    log-probability of each pick given the picks before it (0 for a tau == 0 row and past the last competitor).  2-D
+    arguments may be strided views."""
+    tau, tau_rows, seed_words = sample
+    _chk(cand, torch.int32, 'cand'); _chk(scores, torch.float32, 'scores'); _chk(tau, torch.float32, 'tau')
+    _chk(seed_words, torch.int32, 'seed_words'); _chk(ids, torch.int32, 'ids'); _chk(values, torch.float32, 'values')
+    _chk(pos, torch.int32, 'pos'); _chk(logp, torch.float32, 'logp')
+    if cand.dim() != 2 or tuple(scores.shape) != tuple(cand.shape):
+        raise ValueError("slate_sample: cand and scores [B, C]")
+    B, C, k = int(cand.shape[0]), int(cand.shape[1]), int(k)
+    if any(t.dim() != 2 or tuple(t.shape) != (B, k) for t in (ids, values, pos) + ((logp,) if logp is not None else ())):
+        raise ValueError("slate_sample: ids, values, pos and logp [B, k]")
+    if tau.dim() != 1 or not tau.is_contiguous() or int(tau_rows) < 1 or int(tau.shape[0]) < min(int(tau_rows), B) \
+            or seed_words.dim() != 1 or int(seed_words.shape[0]) < 2 or not seed_words.is_contiguous():
+        raise ValueError("slate_sample: tau needs one contiguous entry per noise row, seed_words two int32 words")
+    call("arx_slate_sample", _p(cand), _ld(cand), _p(scores), _ld(scores), B, C, _p(tau), int(tau_rows),
+         _p(seed_words), k, _p(ids), _ld(ids), _p(values), _ld(values), _p(pos), _ld(pos), _p(logp),
+         _ld(logp) if logp is not None else 0, _stream())
+
+
 def lstm_fwd(x, W, b, L, B, din, h, forget_bias, hs, cs, gates):
     call("arx_lstm_fwd", _p(x), _p(W), _p(b), int(L), int(B), int(din), int(h), float(forget_bias),
          _p(hs), _p(cs), _p(gates), _stream())

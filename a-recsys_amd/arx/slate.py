@@ -4,7 +4,10 @@ slate may hold (check_slate), which k is legal (check_k), the scoring node (Slat
 (slate_order: score desc, slot asc; (-1, -inf) past the live slots) and the plan cache of the single-process models
 (score_items).  Also the diversified order of a scored slate (arx_diverse.h): what lambda and a per-group cap may be
 (check_diversify, check_max_per_group), the item groups by logit column (item_group_ids, prepare_item_groups) and the
-re-rank node (SlateDiverse).  Depends on graph and ops only.  Build-defined: the reference has no such call.
+re-rank node (SlateDiverse).  And the sampled slate (arx_slate_sample.h): k draws from softmax(score / tau) over the
+row's distinct candidates with their log-probabilities (SlateSample; what a temperature and a seed may be is
+topk.sample_params, the placeholders are the sampled recommend's).  Depends on graph, ops and topk only.
+Build-defined: the reference has no such call.
 """
 from __future__ import annotations
 
@@ -13,8 +16,9 @@ import torch
 
 from . import graph as G
 from . import ops
+from .topk import sample_params
 
-MAX_PLANS = 8           # ('score_items', C, k[, 'mmr', capped]) plans a model keeps; the oldest goes first
+MAX_PLANS = 8           # ('score_items', C, k[, 'mmr', capped | 'sample']) plans a model keeps; the oldest goes first
 
 
 def check_slate(candidates, rows, V, what='score_items'):
@@ -196,7 +200,38 @@ class SlateDiverse(G.Node):
                       self.pos)
 
 
-def score_items(model, feed, candidates, k=None, diversify=None, max_per_group=None):
+class SlateSample(G.Node):
+    """top_ids / top_values / pos / logp [rows, k] = k draws without replacement from softmax(score / tau) over the
+    distinct live candidates of the slate a SlateScore node scored, in selection order (arx_slate_sample): the top-k of
+    the keys fmaf(tau, g, score), g the noise of the sampled recommend, a function of (seed, row, item) -- the draw
+    does not depend on the order of the slate; values are the scores themselves; logp[t] is the log-probability of pick
+    t given picks 0 .. t - 1 (0 on a tau == 0 row); (-1, -inf, -1, 0) past the last competitor.  sample: a callable
+    giving (tau [tau_rows], tau_rows, seed_words int32 [2]) on the device (EmbeddingAttribute.sample_args), or that
+    tuple: placeholders read by the kernel, a captured plan replays with new values.  Every buffer is static."""
+
+    def __init__(self, rt, slate_score_node, k, sample):
+        rows, C = slate_score_node.shape
+        k = check_k(k, C, 'SlateSample')
+        if k is None:
+            raise ValueError("SlateSample: k is required")
+        if not ops.slate_sample_supported(C):
+            raise ValueError("SlateSample: arx_slate_sample_supported refuses C=%d" % C)
+        super().__init__(rt, (rows, k), (slate_score_node,))
+        self.k, self.sample = k, sample
+        self.top_values = torch.empty((rows, k), dtype=torch.float32, device=rt.device)
+        self.top_ids = torch.empty((rows, k), dtype=torch.int32, device=rt.device)
+        self.pos = torch.empty((rows, k), dtype=torch.int32, device=rt.device)
+        self.logp = torch.empty((rows, k), dtype=torch.float32, device=rt.device)
+
+    def forward(self, train):
+        sl = self.inputs[0]
+        cand = sl.inputs[2].value.view(sl.shape)
+        sample = self.sample() if callable(self.sample) else self.sample
+        ops.slate_sample(cand, sl.value, sample, self.k, self.top_ids, self.top_values, self.pos, self.logp)
+
+
+def score_items(model, feed, candidates, k=None, diversify=None, max_per_group=None, sample_temperature=None,
+                sample_seed=None, return_logprob=False):
     """The body of LatentProductModel.score_items / LinearSeq.score_items.  model: has rt, _plans, output (the
     full-vocabulary logits node), batch_size; feed(): feeds the request's user (and context) placeholders as a
     recommend step does.  candidates [batch_size, C] logit indices, -1 an empty slot.  Returns float32 [mb, C] on
@@ -205,7 +240,15 @@ def score_items(model, feed, candidates, k=None, diversify=None, max_per_group=N
     diversify (lambda in [0, 1], a scalar or one per row) and / or max_per_group (a cap >= 1 on the picks of one item
     group, after model.prepare_item_groups): k is required and (ids, values) come in SELECTION order of the greedy MMR
     re-rank (SlateDiverse); a cap alone means lambda = 1, the best k by score under the cap.  Those plans are keyed
-    ('score_items', C, k, 'mmr', capped) and count toward MAX_PLANS; lambda and the cap are fed per call."""
+    ('score_items', C, k, 'mmr', capped) and count toward MAX_PLANS; lambda and the cap are fed per call.
+    sample_temperature (topk.sample_params: a number >= 0 or one per row): k is required and (ids, values) are k draws
+    without replacement from softmax(score / tau) over the row's distinct live candidates, in selection order
+    (SlateSample); return_logprob adds logprob float32 [mb, k], the log-probability of each draw given those before it.
+    sample_seed: an int in [0, 2^63), None takes model.att_emb's draw counter (next_sample_seed: a refused call does not
+    move it).  One plan per (C, k), keyed ('score_items', C, k, 'sample') -- four entries: prepare_item_groups tells the
+    capped plans by their five; the temperature and the seed are the placeholders of att_emb.sample_args, fed per
+    call.  ValueError, before any feed: a temperature without k or together with diversify / max_per_group, a seed or
+    return_logprob without a temperature, a C outside arx_slate_sample_supported."""
     out = model.output
     if type(out) is not G.Prediction:
         raise NotImplementedError("score_items: output_feat 2 / 3 pool the token SCORES of an item -- there is no "
@@ -215,6 +258,18 @@ def score_items(model, feed, candidates, k=None, diversify=None, max_per_group=N
     C = int(cand.shape[1])
     k = check_k(k, C)
     mmr = diversify is not None or max_per_group is not None
+    sampled = sample_temperature is not None
+    if not sampled and (sample_seed is not None or return_logprob):
+        raise ValueError("score_items: sample_seed / return_logprob need sample_temperature")
+    if sampled:
+        if k is None:
+            raise ValueError("score_items: sample_temperature needs k")
+        if mmr:
+            raise ValueError("score_items: sample_temperature does not combine with diversify / max_per_group")
+        if not ops.slate_sample_supported(C):
+            raise ValueError("score_items: sample_temperature over C=%d slots: outside the envelope of "
+                             "arx_slate_sample_supported" % C)
+        sample_params(sample_temperature, 0 if sample_seed is None else sample_seed, model.batch_size)
     lam = cap = groups = None
     if mmr:
         if k is None:
@@ -228,7 +283,8 @@ def score_items(model, feed, candidates, k=None, diversify=None, max_per_group=N
         if not ops.slate_mmr_supported(C, int(pool.shape[1])):
             raise ValueError("score_items: diversify / max_per_group over C=%d slots of d=%d: outside the envelope of "
                              "arx_slate_mmr_supported" % (C, pool.shape[1]))
-    key = ('score_items', C, k, 'mmr', cap is not None) if mmr else ('score_items', C, k)
+    key = ('score_items', C, k, 'mmr', cap is not None) if mmr else \
+        ('score_items', C, k, 'sample') if sampled else ('score_items', C, k)
     entry = model._plans.get(key)
     if entry is None:
         mine = [q for q in model._plans if isinstance(q, tuple) and q[0] == 'score_items']   # (insertion order)
@@ -239,13 +295,20 @@ def score_items(model, feed, candidates, k=None, diversify=None, max_per_group=N
             sl = SlateScore(model.rt, latent, pool, ids, None)
             node = SlateDiverse(model.rt, sl, pool, k, groups)
             node.own_nodes = (ids, sl, node.lam) + ((node.cap,) if node.cap is not None else ()) + (node,)
+        elif sampled:
+            sl = SlateScore(model.rt, latent, pool, ids, None)
+            node = SlateSample(model.rt, sl, k, model.att_emb.sample_args)
+            node.own_nodes = (ids, sl, node)                   # (the placeholders are att_emb's, shared with recommend)
         else:
             node = SlateScore(model.rt, latent, pool, ids, k)
             node.own_nodes = (ids, node)
         entry = model._plans[key] = G.Plan(model.rt, [node], False, [])
     node = entry.fetch[0]
     feed()
-    if mmr:
+    if sampled:
+        model.att_emb.feed_sample(sample_temperature, sample_seed)
+        node.inputs[0].inputs[2].feed(cand.reshape(-1))
+    elif mmr:
         node.inputs[0].inputs[2].feed(cand.reshape(-1))
         node.lam.feed(lam)
         if cap is not None:
@@ -255,4 +318,6 @@ def score_items(model, feed, candidates, k=None, diversify=None, max_per_group=N
     entry.run()
     if k is None:
         return node.value.clone()
+    if return_logprob:
+        return node.top_ids.clone(), node.top_values.clone(), node.logp.clone()
     return node.top_ids.clone(), node.top_values.clone()

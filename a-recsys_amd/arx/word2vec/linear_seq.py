@@ -198,7 +198,8 @@ class LinearSeq(object):
         them."""
         slate.prepare_item_groups(self, groups)
 
-    def score_items(self, user_input, item_input, candidates, k=None, diversify=None, max_per_group=None):
+    def score_items(self, user_input, item_input, candidates, k=None, diversify=None, max_per_group=None,
+                    sample_temperature=None, sample_seed=None, return_logprob=False):
         """Row r of one full batch (user_input and the [n_input][mb] context item_input, the rules of
         step(recommend=True)) against its own slate candidates[r]: [batch_size, C] logit indices, -1 an empty slot.
         The latent is recommend's x_test of the full window, the pool the OUTPUT item latents; dropout off.
@@ -209,10 +210,18 @@ class LinearSeq(object):
         values) come in the selection order of the greedy MMR re-rank, cosines between the OUTPUT item latents
         (LatentProductModel.score_items states the rule):
             cands = model.step(None, users, context, recommend=True)
-            ids, values = model.score_items(users, context, cands, k, diversify=0.7)"""
+            ids, values = model.score_items(users, context, cands, k, diversify=0.7)
+        sample_temperature (a number >= 0 or one per row) / sample_seed / return_logprob: k is required and (ids,
+        values) are k distinct items DRAWN from softmax(score / tau) over the row's distinct live candidates, without
+        replacement, in selection order, with the noise of the sampled recommend; return_logprob=True adds logprob
+        float32 [mb, k], the log-probability of each draw given those before it (LatentProductModel.score_items states
+        the rules and the errors; sample_seed=None takes att_emb's draw counter):
+            ids, values, logp = model.score_items(users, context, cands, k, sample_temperature=0.5, sample_seed=s,
+                                                  return_logprob=True)"""
         def feed():
             self.att_emb.add_input({}, user_input, item_input, recommend=True, loss=self.loss_function)
-        return slate.score_items(self, feed, candidates, k, diversify, max_per_group)
+        return slate.score_items(self, feed, candidates, k, diversify, max_per_group, sample_temperature, sample_seed,
+                                 return_logprob)
 
     def _plan(self, key):
         if key not in self._plans:

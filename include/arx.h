@@ -1172,4 +1172,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_slate.h"
 #include "arx_diverse.h"
 #include "arx_sample.h"
+#include "arx_slate_sample.h"
 #endif /* ARX_H_ */

@@ -1,5 +1,6 @@
 """ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
-include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h and include/arx_slate_sample.h).
+include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h, include/arx_slate_sample.h and
+include/arx_sample_logp.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -271,6 +272,17 @@ SLATE_SAMPLE_PROTOTYPES = {
                                 f32p, i64, vp]),
 }
 
+# include/arx_sample_logp.h (recommend(sample_temperature=, return_logprob=True): the propensity of the draw), one-to-one
+SAMPLE_LOGP_PROTOTYPES = {
+    "arx_sample_logp_sort": (cint, [i32p, i64, i64, cint, i32p, i32p, i64, vp]),
+    "arx_gemm_nt_rest_mass": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, i32, f32p, i64, i32p, i64, i32p, i32p,
+                                     i32p, i32p, i32p, i64, i32p, i32p, i64, cint, f32p, f32p, i64, f32p, i64, vp]),
+    "arx_rest_mass_chunk": (cint, [f32p, i64, i64, i32, i64, f32p, i64, i32p, i32p, i64, cint, cint, f32p, f32p, f32p,
+                                   i64, vp]),
+    "arx_sample_logp_finish": (cint, [i32p, i64, f32p, i64, f32p, f32p, i64, cint, f32p, i64, i64, cint, f32p, i64,
+                                      f32p, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -284,7 +296,8 @@ def _load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(PROTOTYPES.items()) + list(TAGS_PROTOTYPES.items())
                               + list(SLATE_PROTOTYPES.items()) + list(DIVERSE_PROTOTYPES.items())
-                              + list(SAMPLE_PROTOTYPES.items()) + list(SLATE_SAMPLE_PROTOTYPES.items())):
+                              + list(SAMPLE_PROTOTYPES.items()) + list(SLATE_SAMPLE_PROTOTYPES.items())
+                              + list(SAMPLE_LOGP_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -43,7 +43,7 @@ import torch.distributed as dist
 
 from . import ops as _ops
 from . import slate as _slate
-from .topk import TopKScan, run_complete, similar_scan, tag_words
+from .topk import TopKScan, no_return_logprob, run_complete, similar_scan, tag_words
 from .utils.prepare_train import pair_draw_tables
 
 
@@ -1567,8 +1567,9 @@ class ShardedHMF(object):
         return vo, io
 
     # ------------------------------------------------------------ similar_items
-    def similar_items(self, items, k, include_self=False, return_values=False):
-        """Cosine nearest neighbours of items over the full item vocabulary of the row-sharded model, in the latent
+    def similar_items(self, items, k, include_self=False, return_values=False, return_logprob=False):
+        """(return_logprob=True: NotImplementedError.)
+        Cosine nearest neighbours of items over the full item vocabulary of the row-sharded model, in the latent
         space recommend scores against (E_item; the bias plays no part).  A collective with recommend's calling rules:
         every rank calls it with the same k and include_self.  items: global ids this rank OWNS (id % world == rank),
         0 <= len(items) <= B_loc (the count may differ between ranks; an id may come twice).  Returns int32 global item
@@ -1585,6 +1586,7 @@ class ShardedHMF(object):
           (local)         W-way merge into global ids (arx_topk_merge_shards)
 
         Eager, joined with the model's stream as recommend is; its buffers are its own, per k."""
+        no_return_logprob("%s.similar_items" % type(self).__name__, return_logprob)
         W, r = self.world, self.rank
         it = items.cpu().numpy() if isinstance(items, torch.Tensor) else np.asarray(items)
         it = it.astype(np.int64).reshape(-1)

@@ -17,8 +17,8 @@ from .. import graph as G
 from .. import ops
 from .. import slate
 from ..attributes import embed_attribute
-from ..topk import (StreamTopK, TopK, TopKScan, excluding_twin, recommend_key, recommend_node,  # noqa: F401
-                    run_complete)                                                            # (re-exported)
+from ..topk import (StreamTopK, TopK, TopKScan, check_return_logprob, excluding_twin, recommend_key,  # noqa: F401
+                    recommend_node, run_complete)                                                  # (re-exported)
 from ..utils.checkpoint import Saver
 
 
@@ -254,7 +254,8 @@ class LatentProductModel(object):
         """The items recommend(exclude_seen=True) leaves out per user -- typically the training history:
         {user_index: items} or a (ptr, items) CSR pair in item-index space (EmbeddingAttribute.
         prepare_recommend_exclusions).  A second call replaces the lists (the captured plan is dropped)."""
-        for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample'):
+        for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample', 'recommend_ex_sample_logp',
+                    'recommend_ex_tags_sample_logp'):
             self._plans.pop(key, None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
@@ -262,21 +263,24 @@ class LatentProductModel(object):
         """The items' 32-bit tag words for recommend(tags_any=, tags_all=): an integer array [n_items] or
         {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces the words
         (the captured plans that read them are dropped)."""
-        for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample'):
+        for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample',
+                    'recommend_tags_sample_logp', 'recommend_ex_tags_sample_logp'):
             self._plans.pop(key, None)
         self.att_emb.prepare_item_tags(tags)
 
     def _recommend_node(self, key):
-        if key.endswith('_sample'):
+        if key.endswith('_sample') or key.endswith('_sample_logp'):
             return getattr(self, '_sample_nodes', {}).get(key)
         return {'recommend': self.topk, 'recommend_ex': getattr(self, 'topk_ex', None),
                 'recommend_tags': getattr(self, 'topk_tags', None),
                 'recommend_ex_tags': getattr(self, 'topk_ex_tags', None)}[key]
 
-    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536):
+    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536,
+                      return_logprob=False):
         """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the item latent space
         recommend scores against: EmbeddingAttribute.similar_items."""
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
+                                          return_logprob=return_logprob,
                                           chunk=chunk)
 
     def prepare_item_groups(self, groups):
@@ -375,8 +379,9 @@ class LatentProductModel(object):
             p = G.Plan(rt, [self.topk_ex_tags], False, [])
         elif key == 'warp_eval':
             p = G.Plan(rt, [self.batch_loss], False, [m.mask['warp_eval']])
-        elif key.startswith('recommend') and key.endswith('_sample'):
-            # the sampled twins (topk.recommend_key): the same filters, the keys of m.sample_args
+        elif key.startswith('recommend') and (key.endswith('_sample') or key.endswith('_sample_logp')):
+            # the sampled twins (topk.recommend_key): the same filters, the keys of m.sample_args; '_logp': the twin
+            # that also runs the mass pass (node.logp: the log-probability of every draw)
             ex, tg = '_ex' in key, '_tags' in key
             if ex:
                 m.exclusion_args()
@@ -385,7 +390,8 @@ class LatentProductModel(object):
             nodes = self.__dict__.setdefault('_sample_nodes', {})
             if key not in nodes:
                 nodes[key] = excluding_twin(rt, self.topk, m.exclusion_args if ex else None,
-                                            m.tag_args if tg else None, sample_args=m.sample_args)
+                                            m.tag_args if tg else None, sample_args=m.sample_args,
+                                            logp=key.endswith('_logp'))
             p = G.Plan(rt, [nodes[key]], False, [])
         else:
             raise KeyError(key)
@@ -469,7 +475,7 @@ class LatentProductModel(object):
     def step_async(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
                    item_sampled_id2idx=None, forward_only=False, recommend=False,
                    recommend_new=False, loss=None, run_op=None, run_meta=None, exclude_seen=False,
-                   tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None):
+                   tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None, return_logprob=False):
         """step() without the device->host read of the result: returns the MeanLoss
         node (call .read() for the device scalar) / the top-k index tensor.  recommend with the streaming top-k
         (StreamTopK, fused form): the result is complete only if `self.topk.overflowed()` is False afterwards
@@ -479,9 +485,11 @@ class LatentProductModel(object):
         tags_any / tags_all (with recommend; an int or one int per row): only the items eligible by their tag words
         of prepare_item_tags -- plans 'recommend_tags' / 'recommend_ex_tags'; both None: the calls above.
         sample_temperature / sample_seed (with recommend): the sampled recommend of step() -- the plans ending in
-        '_sample'; None: the calls above."""
+        '_sample'; None: the calls above.  return_logprob (with sample_temperature): the plans ending in
+        '_sample_logp' -- returns (indices, logprob), the two device tensors [mb, top_N]."""
         if loss is None:
             loss = self.loss_function
+        check_return_logprob(return_logprob, recommend, sample_temperature)
         if exclude_seen and recommend:
             self.att_emb.exclusion_args()      # ValueError before any feed when nothing was prepared
         tagged = recommend and (tags_any is not None or tags_all is not None)
@@ -504,9 +512,10 @@ class LatentProductModel(object):
                 self.rt.drop_feed(self.att_emb.i_indices['neg'].value)    # (a queued older feed must not overwrite the draw)
             self.batch_loss.draw = self.att_emb.neg_draw if draw else None
         if tagged or sampled:
-            key = recommend_key(exclude_seen, tagged, sampled)
+            key = recommend_key(exclude_seen, tagged, sampled, bool(return_logprob))
             self._plan(key).run()
-            return self._recommend_node(key).indices
+            node = self._recommend_node(key)
+            return (node.indices, node.logp) if return_logprob else node.indices
         if recommend and exclude_seen:
             self._plan('recommend_ex').run()
             return self.topk_ex.indices
@@ -531,7 +540,7 @@ class LatentProductModel(object):
     def step(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
              loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None,
-             sample_temperature=None, sample_seed=None):
+             sample_temperature=None, sample_seed=None, return_logprob=False):
         """hmf_model.py:162-228.  Returns: train -> mean loss (float); forward_only ->
         loss_eval (float); recommend -> int32 [mb, top_N]; warp_eval -> [loss, rank].
         'bpr' / 'bpr-hinge': neg_item_input (list, array or device tensor) holds one negative item per row; None or
@@ -547,7 +556,14 @@ class LatentProductModel(object):
         replacement, returned in SELECTION order (the first id is the first draw); a row of temperature 0 is its plain
         top-k.  sample_seed: an int in [0, 2^63) -- the same seed gives the same items, on every path; None takes the
         model's draw counter (att_emb.sample_draws: starts at 0, one up per such call).  Composes with exclude_seen
-        and the tags."""
+        and the tags.
+        return_logprob=True (with sample_temperature): returns (ids int32 [mb, top_N], logprob float32 [mb, top_N]) --
+        logprob[r][t] is the log-probability of draw t given the draws before it under THIS policy, softmax(score /
+        temperature) over the row's whole eligible vocabulary (arx_sample_logp.h); the row sum is the log-propensity
+        of the ordered list; 0 for a temperature-0 row and beside an id -1.  The ids are those of the call without it
+        (a drawn item of score -inf -- a row with fewer than top_N finite scores -- is not eligible: -1 stands there).
+        ValueError without sample_temperature or without recommend."""
+        check_return_logprob(return_logprob, recommend, sample_temperature)
         sampled = recommend and sample_temperature is not None
         if sampled:
             # resolved once here: the chunked re-run after a candidate overflow must draw the same sample
@@ -556,13 +572,17 @@ class LatentProductModel(object):
                                       item_sampled_id2idx, forward_only, recommend, recommend_new, loss,
                                       run_op, run_meta, exclude_seen=exclude_seen, tags_any=tags_any,
                                       tags_all=tags_all, sample_temperature=sample_temperature,
-                                      sample_seed=sample_seed)
+                                      sample_seed=sample_seed, return_logprob=return_logprob)
         if recommend:
             # (a candidate list of the fused top-k too short for this batch: the request once more, chunked)
-            key = recommend_key(exclude_seen, tags_any is not None or tags_all is not None, sampled)
+            key = recommend_key(exclude_seen, tags_any is not None or tags_all is not None, sampled,
+                                bool(return_logprob))
             self._plan(key)                    # builds the twin node / raises as the step would
             node = self._recommend_node(key)
-            return run_complete(node, run, lambda: self._plans.pop(key, None)).cpu().numpy()
+            out = run_complete(node, run, lambda: self._plans.pop(key, None))
+            if return_logprob:
+                return out[0].cpu().numpy(), out[1].cpu().numpy()
+            return out.cpu().numpy()
         out = run()
         if isinstance(out, list):
             return [o.cpu().numpy() for o in out]

@@ -23,7 +23,8 @@ from .. import graph as G
 from .. import ops
 from ..attributes.embed_attribute import Dropout, ZeroEmbed
 from ..hmf.hmf_model import _Op, _Var
-from ..topk import StreamTopK, excluding_twin, logits_too_big, recommend_key, run_complete
+from ..topk import (StreamTopK, excluding_twin, logits_too_big, no_return_logprob, recommend_key,
+                    run_complete)
 from ..utils.checkpoint import Saver
 from .batching import SeqBatching
 
@@ -838,14 +839,16 @@ class SeqModel(SeqBatching):
                 bk['plans'].pop(key, None)
         self.att_emb.prepare_item_tags(tags)
 
-    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536):
+    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536,
+                      return_logprob=False):
         """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the output item latents
         step_recommend scores against (EmbeddingAttribute.similar_items); output_feat 2 / 3: NotImplementedError."""
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
+                                          return_logprob=return_logprob,
                                           chunk=chunk, output_feat=self.output_feat)
 
     def step_recommend(self, session, user_input, item_inputs, positions, bucket_id, exclude_seen=False,
-                       tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None):
+                       tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None, return_logprob=False):
         """seqModel.py:326-353 -> [(uid, values[topk_n], indexes[topk_n])]: the top-k softmax
         values / logit indexes at time position positions[i] of sequence i.  Small vocabularies: the full
         [L*mb, V] logits are materialised; past ARX_STREAM_TOPK_BYTES (1 GB) the mb rows asked for are gathered
@@ -860,7 +863,9 @@ class SeqModel(SeqBatching):
         sample_temperature (a number >= 0 or one per sequence; None: the call above) / sample_seed: topk_n distinct
         items DRAWN with probability proportional to exp(logit / temperature), in selection order
         (LatentProductModel.step states the rules); a value is still exp(logit - lse) with lse over the full
-        vocabulary: the item's softmax probability at temperature 1, whatever the temperature was."""
+        vocabulary: the item's softmax probability at temperature 1, whatever the temperature was.
+        return_logprob=True: NotImplementedError (the rows are [L * B] and the values softmax at temperature 1)."""
+        no_return_logprob("SeqModel.step_recommend", return_logprob)
         dp = self.rt.dp
         tagged = tags_any is not None or tags_all is not None
         drawn = sample_temperature is not None

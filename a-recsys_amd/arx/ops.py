@@ -1605,6 +1605,66 @@ def slate_sample(cand, scores, sample, k, ids, values, pos, logp=None):
          _ld(logp) if logp is not None else 0, _stream())
 
 
+def sample_logp_sort(indices, pk_cols, pk_slot):
+    """The picks of every row sorted by column, (column, selection slot) with the -1 entries last (arx_sample_logp.h).
+    indices int32 [B, k] (may be a strided view); pk_cols / pk_slot int32 [B, k]."""
+    _chk(indices, torch.int32, 'indices'); _chk(pk_cols, torch.int32, 'pk_cols'); _chk(pk_slot, torch.int32, 'pk_slot')
+    if indices.dim() != 2 or tuple(pk_cols.shape) != tuple(indices.shape) or pk_slot.shape != pk_cols.shape \
+            or pk_slot.stride(0) != pk_cols.stride(0):
+        raise ValueError("sample_logp_sort: indices, pk_cols, pk_slot [B, k], the two lists with one leading dimension")
+    call("arx_sample_logp_sort", _p(indices), _ld(indices), int(indices.shape[0]), int(indices.shape[1]), _p(pk_cols),
+         _p(pk_slot), _ld(pk_cols), _stream())
+
+
+def gemm_nt_rest_mass(A, Bm, col_bias, col_base, sample, picks, m_part, s_part, pick_score, tags=None, ex=None):
+    """The streaming mass pass: per row and column range of A . Bm^T + col_bias the (m, S) pair of the eligible columns
+    that are no picks of the row, and the picks' scores (arx_sample_logp.h).  sample: (tau, tau_rows, seed_words) --
+    the seed is not read; picks: (pk_cols, pk_slot) of sample_logp_sort; tags: (col_tags ALREADY sliced to this launch's
+    columns, want_any, want_all, want_rows) or None; ex: exclusion lists or None; m_part / s_part float32
+    [M, >= gemm_nt_topk_parts(M, N)]; pick_score float32 [M, k]."""
+    tau, tau_rows = sample[0], sample[1]
+    pk_cols, pk_slot = picks
+    col_tags, want_any, want_all, want_rows = tags if tags is not None else (None, None, None, 0)
+    if tags is not None and int(col_tags.shape[0]) < int(Bm.shape[0]):
+        raise ValueError("gemm_nt_rest_mass: %d tag words for %d columns" % (int(col_tags.shape[0]), int(Bm.shape[0])))
+    if pk_slot.stride(0) != pk_cols.stride(0) or s_part.stride(0) != m_part.stride(0):
+        raise ValueError("gemm_nt_rest_mass: pk_cols / pk_slot and m_part / s_part each share a leading dimension")
+    keys, key_rows, ptr, cols = ex if ex is not None else (None, 0, None, None)
+    call("arx_gemm_nt_rest_mass", _p(A), _ld(A), int(A.shape[0]), _p(Bm), _ld(Bm), int(Bm.shape[0]), int(A.shape[1]),
+         _p(col_bias), int(col_base), _p(tau), int(tau_rows), _p(keys), int(key_rows), _p(ptr), _p(cols), _p(col_tags),
+         _p(want_any), _p(want_all), int(want_rows), _p(pk_cols), _p(pk_slot), _ld(pk_cols), int(pk_cols.shape[1]),
+         _p(m_part), _p(s_part), int(m_part.stride(0)), _p(pick_score), _ld(pick_score), _stream())
+
+
+def rest_mass_chunk(logits, col0, sample, picks, first, m_run, s_run, pick_score):
+    """The materialised mass pass: the columns [col0, col0 + logits.shape[1]) of logits (-inf where ineligible) folded
+    into each row's running pair (m_run, s_run) [B] -- first: the pairs start empty -- without the row's picks, whose
+    scores go to pick_score [B, k] (arx_sample_logp.h)."""
+    tau, tau_rows = sample[0], sample[1]
+    pk_cols, pk_slot = picks
+    if pk_slot.stride(0) != pk_cols.stride(0):
+        raise ValueError("rest_mass_chunk: pk_cols and pk_slot share a leading dimension")
+    call("arx_rest_mass_chunk", _p(logits), _ld(logits), int(logits.shape[0]), int(col0), int(logits.shape[1]),
+         _p(tau), int(tau_rows), _p(pk_cols), _p(pk_slot), _ld(pk_cols), int(pk_cols.shape[1]), int(bool(first)),
+         _p(m_run), _p(s_run), _p(pick_score), _ld(pick_score), _stream())
+
+
+def sample_logp_finish(indices, pick_score, m_part, s_part, P, sample, logp, values=None):
+    """logp [B, k] of the picks `indices` in selection order from REST's P parts per row and the picks' scores; values
+    (optional) receive those scores, -inf beside an index -1 (arx_sample_logp.h).  m_part / s_part: [B, >= P], or the
+    running pairs [B] with P = 1."""
+    tau, tau_rows = sample[0], sample[1]
+    _chk(logp, torch.float32, 'logp'); _chk(values, torch.float32, 'values'); _chk(indices, torch.int32, 'indices')
+    if tuple(logp.shape) != tuple(indices.shape) or (values is not None and values.shape != logp.shape):
+        raise ValueError("sample_logp_finish: indices, logp and values [B, k]")
+    ldl = int(m_part.stride(0)) if m_part.dim() == 2 else 1
+    if (int(s_part.stride(0)) if s_part.dim() == 2 else 1) != ldl:
+        raise ValueError("sample_logp_finish: m_part and s_part share a leading dimension")
+    call("arx_sample_logp_finish", _p(indices), _ld(indices), _p(pick_score), _ld(pick_score), _p(m_part), _p(s_part),
+         ldl, int(P), _p(tau), int(tau_rows), int(indices.shape[0]), int(indices.shape[1]), _p(logp), _ld(logp),
+         _p(values), _ld(values) if values is not None else 0, _stream())
+
+
 def lstm_fwd(x, W, b, L, B, din, h, forget_bias, hs, cs, gates):
     call("arx_lstm_fwd", _p(x), _p(W), _p(b), int(L), int(B), int(din), int(h), float(forget_bias),
          _p(hs), _p(cs), _p(gates), _stream())

@@ -54,13 +54,22 @@ class TopK(G.Node):
     the eligible logits become Gumbel keys before the select (k draws without replacement from softmax(logits / tau),
     in selection order) and the winners' values are turned back into logits after it."""
 
-    def __init__(self, rt, logits, k, exclude=None, tags=None, sample=None):
+    def __init__(self, rt, logits, k, exclude=None, tags=None, sample=None, logp=False):
         super().__init__(rt, (logits.shape[0], k), (logits,))
         self.k = k
         self.exclude = exclude
         self.tags = tags
         self.sample = sample
         self.indices = torch.empty((logits.shape[0], k), dtype=torch.int32, device=rt.device)
+        # logp (with sample): self.logp [rows, k], the log-probability of every draw (arx_sample_logp.h).  The keys
+        # then go into a buffer of their own: the logits stay scores for the mass pass, and the values are those scores
+        self.logp = self._keys = None
+        if logp:
+            if sample is None:
+                raise ValueError("TopK: logp goes with sample")
+            self.logp = torch.empty((logits.shape[0], k), dtype=torch.float32, device=rt.device)
+            self._keys = torch.empty(tuple(logits.shape), dtype=torch.float32, device=rt.device)
+            self._lp = LogpBuffers(logits.shape[0], k, rt.device)
 
     def forward(self, train):
         x = self.inputs[0].value
@@ -69,13 +78,45 @@ class TopK(G.Node):
         if self.tags is not None:
             ops.topk_tags_fill(x, 0, self.tags() if callable(self.tags) else self.tags)
         sample = self.sample() if callable(self.sample) else self.sample
+        keys = x
         if sample is not None:
-            ops.topk_gumbel_add(x, 0, sample)
-        ops.topk(x, self.k, self.alloc_value(), self.indices)
-        if self.exclude is not None or self.tags is not None:
-            ops.topk_mark_empty(self.value, self.indices)
-        if sample is not None:
+            if self.logp is not None:
+                keys = self._keys
+                keys.copy_(x)
+            ops.topk_gumbel_add(keys, 0, sample)
+        ops.topk(keys, self.k, self.alloc_value(), self.indices)
+        if self.exclude is not None or self.tags is not None or self.logp is not None:
+            ops.topk_mark_empty(self.value, self.indices)     # (logp: a -inf pick is not eligible, filters or not)
+        if sample is not None and self.logp is not None:
+            lp = self._lp
+            ops.sample_logp_sort(self.indices, lp.pk_cols, lp.pk_slot)
+            ops.rest_mass_chunk(x, 0, sample, lp.picks, True, lp.m_run, lp.s_run, lp.pick_score)
+            ops.sample_logp_finish(self.indices, lp.pick_score, lp.m_run, lp.s_run, 1, sample, self.logp, self.value)
+        elif sample is not None:
             ops.topk_gumbel_strip(self.value, self.indices, sample)
+
+
+class LogpBuffers(object):
+    """What the mass pass of the sampled recommend's propensities keeps per request row (arx_sample_logp.h): the picks
+    sorted by column with their slots, the picks' scores, the running REST pair of the materialised form and -- made
+    by parts() at first use -- REST's pairs per column range of the streaming form."""
+
+    def __init__(self, B, k, device):
+        i32, f32 = torch.int32, torch.float32
+        self.pk_cols = torch.empty((B, k), dtype=i32, device=device)
+        self.pk_slot = torch.empty((B, k), dtype=i32, device=device)
+        self.picks = (self.pk_cols, self.pk_slot)
+        self.pick_score = torch.empty((B, k), dtype=f32, device=device)
+        self.m_run = torch.empty(B, dtype=f32, device=device)
+        self.s_run = torch.empty(B, dtype=f32, device=device)
+        self._parts = None
+
+    def parts(self, P):
+        if self._parts is None or self._parts[0].shape[1] != P:
+            B, dev = self.pk_cols.shape[0], self.pk_cols.device
+            self._parts = (torch.empty((B, P), dtype=torch.float32, device=dev),
+                           torch.empty((B, P), dtype=torch.float32, device=dev))
+        return self._parts
 
 
 class TopKScan(object):
@@ -148,7 +189,7 @@ class TopKScan(object):
             self.fused = was
 
     def run(self, latent, pool, bias, ws, values, indices, ex=None, col_scale=None, self_col=None, tags=None,
-            sample=None):
+            sample=None, logp=None):
         """values / indices [B, k] = the top-k of latent . pool^T + bias (bias may be None) over all V >= k pool rows;
         ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace.
         col_scale [V] (None: every launch is the one above): the scores are (latent . pool^T) * col_scale[column] --
@@ -162,16 +203,24 @@ class TopKScan(object):
         sample: (tau [tau_rows], tau_rows, seed_words) or None -- the sampled recommend: per chunk the order is GEMM,
         log-sum-exp, exclusion fill, tags fill, gumbel_add, select; the fused rest goes through
         gemm_nt_topk_filter_sample (threshold and candidates are keys); after the merge and mark_empty, gumbel_strip
-        turns the winners' keys back into scores.  Not with col_scale."""
+        turns the winners' keys back into scores.  Not with col_scale.
+        logp (with sample): float32 [B, k] -- the log-probability of every draw (arx_sample_logp.h).  After the selection
+        is complete (the merge and mark_empty) the mass pass runs INSTEAD of gumbel_strip: one streaming launch over
+        [0, V) where the fused form applies, a second sweep of chunks otherwise (chunked() forces it, as it does for
+        the selection); `values` are then the picks' exact scores."""
         V, k = pool.shape[0], self.k
         cos = col_scale is not None
+        if logp is not None and sample is None:
+            raise ValueError("TopKScan.run: logp goes with sample")
         if cos and sample is not None:
             raise ValueError("TopKScan.run: col_scale (the cosine form) takes no sample")
         if cos and tags is not None:
             raise ValueError("TopKScan.run: col_scale (the cosine form) takes no item tags")
         if tags is not None and int(tags[0].shape[0]) != V:
             raise ValueError("TopKScan.run: %d tag words for %d pool rows" % (int(tags[0].shape[0]), V))
-        empties = ex is not None or self_col is not None or tags is not None
+        # (logp: a pick of score -inf -- a row with fewer than k finite scores -- is not eligible and becomes -1, filters
+        # or not: ELIGIBLE of arx_sample_logp.h)
+        empties = ex is not None or self_col is not None or tags is not None or logp is not None
         if cos and (self.want_lse or bias is not None or ex is not None):
             raise ValueError("TopKScan.run: col_scale goes with no bias, no exclusion lists and no log-sum-exp")
         if self_col is not None and not cos:
@@ -227,7 +276,9 @@ class TopKScan(object):
             indices.copy_(out_i)
             if empties:
                 ops.topk_mark_empty(values, indices)
-            if sample is not None:
+            if logp is not None:
+                self._logp_pass(latent, pool, bias, ws, values, indices, ex, tags, sample, logp, True)
+            elif sample is not None:
                 ops.topk_gumbel_strip(values, indices, sample)
             return
         nch = (V + self.chunk - 1) // self.chunk
@@ -261,10 +312,39 @@ class TopKScan(object):
             indices.copy_(run_i)
         if empties:
             ops.topk_mark_empty(values, indices)
-        if sample is not None:
+        if logp is not None:
+            self._logp_pass(latent, pool, bias, ws, values, indices, ex, tags, sample, logp, False)
+        elif sample is not None:
             ops.topk_gumbel_strip(values, indices, sample)
         if self.want_lse:
             ops.row_logsumexp(lp, self.lse)
+
+    def _logp_pass(self, latent, pool, bias, ws, values, indices, ex, tags, sample, logp, streaming):
+        """The mass pass and the finish of run(logp=) over the complete selection: REST's mass per row -- the eligible
+        columns that are no picks -- from one streaming scan, or chunk by chunk through the logits buffer (GEMM,
+        exclusion fill, tags fill, rest_mass_chunk); the picks' scores on the way; then logp and the exact values."""
+        V = pool.shape[0]
+        lb = getattr(self, '_lp', None)
+        if lb is None:
+            lb = self._lp = LogpBuffers(self._rows, self.k, self._dev)
+        ops.sample_logp_sort(indices, lb.pk_cols, lb.pk_slot)
+        if streaming:
+            P = ops.gemm_nt_topk_parts(self._rows, V)
+            m_part, s_part = lb.parts(P)
+            ops.gemm_nt_rest_mass(latent, pool, bias, 0, sample, lb.picks, m_part, s_part, lb.pick_score, tags=tags,
+                                  ex=ex)
+            ops.sample_logp_finish(indices, lb.pick_score, m_part, s_part, P, sample, logp, values)
+            return
+        for c0 in range(0, V, self.chunk):
+            c1 = min(V, c0 + self.chunk)
+            lg = self._buf[:, :c1 - c0]
+            ops.gemm(latent, pool[c0:c1], lg, ws, transB=True, col_bias=bias[c0:c1] if bias is not None else None)
+            if ex is not None:
+                ops.topk_exclude_fill(lg, c0, ex)
+            if tags is not None:
+                ops.topk_tags_fill(lg, c0, tags)
+            ops.rest_mass_chunk(lg, c0, sample, lb.picks, c0 == 0, lb.m_run, lb.s_run, lb.pick_score)
+        ops.sample_logp_finish(indices, lb.pick_score, lb.m_run, lb.s_run, 1, sample, logp, values)
 
 
 class StreamTopK(G.Node, TopKScan):
@@ -288,7 +368,7 @@ class StreamTopK(G.Node, TopKScan):
     The algorithm and its buffers: TopKScan."""
 
     def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None, tags=None,
-                 sample=None):
+                 sample=None, logp=False):
         G.Node.__init__(self, rt, (latent.shape[0], k), (latent, pool))
         TopKScan.__init__(self, latent.shape[0], pool.shape[0], latent.shape[1], k, rt.device, chunk=chunk,
                           want_lse=want_lse, share=share)
@@ -296,6 +376,10 @@ class StreamTopK(G.Node, TopKScan):
         self.tags = tags
         self.sample = sample
         self.fused = self.fused and pool.shape[1] == latent.shape[1]
+        # logp (with sample): self.logp [rows, k], the log-probability of every draw (TopKScan.run(logp=))
+        if logp and sample is None:
+            raise ValueError("StreamTopK: logp goes with sample")
+        self.logp = torch.empty((latent.shape[0], k), dtype=torch.float32, device=rt.device) if logp else None
 
     def forward(self, train):
         latent, pool = self.inputs
@@ -303,7 +387,7 @@ class StreamTopK(G.Node, TopKScan):
         tags = self.tags() if callable(self.tags) else self.tags
         sample = self.sample() if callable(self.sample) else self.sample
         self.run(latent.value, pool.value, pool.bias_value, self.rt.ws, self.alloc_value(), self.indices, ex, tags=tags,
-                 sample=sample)
+                 sample=sample, logp=self.logp)
 
 
 def recommend_node(rt, logits, k, rows):
@@ -315,16 +399,25 @@ def recommend_node(rt, logits, k, rows):
     return TopK(rt, logits, k)
 
 
-def excluding_twin(rt, node, exclusion_args=None, tag_args=None, sample_args=None):
+def excluding_twin(rt, node, exclusion_args=None, tag_args=None, sample_args=None, logp=False):
     """The twin of a recommend node that leaves columns out -- by the exclusion lists, by the item tags, or by both
     (the plain node and its plan stay as they are); a streaming twin shares the plain node's chunk buffer.
-    sample_args: the SAMPLED twin (alone, or on top of either filter)."""
+    sample_args: the SAMPLED twin (alone, or on top of either filter); logp: that twin also gives node.logp, the
+    log-probability of every draw."""
     if exclusion_args is None and tag_args is None and sample_args is None:
         raise ValueError("excluding_twin: exclusion lists, item tags or both")
+    if logp and sample_args is None:
+        raise ValueError("excluding_twin: logp goes with sample_args")
+    if logp and not isinstance(node, StreamTopK) and type(node) is not TopK:
+        raise NotImplementedError("excluding_twin: no log-probabilities for a %s node" % type(node).__name__)
     if isinstance(node, StreamTopK):
         more = {} if sample_args is None else {'sample': sample_args}
+        if logp:
+            more['logp'] = True
         return StreamTopK(rt, node.inputs[0], node.inputs[1], node.k, chunk=node.chunk, want_lse=node.want_lse,
                           exclude=exclusion_args, share=node, tags=tag_args, **more)
+    if logp:
+        return TopK(rt, node.inputs[0], node.k, exclude=exclusion_args, tags=tag_args, sample=sample_args, logp=True)
     if sample_args is not None:
         return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args, tags=tag_args, sample=sample_args)
     if tag_args is None:
@@ -332,10 +425,30 @@ def excluding_twin(rt, node, exclusion_args=None, tag_args=None, sample_args=Non
     return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args, tags=tag_args)
 
 
-def recommend_key(exclude_seen, tagged, sampled=False):
+def recommend_key(exclude_seen, tagged, sampled=False, logp=False):
     """The plan of a recommend call: 'recommend', 'recommend_ex', 'recommend_tags' or 'recommend_ex_tags'; the sampled
-    twins end in '_sample'."""
-    return 'recommend' + ('_ex' if exclude_seen else '') + ('_tags' if tagged else '') + ('_sample' if sampled else '')
+    twins end in '_sample', those that also give the draws' log-probabilities in '_sample_logp'."""
+    if logp and not sampled:
+        raise ValueError("recommend_key: log-probabilities belong to the sampled recommend")
+    return 'recommend' + ('_ex' if exclude_seen else '') + ('_tags' if tagged else '') + \
+        ('_sample' if sampled else '') + ('_logp' if logp else '')
+
+
+def check_return_logprob(return_logprob, recommend, sample_temperature):
+    """The one rule of return_logprob on the models: the log-probabilities are those of the sampled recommend --
+    ValueError (before any feed) without recommend or without sample_temperature."""
+    if return_logprob and not recommend:
+        raise ValueError("return_logprob=True goes with recommend=True")
+    if return_logprob and sample_temperature is None:
+        raise ValueError("return_logprob=True needs sample_temperature (the propensity of a sampled recommend)")
+
+
+def no_return_logprob(what, return_logprob):
+    """The entries that do not give the draws' log-probabilities (SeqModel.step_recommend: its rows are [L * B] and its
+    values are softmax at temperature 1; every similar_items): NotImplementedError where one is asked."""
+    if return_logprob:
+        raise NotImplementedError("%s: return_logprob is not implemented (LatentProductModel.step and LinearSeq.step "
+                                  "give the propensities of recommend(sample_temperature=))" % what)
 
 
 def sample_params(temperature, seed, rows):

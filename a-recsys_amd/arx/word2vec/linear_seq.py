@@ -26,7 +26,7 @@ from .. import slate
 from ..attributes import embed_attribute
 from ..attributes.embed_attribute import Dropout
 from ..hmf.hmf_model import _Op, _Var
-from ..topk import excluding_twin, recommend_key, recommend_node, run_complete
+from ..topk import check_return_logprob, excluding_twin, recommend_key, recommend_node, run_complete
 from ..utils.checkpoint import Saver
 
 
@@ -175,21 +175,25 @@ class LinearSeq(object):
     def prepare_recommend_exclusions(self, item_sets):
         """The items step(recommend=True, exclude_seen=True) leaves out per user: {user_index: items} or a (ptr, items)
         CSR pair in item-index space (EmbeddingAttribute.prepare_recommend_exclusions).  A second call replaces them."""
-        for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample'):
+        for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample', 'recommend_ex_sample_logp',
+                    'recommend_ex_tags_sample_logp'):
             self._plans.pop(key, None)
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
     def prepare_item_tags(self, tags):
         """The items' 32-bit tag words for step(recommend=True, tags_any=, tags_all=): an integer array [n_items] or
         {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces them."""
-        for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample'):
+        for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample',
+                    'recommend_tags_sample_logp', 'recommend_ex_tags_sample_logp'):
             self._plans.pop(key, None)
         self.att_emb.prepare_item_tags(tags)
 
-    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536):
+    def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536,
+                      return_logprob=False):
         """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the OUTPUT item latents the
         model scores against (EmbeddingAttribute.similar_items); output_feat 2 / 3: NotImplementedError."""
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
+                                          return_logprob=return_logprob,
                                           chunk=chunk, output_feat=self.output_feat)
 
     def prepare_item_groups(self, groups):
@@ -243,11 +247,12 @@ class LinearSeq(object):
                 if getattr(self, 'topk_ex_tags', None) is None:
                     self.topk_ex_tags = excluding_twin(rt, self.topk, m.exclusion_args, m.tag_args)
                 self._plans[key] = G.Plan(rt, [self.topk_ex_tags], False, [])
-            elif key.endswith('_sample'):                       # the sampled twins (topk.recommend_key)
+            elif key.endswith('_sample') or key.endswith('_sample_logp'):   # the sampled twins (topk.recommend_key)
                 nodes = self.__dict__.setdefault('_sample_nodes', {})
                 if key not in nodes:
                     nodes[key] = excluding_twin(rt, self.topk, m.exclusion_args if '_ex' in key else None,
-                                                m.tag_args if '_tags' in key else None, sample_args=m.sample_args)
+                                                m.tag_args if '_tags' in key else None, sample_args=m.sample_args,
+                                                logp=key.endswith('_logp'))
                 self._plans[key] = G.Plan(rt, [nodes[key]], False, [])
             else:
                 self._plans[key] = G.Plan(rt, [self.topk], False, [])
@@ -257,25 +262,29 @@ class LinearSeq(object):
         """Run the 'recommend' / 'recommend_ex' / 'recommend_tags' / 'recommend_ex_tags' plan; a streaming top-k whose fused candidate lists overflowed runs
         once more on the chunked path (as LatentProductModel.step)."""
         self._plan(key)
-        node = self._sample_nodes[key] if key.endswith('_sample') else \
+        node = self._sample_nodes[key] if key.endswith('_sample') or key.endswith('_sample_logp') else \
                {'recommend': self.topk, 'recommend_ex': getattr(self, 'topk_ex', None),
                 'recommend_tags': getattr(self, 'topk_tags', None),
                 'recommend_ex_tags': getattr(self, 'topk_ex_tags', None)}[key]
         # (the placeholders still hold this request's ids in the second run)
         run_complete(node, lambda: self._plan(key).run(), lambda: self._plans.pop(key, None))
+        if key.endswith('_logp'):
+            return node.indices.cpu().numpy(), node.logp.cpu().numpy()
         return node.indices.cpu().numpy()
 
     def step(self, session, user_input, item_input=None, item_output=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
              loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None,
-             sample_temperature=None, sample_seed=None):
+             sample_temperature=None, sample_seed=None, return_logprob=False):
         """linear_seq.py:67-121.  item_input: [n_input][mb] context items (time-major);
         item_output: [mb] target items.  Returns the mean loss (train / forward_only) or the
         top-N logit indices [mb, top_N] (recommend; exclude_seen=True: without each user's items of
         prepare_recommend_exclusions, -1 where a user has fewer eligible items; tags_any / tags_all -- an int or one
         int per row: only the items eligible by their tag words of prepare_item_tags, composing with exclude_seen;
         sample_temperature / sample_seed: top_N distinct items DRAWN with probability proportional to
-        exp(score / temperature), in selection order -- LatentProductModel.step states the rules).
+        exp(score / temperature), in selection order; return_logprob=True with it: (ids, logprob float32 [mb, top_N]), the
+        log-probability of every draw -- LatentProductModel.step states the rules; ValueError without
+        sample_temperature or without recommend).
         'mw' / 'mce': item_sampled (n_sampled item ids) stages a new pool -- the first training step needs one,
         later steps keep it until the next is given (run_w2v.py:315-317); item_sampled_id2idx is the host twin of
         the pool's item -> slot map.  forward_only evaluates 'mw' with the full-vocabulary 'warp' loss and 'mce'
@@ -284,6 +293,7 @@ class LinearSeq(object):
         sampled = self.loss_function in ('mw', 'mce')
         if recommend_new:
             raise NotImplementedError("indices_test is never built by the reference (linear_seq.py:98)")
+        check_return_logprob(return_logprob, recommend, sample_temperature)
         if recommend and exclude_seen:
             m.exclusion_args()                 # ValueError before any feed when nothing was prepared
         tagged = recommend and (tags_any is not None or tags_all is not None)
@@ -310,7 +320,7 @@ class LinearSeq(object):
         for op in update_sampled:              # stage the pool (embed_attribute.py:320-348)
             op()
         if recommend:
-            return self._recommend(recommend_key(exclude_seen, tagged, drawn))
+            return self._recommend(recommend_key(exclude_seen, tagged, drawn, bool(return_logprob)))
         if forward_only:
             self._plan('eval').run()
             return float(self.loss_test.read().item())

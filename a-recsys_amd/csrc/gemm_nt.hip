@@ -21,6 +21,7 @@
 //   * 64 KB of LDS and ~200 VGPRs => two workgroups per CU.
 #include "common.h"
 #include "gumbel.h"
+#include "rest_mass.h"
 
 namespace arx {
 
@@ -74,6 +75,12 @@ struct NtFilter {
   // kNtGumbel (the sampled recommend, gumbel.h): row r competes with the KEYS fmaf(tau, g, v), tau = tau[r % tau_rows],
   // g the noise of (seed_words, r % tau_rows, col_base + col); thr and cand_v are keys, lse_part stays over v
   const float* tau; int64_t tau_rows; const int32_t* seed_words;
+  // kNtRest (the mass pass of the sampled recommend's propensities, arx_sample_logp.h): row r's picks sorted by
+  // ABSOLUTE column, pk_cols[r * ldp + j] with the selection slot pk_slot[r * ldp + j] beside it, j < pk_k (-1 entries
+  // last); per column range REST's pair (m_part, s_part)[row * ldl + part], and pick_score[row * ldps + slot] = the
+  // score of a pick's column.  Reads tau, the exclusion lists and the tag arrays above (each group nullable)
+  const int32_t* pk_cols; const int32_t* pk_slot; int64_t ldp; int pk_k;
+  float* m_part; float* s_part; float* pick_score; int64_t ldps;
 };
 
 // MODE (FILTER kernels): bit 0 candidate lists (thr), bit 1 lse_part, bit 2 relu_part, bit 3 exclusion lists (with
@@ -89,6 +96,12 @@ struct NtFilter {
 // fit, and the 16 of the thresholds are given back
 constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8, kNtRank = 16, kNtCos = 32, kNtSelf = 64, kNtTags = 128;
 constexpr int kNtGumbel = 256;
+// bit 9 (alone) REST's mass per column range, an eval-style scan without candidate lists: the 32 registers of the lse
+// mode hold each row's (m, S) at ITS temperature, the column's tag word travels beside the bias (no lists: there are
+// registers for it), and the two sorted lists a row leaves out -- its exclusion list and its picks -- are walked by
+// cursors: lane (list = lane / 32, row = lane % 32) of a wave keeps the next listed column of its row in a register,
+// and only a tile that holds one for some row of the wave takes the compare path (rows' next columns by ds_bpermute)
+constexpr int kNtRest = 512;
 
 template <int KT, int MODE = 0>
 __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
@@ -107,6 +120,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   static_assert(!want_tags || (want_topk && !want_relu && !want_cos), "the item tags filter the recommend candidates");
   constexpr bool want_gumbel = (MODE & kNtGumbel) != 0;
   static_assert(!want_gumbel || (want_topk && !want_relu && !want_cos), "the Gumbel keys rank the recommend candidates");
+  constexpr bool want_rest = (MODE & kNtRest) != 0;
+  static_assert(!want_rest || MODE == kNtRest, "the mass pass is a scan of its own");
   constexpr int NS = KT / 8;                  // steps of 4 MFMAs
   constexpr int CPR = KT / 4;                 // 16-B chunks per pool row
   constexpr int NLB = kNtBN * CPR / 256;      // DMA pieces per thread per tile
@@ -182,6 +197,19 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   // kNtRank: the rows' target columns (read per tile by one lane per row, per logit only in a tile that holds one)
   // kNtSelf: the rows' own columns, absolute (read only by a lane whose logit beat the threshold)
   __shared__ int s_tc[(want_rank || want_self) ? kNtBM : 1];
+  // kNtRest: each row's tau (> 0: rm_tau), its finite reciprocal and its two request words (2 KB; read four rows at a
+  // time per tile)
+  __shared__ __attribute__((aligned(16))) float s_rt[want_rest ? kNtBM : 1];
+  __shared__ __attribute__((aligned(16))) float s_ri[want_rest ? kNtBM : 1];
+  __shared__ __attribute__((aligned(16))) uint32_t s_ra[want_rest ? kNtBM : 1];
+  __shared__ __attribute__((aligned(16))) uint32_t s_rl[want_rest ? kNtBM : 1];
+  // kNtRest: the masses of the lane's 16 rows; the cursor of the lane's own (list, row): [r_cur, r_end) of r_lp
+  // narrowed to this workgroup's columns, r_nxt the next listed column (none: 0xffffffff), r_slot its pick slot
+  float rm_m[want_rest ? 16 : 1], rm_s[want_rest ? 16 : 1];
+  int r_cur = 0, r_end = 0, r_slot = 0;
+  uint32_t r_nxt = 0xffffffffu;
+  const int32_t* r_lp = nullptr;
+  const int32_t* r_ls = nullptr;
   float lm[want_lse ? 16 : 1], ls[want_lse ? 16 : 1], rsum[want_relu ? 16 : 1];
   // kNtRank: ONE register per count -- a row's count is the popcount of its half of a ballot (wave-uniform), kept by
   // the lane l31 == e of the half (16 counters spilled at K=128: the margin mode already holds 236 VGPRs).  The margin
@@ -242,6 +270,59 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
         s_gm[threadIdx.x] = make_uint4(__float_as_uint(row < M ? flt.tau[nr] : 0.f), gr.b0, gr.b1,
                                        __float_as_uint(row < M ? flt.thr[row * flt.ldthr] : __builtin_inff()));
       }
+      if (want_rest) {
+        const float t = rm_tau(row < M ? flt.tau[row % flt.tau_rows] : 1.f);
+        s_rt[threadIdx.x] = t;
+        s_ri[threadIdx.x] = rm_itau(t);
+        const bool tg = row < M && flt.col_tags != nullptr;
+        s_ra[threadIdx.x] = tg ? (uint32_t)flt.want_any[row % flt.want_rows] : 0u;
+        s_rl[threadIdx.x] = tg ? (uint32_t)flt.want_all[row % flt.want_rows] : 0u;
+      }
+    }
+    if (want_rest) {
+      // lane (lhi, l31): list lhi (0 the exclusion list, 1 the picks) of row wave * 32 + l31, narrowed to this
+      // workgroup's columns [c_lo, c_hi) once; columns compare as unsigned (the picks' -1 entries sort last)
+      const int64_t row = m0 + wave * 32 + l31;
+      const uint32_t c_lo = (uint32_t)flt.col_base + (uint32_t)(t_beg * kNtBN);
+      const uint32_t c_hi = (uint32_t)flt.col_base + (uint32_t)min(t_end * kNtBN, N);
+      int lo = 0, hi = 0;
+      if (row < M) {
+        if (lhi) {
+          r_lp = flt.pk_cols + row * flt.ldp;
+          r_ls = flt.pk_slot + row * flt.ldp;
+          hi = flt.pk_k;
+        } else if (flt.row_keys) {
+          const int32_t key = flt.row_keys[row % flt.key_rows];
+          if (key >= 0) {
+            r_lp = flt.ex_cols;
+            lo = flt.ex_ptr[key];
+            hi = flt.ex_ptr[key + 1];
+          }
+        }
+      }
+      const int top = hi;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((uint32_t)r_lp[mid] < c_lo) lo = mid + 1;
+        else hi = mid;
+      }
+      r_cur = lo;
+      hi = top;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((uint32_t)r_lp[mid] < c_hi) lo = mid + 1;
+        else hi = mid;
+      }
+      r_end = lo;
+      if (r_cur < r_end) {
+        r_nxt = (uint32_t)r_lp[r_cur];
+        if (lhi) r_slot = r_ls[r_cur];
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        rm_m[e] = -__FLT_MAX__;
+        rm_s[e] = 0.f;
+      }
     }
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -262,18 +343,29 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
     bias0 = col_bias[c0];
     bias1 = col_bias[c1];
   }
+  // kNtRest: the tag words of the tile's two columns, fetched like the bias (0 without tags: every row's words are 0)
+  uint32_t tg0 = 0u, tg1 = 0u;
+  if (want_rest && flt.col_tags) {
+    tg0 = (uint32_t)flt.col_tags[min(t_beg * kNtBN + l31, N - 1)];
+    tg1 = (uint32_t)flt.col_tags[min(t_beg * kNtBN + 32 + l31, N - 1)];
+  }
   __syncthreads();
 
   // read-side swizzle: chunk 2s + lhi of pool row (l31 [+32]); swz(l31) == swz(l31 + 32)
   const int sw = nt_swz<KT>(l31);
   auto tile = [&](int64_t t, const float* cur_img, float* nxt_img) {
     float nb0 = 0.f, nb1 = 0.f;
+    uint32_t ng0 = 0u, ng1 = 0u;
     if (t + 1 < t_end) {
       if (col_bias) {
         const int64_t c0 = min((t + 1) * kNtBN + l31, N - 1);
         const int64_t c1 = min((t + 1) * kNtBN + 32 + l31, N - 1);
         nb0 = col_bias[c0];
         nb1 = col_bias[c1];
+      }
+      if (want_rest && flt.col_tags) {
+        ng0 = (uint32_t)flt.col_tags[min((t + 1) * kNtBN + l31, N - 1)];
+        ng1 = (uint32_t)flt.col_tags[min((t + 1) * kNtBN + 32 + l31, N - 1)];
       }
       dma_b(t + 1, nxt_img);
     }
@@ -313,7 +405,61 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
     // epilogue.  C/D map of the 32x32 MFMA: col = lane&31, row = (e&3) + 8*(e>>2) + 4*(lane>>5)
     const int64_t n0 = t * kNtBN;
     const int64_t rbase = m0 + wave * 32 + 4 * lhi;
-    if (FILTER) {
+    if (want_rest) {
+      const int rl0 = wave * 32 + 4 * lhi;
+      const uint32_t ct = (uint32_t)flt.col_base + (uint32_t)n0;    // the tile's first ABSOLUTE column
+      const uint32_t c0 = ct + (uint32_t)l31, c1 = c0 + 32u;
+      // bit 16 j + e: logit (j, e) is a listed column of its row -- it adds no mass.  One trip per listed column a row
+      // has in this tile (almost always none, else one): the rows' next columns come from their cursor lanes, the
+      // matching lane writes a pick's score, and every cursor that pointed into the tile steps forward
+      uint32_t skip = 0u;
+      while (__ballot(r_nxt < ct + (uint32_t)kNtBN) != 0ull) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int src = 4 * lhi + (e & 3) + 8 * (e >> 2);         // the logit's row within the wave
+          const uint32_t nx = (uint32_t)__shfl((int)r_nxt, src, 64), np = (uint32_t)__shfl((int)r_nxt, src + 32, 64);
+          const bool p0 = np == c0, p1 = np == c1;
+          if (nx == c0 || p0) skip |= 1u << e;
+          if (nx == c1 || p1) skip |= 1u << (16 + e);
+          if (__ballot(p0 || p1) != 0ull) {
+            const int slot = __shfl(r_slot, src + 32, 64);
+            if (p0 || p1) {
+              const float v = alpha * (p0 ? acc0[e] : acc1[e]) + (p0 ? bias0 : bias1);
+              flt.pick_score[(rbase + (e & 3) + 8 * (e >> 2)) * flt.ldps + slot] = v;
+            }
+          }
+        }
+        if (r_nxt < ct + (uint32_t)kNtBN) {
+          ++r_cur;
+          r_nxt = 0xffffffffu;
+          if (r_cur < r_end) {
+            r_nxt = (uint32_t)r_lp[r_cur];
+            if (lhi) r_slot = r_ls[r_cur];
+          }
+        }
+      }
+#pragma unroll
+      for (int g4 = 0; g4 < 4; ++g4) {
+        const float4 it4 = *reinterpret_cast<const float4*>(&s_ri[rl0 + 8 * g4]);
+        const uint4 wa4 = *reinterpret_cast<const uint4*>(&s_ra[rl0 + 8 * g4]);
+        const uint4 wl4 = *reinterpret_cast<const uint4*>(&s_rl[rl0 + 8 * g4]);
+        const float it[4] = {it4.x, it4.y, it4.z, it4.w};
+        const uint32_t wa[4] = {wa4.x, wa4.y, wa4.z, wa4.w}, wl[4] = {wl4.x, wl4.y, wl4.z, wl4.w};
+#pragma unroll
+        for (int e2 = 0; e2 < 4; ++e2) {
+          const int e = 4 * g4 + e2;
+#pragma unroll
+          for (int j = 0; j < 2; ++j) {
+            const int64_t col = n0 + j * 32 + l31;
+            const uint32_t tg = (j == 0) ? tg0 : tg1;
+            const float v = alpha * (j == 0 ? acc0[e] : acc1[e]) + ((j == 0) ? bias0 : bias1);
+            const bool ok = col < N && ((skip >> (16 * j + e)) & 1u) == 0u && (wa[e2] == 0u || (tg & wa[e2]) != 0u) &&
+                            (tg & wl[e2]) == wl[e2];
+            rm_add(rm_m[e], rm_s[e], ok ? v : -__builtin_inff(), it[e2]);
+          }
+        }
+      }
+    } else if (FILTER) {
       const int rl0 = wave * 32 + 4 * lhi;                          // the lane's rows: rl0 + (e & 3) + 8 (e >> 2)
       float th[want_topk ? 16 : 1], tq[want_relu ? 16 : 1];
       // kNtRank: does a row of this wave have its target column in this tile?  (wave-uniform; rarely true)
@@ -448,11 +594,31 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
     }
     bias0 = nb0;
     bias1 = nb1;
+    if (want_rest) {
+      tg0 = ng0;
+      tg1 = ng1;
+    }
     __syncthreads();          // tile t+1 landed (vmcnt(0) rides on the barrier); buffer cur free
   };
   for (int64_t t = t_beg; t < t_end; t += 2) {
     tile(t, sB0, sB1);
     if (t + 1 < t_end) tile(t + 1, sB1, sB0);
+  }
+  if (want_rest) {
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int ro = (e & 3) + 8 * (e >> 2);
+      const float t = s_rt[wave * 32 + 4 * lhi + ro];
+      RmMass x{rm_m[e], rm_s[e]};
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1)                              // the row's 32 lanes (one half wave)
+        x = rm_join(x, RmMass{__shfl_xor(x.m, o, 64), __shfl_xor(x.s, o, 64)}, t);
+      const int64_t row = m0 + wave * 32 + 4 * lhi + ro;
+      if (l31 == 0 && row < M) {
+        flt.m_part[row * flt.ldl + part] = x.m;
+        flt.s_part[row * flt.ldl + part] = x.s;
+      }
+    }
   }
   if (want_topk && ovf) *flt.overflow = 1;
   if (want_lse) {
@@ -728,6 +894,66 @@ int arx_gemm_nt_topk_filter_sample(const float* A, int64_t lda, int64_t M, const
                                                    (int)ns, f);
   else
     nt_launch_sample<kNtTopk | kNtGumbel>(excl, tags, K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_gemm_nt_rest_mass(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N, int64_t K,
+                          const float* col_bias, int32_t col_base, const float* tau, int64_t tau_rows,
+                          const int32_t* row_keys, int64_t key_rows, const int32_t* ex_ptr, const int32_t* ex_cols,
+                          const int32_t* col_tags, const int32_t* want_any, const int32_t* want_all, int64_t want_rows,
+                          const int32_t* pk_cols, const int32_t* pk_slot, int64_t ldp, int k, float* m_part,
+                          float* s_part, int64_t ldl, float* pick_score, int64_t ldps, void* stream) {
+  ARX_CHECK_ARG(A && Bm && tau && pk_cols && pk_slot && m_part && s_part && pick_score,
+                "arx_gemm_nt_rest_mass: null pointer (col_bias, the exclusion lists and the tag arrays may be NULL)");
+  ARX_CHECK_ARG(M >= 0 && N > 0 && lda >= K && ldb >= K && tau_rows > 0,
+                "arx_gemm_nt_rest_mass: need M >= 0, N > 0, lda >= K, ldb >= K, tau_rows > 0");
+  const bool tags = col_tags || want_any || want_all;
+  ARX_CHECK_ARG(!tags || (col_tags && want_any && want_all && want_rows > 0),
+                "arx_gemm_nt_rest_mass: col_tags, want_any, want_all go together (all NULL: no tags), want_rows > 0");
+  const bool excl = row_keys || ex_ptr || ex_cols;
+  ARX_CHECK_ARG(!excl || (row_keys && ex_ptr && ex_cols && key_rows > 0),
+                "arx_gemm_nt_rest_mass: row_keys, ex_ptr, ex_cols go together (all NULL: no lists), key_rows > 0");
+  ARX_CHECK_ARG(col_base >= 0 && (int64_t)col_base + N <= 0x7fffffff,
+                "arx_gemm_nt_rest_mass: need col_base >= 0 and col_base + N < 2^31");
+  ARX_CHECK_ARG(k >= 1 && k <= 1024 && ldp >= k && ldps >= k,
+                "arx_gemm_nt_rest_mass: need 1 <= k <= 1024, ldp >= k, ldps >= k (k=%d ldp=%lld ldps=%lld)", k,
+                (long long)ldp, (long long)ldps);
+  if (!(K == 32 || K == 64 || K == 128)) {
+    set_error("arx_gemm_nt_rest_mass: K=%lld unsupported (K must be 32, 64 or 128)", (long long)K);
+    return ARX_EUNSUPPORTED;
+  }
+  ARX_CHECK_ARG(!((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) && lda % 4 == 0 &&
+                    ldb % 4 == 0,
+                "arx_gemm_nt_rest_mass: operands must be 16-byte aligned");
+  if (M == 0) return ARX_OK;
+  int64_t tpb, ns;
+  nt_split(M, N, &tpb, &ns);
+  ARX_CHECK_ARG(ldl >= ns, "arx_gemm_nt_rest_mass: part rows too short (ldl < parts)");
+  const int64_t grid = ceil_div(M, (int64_t)kNtBM) * ns;
+  ARX_CHECK_ARG(grid <= 0x7fffffff, "arx_gemm_nt_rest_mass: grid too large");
+  NtFilter f{};
+  f.col_base = col_base;
+  f.ldl = ldl;
+  f.row_keys = row_keys;
+  f.key_rows = key_rows;
+  f.ex_ptr = ex_ptr;
+  f.ex_cols = ex_cols;
+  f.col_tags = col_tags;
+  f.want_any = want_any;
+  f.want_all = want_all;
+  f.want_rows = want_rows;
+  f.tau = tau;
+  f.tau_rows = tau_rows;
+  f.pk_cols = pk_cols;
+  f.pk_slot = pk_slot;
+  f.ldp = ldp;
+  f.pk_k = k;
+  f.m_part = m_part;
+  f.s_part = s_part;
+  f.pick_score = pick_score;
+  f.ldps = ldps;
+  nt_launch_mode<kNtRest>(K, grid, as_stream(stream), M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

@@ -1173,4 +1173,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_diverse.h"
 #include "arx_sample.h"
 #include "arx_slate_sample.h"
+#include "arx_sample_logp.h"
 #endif /* ARX_H_ */

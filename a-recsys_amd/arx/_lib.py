@@ -283,6 +283,18 @@ SAMPLE_LOGP_PROTOTYPES = {
                                       f32p, i64, vp]),
 }
 
+# include/arx_sample_shard.h (the sampled recommend and its propensities on the row-sharded models), one-to-one as above
+SAMPLE_SHARD_PROTOTYPES = {
+    "arx_topk_gumbel_add_keyed": (cint, [f32p, i64, i64, i32, i64, f32p, i64, i32p, i32, i32, i32p, vp]),
+    "arx_topk_gumbel_strip_keyed": (cint, [f32p, i64, i32p, i64, i64, cint, f32p, i64, i32p, i32, i32, i32p, vp]),
+    "arx_gemm_nt_topk_filter_sample_keyed": (cint, [f32p, i64, i64, f32p, i64, i64, i64, f32p, f32p, i64, i32, f32p,
+                                                    i32p, i64, cint, i32p, f32p, i64, i32p, i64, i32p, i32p, i32p, i32p,
+                                                    i32p, i64, f32p, i64, i32p, i32, i32, i32p, vp]),
+    "arx_picks_to_shard": (cint, [i32p, i64, i64, cint, cint, cint, i32p, i64, vp]),
+    "arx_sample_logp_finish_shards": (cint, [i32p, i64, f32p, i64, i64, f32p, f32p, i64, i64, cint, cint, f32p, i64,
+                                             i64, cint, f32p, i64, f32p, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -297,7 +309,7 @@ def _load():
     for name, (res, args) in (list(PROTOTYPES.items()) + list(TAGS_PROTOTYPES.items())
                               + list(SLATE_PROTOTYPES.items()) + list(DIVERSE_PROTOTYPES.items())
                               + list(SAMPLE_PROTOTYPES.items()) + list(SLATE_SAMPLE_PROTOTYPES.items())
-                              + list(SAMPLE_LOGP_PROTOTYPES.items())):
+                              + list(SAMPLE_LOGP_PROTOTYPES.items()) + list(SAMPLE_SHARD_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -43,7 +43,8 @@ import torch.distributed as dist
 
 from . import ops as _ops
 from . import slate as _slate
-from .topk import TopKScan, no_return_logprob, run_complete, similar_scan, tag_words
+from .topk import (LogpBuffers, TopKScan, check_return_logprob, no_return_logprob, run_complete, sample_params,
+                   similar_scan, tag_words)
 from .utils.prepare_train import pair_draw_tables
 
 
@@ -303,7 +304,7 @@ class HipBackend(object):
         self.ops.het_rows_range(E_id, bias_id, E_tok, bias_tok, vals, starts, lens, n_items, world, rank, c0, c1, out,
                                 bias_out=bias_out, all_owners=all_owners, scale=scale, block_rows=block_rows)
 
-    def shard_topk(self, U, E, bias, k, ex, values, indices, lse=None, tags=None):
+    def shard_topk(self, U, E, bias, k, ex, values, indices, lse=None, tags=None, sample=None):
         """Recommend's local stage: values / indices [B, k] = every row's k best of U . E^T + bias over the shard's
         rows, by (value desc, local column asc); ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols of local
         columns) or None.  The streaming top-k of StreamTopK (topk.TopKScan: fused filter GEMM, the chunked path
@@ -311,7 +312,10 @@ class HipBackend(object):
         with (-inf, -1).  lse [B] (optional): the log-sum-exp of every row's logits over ALL the shard's rows, excluded
         ones included (TopKScan's want_lse); -inf for a shard without rows.  tags (optional): (col_tags [V] int32 of
         the shard's rows, want_any, want_all, want_rows) -- only the rows eligible by their tag words enter a result
-        (TopKScan.run).  Buffers and GEMM workspace are this stage's own (captured step graphs keep theirs)."""
+        (TopKScan.run).  sample (optional): the keyed sample of the sampled recommend (tau [B], B, seed_words,
+        world, shard, the rows' global user ids: arx_sample_shard.h) -- the lists are then the k best KEYS, NOT
+        stripped: the merge across shards compares keys.  Buffers and GEMM workspace are this stage's own (captured
+        step graphs keep theirs)."""
         ops = self.ops
         B, V, d = int(U.shape[0]), int(E.shape[0]), int(U.shape[1])
         if getattr(self, 'ws_rec', None) is None:
@@ -338,12 +342,71 @@ class HipBackend(object):
                               torch.empty((B, kk), dtype=torch.int32, device=U.device))
         vo, io = (values, indices) if kk == k else scan.short
         # (a candidate segment too short: this rank once more, chunked)
-        run_complete(scan, lambda: scan.run(U, E, bias, self.ws_rec, vo, io, ex, tags=tags))
+        if sample is None:
+            run_complete(scan, lambda: scan.run(U, E, bias, self.ws_rec, vo, io, ex, tags=tags))
+        else:
+            run_complete(scan, lambda: scan.run(U, E, bias, self.ws_rec, vo, io, ex, tags=tags, sample=sample,
+                                                strip=False))
         if kk < k:
             values[:, :kk].copy_(vo)
             indices[:, :kk].copy_(io)
         if lse is not None:
             lse.copy_(scan.lse)
+
+    def shard_mass_parts(self, B, V, d):
+        """The number of REST parts per row shard_rest_mass writes for a shard of V rows (every rank computes it for
+        every shard: the packed rows are sized by the largest): the column ranges of the streaming mass pass where the
+        fused scorer applies and the shard is past the first chunk, else the one running pair."""
+        if V > 65536 and d in (32, 64, 128) and os.environ.get('ARX_TOPK_FUSED', '1') != '0':
+            return self.ops.gemm_nt_topk_parts(B, V)
+        return 1
+
+    def shard_rest_mass(self, U, E, bias, ex, picks, world, shard, sample, packed, P_max, tags=None):
+        """The propensities' local stage (arx_sample_logp.h's mass pass over ONE shard): picks [B, k] GLOBAL ids in
+        selection order -> this shard's columns (arx_picks_to_shard), REST's mass of the shard's rows per request row,
+        and the scores of the picks the shard owns.  packed float32 [B, 2 P_max + k]: columns [0, P_max) the m parts,
+        [P_max, 2 P_max) the S parts -- past this shard's own parts the empty mass (-FLT_MAX, 0) --, the rest the pick
+        scores, -inf where the shard does not own the pick."""
+        ops = self.ops
+        B, V, d, k = int(U.shape[0]), int(E.shape[0]), int(U.shape[1]), int(picks.shape[1])
+        ops.fill_f32(packed[:, :P_max], -3.4028234663852886e38)
+        ops.fill_f32(packed[:, P_max:2 * P_max], 0.0)
+        ops.fill_f32(packed[:, 2 * P_max:], float('-inf'))
+        if V == 0 or B == 0:
+            return
+        if getattr(self, 'ws_rec', None) is None:
+            self.ws_rec, self._scans = ops.Workspace(U.device), {}
+        lbs = self.__dict__.setdefault('_mass_bufs', {})
+        lb = lbs.get((B, k))
+        if lb is None:
+            if len(lbs) > 8:
+                lbs.clear()
+            lb = lbs[(B, k)] = (LogpBuffers(B, k, U.device), torch.empty((B, k), dtype=torch.int32, device=U.device))
+        lb, cols = lb
+        ops.picks_to_shard(picks, world, shard, cols)
+        key = (B, V, d, 'mass')
+        scan = self._scans.get(key)
+        if scan is None:
+            scan = self._scans[key] = TopKScan(B, V, d, 1, U.device)
+            scan.fused = scan.fused and int(E.shape[1]) == d
+        streaming = scan.mass_streams(U, E) and self.shard_mass_parts(B, V, d) > 1
+        ops.fill_f32(lb.pick_score, float('-inf'))
+        m, sp, P = scan.mass_pass(U, E, bias, self.ws_rec, cols, ex, tags, sample, streaming, lb)
+        if P > P_max:
+            raise RuntimeError("shard_rest_mass: %d parts for rows of %d" % (P, P_max))
+        packed[:, :P].copy_(m if m.dim() == 2 else m.view(B, 1))
+        packed[:, P_max:P_max + P].copy_(sp if sp.dim() == 2 else sp.view(B, 1))
+        packed[:, 2 * P_max:].copy_(lb.pick_score)
+
+    def sample_strip(self, values, indices, sample):
+        """The merged winners' keys back into scores at their owner (arx_topk_gumbel_strip_keyed over global ids)."""
+        self.ops.topk_gumbel_strip(values, indices, sample)
+
+    def sample_logp_finish_shards(self, indices, recv, P_max, sample, logp, values):
+        """logp / exact values [B_loc, k] of the picks `indices` (global ids in selection order) from the W packed
+        slabs recv [W, B_loc, 2 P_max + k] of shard_rest_mass (arx_sample_logp_finish_shards)."""
+        self.ops.sample_logp_finish_shards(indices, recv[:, :, 2 * P_max:], recv[:, :, :P_max],
+                                           recv[:, :, P_max:2 * P_max], P_max, sample, logp, values)
 
     sim_chunk = 65536       # first-chunk width of shard_similar's TopKScan (tests narrow it to reach the fused kernel)
 
@@ -1484,7 +1547,45 @@ class ShardedHMF(object):
           (local)         W-way merge into global ids c * W + s (arx_topk_merge_shards)
 
         Eager (no capture); with graph segments on the model's stream, joined with the caller's on both sides as
-        step() is, so a recommend right after a step reads that step's tables.  Its buffers are its own, per k."""
+        step() is, so a recommend right after a step reads that step's tables.  Its buffers are its own, per k.
+        (The SAMPLED recommend and its propensities: recommend_sampled, an entry of its own -- this parameter list is
+        pinned by tests/test_sharded_recommend_tags_cpu.py.)"""
+        return self.recommend_sampled(users, k, exclude_seen=exclude_seen, return_values=return_values,
+                                      tags_any=tags_any, tags_all=tags_all)
+
+    def recommend_sampled(self, users, k, exclude_seen=False, return_values=False, tags_any=None, tags_all=None,
+                          sample_temperature=None, sample_seed=None, return_logprob=False):
+        """recommend (its rules for users, k, exclude_seen, return_values and the tags hold) with
+        sample_temperature (None: recommend itself, bit for bit -- no further collective, no further launch): the SAMPLED
+        recommend -- k distinct items drawn from softmax(score / tau) over the user's whole eligible vocabulary ACROSS
+        the shards, one after the other without replacement, ids in SELECTION order; one number, or one per user of
+        this rank (topk.sample_params; tau = 0: that user's row is the plain top-k).  All ranks pass a temperature, or
+        none does.  sample_seed: an int in [0, 2^63), the SAME on every rank like k (ValueError on every rank where
+        the ranks' seeds differ); None counts up a per-model counter, the same on every rank that calls in lockstep.
+        The noise is g(seed, GLOBAL user id, GLOBAL item id) of arx_sample.h: a draw depends on (seed, user, item) and
+        the scores alone -- not on the world size, B_loc, the user's position in the call or who else is in it, so a
+        logged draw can be recomputed for one user later.  (Not the single-device convention, where the noise row is
+        the batch row.)  Two rows of the same user in one call (possible with ShardedW2V) share their noise.
+        return_values: the picks' scores -- the stripped keys, within 2^-23 (|key| + |score|) of the score; with
+        return_logprob the exact bits of the shard's scorer GEMM.  return_logprob=True (ValueError without a
+        temperature: topk.check_return_logprob): the tuple ends with logprob [len(users), k], the log-probability of
+        every pick given the picks before it by the rule of arx_sample_logp.h over the whole eligible vocabulary
+        (exclude_seen and the tags included): 0 for a tau = 0 row and beside an id -1.  The sampled call adds:
+
+          all_gather      + tau bits [B_loc] and the two seed words, in ONE int32 buffer -> every rank
+          (local)         the shard top-k is that of the KEYS (TopKScan with the keyed sample: noise column
+                          c * W + s, noise row the user id), NOT stripped; overflow -> chunked, as above
+          all_to_all      key / local-column lists, as above
+          (local)         arx_topk_merge_shards on the keys (ties: lower global id) -> ids in selection order
+           without logp:  arx_topk_gumbel_strip_keyed at the owner (global ids: col_mul 1, col_add 0)
+           with logp:     all_gather of the picks [B_loc, k] -> [B, k]; per shard: arx_picks_to_shard,
+                          arx_sample_logp_sort, the rest-mass pass over the shard (arx_gemm_nt_rest_mass where the
+                          fused form applies, arx_rest_mass_chunk otherwise), pick scores pre-filled with -inf;
+                          ONE all_to_all of a packed float buffer [B, 2 P_max + k] (m parts, S parts, pick scores;
+                          a shard with fewer parts pads with the empty mass) -> owners;
+                          arx_sample_logp_finish_shards over the W slabs
+
+        Eager, on the model's stream, as recommend is."""
         W, r = self.world, self.rank
         u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
         u = u.astype(np.int64).reshape(-1)
@@ -1502,16 +1603,25 @@ class ShardedHMF(object):
             if getattr(self, '_rec_tags', None) is None:
                 raise ValueError("tags_any / tags_all need prepare_item_tags() first")
             words = tag_words(tags_any, tags_all, len(u))
+        check_return_logprob(return_logprob, True, sample_temperature)
+        more = {}
+        if sample_temperature is not None:
+            seed = sample_seed if sample_seed is not None else getattr(self, 'sample_draws', 0)
+            tau, seed_words = sample_params(sample_temperature, seed, len(u))
+            if sample_seed is None:                     # (after the checks: a refused call does not move the counter)
+                self.sample_draws = seed + 1
+            more['sample'] = (tau, seed_words, bool(return_logprob))
+        if words is not None:
+            more['tags'] = words
         with _ops.joined(self._stream if self.use_graphs else None):
-            if words is None:
-                vo, io = self._recommend(u, k, exclude_seen)
-            else:
-                vo, io = self._recommend(u, k, exclude_seen, tags=words)
+            out = self._recommend(u, k, exclude_seen, **more)
         n = len(u)
-        ids = io[:n].clone()
-        return (ids, vo[:n].clone()) if return_values else ids
+        ids = out[1][:n].clone()
+        res = (ids,) + ((out[0][:n].clone(),) if return_values else ()) + \
+            ((out[2][:n].clone(),) if return_logprob else ())
+        return res if len(res) > 1 else ids
 
-    def _recommend(self, u, k, exclude_seen, tags=None):
+    def _recommend(self, u, k, exclude_seen, tags=None, sample=None):
         be, W, B_loc, B, d = self.be, self.world, self.B_loc, self.B, self.d
         dev, f32, i32 = self.device, torch.float32, torch.int32
         n = len(u)
@@ -1539,6 +1649,30 @@ class ShardedHMF(object):
             dist.all_gather_into_tensor(keys_all, keys_loc, group=self.group)
         ex = (keys_all, B, self._rec_ex[0], self._rec_ex[1]) if exclude_seen else None
         ni = self.ni_loc
+        more, smp = {}, None
+        if sample is not None:
+            # this rank's temperatures (as bits; padding rows: 0) and the two seed words -> every rank in ONE buffer;
+            # `sample=` goes to the backend only here, as `tags=` does
+            tau_h, seed_h, want_logp = sample
+            if getattr(self, '_rec_smp', None) is None:
+                loc = torch.zeros((B_loc + 2,), dtype=i32, device=dev)
+                self._rec_smp = (loc, loc if W == 1 else torch.empty((W * (B_loc + 2),), dtype=i32, device=dev),
+                                 torch.empty((B,), dtype=f32, device=dev), torch.empty((2,), dtype=i32, device=dev))
+            smp_loc, smp_all, tau_all, seed_dev = self._rec_smp
+            h = np.zeros(B_loc + 2, dtype=np.int32)
+            h[:n] = np.ascontiguousarray(tau_h, dtype=np.float32).view(np.int32)
+            h[B_loc:] = seed_h
+            smp_loc.copy_(torch.from_numpy(h))
+            if W > 1:
+                dist.all_gather_into_tensor(smp_all, smp_loc, group=self.group)
+                sw = smp_all.view(W, B_loc + 2)[:, B_loc:].cpu().numpy()
+                if np.any(sw != sw[0]):                 # (every rank sees the same words: they all raise)
+                    raise ValueError("recommend: sample_seed must be the same on every rank")
+            g = smp_all.view(W, B_loc + 2)
+            tau_all.view(W, B_loc).copy_(g[:, :B_loc].view(f32))
+            seed_dev.copy_(g[0, B_loc:])
+            smp = (tau_all, B, seed_dev, W, self.rank, keys_all)
+            more['sample'] = smp
         if tags is not None:
             # the request words of this rank's users (padding rows: no constraint) -> every rank, like the keys;
             # `tags=` goes to the backend only here, so one that does not know the argument serves the plain calls
@@ -1554,17 +1688,43 @@ class ShardedHMF(object):
             if W > 1:
                 dist.all_gather_into_tensor(any_all, any_loc, group=self.group)
                 dist.all_gather_into_tensor(all_all, all_loc, group=self.group)
-            be.shard_topk(U_all, self.E_item[:ni], self.b_item[:ni], k, ex, out_v, out_i,
-                          tags=(self._rec_tags[:ni], any_all, all_all, B))
-        else:
-            be.shard_topk(U_all, self.E_item[:ni], self.b_item[:ni], k, ex, out_v, out_i)
+            more['tags'] = (self._rec_tags[:ni], any_all, all_all, B)
+        be.shard_topk(U_all, self.E_item[:ni], self.b_item[:ni], k, ex, out_v, out_i, **more)
         if W == 1:
             recv_v, recv_c = out_v.view(1, B, k), out_i.view(1, B, k)
         else:
             _all_to_all(recv_v.view(B, k), out_v, group=self.group)
             _all_to_all(recv_c.view(B, k), out_i, group=self.group)
         be.topk_merge_shards(recv_v, recv_c, vo, io)
-        return vo, io
+        if smp is None:
+            return vo, io
+        # the owner's own rows: its temperatures, global item ids as the noise columns
+        r0 = self.rank * B_loc
+        own = (tau_all[r0:r0 + B_loc], B_loc, seed_dev, 1, 0, keys_loc)
+        if not want_logp:
+            be.sample_strip(vo, io, own)
+            return vo, io
+        P_max = max(be.shard_mass_parts(B, len(range(s, self.n_items, W)), d) for s in range(W))
+        lk = self.__dict__.setdefault('_rec_logp', {})
+        bl = lk.get((k, P_max))
+        if bl is None:
+            wd = 2 * P_max + k
+            bl = lk[(k, P_max)] = (torch.empty((B, wd), dtype=f32, device=dev),
+                                   None if W == 1 else torch.empty((W, B_loc, wd), dtype=f32, device=dev),
+                                   io if W == 1 else torch.empty((B, k), dtype=i32, device=dev),
+                                   torch.empty((B_loc, k), dtype=f32, device=dev))
+        packed, recv_p, picks_all, lp = bl
+        if W > 1:
+            dist.all_gather_into_tensor(picks_all, io, group=self.group)
+        kw = {'tags': more['tags']} if tags is not None else {}
+        be.shard_rest_mass(U_all, self.E_item[:ni], self.b_item[:ni], ex, picks_all, W, self.rank, smp, packed, P_max,
+                           **kw)
+        if W == 1:
+            recv_p = packed.view(1, B, 2 * P_max + k)
+        else:
+            _all_to_all(recv_p.view(B, 2 * P_max + k), packed, group=self.group)
+        be.sample_logp_finish_shards(io, recv_p, P_max, own, lp, vo)
+        return vo, io, lp
 
     # ------------------------------------------------------------ similar_items
     def similar_items(self, items, k, include_self=False, return_values=False, return_logprob=False):
@@ -2118,11 +2278,20 @@ class ShardedW2V(ShardedHMF):
 
     def recommend(self, users, context, k, exclude_seen=False, return_values=False, tags_any=None, tags_all=None):
         """ShardedHMF.recommend over x_test of (users, context): context is [n_input][len(users)], time-major."""
+        return self.recommend_sampled(users, context, k, exclude_seen=exclude_seen, return_values=return_values,
+                                      tags_any=tags_any, tags_all=tags_all)
+
+    def recommend_sampled(self, users, context, k, exclude_seen=False, return_values=False, tags_any=None,
+                          tags_all=None, sample_temperature=None, sample_seed=None, return_logprob=False):
+        """ShardedHMF.recommend_sampled over x_test of (users, context).  The sampled recommend's noise row is the USER
+        id: two rows of the same user in one call share their noise."""
         u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
         self._serve_ctx = self._context_array(context, int(u.size), "recommend")
         try:
-            return super().recommend(users, k, exclude_seen=exclude_seen, return_values=return_values,
-                                     tags_any=tags_any, tags_all=tags_all)
+            return super().recommend_sampled(users, k, exclude_seen=exclude_seen, return_values=return_values,
+                                             tags_any=tags_any, tags_all=tags_all,
+                                             sample_temperature=sample_temperature, sample_seed=sample_seed,
+                                             return_logprob=return_logprob)
         finally:
             self._serve_ctx = None
 
@@ -2349,6 +2518,11 @@ class ShardedHMFBags(ShardedHMF):
         raise NotImplementedError("%s.recommend: item latents are bag means -- use item_view().recommend"
                                   % type(self).__name__)
 
+    def recommend_sampled(self, *args, **kwargs):
+        """Not on the training class either: item_view().recommend_sampled."""
+        raise NotImplementedError("%s.recommend_sampled: item latents are bag means -- use "
+                                  "item_view().recommend_sampled" % type(self).__name__)
+
     def similar_items(self, items, k, include_self=False, return_values=False):
         """ShardedHMF.similar_items over the materialised item latents 1/2 (id row + bag mean): through a serving view
         (item_view()) this model keeps for the purpose -- it refreshes when the model has stepped or been restored."""
@@ -2524,6 +2698,11 @@ class ShardedHMFRepTokens(ShardedHMF):
         raise NotImplementedError("%s.recommend: item latents are bag means -- use item_view().recommend"
                                   % type(self).__name__)
 
+    def recommend_sampled(self, *args, **kwargs):
+        """Not on the training class either: item_view().recommend_sampled."""
+        raise NotImplementedError("%s.recommend_sampled: item latents are bag means -- use "
+                                  "item_view().recommend_sampled" % type(self).__name__)
+
     def similar_items(self, items, k, include_self=False, return_values=False):
         """ShardedHMF.similar_items over the materialised item latents 1/2 (id row + bag mean): through a serving view
         (item_view()) this model keeps for the purpose -- it refreshes when the model has stepped or been restored."""
@@ -2616,10 +2795,10 @@ class ShardedHetView(ShardedHMF):
         self._seen = (m.steps, m.n_restores)
         self.n_refresh += 1
 
-    def _recommend(self, u, k, exclude_seen, tags=None):
+    def _recommend(self, u, k, exclude_seen, tags=None, sample=None):
         if self._seen != (self.model.steps, self.model.n_restores):
             self._refresh()
-        return super()._recommend(u, k, exclude_seen, tags=tags)
+        return super()._recommend(u, k, exclude_seen, tags=tags, sample=sample)
 
     def _evaluate(self, u, it, loss):
         if self._seen != (self.model.steps, self.model.n_restores):

@@ -1326,22 +1326,52 @@ def gemm_nt_topk_filter_tags(A, Bm, col_bias, thr, col_base, cand_v, cand_i, cap
          _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _stream())
 
 
+def sample_keyed(sample):
+    """A sample tuple's noise key: (tau, tau_rows, seed_words) is the plain convention of arx_sample.h -- None; three
+    more entries (col_mul, col_add, noise_rows int32 [tau_rows] or None) are the keyed one of arx_sample_shard.h --
+    noise column = column * col_mul + col_add, noise row = noise_rows[r % tau_rows]."""
+    if len(sample) == 3:
+        return None
+    col_mul, col_add, noise_rows = sample[3:]
+    _chk(noise_rows, torch.int32, 'noise_rows')
+    if noise_rows is not None and (noise_rows.dim() != 1 or not noise_rows.is_contiguous()
+                                   or int(noise_rows.shape[0]) < int(sample[1])):
+        raise ValueError("sample: noise_rows is a contiguous int32 [tau_rows]")
+    return int(col_mul), int(col_add), noise_rows
+
+
+def sample_rekeyed(sample, col_mul, col_add):
+    """The sample tuple with another column map and the same noise rows (None where the tuple has none)."""
+    return tuple(sample[:3]) + (int(col_mul), int(col_add), sample[5] if len(sample) > 3 else None)
+
+
 def topk_gumbel_add(logits, col0, sample):
-    """logits[r, c] = fmaf(tau[r % tau_rows], g(r % tau_rows, col0 + c), logits[r, c]) in place: the logits become the
-    keys of the sampled recommend (arx_sample.h).  sample: (tau float32 [tau_rows], tau_rows, seed_words int32 [2])."""
+    """logits[r, c] = fmaf(tau[r % tau_rows], g(noise row, noise column of col0 + c), logits[r, c]) in place: the
+    logits become the keys of the sampled recommend (arx_sample.h).  sample: (tau float32 [tau_rows], tau_rows,
+    seed_words int32 [2]) -- noise row r % tau_rows, noise column col0 + c -- or the keyed six (sample_keyed)."""
     if logits.numel() == 0:
         return
-    tau, tau_rows, seed_words = sample
-    call("arx_topk_gumbel_add", _p(logits), _ld(logits), int(logits.shape[0]), int(col0), int(logits.shape[1]),
-         _p(tau), int(tau_rows), _p(seed_words), _stream())
+    tau, tau_rows, seed_words = sample[:3]
+    key = sample_keyed(sample)
+    if key is None:
+        call("arx_topk_gumbel_add", _p(logits), _ld(logits), int(logits.shape[0]), int(col0), int(logits.shape[1]),
+             _p(tau), int(tau_rows), _p(seed_words), _stream())
+        return
+    call("arx_topk_gumbel_add_keyed", _p(logits), _ld(logits), int(logits.shape[0]), int(col0), int(logits.shape[1]),
+         _p(tau), int(tau_rows), _p(seed_words), key[0], key[1], _p(key[2]), _stream())
 
 
 def topk_gumbel_strip(values, indices, sample):
     """values = fmaf(-tau, g(r % tau_rows, index), key): the winners' keys back into scores; -inf at index -1
     (arx_sample.h)."""
-    tau, tau_rows, seed_words = sample
-    call("arx_topk_gumbel_strip", _p(values), _ld(values), _p(indices), _ld(indices), int(values.shape[0]),
-         int(values.shape[1]), _p(tau), int(tau_rows), _p(seed_words), _stream())
+    tau, tau_rows, seed_words = sample[:3]
+    key = sample_keyed(sample)
+    if key is None:
+        call("arx_topk_gumbel_strip", _p(values), _ld(values), _p(indices), _ld(indices), int(values.shape[0]),
+             int(values.shape[1]), _p(tau), int(tau_rows), _p(seed_words), _stream())
+        return
+    call("arx_topk_gumbel_strip_keyed", _p(values), _ld(values), _p(indices), _ld(indices), int(values.shape[0]),
+         int(values.shape[1]), _p(tau), int(tau_rows), _p(seed_words), key[0], key[1], _p(key[2]), _stream())
 
 
 def gemm_nt_topk_filter_sample(A, Bm, col_bias, thr, col_base, cand_v, cand_i, capp, overflow, sample, tags=None,
@@ -1349,17 +1379,22 @@ def gemm_nt_topk_filter_sample(A, Bm, col_bias, thr, col_base, cand_v, cand_i, c
     """gemm_nt_topk_filter_tags on the KEYS fmaf(tau, g, logit): thr and cand_v are keys, lse_part stays over the
     logits (arx_sample.h).  sample: (tau, tau_rows, seed_words); tags: (col_tags ALREADY sliced to this launch's
     columns, want_any, want_all, want_rows) or None; ex: exclusion lists or None."""
-    tau, tau_rows, seed_words = sample
+    tau, tau_rows, seed_words = sample[:3]
+    key = sample_keyed(sample)
     col_tags, want_any, want_all, want_rows = tags if tags is not None else (None, None, None, 0)
     if tags is not None and int(col_tags.shape[0]) < int(Bm.shape[0]):
         raise ValueError("gemm_nt_topk_filter_sample: %d tag words for %d columns"
                          % (int(col_tags.shape[0]), int(Bm.shape[0])))
     keys, key_rows, ptr, cols = ex if ex is not None else (None, 0, None, None)
-    call("arx_gemm_nt_topk_filter_sample", _p(A), _ld(A), int(A.shape[0]), _p(Bm), _ld(Bm), int(Bm.shape[0]),
-         int(A.shape[1]), _p(col_bias), _p(thr), int(thr.stride(0)), int(col_base), _p(cand_v), _p(cand_i),
-         int(cand_v.stride(0)), int(capp), _p(overflow), _p(lse_part),
-         int(lse_part.stride(0)) if lse_part is not None else 0, _p(keys), int(key_rows), _p(ptr), _p(cols),
-         _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _p(tau), int(tau_rows), _p(seed_words), _stream())
+    args = (_p(A), _ld(A), int(A.shape[0]), _p(Bm), _ld(Bm), int(Bm.shape[0]),
+            int(A.shape[1]), _p(col_bias), _p(thr), int(thr.stride(0)), int(col_base), _p(cand_v), _p(cand_i),
+            int(cand_v.stride(0)), int(capp), _p(overflow), _p(lse_part),
+            int(lse_part.stride(0)) if lse_part is not None else 0, _p(keys), int(key_rows), _p(ptr), _p(cols),
+            _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _p(tau), int(tau_rows), _p(seed_words))
+    if key is None:
+        call("arx_gemm_nt_topk_filter_sample", *(args + (_stream(),)))
+    else:
+        call("arx_gemm_nt_topk_filter_sample_keyed", *(args + (key[0], key[1], _p(key[2]), _stream())))
 
 
 def topk_mark_empty(values, indices):
@@ -1663,6 +1698,38 @@ def sample_logp_finish(indices, pick_score, m_part, s_part, P, sample, logp, val
     call("arx_sample_logp_finish", _p(indices), _ld(indices), _p(pick_score), _ld(pick_score), _p(m_part), _p(s_part),
          ldl, int(P), _p(tau), int(tau_rows), int(indices.shape[0]), int(indices.shape[1]), _p(logp), _ld(logp),
          _p(values), _ld(values) if values is not None else 0, _stream())
+
+
+def picks_to_shard(ids, W, s, cols):
+    """cols[r, j] = ids[r, j] // W where the global id ids[r, j] >= 0 belongs to shard s of W (id % W == s), else -1
+    (arx_sample_shard.h).  ids / cols int32 [B, k]."""
+    _chk(ids, torch.int32, 'ids'); _chk(cols, torch.int32, 'cols')
+    if ids.dim() != 2 or tuple(cols.shape) != tuple(ids.shape):
+        raise ValueError("picks_to_shard: ids and cols [B, k]")
+    call("arx_picks_to_shard", _p(ids), _ld(ids), int(ids.shape[0]), int(ids.shape[1]), int(W), int(s), _p(cols),
+         _ld(cols), _stream())
+
+
+def sample_logp_finish_shards(indices, pick_score, m_part, s_part, P, sample, logp, values=None):
+    """sample_logp_finish over W shard-major slabs (arx_sample_shard.h): m_part / s_part [W, B, >= P] and pick_score
+    [W, B, k] (views of one packed buffer are fine: each slab [B, .] with its row stride, the slabs one stride apart);
+    indices [B, k]: GLOBAL ids in selection order -- pick t's score is read from slab id % W."""
+    tau, tau_rows = sample[0], sample[1]
+    _chk(logp, torch.float32, 'logp'); _chk(values, torch.float32, 'values'); _chk(indices, torch.int32, 'indices')
+    if tuple(logp.shape) != tuple(indices.shape) or (values is not None and values.shape != logp.shape):
+        raise ValueError("sample_logp_finish_shards: indices, logp and values [B, k]")
+    B, k = int(indices.shape[0]), int(indices.shape[1])
+    W = int(m_part.shape[0])
+    if m_part.dim() != 3 or s_part.dim() != 3 or pick_score.dim() != 3 or int(pick_score.shape[0]) != W \
+            or int(s_part.shape[0]) != W or s_part.stride() != m_part.stride() or int(m_part.shape[2]) < int(P) \
+            or tuple(pick_score.shape[1:]) != (B, k) or int(m_part.shape[1]) != B \
+            or m_part.stride(2) != 1 or pick_score.stride(2) != 1:
+        raise ValueError("sample_logp_finish_shards: m_part / s_part [W, B, >= P] with the same strides, pick_score "
+                         "[W, B, k], unit stride along a row")
+    call("arx_sample_logp_finish_shards", _p(indices), _ld(indices), _p(pick_score), int(pick_score.stride(1)),
+         int(pick_score.stride(0)), _p(m_part), _p(s_part), int(m_part.stride(1)), int(m_part.stride(0)), W, int(P),
+         _p(tau), int(tau_rows), B, k, _p(logp), _ld(logp), _p(values), _ld(values) if values is not None else 0,
+         _stream())
 
 
 def lstm_fwd(x, W, b, L, B, din, h, forget_bias, hs, cs, gates):

@@ -189,7 +189,7 @@ class TopKScan(object):
             self.fused = was
 
     def run(self, latent, pool, bias, ws, values, indices, ex=None, col_scale=None, self_col=None, tags=None,
-            sample=None, logp=None):
+            sample=None, logp=None, strip=True):
         """values / indices [B, k] = the top-k of latent . pool^T + bias (bias may be None) over all V >= k pool rows;
         ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace.
         col_scale [V] (None: every launch is the one above): the scores are (latent . pool^T) * col_scale[column] --
@@ -207,7 +207,12 @@ class TopKScan(object):
         logp (with sample): float32 [B, k] -- the log-probability of every draw (arx_sample_logp.h).  After the selection
         is complete (the merge and mark_empty) the mass pass runs INSTEAD of gumbel_strip: one streaming launch over
         [0, V) where the fused form applies, a second sweep of chunks otherwise (chunked() forces it, as it does for
-        the selection); `values` are then the picks' exact scores."""
+        the selection); `values` are then the picks' exact scores.
+        A keyed sample -- three more entries (col_mul, col_add, noise_rows), ops.sample_keyed -- feeds the noise other
+        rows and columns (arx_sample_shard.h: shard s of W passes (W, s, the rows' user ids)); strip=False returns the
+        winners' KEYS (what a merge across shards compares); not with logp."""
+        if logp is not None and not strip:
+            raise ValueError("TopKScan.run: strip=False (the keys) does not go with logp")
         V, k = pool.shape[0], self.k
         cos = col_scale is not None
         if logp is not None and sample is None:
@@ -278,7 +283,7 @@ class TopKScan(object):
                 ops.topk_mark_empty(values, indices)
             if logp is not None:
                 self._logp_pass(latent, pool, bias, ws, values, indices, ex, tags, sample, logp, True)
-            elif sample is not None:
+            elif sample is not None and strip:
                 ops.topk_gumbel_strip(values, indices, sample)
             return
         nch = (V + self.chunk - 1) // self.chunk
@@ -314,27 +319,33 @@ class TopKScan(object):
             ops.topk_mark_empty(values, indices)
         if logp is not None:
             self._logp_pass(latent, pool, bias, ws, values, indices, ex, tags, sample, logp, False)
-        elif sample is not None:
+        elif sample is not None and strip:
             ops.topk_gumbel_strip(values, indices, sample)
         if self.want_lse:
             ops.row_logsumexp(lp, self.lse)
 
     def _logp_pass(self, latent, pool, bias, ws, values, indices, ex, tags, sample, logp, streaming):
-        """The mass pass and the finish of run(logp=) over the complete selection: REST's mass per row -- the eligible
-        columns that are no picks -- from one streaming scan, or chunk by chunk through the logits buffer (GEMM,
-        exclusion fill, tags fill, rest_mass_chunk); the picks' scores on the way; then logp and the exact values."""
-        V = pool.shape[0]
+        """The mass pass and the finish of run(logp=) over the complete selection (mass_pass), then logp and the exact
+        values."""
         lb = getattr(self, '_lp', None)
         if lb is None:
             lb = self._lp = LogpBuffers(self._rows, self.k, self._dev)
-        ops.sample_logp_sort(indices, lb.pk_cols, lb.pk_slot)
+        m_part, s_part, P = self.mass_pass(latent, pool, bias, ws, indices, ex, tags, sample, streaming, lb)
+        ops.sample_logp_finish(indices, lb.pick_score, m_part, s_part, P, sample, logp, values)
+
+    def mass_pass(self, latent, pool, bias, ws, cols, ex, tags, sample, streaming, lb):
+        """REST's mass per row -- the eligible columns that are not among the row's picks `cols` [B, k] (columns of
+        this pool, -1: none) -- from one streaming scan, or chunk by chunk through the logits buffer (GEMM, exclusion
+        fill, tags fill, rest_mass_chunk); the picks' scores go to lb.pick_score on the way.  lb: the LogpBuffers of
+        (B, k).  Returns (m_part, s_part, P): [B, P] parts, or the running pairs [B] with P = 1."""
+        V = pool.shape[0]
+        ops.sample_logp_sort(cols, lb.pk_cols, lb.pk_slot)
         if streaming:
             P = ops.gemm_nt_topk_parts(self._rows, V)
             m_part, s_part = lb.parts(P)
             ops.gemm_nt_rest_mass(latent, pool, bias, 0, sample, lb.picks, m_part, s_part, lb.pick_score, tags=tags,
                                   ex=ex)
-            ops.sample_logp_finish(indices, lb.pick_score, m_part, s_part, P, sample, logp, values)
-            return
+            return m_part, s_part, P
         for c0 in range(0, V, self.chunk):
             c1 = min(V, c0 + self.chunk)
             lg = self._buf[:, :c1 - c0]
@@ -344,7 +355,12 @@ class TopKScan(object):
             if tags is not None:
                 ops.topk_tags_fill(lg, c0, tags)
             ops.rest_mass_chunk(lg, c0, sample, lb.picks, c0 == 0, lb.m_run, lb.s_run, lb.pick_score)
-        ops.sample_logp_finish(indices, lb.pick_score, lb.m_run, lb.s_run, 1, sample, logp, values)
+        return lb.m_run, lb.s_run, 1
+
+    def mass_streams(self, latent, pool):
+        """Whether mass_pass over this pool may take the streaming form: where run() takes the fused one."""
+        return bool(self.fused and pool.shape[0] > self.chunk and pool.stride(0) % 4 == 0
+                    and latent.stride(0) % 4 == 0)
 
 
 class StreamTopK(G.Node, TopKScan):

@@ -73,8 +73,13 @@ struct NtFilter {
   // (any == 0 || (tags & any) != 0) && (tags & all) == all -- a zero word is no constraint
   const int32_t* col_tags; const int32_t* want_any; const int32_t* want_all; int64_t want_rows;
   // kNtGumbel (the sampled recommend, gumbel.h): row r competes with the KEYS fmaf(tau, g, v), tau = tau[r % tau_rows],
-  // g the noise of (seed_words, r % tau_rows, col_base + col); thr and cand_v are keys, lse_part stays over v
+  // g the noise of (seed_words, noise row, noise column); thr and cand_v are keys, lse_part stays over v.  The noise
+  // row is noise_rows[r % tau_rows] (nullptr: r % tau_rows; negative: the row competes as a tau == 0 row), the noise
+  // column col * noise_mul + noise_add (unsigned, wrapping), noise_add = col_base * col_mul + col_add formed on the host
+  // and added to the row word b0 in the prologue (kNtKeyed, arx_sample_shard.h); without that bit the plain convention
+  // of arx_sample.h: noise row r % tau_rows, noise column col_base + col
   const float* tau; int64_t tau_rows; const int32_t* seed_words;
+  const int32_t* noise_rows; uint32_t noise_mul, noise_add;
   // kNtRest (the mass pass of the sampled recommend's propensities, arx_sample_logp.h): row r's picks sorted by
   // ABSOLUTE column, pk_cols[r * ldp + j] with the selection slot pk_slot[r * ldp + j] beside it, j < pk_k (-1 entries
   // last); per column range REST's pair (m_part, s_part)[row * ldl + part], and pick_score[row * ldps + slot] = the
@@ -96,6 +101,12 @@ struct NtFilter {
 // fit, and the 16 of the thresholds are given back
 constexpr int kNtTopk = 1, kNtLse = 2, kNtRelu = 4, kNtExcl = 8, kNtRank = 16, kNtCos = 32, kNtSelf = 64, kNtTags = 128;
 constexpr int kNtGumbel = 256;
+// bit 10 (with bit 8) the keyed noise of arx_sample_shard.h: the noise row comes from NtFilter::noise_rows and the noise
+// column is col * noise_mul + noise_add.  A mode bit like every other feature of this body, not a run-time operand of
+// the plain Gumbel instances: with the multiply in them the K = 128 instance of bits 0 + 8 went from 200 to 248 bytes of
+// scratch per lane and the un-keyed sampled scan from 18.8 to 20.2 ms (4096 x 1 M x 128) -- with
+// the bit off the instances are the ones they were, instruction for instruction
+constexpr int kNtKeyed = 1024;
 // bit 9 (alone) REST's mass per column range, an eval-style scan without candidate lists: the 32 registers of the lse
 // mode hold each row's (m, S) at ITS temperature, the column's tag word travels beside the bias (no lists: there are
 // registers for it), and the two sorted lists a row leaves out -- its exclusion list and its picks -- are walked by
@@ -120,6 +131,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
   static_assert(!want_tags || (want_topk && !want_relu && !want_cos), "the item tags filter the recommend candidates");
   constexpr bool want_gumbel = (MODE & kNtGumbel) != 0;
   static_assert(!want_gumbel || (want_topk && !want_relu && !want_cos), "the Gumbel keys rank the recommend candidates");
+  constexpr bool want_keyed = (MODE & kNtKeyed) != 0;
+  static_assert(!want_keyed || want_gumbel, "the keyed noise belongs to the Gumbel keys");
   constexpr bool want_rest = (MODE & kNtRest) != 0;
   static_assert(!want_rest || MODE == kNtRest, "the mass pass is a scan of its own");
   constexpr int NS = KT / 8;                  // steps of 4 MFMAs
@@ -264,11 +277,20 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
         s_wa[threadIdx.x] = row < M ? (uint32_t)flt.want_any[wr] : 0u;
         s_wl[threadIdx.x] = row < M ? (uint32_t)flt.want_all[wr] : 0u;
       }
-      if (want_gumbel) {
+      if (want_gumbel && !want_keyed) {
         const int64_t nr = row < M ? row % flt.tau_rows : 0;
         const GumbelRow gr = gumbel_row(flt.seed_words, nr);
         s_gm[threadIdx.x] = make_uint4(__float_as_uint(row < M ? flt.tau[nr] : 0.f), gr.b0, gr.b1,
                                        __float_as_uint(row < M ? flt.thr[row * flt.ldthr] : __builtin_inff()));
+      }
+      if (want_keyed) {
+        // the row words are formed once here; noise_add rides in b0: the column's hash starts with
+        // noise column + b0 = col * noise_mul + (noise_add + b0)
+        const int64_t tr = row < M ? row % flt.tau_rows : 0;
+        const int64_t nr = flt.noise_rows ? (int64_t)flt.noise_rows[tr] : tr;
+        const GumbelRow gr = gumbel_row(flt.seed_words, nr);
+        s_gm[threadIdx.x] = make_uint4(__float_as_uint(row < M && nr >= 0 ? flt.tau[tr] : 0.f), gr.b0 + flt.noise_add,
+                                       gr.b1, __float_as_uint(row < M ? flt.thr[row * flt.ldthr] : __builtin_inff()));
       }
       if (want_rest) {
         const float t = rm_tau(row < M ? flt.tau[row % flt.tau_rows] : 1.f);
@@ -524,7 +546,8 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nt_areg(
             // logarithms run only in a wave where some lane's bound passes (tau == 0: key == v bit for bit)
             const uint4 gm = s_gm[rl];
             const float tau = __uint_as_float(gm.x);
-            const uint32_t x = gumbel_bits(gm.y, gm.z, (uint32_t)flt.col_base + (uint32_t)col);
+            const uint32_t x = want_keyed ? gumbel_bits(gm.y, gm.z, (uint32_t)col * flt.noise_mul)
+                                          : gumbel_bits(gm.y, gm.z, (uint32_t)flt.col_base + (uint32_t)col);
             const float thk = __uint_as_float(gm.w);
             pred = col < N && fmaf(tau, gumbel_upper(x), v) > thk;
             if (__ballot(pred) == 0ull) continue;
@@ -845,40 +868,45 @@ int arx_gemm_nt_topk_filter_tags(const float* A, int64_t lda, int64_t M, const f
   return ARX_OK;
 }
 
-int arx_gemm_nt_topk_filter_sample(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
-                                   int64_t K, const float* col_bias, const float* thr, int64_t ldthr, int32_t col_base,
-                                   float* cand_v, int32_t* cand_i, int64_t ldcand, int capp, int* overflow,
-                                   float* lse_part, int64_t ldl, const int32_t* row_keys, int64_t key_rows,
-                                   const int32_t* ex_ptr, const int32_t* ex_cols, const int32_t* col_tags,
-                                   const int32_t* want_any, const int32_t* want_all, int64_t want_rows, const float* tau,
-                                   int64_t tau_rows, const int32_t* seed_words, void* stream) {
+static int filter_sample(const char* fn, const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb,
+                         int64_t N, int64_t K, const float* col_bias, const float* thr, int64_t ldthr, int32_t col_base,
+                         float* cand_v, int32_t* cand_i, int64_t ldcand, int capp, int* overflow, float* lse_part,
+                         int64_t ldl, const int32_t* row_keys, int64_t key_rows, const int32_t* ex_ptr,
+                         const int32_t* ex_cols, const int32_t* col_tags, const int32_t* want_any,
+                         const int32_t* want_all, int64_t want_rows, const float* tau, int64_t tau_rows,
+                         const int32_t* seed_words, int32_t col_mul, int32_t col_add, const int32_t* noise_rows,
+                         void* stream) {
   ARX_CHECK_ARG(A && Bm && thr && cand_v && cand_i && overflow && tau && seed_words,
-                "arx_gemm_nt_topk_filter_sample: null pointer (col_bias, lse_part, the exclusion lists and the tag "
-                "arrays may be NULL)");
+                "%s: null pointer (col_bias, lse_part, the exclusion lists and the tag "
+                "arrays may be NULL)", fn);
   ARX_CHECK_ARG(M > 0 && N > 0 && capp > 0 && ldcand > 0 && lda >= K && ldb >= K && tau_rows > 0,
-                "arx_gemm_nt_topk_filter_sample: need M > 0, N > 0, capp > 0, ldcand > 0, lda >= K, ldb >= K, "
-                "tau_rows > 0");
+                "%s: need M > 0, N > 0, capp > 0, ldcand > 0, lda >= K, ldb >= K, "
+                "tau_rows > 0", fn);
   const bool tags = col_tags || want_any || want_all;
   ARX_CHECK_ARG(!tags || (col_tags && want_any && want_all && want_rows > 0),
-                "arx_gemm_nt_topk_filter_sample: col_tags, want_any, want_all go together (all NULL: no tags), "
-                "want_rows > 0");
+                "%s: col_tags, want_any, want_all go together (all NULL: no tags), "
+                "want_rows > 0", fn);
   const bool excl = row_keys || ex_ptr || ex_cols;
   ARX_CHECK_ARG(!excl || (row_keys && ex_ptr && ex_cols && key_rows > 0),
-                "arx_gemm_nt_topk_filter_sample: row_keys, ex_ptr, ex_cols go together (all NULL: no lists), "
-                "key_rows > 0");
+                "%s: row_keys, ex_ptr, ex_cols go together (all NULL: no lists), "
+                "key_rows > 0", fn);
   ARX_CHECK_ARG(col_base >= 0 && (int64_t)col_base + N <= 0x7fffffff,
-                "arx_gemm_nt_topk_filter_sample: need col_base >= 0 and col_base + N < 2^31");
-  ARX_CHECK_ARG(K == 32 || K == 64 || K == 128, "arx_gemm_nt_topk_filter_sample: K must be 32, 64 or 128");
+                "%s: need col_base >= 0 and col_base + N < 2^31", fn);
+  ARX_CHECK_ARG(col_mul >= 1 && col_add >= 0 && col_add < col_mul &&
+                    (int64_t)col_base + N - 1 <= (0x7fffffffll - col_add) / col_mul,
+                "%s: need col_mul >= 1, 0 <= col_add < col_mul and every noise column (col_base + c) * col_mul + "
+                "col_add < 2^31", fn);
+  ARX_CHECK_ARG(K == 32 || K == 64 || K == 128, "%s: K must be 32, 64 or 128", fn);
   ARX_CHECK_ARG(!((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(Bm)) & 15) && lda % 4 == 0 &&
                     ldb % 4 == 0,
-                "arx_gemm_nt_topk_filter_sample: operands must be 16-byte aligned");
+                "%s: operands must be 16-byte aligned", fn);
   int64_t tpb, ns;
   nt_split(M, N, &tpb, &ns);
   ARX_CHECK_ARG(ns * capp <= ldcand,
-                "arx_gemm_nt_topk_filter_sample: candidate rows too short (parts * capp > ldcand)");
+                "%s: candidate rows too short (parts * capp > ldcand)", fn);
   const int64_t grid = ceil_div(M, (int64_t)kNtBM) * ns;
-  ARX_CHECK_ARG(grid <= 0x7fffffff, "arx_gemm_nt_topk_filter_sample: grid too large");
-  ARX_CHECK_ARG(!lse_part || ldl >= ns, "arx_gemm_nt_topk_filter_sample: lse_part rows too short (ldl < parts)");
+  ARX_CHECK_ARG(grid <= 0x7fffffff, "%s: grid too large", fn);
+  ARX_CHECK_ARG(!lse_part || ldl >= ns, "%s: lse_part rows too short (ldl < parts)", fn);
   NtFilter f{thr,      ldthr,   cand_v,   cand_i,   ldcand,   capp,   col_base, overflow, lse_part,
              ldl,      nullptr, nullptr,  row_keys, key_rows, ex_ptr, ex_cols};
   f.col_tags = col_tags;
@@ -888,14 +916,51 @@ int arx_gemm_nt_topk_filter_sample(const float* A, int64_t lda, int64_t M, const
   f.tau = tau;
   f.tau_rows = tau_rows;
   f.seed_words = seed_words;
+  f.noise_rows = noise_rows;
+  f.noise_mul = (uint32_t)col_mul;
+  f.noise_add = (uint32_t)col_base * (uint32_t)col_mul + (uint32_t)col_add;
   hipStream_t s = as_stream(stream);
-  if (lse_part)
+  const bool keyed = col_mul != 1 || col_add != 0 || noise_rows != nullptr;    // (1, 0, NULL): the plain instances
+  if (lse_part && keyed)
+    nt_launch_sample<kNtTopk | kNtGumbel | kNtKeyed | kNtLse>(excl, tags, K, grid, s, M, N, A, lda, Bm, ldb, col_bias,
+                                                              (int)tpb, (int)ns, f);
+  else if (keyed)
+    nt_launch_sample<kNtTopk | kNtGumbel | kNtKeyed>(excl, tags, K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb,
+                                                     (int)ns, f);
+  else if (lse_part)
     nt_launch_sample<kNtTopk | kNtGumbel | kNtLse>(excl, tags, K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb,
                                                    (int)ns, f);
   else
     nt_launch_sample<kNtTopk | kNtGumbel>(excl, tags, K, grid, s, M, N, A, lda, Bm, ldb, col_bias, (int)tpb, (int)ns, f);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
+}
+
+int arx_gemm_nt_topk_filter_sample(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N,
+                                   int64_t K, const float* col_bias, const float* thr, int64_t ldthr, int32_t col_base,
+                                   float* cand_v, int32_t* cand_i, int64_t ldcand, int capp, int* overflow,
+                                   float* lse_part, int64_t ldl, const int32_t* row_keys, int64_t key_rows,
+                                   const int32_t* ex_ptr, const int32_t* ex_cols, const int32_t* col_tags,
+                                   const int32_t* want_any, const int32_t* want_all, int64_t want_rows, const float* tau,
+                                   int64_t tau_rows, const int32_t* seed_words, void* stream) {
+  return filter_sample("arx_gemm_nt_topk_filter_sample", A, lda, M, Bm, ldb, N, K, col_bias, thr, ldthr, col_base,
+                       cand_v, cand_i, ldcand, capp, overflow, lse_part, ldl, row_keys, key_rows, ex_ptr, ex_cols,
+                       col_tags, want_any, want_all, want_rows, tau, tau_rows, seed_words, 1, 0, nullptr, stream);
+}
+
+int arx_gemm_nt_topk_filter_sample_keyed(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb,
+                                         int64_t N, int64_t K, const float* col_bias, const float* thr, int64_t ldthr,
+                                         int32_t col_base, float* cand_v, int32_t* cand_i, int64_t ldcand, int capp,
+                                         int* overflow, float* lse_part, int64_t ldl, const int32_t* row_keys,
+                                         int64_t key_rows, const int32_t* ex_ptr, const int32_t* ex_cols,
+                                         const int32_t* col_tags, const int32_t* want_any, const int32_t* want_all,
+                                         int64_t want_rows, const float* tau, int64_t tau_rows,
+                                         const int32_t* seed_words, int32_t col_mul, int32_t col_add,
+                                         const int32_t* noise_rows, void* stream) {
+  return filter_sample("arx_gemm_nt_topk_filter_sample_keyed", A, lda, M, Bm, ldb, N, K, col_bias, thr, ldthr, col_base,
+                       cand_v, cand_i, ldcand, capp, overflow, lse_part, ldl, row_keys, key_rows, ex_ptr, ex_cols,
+                       col_tags, want_any, want_all, want_rows, tau, tau_rows, seed_words, col_mul, col_add, noise_rows,
+                       stream);
 }
 
 int arx_gemm_nt_rest_mass(const float* A, int64_t lda, int64_t M, const float* Bm, int64_t ldb, int64_t N, int64_t K,

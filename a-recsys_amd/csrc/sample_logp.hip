@@ -4,7 +4,7 @@
 //                   (column, slot) with the -1 entries last -- what both forms of the mass pass walk;
 //   k_rest_chunk    the materialised form: one workgroup per row folds a chunk of logits (-inf where ineligible) into
 //                   the row's running REST pair, leaves the picks out and writes their scores;
-//   k_logp_finish   one wave per row: the P parts joined in part order, then the backward join over the picks in
+//   k_logp_finish   one wave per row: the P parts (of each of W shard slabs, arx_sample_shard.h) joined in order, then the backward join over the picks in
 //                   selection order -- lane l owns the picks [l E, l E + E), E = ceil(k / 64): its own suffix, a suffix
 //                   scan over the lanes, its own suffix again on top of what lies above.
 // Rows walk grid-stride loops under capped grids; every LDS word is rewritten on every trip.  The order of every join
@@ -117,11 +117,14 @@ __global__ __launch_bounds__(kLpThreads) void k_rest_chunk(
   }
 }
 
+// W slabs (arx_sample_logp_finish_shards; W == 1, strides 0: the single-device finish): shard w's parts of row r at
+// m_part[w * slab_l + r * ldl + p], its pick scores at pick_score[w * slab_ps + r * ldps + t]; the parts join in
+// (shard, part) order and pick t's score is read from the slab of its owner, indices[t] % W
 __global__ __launch_bounds__(kLpThreads) void k_logp_finish(
     const int32_t* __restrict__ indices, int64_t ldi, const float* __restrict__ pick_score, int64_t ldps,
-    const float* __restrict__ m_part, const float* __restrict__ s_part, int64_t ldl, int P,
-    const float* __restrict__ tau, int64_t tau_rows, int64_t B, int k, float* __restrict__ logp, int64_t ldo,
-    float* __restrict__ values, int64_t ldv) {
+    int64_t slab_ps, const float* __restrict__ m_part, const float* __restrict__ s_part, int64_t ldl, int64_t slab_l,
+    int W, int P, const float* __restrict__ tau, int64_t tau_rows, int64_t B, int k, float* __restrict__ logp,
+    int64_t ldo, float* __restrict__ values, int64_t ldv) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int E = (k + 63) / 64;
   const int lo = min(k, lane * E), hi = min(k, lane * E + E);
@@ -129,12 +132,20 @@ __global__ __launch_bounds__(kLpThreads) void k_logp_finish(
     const float tau0 = tau[r % tau_rows];
     const float t = rm_tau(tau0);
     RmMass rest = rm_empty();
-    for (int p = 0; p < P; ++p) rest = rm_join(rest, RmMass{m_part[r * ldl + p], s_part[r * ldl + p]}, t);
+    for (int w = 0; w < W; ++w)
+      for (int p = 0; p < P; ++p) {
+        const int64_t at = w * slab_l + r * ldl + p;
+        rest = rm_join(rest, RmMass{m_part[at], s_part[at]}, t);
+      }
     const int32_t* ir = indices + r * ldi;
     const float* sr = pick_score + r * ldps;
+    // (an index < 0 reads slab 0: the value is not used)
+    auto score = [&](int j) { return sr[(ir[j] >= 0 ? ir[j] % W : 0) * slab_ps + j]; };
     RmMass acc = rm_empty();
-    for (int j = hi - 1; j >= lo; --j)
-      if (ir[j] >= 0 && sr[j] > -__builtin_inff()) acc = rm_join(RmMass{sr[j], 1.f}, acc, t);
+    for (int j = hi - 1; j >= lo; --j) {
+      const float sj = score(j);
+      if (ir[j] >= 0 && sj > -__builtin_inff()) acc = rm_join(RmMass{sj, 1.f}, acc, t);
+    }
     // the wave: tot = this lane's picks and those of the lanes above it
     RmMass tot = acc;
 #pragma unroll
@@ -146,8 +157,9 @@ __global__ __launch_bounds__(kLpThreads) void k_logp_finish(
     if (lane == 63) above = rm_empty();
     acc = rm_join(above, rest, t);
     for (int j = hi - 1; j >= lo; --j) {
-      const bool live = ir[j] >= 0 && sr[j] > -__builtin_inff();     // (a -inf score is not eligible: a -1 column)
-      const float s = live ? sr[j] : -__builtin_inff();
+      const float sj = score(j);
+      const bool live = ir[j] >= 0 && sj > -__builtin_inff();        // (a -inf score is not eligible: a -1 column)
+      const float s = live ? sj : -__builtin_inff();
       float lp = 0.f;
       if (live) {
         acc = rm_join(RmMass{s, 1.f}, acc, t);
@@ -206,24 +218,42 @@ int arx_rest_mass_chunk(const float* logits, int64_t ld, int64_t B, int32_t col0
   return ARX_OK;
 }
 
+static int logp_finish(const char* fn, const int32_t* indices, int64_t ldi, const float* pick_score, int64_t ldps,
+                       int64_t slab_ps, const float* m_part, const float* s_part, int64_t ldl, int64_t slab_l, int W,
+                       int P, const float* tau, int64_t tau_rows, int64_t B, int k, float* logp, int64_t ldo,
+                       float* values, int64_t ldv, void* stream) {
+  ARX_CHECK_ARG(indices && pick_score && m_part && s_part && tau && logp,
+                "%s: null pointer (only values may be NULL)", fn);
+  ARX_CHECK_ARG(B >= 0, "%s: need B >= 0 (B=%lld)", fn, (long long)B);
+  ARX_CHECK_ARG(tau_rows > 0, "%s: need tau_rows > 0 (tau_rows=%lld)", fn, (long long)tau_rows);
+  ARX_CHECK_ARG(k >= 1 && k <= kLpMaxK, "%s: need 1 <= k <= %d (k=%d)", fn, kLpMaxK, k);
+  ARX_CHECK_ARG(P >= 1 && ldl >= P, "%s: need P >= 1 and ldl >= P (P=%d ldl=%lld)", fn, P, (long long)ldl);
+  ARX_CHECK_ARG(ldi >= k && ldps >= k && ldo >= k && (!values || ldv >= k),
+                "%s: need ldi, ldps, ldo (and ldv with values) >= k (k=%d)", fn, k);
+  ARX_CHECK_ARG(W >= 1 && W <= 64 && (W == 1 || (slab_ps >= 0 && slab_l >= 0)),
+                "%s: need 1 <= W <= 64 and slab strides >= 0 (W=%d)", fn, W);
+  if (B == 0) return ARX_OK;
+  k_logp_finish<<<lp_grid(ceil_div(B, (int64_t)kLpWaves)), kLpThreads, 0, as_stream(stream)>>>(
+      indices, ldi, pick_score, ldps, slab_ps, m_part, s_part, ldl, slab_l, W, P, tau, tau_rows, B, k, logp, ldo, values,
+      ldv);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
 int arx_sample_logp_finish(const int32_t* indices, int64_t ldi, const float* pick_score, int64_t ldps,
                            const float* m_part, const float* s_part, int64_t ldl, int P, const float* tau,
                            int64_t tau_rows, int64_t B, int k, float* logp, int64_t ldo, float* values, int64_t ldv,
                            void* stream) {
-  ARX_CHECK_ARG(indices && pick_score && m_part && s_part && tau && logp,
-                "arx_sample_logp_finish: null pointer (only values may be NULL)");
-  ARX_CHECK_ARG(B >= 0, "arx_sample_logp_finish: need B >= 0 (B=%lld)", (long long)B);
-  ARX_CHECK_ARG(tau_rows > 0, "arx_sample_logp_finish: need tau_rows > 0 (tau_rows=%lld)", (long long)tau_rows);
-  ARX_CHECK_ARG(k >= 1 && k <= kLpMaxK, "arx_sample_logp_finish: need 1 <= k <= %d (k=%d)", kLpMaxK, k);
-  ARX_CHECK_ARG(P >= 1 && ldl >= P, "arx_sample_logp_finish: need P >= 1 and ldl >= P (P=%d ldl=%lld)", P,
-                (long long)ldl);
-  ARX_CHECK_ARG(ldi >= k && ldps >= k && ldo >= k && (!values || ldv >= k),
-                "arx_sample_logp_finish: need ldi, ldps, ldo (and ldv with values) >= k (k=%d)", k);
-  if (B == 0) return ARX_OK;
-  k_logp_finish<<<lp_grid(ceil_div(B, (int64_t)kLpWaves)), kLpThreads, 0, as_stream(stream)>>>(
-      indices, ldi, pick_score, ldps, m_part, s_part, ldl, P, tau, tau_rows, B, k, logp, ldo, values, ldv);
-  ARX_CHECK_LAUNCH();
-  return ARX_OK;
+  return logp_finish("arx_sample_logp_finish", indices, ldi, pick_score, ldps, 0, m_part, s_part, ldl, 0, 1, P, tau,
+                     tau_rows, B, k, logp, ldo, values, ldv, stream);
+}
+
+int arx_sample_logp_finish_shards(const int32_t* indices, int64_t ldi, const float* pick_score, int64_t ldps,
+                                  int64_t slab_ps, const float* m_part, const float* s_part, int64_t ldl,
+                                  int64_t slab_l, int W, int P, const float* tau, int64_t tau_rows, int64_t B, int k,
+                                  float* logp, int64_t ldo, float* values, int64_t ldv, void* stream) {
+  return logp_finish("arx_sample_logp_finish_shards", indices, ldi, pick_score, ldps, slab_ps, m_part, s_part, ldl,
+                     slab_l, W, P, tau, tau_rows, B, k, logp, ldo, values, ldv, stream);
 }
 
 }  // extern "C"

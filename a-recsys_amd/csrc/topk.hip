@@ -257,28 +257,37 @@ __global__ __launch_bounds__(256) void k_topk_tags_fill(float* __restrict__ logi
   }
 }
 
-// The sampled recommend (arx_sample.h): key = fmaf(tau, g(row % tau_rows, column), logit) in place, g the Gumbel noise
-// of gumbel.h.  One workgroup per row strides over [col0, col0 + ncols); a row of tau == 0 returns (its keys ARE its
-// logits); a -inf logit stays -inf (g is finite).
+// The sampled recommend (arx_sample.h, arx_sample_shard.h): key = fmaf(tau, g(noise row, noise column), logit) in place,
+// g the Gumbel noise of gumbel.h.  The noise row of batch row r is noise_rows[r % tau_rows] (nullptr: r % tau_rows), the
+// noise column of absolute column c is c * col_mul + col_add (unsigned, wrapping) -- (1, 0, nullptr) is the plain
+// convention of arx_sample.h, (W, s, user ids) the row-sharded one.  One workgroup per row strides over
+// [col0, col0 + ncols); a row of tau == 0 or of a negative noise row returns (its keys ARE its logits); a -inf logit
+// stays -inf (g is finite).
 __global__ __launch_bounds__(256) void k_topk_gumbel_add(float* __restrict__ logits, int64_t ld, int32_t col0,
                                                          int64_t ncols, const float* __restrict__ tau, int64_t tau_rows,
-                                                         const int32_t* __restrict__ seed_words) {
-  const int64_t r = blockIdx.x, nr = r % tau_rows;
-  const float t = tau[nr];
-  if (t == 0.f) return;
+                                                         const int32_t* __restrict__ seed_words, uint32_t col_mul,
+                                                         uint32_t col_add, const int32_t* __restrict__ noise_rows) {
+  const int64_t r = blockIdx.x, tr = r % tau_rows;
+  const int64_t nr = noise_rows ? (int64_t)noise_rows[tr] : tr;
+  const float t = tau[tr];
+  if (t == 0.f || nr < 0) return;
   const GumbelRow gr = gumbel_row(seed_words, nr);
   float* row = logits + r * ld;
-  for (int64_t c = threadIdx.x; c < ncols; c += 256)
-    row[c] = fmaf(t, gumbel_of_bits(gumbel_bits(gr.b0, gr.b1, (uint32_t)col0 + (uint32_t)c)), row[c]);
+  for (int64_t c = threadIdx.x; c < ncols; c += 256) {
+    const uint32_t nc = ((uint32_t)col0 + (uint32_t)c) * col_mul + col_add;
+    row[c] = fmaf(t, gumbel_of_bits(gumbel_bits(gr.b0, gr.b1, nc)), row[c]);
+  }
 }
 
-// the winners' keys back into the model's scores: value = fmaf(-tau, g(row % tau_rows, index), key); index -1: -inf
+// the winners' keys back into the model's scores: value = fmaf(-tau, g(noise row, index * col_mul + col_add), key);
+// index -1: -inf; a negative noise row is a tau == 0 row
 __global__ void k_topk_gumbel_strip(float* __restrict__ values, int64_t ldv, const int32_t* __restrict__ indices,
                                     int64_t ldi, int64_t B, int k, const float* __restrict__ tau, int64_t tau_rows,
-                                    const int32_t* __restrict__ seed_words) {
+                                    const int32_t* __restrict__ seed_words, uint32_t col_mul, uint32_t col_add,
+                                    const int32_t* __restrict__ noise_rows) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= B * k) return;
-  const int64_t r = i / k, nr = r % tau_rows;
+  const int64_t r = i / k, tr = r % tau_rows;
   const int j = (int)(i % k);
   const int32_t c = indices[r * ldi + j];
   float* v = values + r * ldv + j;
@@ -286,10 +295,23 @@ __global__ void k_topk_gumbel_strip(float* __restrict__ values, int64_t ldv, con
     *v = -__builtin_inff();
     return;
   }
-  const float t = tau[nr];
-  if (t == 0.f) return;
+  const int64_t nr = noise_rows ? (int64_t)noise_rows[tr] : tr;
+  const float t = tau[tr];
+  if (t == 0.f || nr < 0) return;
   const GumbelRow gr = gumbel_row(seed_words, nr);
-  *v = fmaf(-t, gumbel_of_bits(gumbel_bits(gr.b0, gr.b1, (uint32_t)c)), *v);
+  *v = fmaf(-t, gumbel_of_bits(gumbel_bits(gr.b0, gr.b1, (uint32_t)c * col_mul + col_add)), *v);
+}
+
+// the picks of the merged lists as columns of ONE shard (arx_sample_shard.h): global id -> id / W where id % W == s,
+// -1 for a pick of another shard and for an id -1
+__global__ void k_picks_to_shard(const int32_t* __restrict__ ids, int64_t ldi, int64_t B, int k, int W, int s,
+                                 int32_t* __restrict__ cols, int64_t ldc) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < B * k; i += (int64_t)gridDim.x * 256) {
+    const int64_t r = i / k;
+    const int j = (int)(i % k);
+    const int32_t id = ids[r * ldi + j];
+    cols[r * ldc + j] = (id >= 0 && id % W == s) ? id / W : -1;
+  }
 }
 
 // a winner whose value is -inf is no item (a row with fewer eligible columns than k): index -1
@@ -494,29 +516,81 @@ int arx_topk_tags_fill(float* logits, int64_t ld, int64_t M, int32_t col0, int64
   return ARX_OK;
 }
 
-int arx_topk_gumbel_add(float* logits, int64_t ld, int64_t M, int32_t col0, int64_t ncols, const float* tau,
-                        int64_t tau_rows, const int32_t* seed_words, void* stream) {
-  ARX_CHECK_ARG(logits && tau && seed_words, "arx_topk_gumbel_add: null pointer");
+// the column map of arx_sample_shard.h: the largest noise column of the columns [col0, col0 + ncols) stays below 2^31
+static bool noise_cols_ok(int64_t col0, int64_t ncols, int32_t col_mul, int32_t col_add) {
+  if (col_mul < 1 || col_add < 0 || col_add >= col_mul) return false;
+  if (ncols <= 0) return true;
+  return (col0 + ncols - 1) <= (0x7fffffffll - col_add) / col_mul;
+}
+
+static int gumbel_add(const char* fn, float* logits, int64_t ld, int64_t M, int32_t col0, int64_t ncols,
+                      const float* tau, int64_t tau_rows, const int32_t* seed_words, int32_t col_mul, int32_t col_add,
+                      const int32_t* noise_rows, void* stream) {
+  ARX_CHECK_ARG(logits && tau && seed_words, "%s: null pointer", fn);
   ARX_CHECK_ARG(M >= 0 && ncols >= 0 && col0 >= 0 && tau_rows > 0,
-                "arx_topk_gumbel_add: need M >= 0, ncols >= 0, col0 >= 0, tau_rows > 0");
-  ARX_CHECK_ARG((int64_t)col0 + ncols <= 0x7fffffff, "arx_topk_gumbel_add: need col0 + ncols < 2^31");
-  ARX_CHECK_ARG(M <= 1 || ld >= ncols, "arx_topk_gumbel_add: ld < ncols");
-  ARX_CHECK_ARG(M <= 0x7fffffff, "arx_topk_gumbel_add: too many rows");
+                "%s: need M >= 0, ncols >= 0, col0 >= 0, tau_rows > 0", fn);
+  ARX_CHECK_ARG((int64_t)col0 + ncols <= 0x7fffffff, "%s: need col0 + ncols < 2^31", fn);
+  ARX_CHECK_ARG(noise_cols_ok(col0, ncols, col_mul, col_add),
+                "%s: need col_mul >= 1, 0 <= col_add < col_mul and every noise column (col0 + c) * col_mul + col_add "
+                "< 2^31", fn);
+  ARX_CHECK_ARG(M <= 1 || ld >= ncols, "%s: ld < ncols", fn);
+  ARX_CHECK_ARG(M <= 0x7fffffff, "%s: too many rows", fn);
   if (M == 0 || ncols == 0) return ARX_OK;
-  k_topk_gumbel_add<<<(int)M, 256, 0, as_stream(stream)>>>(logits, ld, col0, ncols, tau, tau_rows, seed_words);
+  k_topk_gumbel_add<<<(int)M, 256, 0, as_stream(stream)>>>(logits, ld, col0, ncols, tau, tau_rows, seed_words,
+                                                           (uint32_t)col_mul, (uint32_t)col_add, noise_rows);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }
 
+static int gumbel_strip(const char* fn, float* values, int64_t ldv, const int32_t* indices, int64_t ldi, int64_t B,
+                        int k, const float* tau, int64_t tau_rows, const int32_t* seed_words, int32_t col_mul,
+                        int32_t col_add, const int32_t* noise_rows, void* stream) {
+  ARX_CHECK_ARG(values && indices && tau && seed_words, "%s: null pointer", fn);
+  ARX_CHECK_ARG(B >= 0 && k > 0 && tau_rows > 0 && (B <= 1 || (ldv >= k && ldi >= k)),
+                "%s: need B >= 0, k > 0, tau_rows > 0, ldv >= k, ldi >= k", fn);
+  ARX_CHECK_ARG(col_mul >= 1 && col_add >= 0 && col_add < col_mul, "%s: need col_mul >= 1, 0 <= col_add < col_mul", fn);
+  ARX_CHECK_ARG(ceil_div(B * k, (int64_t)256) <= 0x7fffffff, "%s: too many entries", fn);
+  if (B == 0) return ARX_OK;
+  k_topk_gumbel_strip<<<(int)ceil_div(B * k, (int64_t)256), 256, 0, as_stream(stream)>>>(
+      values, ldv, indices, ldi, B, k, tau, tau_rows, seed_words, (uint32_t)col_mul, (uint32_t)col_add, noise_rows);
+  ARX_CHECK_LAUNCH();
+  return ARX_OK;
+}
+
+int arx_topk_gumbel_add(float* logits, int64_t ld, int64_t M, int32_t col0, int64_t ncols, const float* tau,
+                        int64_t tau_rows, const int32_t* seed_words, void* stream) {
+  return gumbel_add("arx_topk_gumbel_add", logits, ld, M, col0, ncols, tau, tau_rows, seed_words, 1, 0, nullptr, stream);
+}
+
+int arx_topk_gumbel_add_keyed(float* logits, int64_t ld, int64_t M, int32_t col0, int64_t ncols, const float* tau,
+                              int64_t tau_rows, const int32_t* seed_words, int32_t col_mul, int32_t col_add,
+                              const int32_t* noise_rows, void* stream) {
+  return gumbel_add("arx_topk_gumbel_add_keyed", logits, ld, M, col0, ncols, tau, tau_rows, seed_words, col_mul,
+                    col_add, noise_rows, stream);
+}
+
 int arx_topk_gumbel_strip(float* values, int64_t ldv, const int32_t* indices, int64_t ldi, int64_t B, int k,
                           const float* tau, int64_t tau_rows, const int32_t* seed_words, void* stream) {
-  ARX_CHECK_ARG(values && indices && tau && seed_words, "arx_topk_gumbel_strip: null pointer");
-  ARX_CHECK_ARG(B >= 0 && k > 0 && tau_rows > 0 && (B <= 1 || (ldv >= k && ldi >= k)),
-                "arx_topk_gumbel_strip: need B >= 0, k > 0, tau_rows > 0, ldv >= k, ldi >= k");
-  ARX_CHECK_ARG(ceil_div(B * k, (int64_t)256) <= 0x7fffffff, "arx_topk_gumbel_strip: too many entries");
+  return gumbel_strip("arx_topk_gumbel_strip", values, ldv, indices, ldi, B, k, tau, tau_rows, seed_words, 1, 0,
+                      nullptr, stream);
+}
+
+int arx_topk_gumbel_strip_keyed(float* values, int64_t ldv, const int32_t* indices, int64_t ldi, int64_t B, int k,
+                                const float* tau, int64_t tau_rows, const int32_t* seed_words, int32_t col_mul,
+                                int32_t col_add, const int32_t* noise_rows, void* stream) {
+  return gumbel_strip("arx_topk_gumbel_strip_keyed", values, ldv, indices, ldi, B, k, tau, tau_rows, seed_words,
+                      col_mul, col_add, noise_rows, stream);
+}
+
+int arx_picks_to_shard(const int32_t* ids, int64_t ldi, int64_t B, int k, int W, int s, int32_t* cols, int64_t ldc,
+                       void* stream) {
+  ARX_CHECK_ARG(ids && cols, "arx_picks_to_shard: null pointer");
+  ARX_CHECK_ARG(B >= 0 && k >= 1 && ldi >= k && ldc >= k, "arx_picks_to_shard: need B >= 0, k >= 1, ldi >= k, ldc >= k");
+  ARX_CHECK_ARG(W >= 1 && s >= 0 && s < W, "arx_picks_to_shard: need W >= 1 and 0 <= s < W");
   if (B == 0) return ARX_OK;
-  k_topk_gumbel_strip<<<(int)ceil_div(B * k, (int64_t)256), 256, 0, as_stream(stream)>>>(values, ldv, indices, ldi, B, k,
-                                                                                       tau, tau_rows, seed_words);
+  const int64_t blocks = ceil_div(B * k, (int64_t)256);
+  k_picks_to_shard<<<(int)(blocks < 65536 ? blocks : 65536), 256, 0, as_stream(stream)>>>(ids, ldi, B, k, W, s, cols,
+                                                                                            ldc);
   ARX_CHECK_LAUNCH();
   return ARX_OK;
 }

@@ -1174,4 +1174,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_sample.h"
 #include "arx_slate_sample.h"
 #include "arx_sample_logp.h"
+#include "arx_sample_shard.h"
 #endif /* ARX_H_ */

@@ -1,6 +1,6 @@
 """ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
-include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h, include/arx_slate_sample.h and
-include/arx_sample_logp.h).
+include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h, include/arx_slate_sample.h,
+include/arx_sample_logp.h, include/arx_sample_shard.h and include/arx_list_logp.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -295,6 +295,13 @@ SAMPLE_SHARD_PROTOTYPES = {
                                              i64, cint, f32p, i64, f32p, i64, vp]),
 }
 
+# include/arx_list_logp.h (list_logprob: the propensity of a GIVEN ordered list under the sampling policy), one-to-one
+LIST_LOGP_PROTOTYPES = {
+    "arx_list_logp_prepare": (cint, [i32p, i64, i64, cint, i64, i32p, i64, i32p, i32p, i32p, i32p, i32p, i64, i32p, i64,
+                                     i32p, i64, i32p, i32p, i64, vp]),
+    "arx_list_logp_stamp": (cint, [i32p, i64, f32p, i64, i64, cint, i32p, i64, f32p, i64, f32p, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -309,7 +316,8 @@ def _load():
     for name, (res, args) in (list(PROTOTYPES.items()) + list(TAGS_PROTOTYPES.items())
                               + list(SLATE_PROTOTYPES.items()) + list(DIVERSE_PROTOTYPES.items())
                               + list(SAMPLE_PROTOTYPES.items()) + list(SLATE_SAMPLE_PROTOTYPES.items())
-                              + list(SAMPLE_LOGP_PROTOTYPES.items()) + list(SAMPLE_SHARD_PROTOTYPES.items())):
+                              + list(SAMPLE_LOGP_PROTOTYPES.items()) + list(SAMPLE_SHARD_PROTOTYPES.items())
+                              + list(LIST_LOGP_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

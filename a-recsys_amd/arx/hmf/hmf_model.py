@@ -16,6 +16,7 @@ import torch
 from .. import graph as G
 from .. import ops
 from .. import slate
+from .. import topk as _topk
 from ..attributes import embed_attribute
 from ..topk import (StreamTopK, TopK, TopKScan, check_return_logprob, excluding_twin, recommend_key,  # noqa: F401
                     recommend_node, run_complete)                                                  # (re-exported)
@@ -257,6 +258,7 @@ class LatentProductModel(object):
         for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample', 'recommend_ex_sample_logp',
                     'recommend_ex_tags_sample_logp'):
             self._plans.pop(key, None)
+        _topk.drop_list_logp_plans(self, '_ex')
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
     def prepare_item_tags(self, tags):
@@ -266,6 +268,7 @@ class LatentProductModel(object):
         for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample',
                     'recommend_tags_sample_logp', 'recommend_ex_tags_sample_logp'):
             self._plans.pop(key, None)
+        _topk.drop_list_logp_plans(self, '_tags')
         self.att_emb.prepare_item_tags(tags)
 
     def _recommend_node(self, key):
@@ -331,6 +334,33 @@ class LatentProductModel(object):
         return slate.score_items(self, lambda: self._feed(user_input, None, True, self.loss_function, None, None, True),
                                  candidates, k, diversify, max_per_group, sample_temperature, sample_seed,
                                  return_logprob)
+
+    def list_logprob(self, user_input, lists, sample_temperature, exclude_seen=False, tags_any=None, tags_all=None,
+                     return_values=False, return_why=False):
+        """How likely would THIS model have been to show THESE items in THIS order: the log-probability of a given
+        ordered list under the policy of step(recommend=True, sample_temperature=) -- the numerator of an importance
+        weight whose denominator return_logprob=True logged at serving time (arx_list_logp.h).  One full batch of
+        users (the rules of step(recommend=True), dropout off); lists [batch_size, k]: logit indices, the space
+        recommend returns -- a list, a numpy array or a device tensor; k is read from the shape, 1 <= k <= 1024, not
+        tied to top_N_items; -1 is an empty slot.  sample_temperature: a number > 0 or one per row.  exclude_seen /
+        tags_any / tags_all: the filters of the policy, as in step().  Returns float32 [mb, k] numpy: logprob[r][t]
+        is the log-probability of entry t given the DRAWABLE entries before it; 0 at a -1; -inf at an entry the
+        policy could never draw (out of range, excluded, outside the tags, a repeat of an earlier entry, a score of
+        -inf) -- such an entry is ABSENT for the others, and the row sum, the log-probability of the whole ordered
+        list, is -inf.  A list this policy drew itself gives back the bits return_logprob=True reported with it.
+        return_values / return_why: the tuple (logprob[, values][, why]) -- values float32 the model's scores of the
+        drawable entries (-inf elsewhere), why int32 the reason codes 0 OK, 1 EMPTY, 2 RANGE, 3 EXCLUDED, 4 TAGS,
+        5 REPEAT, 6 NOSCORE.  Nothing is drawn: there is no seed.  ValueError, before any feed: k outside [1, 1024],
+        a wrong row count, a temperature that is not finite and > 0 (0: a deterministic policy has no propensities --
+        compare the list with recommend()), exclude_seen / tags without their prepare_*; NotImplementedError for
+        output_feat 2 / 3.  One plan per (filters, k); the temperatures, tag words and lists are fed per call:
+            ids, logged = old.step(None, users, None, recommend=True, sample_temperature=0.7, return_logprob=True)
+            target = new.list_logprob(users, ids, 0.7)
+            w = arx.utils.ope.list_weights(target, logged); value = arx.utils.ope.snips(rewards, w)"""
+        return _topk.list_logprob(self, lambda: self._feed(user_input, None, True, self.loss_function, None, None,
+                                                           True),
+                                  lists, sample_temperature, exclude_seen, tags_any, tags_all, return_values,
+                                  return_why)
 
     def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
         """'bpr' / 'bpr-hinge': the items a DRAWN negative must not hit, per user -- typically the training history:

@@ -1700,6 +1700,40 @@ def sample_logp_finish(indices, pick_score, m_part, s_part, P, sample, logp, val
          _p(values), _ld(values) if values is not None else 0, _stream())
 
 
+def list_logp_prepare(lists, V, ex, tags, clean, why, pk_cols, pk_slot):
+    """A foreign list made fit for the mass pass (arx_list_logp.h): lists int32 [B, k] of logit indices in [0, V), -1 an
+    empty slot, anything else allowed; ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None; tags:
+    (col_tags [V] by ABSOLUTE column, want_any, want_all, want_rows) or None.  clean int32 [B, k]: the column where the
+    entry may still be drawn, else -1; why int32 [B, k]: the reason codes 0-5; pk_cols / pk_slot int32 [B, k]: what
+    sample_logp_sort writes for `clean`."""
+    for t, n in ((lists, 'lists'), (clean, 'clean'), (why, 'why'), (pk_cols, 'pk_cols'), (pk_slot, 'pk_slot')):
+        _chk(t, torch.int32, n)
+    if lists.dim() != 2 or any(tuple(t.shape) != tuple(lists.shape) for t in (clean, why, pk_cols, pk_slot)) \
+            or pk_slot.stride(0) != pk_cols.stride(0):
+        raise ValueError("list_logp_prepare: lists, clean, why, pk_cols, pk_slot [B, k], the two sorted lists with one "
+                         "leading dimension")
+    col_tags, want_any, want_all, want_rows = tags if tags is not None else (None, None, None, 0)
+    if tags is not None and int(col_tags.shape[0]) < int(V):
+        raise ValueError("list_logp_prepare: %d tag words for %d columns" % (int(col_tags.shape[0]), int(V)))
+    keys, key_rows, ptr, cols = ex if ex is not None else (None, 0, None, None)
+    call("arx_list_logp_prepare", _p(lists), _ld(lists), int(lists.shape[0]), int(lists.shape[1]), int(V), _p(keys),
+         int(key_rows), _p(ptr), _p(cols), _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _p(clean),
+         _ld(clean), _p(why), _ld(why), _p(pk_cols), _p(pk_slot), _ld(pk_cols), _stream())
+
+
+def list_logp_stamp(clean, pick_score, why, logp, values=None):
+    """After sample_logp_finish on `clean` (arx_list_logp.h): why = 6 where a clean entry's score came out -inf, then
+    logp (and values, optional) = -inf at every entry of code >= 2.  All [B, k]."""
+    _chk(clean, torch.int32, 'clean'); _chk(why, torch.int32, 'why'); _chk(pick_score, torch.float32, 'pick_score')
+    _chk(logp, torch.float32, 'logp'); _chk(values, torch.float32, 'values')
+    if clean.dim() != 2 or any(tuple(t.shape) != tuple(clean.shape) for t in (pick_score, why, logp)) \
+            or (values is not None and values.shape != clean.shape):
+        raise ValueError("list_logp_stamp: clean, pick_score, why, logp and values [B, k]")
+    call("arx_list_logp_stamp", _p(clean), _ld(clean), _p(pick_score), _ld(pick_score), int(clean.shape[0]),
+         int(clean.shape[1]), _p(why), _ld(why), _p(logp), _ld(logp), _p(values),
+         _ld(values) if values is not None else 0, _stream())
+
+
 def picks_to_shard(ids, W, s, cols):
     """cols[r, j] = ids[r, j] // W where the global id ids[r, j] >= 0 belongs to shard s of W (id % W == s), else -1
     (arx_sample_shard.h).  ids / cols int32 [B, k]."""

@@ -11,6 +11,8 @@ exp(score / tau), one after the other without replacement (Plackett-Luce), in SE
 fmaf(tau, g, score), g the Gumbel noise of arx_sample.h, a pure function of (seed, row % tau_rows, column), so the dense,
 the chunked and the fused path draw the same sample.  The values are the winners' SCORES again (arx_topk_gumbel_strip),
 not monotone along a row.  What a temperature and a seed may be: sample_params.
+The propensity of a GIVEN ordered list under that policy (arx_list_logp.h): TopKScan.list_logp / dense_list_logp, the
+node ListLogp and the body of the models' list_logprob (check_lists, list_taus, list_logp_key, list_logprob).
 """
 from __future__ import annotations
 
@@ -95,6 +97,17 @@ class TopK(G.Node):
         elif sample is not None:
             ops.topk_gumbel_strip(self.value, self.indices, sample)
 
+    def list_logp(self, lists, sample, logp, values, why):
+        """The log-probability of GIVEN lists int32 [rows, k] (any k in [1, 1024]) under this node's policy -- its
+        logits as they stand, its exclusion lists and tags, the temperatures of `sample` (dense_list_logp,
+        arx_list_logp.h).  The logits are filled with -inf at the ineligible columns, as forward() fills them."""
+        own = self.__dict__.setdefault('_llb', {})
+        k = int(lists.shape[1])
+        if k not in own:
+            own[k] = ListLogpBuffers(self.inputs[0].shape[0], k, self.rt.device)
+        dense_list_logp(self.inputs[0].value, lists, self.exclude() if self.exclude is not None else None,
+                        self.tags() if callable(self.tags) else self.tags, sample, own[k], logp, values, why)
+
 
 class LogpBuffers(object):
     """What the mass pass of the sampled recommend's propensities keeps per request row (arx_sample_logp.h): the picks
@@ -117,6 +130,29 @@ class LogpBuffers(object):
             self._parts = (torch.empty((B, P), dtype=torch.float32, device=dev),
                            torch.empty((B, P), dtype=torch.float32, device=dev))
         return self._parts
+
+
+class ListLogpBuffers(LogpBuffers):
+    """LogpBuffers of a GIVEN list (arx_list_logp.h): also `clean` [B, k], the list with the entries the policy could
+    not draw taken out -- what the mass pass and the finish read as the picks."""
+
+    def __init__(self, B, k, device):
+        super().__init__(B, k, device)
+        self.clean = torch.empty((B, k), dtype=torch.int32, device=device)
+
+
+def dense_list_logp(x, lists, ex, tags, sample, lb, logp, values, why):
+    """TopKScan.list_logp over materialised logits x [B, V]: the excluded and the tag-ineligible columns are set to -inf
+    IN x (nothing after this may read them as scores), then prepare, one rest_mass_chunk over [0, V), the unchanged
+    finish and stamp.  lb: the ListLogpBuffers of (B, k)."""
+    if ex is not None:
+        ops.topk_exclude_fill(x, 0, ex)
+    if tags is not None:
+        ops.topk_tags_fill(x, 0, tags)
+    ops.list_logp_prepare(lists, x.shape[1], ex, tags, lb.clean, why, lb.pk_cols, lb.pk_slot)
+    ops.rest_mass_chunk(x, 0, sample, lb.picks, True, lb.m_run, lb.s_run, lb.pick_score)
+    ops.sample_logp_finish(lb.clean, lb.pick_score, lb.m_run, lb.s_run, 1, sample, logp, values)
+    ops.list_logp_stamp(lb.clean, lb.pick_score, why, logp, values)
 
 
 class TopKScan(object):
@@ -333,13 +369,15 @@ class TopKScan(object):
         m_part, s_part, P = self.mass_pass(latent, pool, bias, ws, indices, ex, tags, sample, streaming, lb)
         ops.sample_logp_finish(indices, lb.pick_score, m_part, s_part, P, sample, logp, values)
 
-    def mass_pass(self, latent, pool, bias, ws, cols, ex, tags, sample, streaming, lb):
+    def mass_pass(self, latent, pool, bias, ws, cols, ex, tags, sample, streaming, lb, presorted=False):
         """REST's mass per row -- the eligible columns that are not among the row's picks `cols` [B, k] (columns of
         this pool, -1: none) -- from one streaming scan, or chunk by chunk through the logits buffer (GEMM, exclusion
         fill, tags fill, rest_mass_chunk); the picks' scores go to lb.pick_score on the way.  lb: the LogpBuffers of
-        (B, k).  Returns (m_part, s_part, P): [B, P] parts, or the running pairs [B] with P = 1."""
+        (B, k).  presorted: lb.pk_cols / lb.pk_slot already hold the picks sorted (ops.list_logp_prepare wrote them):
+        no sort launch.  Returns (m_part, s_part, P): [B, P] parts, or the running pairs [B] with P = 1."""
         V = pool.shape[0]
-        ops.sample_logp_sort(cols, lb.pk_cols, lb.pk_slot)
+        if not presorted:
+            ops.sample_logp_sort(cols, lb.pk_cols, lb.pk_slot)
         if streaming:
             P = ops.gemm_nt_topk_parts(self._rows, V)
             m_part, s_part = lb.parts(P)
@@ -361,6 +399,29 @@ class TopKScan(object):
         """Whether mass_pass over this pool may take the streaming form: where run() takes the fused one."""
         return bool(self.fused and pool.shape[0] > self.chunk and pool.stride(0) % 4 == 0
                     and latent.stride(0) % 4 == 0)
+
+    def list_logp(self, latent, pool, bias, ws, lists, ex, tags, sample, logp, values, why, lb=None):
+        """The log-probability of GIVEN lists under the sampling policy (arx_list_logp.h): lists int32 [B, k] of
+        columns of this pool -- any k in [1, 1024], not tied to self.k; -1 an empty slot; anything else may stand
+        there.  prepare (the entries the policy could not draw are taken out and coded in `why`), the mass pass over
+        what is left (streaming where mass_streams says so, chunk by chunk otherwise; chunked() forces that), the
+        unchanged finish, stamp.  logp / values float32 and why int32 [B, k]: logp 0 at -1, -inf at the codes 2-6;
+        values the scores of the drawable entries, -inf elsewhere (may be None).  sample: (tau [tau_rows], tau_rows,
+        ...), every tau > 0 (the callers check it on the host).  lb: the ListLogpBuffers of (B, k) (None: this scan's
+        own, kept per k)."""
+        k = int(lists.shape[1])
+        if tags is not None and int(tags[0].shape[0]) != pool.shape[0]:
+            raise ValueError("TopKScan.list_logp: %d tag words for %d pool rows" % (int(tags[0].shape[0]), pool.shape[0]))
+        if lb is None:
+            own = self.__dict__.setdefault('_llb', {})
+            lb = own.get(k)
+            if lb is None:
+                lb = own[k] = ListLogpBuffers(self._rows, k, self._dev)
+        ops.list_logp_prepare(lists, pool.shape[0], ex, tags, lb.clean, why, lb.pk_cols, lb.pk_slot)
+        m_part, s_part, P = self.mass_pass(latent, pool, bias, ws, lb.clean, ex, tags, sample,
+                                           self.mass_streams(latent, pool), lb, presorted=True)
+        ops.sample_logp_finish(lb.clean, lb.pick_score, m_part, s_part, P, sample, logp, values)
+        ops.list_logp_stamp(lb.clean, lb.pick_score, why, logp, values)
 
 
 class StreamTopK(G.Node, TopKScan):
@@ -448,6 +509,158 @@ def recommend_key(exclude_seen, tagged, sampled=False, logp=False):
         raise ValueError("recommend_key: log-probabilities belong to the sampled recommend")
     return 'recommend' + ('_ex' if exclude_seen else '') + ('_tags' if tagged else '') + \
         ('_sample' if sampled else '') + ('_logp' if logp else '')
+
+
+def list_logp_key(exclude_seen, tagged):
+    """The plans of list_logprob, beside recommend_key's: 'list_logp', 'list_logp_ex', 'list_logp_tags' or
+    'list_logp_ex_tags' -- a model keeps one per (that name, k)."""
+    return 'list_logp' + ('_ex' if exclude_seen else '') + ('_tags' if tagged else '')
+
+
+MAX_LIST_PLANS = 8      # (list_logp_key, k) plans a model keeps; the oldest goes first
+
+
+class ListLogp(G.Node):
+    """value = logp float32 [rows, k]: the log-probability of the GIVEN lists under the sampling policy of the
+    recommend node `source` (arx_list_logp.h) -- with self.values float32 (the scores of the drawable entries, -inf
+    elsewhere) and self.why int32 (the reason codes).  source: a StreamTopK (this node scores its latent against its
+    pool through the scan's mass pass: TopKScan.list_logp, the chunk buffer is the scan's) or a TopK (over its
+    materialised logits: dense_list_logp).  The node owns the list placeholder self.lists (rows * k ids, row-major),
+    its ListLogpBuffers and its outputs; exclude / tags / sample: callables giving the device arguments
+    (EmbeddingAttribute.exclusion_args / tag_args / sample_args) or None.  tau, the tag words and the lists are
+    placeholders read by the kernels: a captured plan replays with new values."""
+
+    def __init__(self, rt, source, k, exclude=None, tags=None, sample=None):
+        rows = int(source.shape[0])
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError("ListLogp: need 1 <= k <= 1024, got %d" % k)
+        if sample is None:
+            raise ValueError("ListLogp: needs sample (the temperatures)")
+        self.scan = source if isinstance(source, StreamTopK) else None
+        if self.scan is None and type(source) is not TopK:
+            raise NotImplementedError("ListLogp: no list log-probabilities for a %s node" % type(source).__name__)
+        self.lists = G.IdsInput(rt, rows * k, 'list_logp_%d' % k)
+        super().__init__(rt, (rows, k), tuple(source.inputs) + (self.lists,))
+        self.k, self.exclude, self.tags, self.sample = k, exclude, tags, sample
+        self.values = torch.empty((rows, k), dtype=torch.float32, device=rt.device)
+        self.why = torch.empty((rows, k), dtype=torch.int32, device=rt.device)
+        self._lb = ListLogpBuffers(rows, k, rt.device)
+        self.own_nodes = (self.lists, self)
+
+    def forward(self, train):
+        lists = self.lists.value.view(self.shape)
+        ex = self.exclude() if self.exclude is not None else None
+        tags = self.tags() if self.tags is not None else None
+        sample = self.sample()
+        logp = self.alloc_value()
+        if self.scan is None:
+            dense_list_logp(self.inputs[0].value, lists, ex, tags, sample, self._lb, logp, self.values, self.why)
+        else:
+            latent, pool = self.inputs[0], self.inputs[1]
+            self.scan.list_logp(latent.value, pool.value, pool.bias_value, self.rt.ws, lists, ex, tags, sample, logp,
+                                self.values, self.why, lb=self._lb)
+
+
+def check_lists(lists, rows, what='list_logprob'):
+    """lists -> ([rows, k] int32 on the host, or a contiguous int32 device tensor), k.  Accepts a list, an integer
+    array or an integer tensor [rows, k] with 1 <= k <= 1024; an id that does not fit int32 is clamped to the nearest
+    int32 (it stays out of range: the kernel codes it RANGE).  ValueError for floats, bools, a wrong rank, a wrong
+    row count or a k outside [1, 1024]."""
+    lo, hi = -2 ** 31, 2 ** 31 - 1
+    if isinstance(lists, torch.Tensor):
+        if lists.dtype in (torch.bool,) or lists.is_floating_point() or lists.is_complex():
+            raise ValueError("%s: lists must hold integers, got %s" % (what, lists.dtype))
+        shape = tuple(lists.shape)
+        a = lists
+    else:
+        a = np.asarray(lists)
+        if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("%s: lists must hold integers, got %s" % (what, a.dtype))
+        shape = tuple(a.shape)
+    if len(shape) != 2 or shape[0] != rows:
+        raise ValueError("%s: lists must be [%d, k], got shape %s" % (what, rows, shape))
+    k = int(shape[1])
+    if not 1 <= k <= 1024:
+        raise ValueError("%s: need 1 <= k <= 1024 entries per list, got %d" % (what, k))
+    if isinstance(a, torch.Tensor):
+        if a.dtype != torch.int32:
+            a = a.clamp(lo, hi).to(torch.int32)
+        return a.contiguous(), k
+    if a.dtype != np.int32:
+        a = np.clip(a, lo, hi) if a.dtype.kind == 'i' else np.minimum(a, hi)
+    return np.ascontiguousarray(a.astype(np.int32)), k
+
+
+def list_taus(temperature, rows, what='list_logprob'):
+    """The temperatures of one list_logprob call as float32 [rows]: a number or one per row (sample_params' checks),
+    every one > 0 as float32 -- ValueError naming the first row of temperature 0: a deterministic policy has no
+    propensities (compare the list with recommend() instead)."""
+    tau, _ = sample_params(temperature, 0, rows)
+    zero = np.nonzero(tau <= 0)[0]
+    if len(zero):
+        raise ValueError("%s: sample_temperature must be > 0 (row %d has %r): a deterministic policy has no "
+                         "propensities -- compare the list with recommend() instead" % (what, int(zero[0]),
+                                                                                       float(tau[zero[0]])))
+    return tau
+
+
+def drop_list_logp_plans(model, part):
+    """Drop the list_logprob plans of `model` whose key names `part` ('_ex' / '_tags'): they captured the arrays a
+    prepare_recommend_exclusions / prepare_item_tags call is about to replace."""
+    for key in [q for q in model._plans if isinstance(q, tuple) and str(q[0]).startswith('list_logp') and part in q[0]]:
+        _drop_list_plan(model, key)
+
+
+def _drop_list_plan(model, key):
+    for n in model._plans.pop(key).fetch[0].own_nodes:
+        model.rt.nodes.remove(n)
+
+
+def list_logprob(model, feed, lists, sample_temperature, exclude_seen=False, tags_any=None, tags_all=None,
+                 return_values=False, return_why=False):
+    """The body of LatentProductModel.list_logprob / LinearSeq.list_logprob.  model: has rt, _plans, output (the
+    full-vocabulary logits node), topk (its recommend node), att_emb, batch_size; feed(): feeds the request's user
+    (and context) placeholders as a recommend step does.  Every check runs before any feed.  One plan per
+    (list_logp_key, k), at most MAX_LIST_PLANS of them; tau, the tag words and the lists are fed per call.  Returns
+    logprob float32 [mb, k] numpy, or the tuple (logprob[, values][, why])."""
+    what = 'list_logprob'
+    if type(model.output) is not G.Prediction:
+        raise NotImplementedError("list_logprob: output_feat 2 / 3 pool the token SCORES of an item -- there is no "
+                                  "item latent pool to take the lists' propensities against")
+    rows = model.batch_size
+    a, k = check_lists(lists, rows, what)
+    tau = list_taus(sample_temperature, rows, what)
+    m = model.att_emb
+    if exclude_seen:
+        m.exclusion_args()                     # ValueError when nothing was prepared
+    tagged = tags_any is not None or tags_all is not None
+    if tagged:
+        m.tag_args()
+        tag_words(tags_any, tags_all, rows, what)
+    key = (list_logp_key(exclude_seen, tagged), k)
+    entry = model._plans.get(key)
+    if entry is None:
+        mine = [q for q in model._plans if isinstance(q, tuple) and str(q[0]).startswith('list_logp')]
+        for old in mine[:max(0, len(mine) - (MAX_LIST_PLANS - 1))]:
+            _drop_list_plan(model, old)
+        node = ListLogp(model.rt, model.topk, k, m.exclusion_args if exclude_seen else None,
+                        m.tag_args if tagged else None, m.sample_args)
+        entry = model._plans[key] = G.Plan(model.rt, [node], False, [])
+    node = entry.fetch[0]
+    feed()
+    if tagged:
+        m.feed_tag_words(tags_any, tags_all, what)
+    m.sample_args()
+    m._sample_tau.feed(tau)
+    node.lists.feed(a.reshape(-1))
+    entry.run()
+    out = [node.value.cpu().numpy()]
+    if return_values:
+        out.append(node.values.cpu().numpy())
+    if return_why:
+        out.append(node.why.cpu().numpy())
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 def check_return_logprob(return_logprob, recommend, sample_temperature):

@@ -23,6 +23,7 @@ import torch
 from .. import graph as G
 from .. import ops
 from .. import slate
+from .. import topk as _topk
 from ..attributes import embed_attribute
 from ..attributes.embed_attribute import Dropout
 from ..hmf.hmf_model import _Op, _Var
@@ -178,6 +179,7 @@ class LinearSeq(object):
         for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample', 'recommend_ex_sample_logp',
                     'recommend_ex_tags_sample_logp'):
             self._plans.pop(key, None)
+        _topk.drop_list_logp_plans(self, '_ex')
         self.att_emb.prepare_recommend_exclusions(item_sets)
 
     def prepare_item_tags(self, tags):
@@ -186,6 +188,7 @@ class LinearSeq(object):
         for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample',
                     'recommend_tags_sample_logp', 'recommend_ex_tags_sample_logp'):
             self._plans.pop(key, None)
+        _topk.drop_list_logp_plans(self, '_tags')
         self.att_emb.prepare_item_tags(tags)
 
     def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536,
@@ -226,6 +229,20 @@ class LinearSeq(object):
             self.att_emb.add_input({}, user_input, item_input, recommend=True, loss=self.loss_function)
         return slate.score_items(self, feed, candidates, k, diversify, max_per_group, sample_temperature, sample_seed,
                                  return_logprob)
+
+    def list_logprob(self, user_input, item_input, lists, sample_temperature, exclude_seen=False, tags_any=None,
+                     tags_all=None, return_values=False, return_why=False):
+        """The log-probability of the given ordered lists [batch_size, k] (logit indices, -1 an empty slot) under the
+        policy of step(recommend=True, sample_temperature=) for one full batch (user_input and the [n_input][mb]
+        context item_input): float32 [mb, k] numpy, 0 at a -1, -inf at an entry the policy could never draw; with
+        return_values / return_why the tuple (logprob[, values][, why]).  LatentProductModel.list_logprob states the
+        rule, the reason codes and the errors (arx_list_logp.h); output_feat 2 / 3: NotImplementedError.
+            ids, logged = model.step(None, users, context, recommend=True, sample_temperature=0.7, return_logprob=True)
+            target = other.list_logprob(users, context, ids, 0.7)"""
+        def feed():
+            self.att_emb.add_input({}, user_input, item_input, recommend=True, loss=self.loss_function)
+        return _topk.list_logprob(self, feed, lists, sample_temperature, exclude_seen, tags_any, tags_all,
+                                  return_values, return_why)
 
     def _plan(self, key):
         if key not in self._plans:

@@ -1175,4 +1175,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_slate_sample.h"
 #include "arx_sample_logp.h"
 #include "arx_sample_shard.h"
+#include "arx_list_logp.h"
 #endif /* ARX_H_ */

@@ -1,6 +1,6 @@
 """ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
 include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h, include/arx_slate_sample.h,
-include/arx_sample_logp.h, include/arx_sample_shard.h and include/arx_list_logp.h).
+include/arx_sample_logp.h, include/arx_sample_shard.h, include/arx_list_logp.h and include/arx_list_logp_shard.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -303,6 +303,14 @@ LIST_LOGP_PROTOTYPES = {
 }
 
 
+# include/arx_list_logp_shard.h (list_logprob on the row-sharded models: the per-shard prepare and the owner's merge)
+LIST_LOGP_SHARD_PROTOTYPES = {
+    "arx_list_logp_prepare_shard": (cint, [i32p, i64, i64, cint, i64, cint, cint, i32p, i64, i32p, i32p, i32p, i32p, i32p,
+                                           i64, i32p, i64, i32p, i64, i32p, i32p, i64, vp]),
+    "arx_list_logp_merge_shards": (cint, [i32p, i64, i64, cint, i64, i32p, i64, i64, cint, i32p, i64, i32p, i64, vp]),
+}
+
+
 class ArxError(RuntimeError):
     pass
 
@@ -317,7 +325,7 @@ def _load():
                               + list(SLATE_PROTOTYPES.items()) + list(DIVERSE_PROTOTYPES.items())
                               + list(SAMPLE_PROTOTYPES.items()) + list(SLATE_SAMPLE_PROTOTYPES.items())
                               + list(SAMPLE_LOGP_PROTOTYPES.items()) + list(SAMPLE_SHARD_PROTOTYPES.items())
-                              + list(LIST_LOGP_PROTOTYPES.items())):
+                              + list(LIST_LOGP_PROTOTYPES.items()) + list(LIST_LOGP_SHARD_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -43,8 +43,8 @@ import torch.distributed as dist
 
 from . import ops as _ops
 from . import slate as _slate
-from .topk import (LogpBuffers, TopKScan, check_return_logprob, no_return_logprob, run_complete, sample_params,
-                   similar_scan, tag_words)
+from .topk import (LogpBuffers, TopKScan, check_lists, check_return_logprob, list_taus, no_return_logprob,
+                   run_complete, sample_params, similar_scan, tag_words)
 from .utils.prepare_train import pair_draw_tables
 
 
@@ -361,29 +361,63 @@ class HipBackend(object):
             return self.ops.gemm_nt_topk_parts(B, V)
         return 1
 
-    def shard_rest_mass(self, U, E, bias, ex, picks, world, shard, sample, packed, P_max, tags=None):
-        """The propensities' local stage (arx_sample_logp.h's mass pass over ONE shard): picks [B, k] GLOBAL ids in
-        selection order -> this shard's columns (arx_picks_to_shard), REST's mass of the shard's rows per request row,
-        and the scores of the picks the shard owns.  packed float32 [B, 2 P_max + k]: columns [0, P_max) the m parts,
-        [P_max, 2 P_max) the S parts -- past this shard's own parts the empty mass (-FLT_MAX, 0) --, the rest the pick
-        scores, -inf where the shard does not own the pick."""
-        ops = self.ops
-        B, V, d, k = int(U.shape[0]), int(E.shape[0]), int(U.shape[1]), int(picks.shape[1])
-        ops.fill_f32(packed[:, :P_max], -3.4028234663852886e38)
-        ops.fill_f32(packed[:, P_max:2 * P_max], 0.0)
-        ops.fill_f32(packed[:, 2 * P_max:], float('-inf'))
-        if V == 0 or B == 0:
-            return
-        if getattr(self, 'ws_rec', None) is None:
-            self.ws_rec, self._scans = ops.Workspace(U.device), {}
+    def _mass_bufs_of(self, B, k, device):
+        """The mass pass's buffers of (B, k): (LogpBuffers, the picks as this shard's columns [B, k])."""
         lbs = self.__dict__.setdefault('_mass_bufs', {})
         lb = lbs.get((B, k))
         if lb is None:
             if len(lbs) > 8:
                 lbs.clear()
-            lb = lbs[(B, k)] = (LogpBuffers(B, k, U.device), torch.empty((B, k), dtype=torch.int32, device=U.device))
-        lb, cols = lb
-        ops.picks_to_shard(picks, world, shard, cols)
+            lb = lbs[(B, k)] = (LogpBuffers(B, k, device), torch.empty((B, k), dtype=torch.int32, device=device))
+        return lb
+
+    def shard_list_prepare(self, lists, n_items, world, shard, V, ex, tags, codes):
+        """list_logprob's per-shard prepare (arx_list_logp_prepare_shard): lists [B, k] GLOBAL ids of ANY origin -> the
+        reason codes this shard can give (codes int32 [B, k]; may be a view into the packed exchange buffer), and the
+        surviving owned entries as this shard's sorted picks, in the buffers shard_rest_mass(prepared=) reads -- in
+        place of arx_picks_to_shard + arx_sample_logp_sort.  V: the shard's rows; ex / tags: as shard_rest_mass takes
+        them.  Returns the handle for shard_rest_mass(prepared=)."""
+        B, k = int(lists.shape[0]), int(lists.shape[1])
+        if V == 0 or B == 0:
+            if B:
+                codes.zero_()                          # (no entry in range is this shard's: nothing to say)
+            return None
+        lb, cols = self._mass_bufs_of(B, k, lists.device)
+        self.ops.list_logp_prepare_shard(lists, n_items, world, shard, ex, tags, cols, codes, lb.pk_cols, lb.pk_slot)
+        return lb, cols
+
+    def list_logp_merge_shards(self, lists, n_items, codes, clean, why):
+        """The owner's merge of list_logprob (arx_list_logp_merge_shards): lists [B_loc, k] global ids, codes
+        [W, B_loc, k] -> why and the global clean list the finish reads."""
+        self.ops.list_logp_merge_shards(lists, n_items, codes, clean, why)
+
+    def list_logp_stamp(self, clean, values, why, logp):
+        """After the finish over `clean`: NOSCORE where a clean entry's score (the finish's values) came out -inf, then
+        logp = value = -inf at every code >= 2 (arx_list_logp_stamp)."""
+        self.ops.list_logp_stamp(clean, values, why, logp, values)
+
+    def shard_rest_mass(self, U, E, bias, ex, picks, world, shard, sample, packed, P_max, tags=None, prepared=None):
+        """The propensities' local stage (arx_sample_logp.h's mass pass over ONE shard): picks [B, k] GLOBAL ids in
+        selection order -> this shard's columns (arx_picks_to_shard), REST's mass of the shard's rows per request row,
+        and the scores of the picks the shard owns.  packed float32 [B, 2 P_max + k]: columns [0, P_max) the m parts,
+        [P_max, 2 P_max) the S parts -- past this shard's own parts the empty mass (-FLT_MAX, 0) --, the rest the pick
+        scores, -inf where the shard does not own the pick.  prepared (list_logprob): the handle of shard_list_prepare
+        over `picks` -- the shard's columns and their sorted form are already in place, everything after is shared."""
+        ops = self.ops
+        B, V, d, k = int(U.shape[0]), int(E.shape[0]), int(U.shape[1]), int(picks.shape[1])
+        # (column blocks of the packed rows are strided views: filled as views, not as runs of numel() words)
+        packed[:, :P_max].fill_(-3.4028234663852886e38)
+        packed[:, P_max:2 * P_max].fill_(0.0)
+        packed[:, 2 * P_max:].fill_(float('-inf'))
+        if V == 0 or B == 0:
+            return
+        if getattr(self, 'ws_rec', None) is None:
+            self.ws_rec, self._scans = ops.Workspace(U.device), {}
+        if prepared is None:
+            lb, cols = self._mass_bufs_of(B, k, U.device)
+            ops.picks_to_shard(picks, world, shard, cols)
+        else:
+            lb, cols = prepared
         key = (B, V, d, 'mass')
         scan = self._scans.get(key)
         if scan is None:
@@ -391,7 +425,8 @@ class HipBackend(object):
             scan.fused = scan.fused and int(E.shape[1]) == d
         streaming = scan.mass_streams(U, E) and self.shard_mass_parts(B, V, d) > 1
         ops.fill_f32(lb.pick_score, float('-inf'))
-        m, sp, P = scan.mass_pass(U, E, bias, self.ws_rec, cols, ex, tags, sample, streaming, lb)
+        m, sp, P = scan.mass_pass(U, E, bias, self.ws_rec, cols, ex, tags, sample, streaming, lb,
+                                  presorted=prepared is not None)
         if P > P_max:
             raise RuntimeError("shard_rest_mass: %d parts for rows of %d" % (P, P_max))
         packed[:, :P].copy_(m if m.dim() == 2 else m.view(B, 1))
@@ -404,8 +439,10 @@ class HipBackend(object):
 
     def sample_logp_finish_shards(self, indices, recv, P_max, sample, logp, values):
         """logp / exact values [B_loc, k] of the picks `indices` (global ids in selection order) from the W packed
-        slabs recv [W, B_loc, 2 P_max + k] of shard_rest_mass (arx_sample_logp_finish_shards)."""
-        self.ops.sample_logp_finish_shards(indices, recv[:, :, 2 * P_max:], recv[:, :, :P_max],
+        slabs recv [W, B_loc, >= 2 P_max + k] of shard_rest_mass (arx_sample_logp_finish_shards; list_logprob's rows
+        carry k more words behind the pick scores)."""
+        k = int(indices.shape[1])
+        self.ops.sample_logp_finish_shards(indices, recv[:, :, 2 * P_max:2 * P_max + k], recv[:, :, :P_max],
                                            recv[:, :, P_max:2 * P_max], P_max, sample, logp, values)
 
     sim_chunk = 65536       # first-chunk width of shard_similar's TopKScan (tests narrow it to reach the fused kernel)
@@ -1621,7 +1658,12 @@ class ShardedHMF(object):
             ((out[2][:n].clone(),) if return_logprob else ())
         return res if len(res) > 1 else ids
 
-    def _recommend(self, u, k, exclude_seen, tags=None, sample=None):
+    def _gather_request(self, u, exclude_seen, tags=None, sample=None):
+        """The request of a full-vocabulary serving call on every rank (recommend, recommend_sampled, list_logprob):
+        this rank's latents and keys (padding rows: zeros, key -1), its temperatures as bits with the two seed words
+        (padding rows: 0) and its tag words (padding rows: 0) are all_gathered; the buffers are kept on the model.
+        tags: (any, all) host words or None; sample: (tau, seed words) on the host or None.  Returns (keys_loc, U_all,
+        keys_all, ex, the backend's tags tuple or None, the backend's sample tuple or None, tau_all, seed_dev)."""
         be, W, B_loc, B, d = self.be, self.world, self.B_loc, self.B, self.d
         dev, f32, i32 = self.device, torch.float32, torch.int32
         n = len(u)
@@ -1632,12 +1674,6 @@ class ShardedHMF(object):
                                          torch.empty((B, d), dtype=f32, device=dev)))
             self._rec_k = {}
         keys_loc, U_loc, keys_all, U_all = self._rec_lat
-        bk = self._rec_k.get(k)
-        if bk is None:
-            e = lambda dt, *sh: torch.empty(sh, dtype=dt, device=dev)
-            bk = self._rec_k[k] = (e(f32, B, k), e(i32, B, k), e(f32, W, B_loc, k), e(i32, W, B_loc, k),
-                                   e(f32, B_loc, k), e(i32, B_loc, k))
-        out_v, out_i, recv_v, recv_c, vo, io = bk
         kh = np.full(B_loc, -1, dtype=np.int32)
         kh[:n] = u
         keys_loc.copy_(torch.from_numpy(kh))
@@ -1648,12 +1684,11 @@ class ShardedHMF(object):
             dist.all_gather_into_tensor(U_all, U_loc, group=self.group)
             dist.all_gather_into_tensor(keys_all, keys_loc, group=self.group)
         ex = (keys_all, B, self._rec_ex[0], self._rec_ex[1]) if exclude_seen else None
-        ni = self.ni_loc
-        more, smp = {}, None
+        smp = tau_all = seed_dev = btags = None
         if sample is not None:
             # this rank's temperatures (as bits; padding rows: 0) and the two seed words -> every rank in ONE buffer;
             # `sample=` goes to the backend only here, as `tags=` does
-            tau_h, seed_h, want_logp = sample
+            tau_h, seed_h = sample
             if getattr(self, '_rec_smp', None) is None:
                 loc = torch.zeros((B_loc + 2,), dtype=i32, device=dev)
                 self._rec_smp = (loc, loc if W == 1 else torch.empty((W * (B_loc + 2),), dtype=i32, device=dev),
@@ -1672,7 +1707,6 @@ class ShardedHMF(object):
             tau_all.view(W, B_loc).copy_(g[:, :B_loc].view(f32))
             seed_dev.copy_(g[0, B_loc:])
             smp = (tau_all, B, seed_dev, W, self.rank, keys_all)
-            more['sample'] = smp
         if tags is not None:
             # the request words of this rank's users (padding rows: no constraint) -> every rank, like the keys;
             # `tags=` goes to the backend only here, so one that does not know the argument serves the plain calls
@@ -1688,7 +1722,27 @@ class ShardedHMF(object):
             if W > 1:
                 dist.all_gather_into_tensor(any_all, any_loc, group=self.group)
                 dist.all_gather_into_tensor(all_all, all_loc, group=self.group)
-            more['tags'] = (self._rec_tags[:ni], any_all, all_all, B)
+            btags = (self._rec_tags[:self.ni_loc], any_all, all_all, B)
+        return keys_loc, U_all, keys_all, ex, btags, smp, tau_all, seed_dev
+
+    def _recommend(self, u, k, exclude_seen, tags=None, sample=None):
+        be, W, B_loc, B, d = self.be, self.world, self.B_loc, self.B, self.d
+        dev, f32, i32 = self.device, torch.float32, torch.int32
+        want_logp = sample is not None and sample[2]
+        keys_loc, U_all, keys_all, ex, btags, smp, tau_all, seed_dev = self._gather_request(
+            u, exclude_seen, tags, sample[:2] if sample is not None else None)
+        bk = self._rec_k.get(k)
+        if bk is None:
+            e = lambda dt, *sh: torch.empty(sh, dtype=dt, device=dev)
+            bk = self._rec_k[k] = (e(f32, B, k), e(i32, B, k), e(f32, W, B_loc, k), e(i32, W, B_loc, k),
+                                   e(f32, B_loc, k), e(i32, B_loc, k))
+        out_v, out_i, recv_v, recv_c, vo, io = bk
+        ni = self.ni_loc
+        more = {}
+        if smp is not None:
+            more['sample'] = smp
+        if btags is not None:
+            more['tags'] = btags
         be.shard_topk(U_all, self.E_item[:ni], self.b_item[:ni], k, ex, out_v, out_i, **more)
         if W == 1:
             recv_v, recv_c = out_v.view(1, B, k), out_i.view(1, B, k)
@@ -1725,6 +1779,107 @@ class ShardedHMF(object):
             _all_to_all(recv_p.view(B, 2 * P_max + k), packed, group=self.group)
         be.sample_logp_finish_shards(io, recv_p, P_max, own, lp, vo)
         return vo, io, lp
+
+    # ------------------------------------------------------------- list_logprob
+    def list_logprob(self, users, lists, sample_temperature, exclude_seen=False, tags_any=None, tags_all=None,
+                     return_values=False, return_why=False):
+        """The log-probability of GIVEN ordered lists under recommend_sampled's policy at sample_temperature -- the
+        numerator of the importance weight whose denominator recommend_sampled(return_logprob=True) logged
+        (arx.utils.ope), over the user's whole eligible vocabulary ACROSS the shards.  A collective with
+        recommend_sampled's calling rules: every rank calls it with the same k = lists.shape[1] (1 <= k <= 1024, tied to
+        nothing else) and exclude_seen, and all with or all without tags; users: global ids this rank owns,
+        0 <= len(users) <= B_loc (the count may differ between ranks); lists [len(users), k]: GLOBAL item ids of any
+        origin (topk.check_lists), -1 an empty slot; sample_temperature: one number or one per user, every one > 0
+        (topk.list_taus).  There is no seed: the noise plays no part in a propensity.  Returns float32 logprob
+        [len(users), k] on the device, or the tuple (logprob[, values][, why]); the semantics are arx_list_logp.h's:
+        logp[r][t] of entry t given the drawable entries before it, 0 at -1, -inf at the reason codes 2-6 (such an
+        entry is ABSENT for the others), so the row sum is -inf exactly when the policy cannot produce the list;
+        values: the exact bits of the owner shard's scorer, -inf elsewhere; why int32: the codes.  A list
+        recommend_sampled(return_logprob=True) drew itself comes back with its logged logprob and values bit for bit.
+        Every check runs before any collective.
+
+          gather / all_gather   latents, keys, tau bits, tag words as recommend_sampled; + the lists [B_loc, k] -> [B, k]
+                                (padding rows: -1)
+          (local)               arx_list_logp_prepare_shard: the codes this shard can give (the exclusion lists and the
+                                tag words live with the item's owner), its surviving entries as sorted picks; then the
+                                rest-mass pass of recommend_sampled over them (no arx_picks_to_shard, no sort)
+          all_to_all            ONE packed float buffer [B, 2 P_max + 2 k] -> owners: m parts, S parts, pick scores and
+                                the k codes, which travel as int32 BITS in the same buffer (it is viewed as int32 where
+                                they are written and where they are read; the exchange moves bytes)
+          (local)               arx_list_logp_merge_shards (why, the global clean list), then
+                                arx_sample_logp_finish_shards over the clean list and arx_list_logp_stamp
+
+        Eager, on the model's stream, as recommend is; its buffers are its own, per (k, P_max)."""
+        what = 'list_logprob'
+        W, r = self.world, self.rank
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        u = u.astype(np.int64).reshape(-1)
+        if len(u) > self.B_loc:
+            raise ValueError("%s: at most B_loc = %d users per call and rank" % (what, self.B_loc))
+        if len(u) and (u.min() < 0 or u.max() >= self.n_users or np.any(u % W != r)):
+            raise ValueError("%s: users must be global ids in [0, %d) owned by rank %d" % (what, self.n_users, r))
+        a, k = check_lists(lists, len(u), what)
+        tau = list_taus(sample_temperature, len(u), what)
+        if not len(u) and np.ndim(sample_temperature) == 0:
+            list_taus(sample_temperature, 1, what)      # (a rank without users refuses the number the others refuse)
+        if exclude_seen and getattr(self, '_rec_ex', None) is None:
+            raise ValueError("exclude_seen=True needs prepare_recommend_exclusions() first")
+        words = None
+        if tags_any is not None or tags_all is not None:
+            if getattr(self, '_rec_tags', None) is None:
+                raise ValueError("tags_any / tags_all need prepare_item_tags() first")
+            words = tag_words(tags_any, tags_all, len(u), what)
+        with _ops.joined(self._stream if self.use_graphs else None):
+            lp, vals, why = self._list_logprob(u, a, k, tau, exclude_seen, words)
+        n = len(u)
+        res = (lp[:n].clone(),) + ((vals[:n].clone(),) if return_values else ()) + \
+            ((why[:n].clone(),) if return_why else ())
+        return res if len(res) > 1 else res[0]
+
+    def _list_logprob(self, u, lists, k, tau, exclude_seen, tags):
+        be, W, B_loc, B, d = self.be, self.world, self.B_loc, self.B, self.d
+        dev, f32, i32 = self.device, torch.float32, torch.int32
+        n = len(u)
+        keys_loc, U_all, keys_all, ex, btags, smp, tau_all, seed_dev = self._gather_request(
+            u, exclude_seen, tags, (tau, np.zeros(2, dtype=np.int32)))
+        P_max = max(be.shard_mass_parts(B, len(range(s, self.n_items, W)), d) for s in range(W))
+        lk = self.__dict__.setdefault('_list_bufs', {})
+        bl = lk.get((k, P_max))
+        if bl is None:
+            if len(lk) > 8:
+                lk.clear()
+            wd = 2 * P_max + 2 * k
+            e = lambda dt, *sh: torch.empty(sh, dtype=dt, device=dev)
+            lists_loc = e(i32, B_loc, k)
+            bl = lk[(k, P_max)] = (lists_loc, lists_loc if W == 1 else e(i32, B, k), e(f32, B, wd),
+                                   None if W == 1 else e(f32, W, B_loc, wd), e(i32, B_loc, k), e(i32, B_loc, k),
+                                   e(f32, B_loc, k), e(f32, B_loc, k))
+        lists_loc, lists_all, packed, recv_p, clean, why, lp, vals = bl
+        wd = 2 * P_max + 2 * k
+        if isinstance(lists, torch.Tensor):
+            lists_loc[:n].copy_(lists)
+        elif n:
+            lists_loc[:n].copy_(torch.from_numpy(lists))
+        if n < B_loc:
+            lists_loc[n:].fill_(-1)
+        if W > 1:
+            dist.all_gather_into_tensor(lists_all, lists_loc, group=self.group)
+        ni = self.ni_loc
+        prepared = be.shard_list_prepare(lists_all, self.n_items, W, self.rank, ni, ex, btags,
+                                         packed.view(i32)[:, 2 * P_max + k:])
+        kw = {'tags': btags} if btags is not None else {}
+        be.shard_rest_mass(U_all, self.E_item[:ni], self.b_item[:ni], ex, lists_all, W, self.rank, smp,
+                           packed[:, :2 * P_max + k], P_max, prepared=prepared, **kw)
+        if W == 1:
+            recv_p = packed.view(1, B, wd)
+        else:
+            _all_to_all(recv_p.view(B, wd), packed, group=self.group)
+        be.list_logp_merge_shards(lists_loc, self.n_items, recv_p.view(i32)[:, :, 2 * P_max + k:], clean, why)
+        r0 = self.rank * B_loc
+        own = (tau_all[r0:r0 + B_loc], B_loc, seed_dev, 1, 0, keys_loc)
+        be.sample_logp_finish_shards(clean, recv_p, P_max, own, lp, vals)
+        be.list_logp_stamp(clean, vals, why, lp)
+        return lp, vals, why
 
     # ------------------------------------------------------------ similar_items
     def similar_items(self, items, k, include_self=False, return_values=False, return_logprob=False):
@@ -2295,6 +2450,17 @@ class ShardedW2V(ShardedHMF):
         finally:
             self._serve_ctx = None
 
+    def list_logprob(self, users, context, lists, sample_temperature, exclude_seen=False, tags_any=None, tags_all=None,
+                     return_values=False, return_why=False):
+        """ShardedHMF.list_logprob over x_test of (users, context): context is [n_input][len(users)], time-major."""
+        u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
+        self._serve_ctx = self._context_array(context, int(u.size), "list_logprob")
+        try:
+            return super().list_logprob(users, lists, sample_temperature, exclude_seen=exclude_seen, tags_any=tags_any,
+                                        tags_all=tags_all, return_values=return_values, return_why=return_why)
+        finally:
+            self._serve_ctx = None
+
     def score_items(self, users, context, candidates, k=None):
         """ShardedHMF.score_items over x_test of (users, context): context is [n_input][len(users)], time-major."""
         u = users.cpu().numpy() if isinstance(users, torch.Tensor) else np.asarray(users)
@@ -2523,6 +2689,11 @@ class ShardedHMFBags(ShardedHMF):
         raise NotImplementedError("%s.recommend_sampled: item latents are bag means -- use "
                                   "item_view().recommend_sampled" % type(self).__name__)
 
+    def list_logprob(self, *args, **kwargs):
+        """Not on the training class either: item_view().list_logprob."""
+        raise NotImplementedError("%s.list_logprob: item latents are bag means -- use "
+                                  "item_view().list_logprob" % type(self).__name__)
+
     def similar_items(self, items, k, include_self=False, return_values=False):
         """ShardedHMF.similar_items over the materialised item latents 1/2 (id row + bag mean): through a serving view
         (item_view()) this model keeps for the purpose -- it refreshes when the model has stepped or been restored."""
@@ -2703,6 +2874,11 @@ class ShardedHMFRepTokens(ShardedHMF):
         raise NotImplementedError("%s.recommend_sampled: item latents are bag means -- use "
                                   "item_view().recommend_sampled" % type(self).__name__)
 
+    def list_logprob(self, *args, **kwargs):
+        """Not on the training class either: item_view().list_logprob."""
+        raise NotImplementedError("%s.list_logprob: item latents are bag means -- use "
+                                  "item_view().list_logprob" % type(self).__name__)
+
     def similar_items(self, items, k, include_self=False, return_values=False):
         """ShardedHMF.similar_items over the materialised item latents 1/2 (id row + bag mean): through a serving view
         (item_view()) this model keeps for the purpose -- it refreshes when the model has stepped or been restored."""
@@ -2799,6 +2975,11 @@ class ShardedHetView(ShardedHMF):
         if self._seen != (self.model.steps, self.model.n_restores):
             self._refresh()
         return super()._recommend(u, k, exclude_seen, tags=tags, sample=sample)
+
+    def _list_logprob(self, u, lists, k, tau, exclude_seen, tags):
+        if self._seen != (self.model.steps, self.model.n_restores):
+            self._refresh()
+        return super()._list_logprob(u, lists, k, tau, exclude_seen, tags)
 
     def _evaluate(self, u, it, loss):
         if self._seen != (self.model.steps, self.model.n_restores):

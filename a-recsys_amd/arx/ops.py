@@ -1734,6 +1734,45 @@ def list_logp_stamp(clean, pick_score, why, logp, values=None):
          _ld(values) if values is not None else 0, _stream())
 
 
+def list_logp_prepare_shard(lists, V_global, W, s, ex, tags, clean, why, pk_cols, pk_slot):
+    """list_logp_prepare on shard s of W (arx_list_logp_shard.h): lists int32 [B, k] of GLOBAL ids; an in-range entry of
+    another shard is no pick (code 0), an owned one is tested as the LOCAL column id // W against ex (local columns) and
+    tags (col_tags of the shard's rows, want_any, want_all, want_rows).  clean: local columns; why: the codes (may be a
+    strided int32 view, e.g. into a packed exchange buffer); pk_cols / pk_slot: what picks_to_shard + sample_logp_sort
+    write for the merged clean list."""
+    for t, n in ((lists, 'lists'), (clean, 'clean'), (why, 'why'), (pk_cols, 'pk_cols'), (pk_slot, 'pk_slot')):
+        _chk(t, torch.int32, n)
+    if lists.dim() != 2 or any(tuple(t.shape) != tuple(lists.shape) for t in (clean, why, pk_cols, pk_slot)) \
+            or pk_slot.stride(0) != pk_cols.stride(0) or any(t.stride(1) != 1 for t in (lists, clean, why, pk_cols)):
+        raise ValueError("list_logp_prepare_shard: lists, clean, why, pk_cols, pk_slot [B, k] with unit stride along a "
+                         "row, the two sorted lists with one leading dimension")
+    col_tags, want_any, want_all, want_rows = tags if tags is not None else (None, None, None, 0)
+    if not 0 <= int(s) < int(W):
+        raise ValueError("list_logp_prepare_shard: need 0 <= s < W")
+    rows = len(range(int(s), int(V_global), int(W)))
+    if tags is not None and int(col_tags.shape[0]) < rows:
+        raise ValueError("list_logp_prepare_shard: %d tag words for the shard's %d rows" % (int(col_tags.shape[0]), rows))
+    keys, key_rows, ptr, cols = ex if ex is not None else (None, 0, None, None)
+    call("arx_list_logp_prepare_shard", _p(lists), _ld(lists), int(lists.shape[0]), int(lists.shape[1]), int(V_global),
+         int(W), int(s), _p(keys), int(key_rows), _p(ptr), _p(cols), _p(col_tags), _p(want_any), _p(want_all),
+         int(want_rows), _p(clean), _ld(clean), _p(why), _ld(why), _p(pk_cols), _p(pk_slot), _ld(pk_cols), _stream())
+
+
+def list_logp_merge_shards(lists, V_global, codes, clean, why):
+    """The owner's merge (arx_list_logp_shard.h): lists int32 [B, k] of GLOBAL ids; codes int32 [W, B, k], shard-major
+    slabs of what list_logp_prepare_shard wrote for these rows (a view into the packed exchange buffer is fine: unit
+    stride along a row) -> why [B, k] (1 at -1, 2 out of range, else the owner shard's code) and clean [B, k] (the id
+    where why is 0, else -1)."""
+    for t, n in ((lists, 'lists'), (codes, 'codes'), (clean, 'clean'), (why, 'why')):
+        _chk(t, torch.int32, n)
+    if lists.dim() != 2 or codes.dim() != 3 or tuple(codes.shape[1:]) != tuple(lists.shape) or codes.stride(2) != 1 \
+            or any(tuple(t.shape) != tuple(lists.shape) or t.stride(1) != 1 for t in (clean, why)) or lists.stride(1) != 1:
+        raise ValueError("list_logp_merge_shards: lists, clean, why [B, k] and codes [W, B, k], unit stride along a row")
+    call("arx_list_logp_merge_shards", _p(lists), _ld(lists), int(lists.shape[0]), int(lists.shape[1]), int(V_global),
+         _p(codes), int(codes.stride(1)), int(codes.stride(0)), int(codes.shape[0]), _p(clean), _ld(clean), _p(why),
+         _ld(why), _stream())
+
+
 def picks_to_shard(ids, W, s, cols):
     """cols[r, j] = ids[r, j] // W where the global id ids[r, j] >= 0 belongs to shard s of W (id % W == s), else -1
     (arx_sample_shard.h).  ids / cols int32 [B, k]."""

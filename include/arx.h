@@ -1176,4 +1176,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_sample_logp.h"
 #include "arx_sample_shard.h"
 #include "arx_list_logp.h"
+#include "arx_list_logp_shard.h"
 #endif /* ARX_H_ */

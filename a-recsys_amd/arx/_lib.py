@@ -1,6 +1,7 @@
 """ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
 include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h, include/arx_slate_sample.h,
-include/arx_sample_logp.h, include/arx_sample_shard.h, include/arx_list_logp.h and include/arx_list_logp_shard.h).
+include/arx_sample_logp.h, include/arx_sample_shard.h, include/arx_list_logp.h, include/arx_list_logp_shard.h and
+include/arx_topk_bf16.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -310,6 +311,14 @@ LIST_LOGP_SHARD_PROTOTYPES = {
     "arx_list_logp_merge_shards": (cint, [i32p, i64, i64, cint, i64, i32p, i64, i64, cint, i32p, i64, i32p, i64, vp]),
 }
 
+# include/arx_topk_bf16.h (recommend(scan_dtype='bf16'): the bf16 filter scan and the exact f32 re-score), one-to-one
+TOPK_BF16_PROTOTYPES = {
+    "arx_rows_bf16_norm": (cint, [f32p, i64, i64, i64, vp, i64, f32p, vp]),
+    "arx_gemm_nt_topk_filter_bf16": (cint, [f32p, i64, i64, vp, i64, f32p, i64, i64, f32, f32p, f32p, i64, i32, f32p,
+                                            i32p, i64, cint, i32p, i32p, i64, i32p, i32p, i32p, i32p, i32p, i64, vp]),
+    "arx_cand_rescore": (cint, [f32p, i64, i64, f32p, i64, f32p, i64, cint, f32p, i32p, i64, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -325,7 +334,8 @@ def _load():
                               + list(SLATE_PROTOTYPES.items()) + list(DIVERSE_PROTOTYPES.items())
                               + list(SAMPLE_PROTOTYPES.items()) + list(SLATE_SAMPLE_PROTOTYPES.items())
                               + list(SAMPLE_LOGP_PROTOTYPES.items()) + list(SAMPLE_SHARD_PROTOTYPES.items())
-                              + list(LIST_LOGP_PROTOTYPES.items()) + list(LIST_LOGP_SHARD_PROTOTYPES.items())):
+                              + list(LIST_LOGP_PROTOTYPES.items()) + list(LIST_LOGP_SHARD_PROTOTYPES.items())
+                              + list(TOPK_BF16_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -23,7 +23,8 @@ import torch
 
 from .. import graph as G
 from .. import ops
-from ..topk import TopKScan, logits_too_big, no_return_logprob, sample_params, similar_scan, tag_words
+from ..topk import (TopKScan, logits_too_big, no_return_logprob, no_scan_dtype, sample_params, similar_scan,
+                    tag_words)
 from ..utils.prepare_train import pair_draw_tables
 
 # the full-vocabulary loss a model trained with a sampled loss evaluates with (hmf_model.py:130,144; 'mce' -> 'ce':
@@ -747,8 +748,9 @@ class EmbeddingAttribute(object):
         self._sample_seed.feed(words)
 
     def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536, output_feat=1,
-                      return_logprob=False):
-        """(return_logprob=True: NotImplementedError -- nothing is drawn here.)
+                      return_logprob=False, scan_dtype=None):
+        """(return_logprob=True: NotImplementedError -- nothing is drawn here; scan_dtype='bf16': NotImplementedError --
+        the bf16 filter scan of recommend has no cosine form.)
         Cosine nearest neighbours of items over the full vocabulary, in the latent space recommend scores against:
         the rows of _pool_embed('full', output_feat) -- the id row of an id-only model, the mean of the id row and the
         attribute bags for HET / MIX items; the bias plays no part.  logit_ids: the items asked about, logit indices in
@@ -760,6 +762,7 @@ class EmbeddingAttribute(object):
         recomputed (topk.similar_scan); buffers are this method's own, cached per (len(ids), k).  chunk: the width of
         TopKScan's first chunk.  output_feat 2 / 3 score each token of a bag: there is no item latent to compare."""
         no_return_logprob("similar_items", return_logprob)
+        no_scan_dtype("similar_items", scan_dtype)
         if output_feat not in (0, 1):
             raise NotImplementedError("similar_items: output_feat 2 / 3 pool the token SCORES of an item -- there is "
                                       "no item latent pool to take cosines in")

@@ -18,8 +18,8 @@ from .. import ops
 from .. import slate
 from .. import topk as _topk
 from ..attributes import embed_attribute
-from ..topk import (StreamTopK, TopK, TopKScan, check_return_logprob, excluding_twin, recommend_key,  # noqa: F401
-                    recommend_node, run_complete)                                                  # (re-exported)
+from ..topk import (StreamTopK, TopK, TopKScan, check_return_logprob, check_scan_dtype,       # noqa: F401
+                    excluding_twin, recommend_key, recommend_node, run_complete)                   # (re-exported)
 from ..utils.checkpoint import Saver
 
 
@@ -256,7 +256,7 @@ class LatentProductModel(object):
         {user_index: items} or a (ptr, items) CSR pair in item-index space (EmbeddingAttribute.
         prepare_recommend_exclusions).  A second call replaces the lists (the captured plan is dropped)."""
         for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample', 'recommend_ex_sample_logp',
-                    'recommend_ex_tags_sample_logp'):
+                    'recommend_ex_tags_sample_logp', 'recommend_ex_bf16', 'recommend_ex_tags_bf16'):
             self._plans.pop(key, None)
         _topk.drop_list_logp_plans(self, '_ex')
         self.att_emb.prepare_recommend_exclusions(item_sets)
@@ -266,12 +266,20 @@ class LatentProductModel(object):
         {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces the words
         (the captured plans that read them are dropped)."""
         for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample',
-                    'recommend_tags_sample_logp', 'recommend_ex_tags_sample_logp'):
+                    'recommend_tags_sample_logp', 'recommend_ex_tags_sample_logp', 'recommend_tags_bf16',
+                    'recommend_ex_tags_bf16'):
             self._plans.pop(key, None)
         _topk.drop_list_logp_plans(self, '_tags')
         self.att_emb.prepare_item_tags(tags)
 
+    def _scan_bf16(self, scan_dtype, recommend, sample_temperature, return_logprob):
+        """topk.check_scan_dtype; True only where the recommend node streams (a dense top-k has no scan to speed up)."""
+        return check_scan_dtype(scan_dtype, recommend, sample_temperature, return_logprob) and \
+            isinstance(self.topk, StreamTopK)
+
     def _recommend_node(self, key):
+        if key.endswith('_bf16'):
+            return getattr(self, '_bf16_nodes', {}).get(key)
         if key.endswith('_sample') or key.endswith('_sample_logp'):
             return getattr(self, '_sample_nodes', {}).get(key)
         return {'recommend': self.topk, 'recommend_ex': getattr(self, 'topk_ex', None),
@@ -279,11 +287,11 @@ class LatentProductModel(object):
                 'recommend_ex_tags': getattr(self, 'topk_ex_tags', None)}[key]
 
     def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536,
-                      return_logprob=False):
+                      return_logprob=False, scan_dtype=None):
         """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the item latent space
         recommend scores against: EmbeddingAttribute.similar_items."""
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
-                                          return_logprob=return_logprob,
+                                          return_logprob=return_logprob, scan_dtype=scan_dtype,
                                           chunk=chunk)
 
     def prepare_item_groups(self, groups):
@@ -409,6 +417,19 @@ class LatentProductModel(object):
             p = G.Plan(rt, [self.topk_ex_tags], False, [])
         elif key == 'warp_eval':
             p = G.Plan(rt, [self.batch_loss], False, [m.mask['warp_eval']])
+        elif key.startswith('recommend') and key.endswith('_bf16'):
+            # the twins whose fused scan filters in bf16 (topk.recommend_key; scan_dtype='bf16'): the same filters, a
+            # node and a plan of their own beside the f32 ones
+            ex, tg = '_ex' in key, '_tags' in key
+            if ex:
+                m.exclusion_args()
+            if tg:
+                m.tag_args()
+            nodes = self.__dict__.setdefault('_bf16_nodes', {})
+            if key not in nodes:
+                nodes[key] = excluding_twin(rt, self.topk, m.exclusion_args if ex else None,
+                                            m.tag_args if tg else None, scan_bf16=True)
+            p = G.Plan(rt, [nodes[key]], False, [])
         elif key.startswith('recommend') and (key.endswith('_sample') or key.endswith('_sample_logp')):
             # the sampled twins (topk.recommend_key): the same filters, the keys of m.sample_args; '_logp': the twin
             # that also runs the mass pass (node.logp: the log-probability of every draw)
@@ -505,7 +526,8 @@ class LatentProductModel(object):
     def step_async(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
                    item_sampled_id2idx=None, forward_only=False, recommend=False,
                    recommend_new=False, loss=None, run_op=None, run_meta=None, exclude_seen=False,
-                   tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None, return_logprob=False):
+                   tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None, return_logprob=False,
+                   scan_dtype=None):
         """step() without the device->host read of the result: returns the MeanLoss
         node (call .read() for the device scalar) / the top-k index tensor.  recommend with the streaming top-k
         (StreamTopK, fused form): the result is complete only if `self.topk.overflowed()` is False afterwards
@@ -516,10 +538,12 @@ class LatentProductModel(object):
         of prepare_item_tags -- plans 'recommend_tags' / 'recommend_ex_tags'; both None: the calls above.
         sample_temperature / sample_seed (with recommend): the sampled recommend of step() -- the plans ending in
         '_sample'; None: the calls above.  return_logprob (with sample_temperature): the plans ending in
-        '_sample_logp' -- returns (indices, logprob), the two device tensors [mb, top_N]."""
+        '_sample_logp' -- returns (indices, logprob), the two device tensors [mb, top_N].
+        scan_dtype='bf16' (with recommend): the plans ending in '_bf16' (step() states the rules)."""
         if loss is None:
             loss = self.loss_function
         check_return_logprob(return_logprob, recommend, sample_temperature)
+        bf16 = self._scan_bf16(scan_dtype, recommend, sample_temperature, return_logprob)
         if exclude_seen and recommend:
             self.att_emb.exclusion_args()      # ValueError before any feed when nothing was prepared
         tagged = recommend and (tags_any is not None or tags_all is not None)
@@ -541,8 +565,8 @@ class LatentProductModel(object):
             if draw:
                 self.rt.drop_feed(self.att_emb.i_indices['neg'].value)    # (a queued older feed must not overwrite the draw)
             self.batch_loss.draw = self.att_emb.neg_draw if draw else None
-        if tagged or sampled:
-            key = recommend_key(exclude_seen, tagged, sampled, bool(return_logprob))
+        if tagged or sampled or bf16:
+            key = recommend_key(exclude_seen, tagged, sampled, bool(return_logprob), bf16)
             self._plan(key).run()
             node = self._recommend_node(key)
             return (node.indices, node.logp) if return_logprob else node.indices
@@ -570,7 +594,7 @@ class LatentProductModel(object):
     def step(self, session, user_input, item_input, neg_item_input=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
              loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None,
-             sample_temperature=None, sample_seed=None, return_logprob=False):
+             sample_temperature=None, sample_seed=None, return_logprob=False, scan_dtype=None):
         """hmf_model.py:162-228.  Returns: train -> mean loss (float); forward_only ->
         loss_eval (float); recommend -> int32 [mb, top_N]; warp_eval -> [loss, rank].
         'bpr' / 'bpr-hinge': neg_item_input (list, array or device tensor) holds one negative item per row; None or
@@ -592,8 +616,15 @@ class LatentProductModel(object):
         temperature) over the row's whole eligible vocabulary (arx_sample_logp.h); the row sum is the log-propensity
         of the ordered list; 0 for a temperature-0 row and beside an id -1.  The ids are those of the call without it
         (a drawn item of score -inf -- a row with fewer than top_N finite scores -- is not eligible: -1 stands there).
-        ValueError without sample_temperature or without recommend."""
+        ValueError without sample_temperature or without recommend.
+        recommend with scan_dtype='bf16' (None / 'f32': the calls above, untouched): where the recommend streams, the
+        scan past the first chunk of the vocabulary multiplies on the bf16 matrix pipe as a FILTER widened by a proven
+        error bound, and what passes is re-scored in f32 (arx_topk_bf16.h) -- the ids are the top_N by (f32 score desc,
+        logit index asc), as without it.  Composes with exclude_seen and the tags; NotImplementedError with
+        sample_temperature or return_logprob.  Where the recommend does not stream (a small vocabulary) or the fused
+        scan does not apply (a width other than 32 / 64 / 128) the call is the f32 one."""
         check_return_logprob(return_logprob, recommend, sample_temperature)
+        bf16 = self._scan_bf16(scan_dtype, recommend, sample_temperature, return_logprob)
         sampled = recommend and sample_temperature is not None
         if sampled:
             # resolved once here: the chunked re-run after a candidate overflow must draw the same sample
@@ -602,11 +633,11 @@ class LatentProductModel(object):
                                       item_sampled_id2idx, forward_only, recommend, recommend_new, loss,
                                       run_op, run_meta, exclude_seen=exclude_seen, tags_any=tags_any,
                                       tags_all=tags_all, sample_temperature=sample_temperature,
-                                      sample_seed=sample_seed, return_logprob=return_logprob)
+                                      sample_seed=sample_seed, return_logprob=return_logprob, scan_dtype=scan_dtype)
         if recommend:
             # (a candidate list of the fused top-k too short for this batch: the request once more, chunked)
             key = recommend_key(exclude_seen, tags_any is not None or tags_all is not None, sampled,
-                                bool(return_logprob))
+                                bool(return_logprob), bf16)
             self._plan(key)                    # builds the twin node / raises as the step would
             node = self._recommend_node(key)
             out = run_complete(node, run, lambda: self._plans.pop(key, None))

@@ -23,7 +23,7 @@ from .. import graph as G
 from .. import ops
 from ..attributes.embed_attribute import Dropout, ZeroEmbed
 from ..hmf.hmf_model import _Op, _Var
-from ..topk import (StreamTopK, excluding_twin, logits_too_big, no_return_logprob, recommend_key,
+from ..topk import (StreamTopK, excluding_twin, logits_too_big, no_return_logprob, no_scan_dtype, recommend_key,
                     run_complete)
 from ..utils.checkpoint import Saver
 from .batching import SeqBatching
@@ -848,7 +848,8 @@ class SeqModel(SeqBatching):
                                           chunk=chunk, output_feat=self.output_feat)
 
     def step_recommend(self, session, user_input, item_inputs, positions, bucket_id, exclude_seen=False,
-                       tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None, return_logprob=False):
+                       tags_any=None, tags_all=None, sample_temperature=None, sample_seed=None, return_logprob=False,
+                       scan_dtype=None):
         """seqModel.py:326-353 -> [(uid, values[topk_n], indexes[topk_n])]: the top-k softmax
         values / logit indexes at time position positions[i] of sequence i.  Small vocabularies: the full
         [L*mb, V] logits are materialised; past ARX_STREAM_TOPK_BYTES (1 GB) the mb rows asked for are gathered
@@ -864,8 +865,11 @@ class SeqModel(SeqBatching):
         items DRAWN with probability proportional to exp(logit / temperature), in selection order
         (LatentProductModel.step states the rules); a value is still exp(logit - lse) with lse over the full
         vocabulary: the item's softmax probability at temperature 1, whatever the temperature was.
-        return_logprob=True: NotImplementedError (the rows are [L * B] and the values softmax at temperature 1)."""
+        return_logprob=True: NotImplementedError (the rows are [L * B] and the values softmax at temperature 1).
+        scan_dtype='bf16': NotImplementedError (the log-sum-exp of the values must stay exact over ALL the columns: the
+        bf16 filter scan of LatentProductModel.step scores only what may reach the top-k)."""
         no_return_logprob("SeqModel.step_recommend", return_logprob)
+        no_scan_dtype("SeqModel.step_recommend", scan_dtype)
         dp = self.rt.dp
         tagged = tags_any is not None or tags_all is not None
         drawn = sample_temperature is not None

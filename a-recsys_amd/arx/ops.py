@@ -1326,6 +1326,52 @@ def gemm_nt_topk_filter_tags(A, Bm, col_bias, thr, col_base, cand_v, cand_i, cap
          _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _stream())
 
 
+def rows_bf16_norm(P, img, norms):
+    """img [N, K] bfloat16 = the round-to-nearest-even bf16 of P [N, K] float32, norms [N] = each row's 2-norm rounded
+    UP (arx_topk_bf16.h) -- the image and the column norms gemm_nt_topk_filter_bf16 scans."""
+    _chk(P, torch.float32, 'P')
+    _chk(img, torch.bfloat16, 'img')
+    _chk(norms, torch.float32, 'norms')
+    if P.dim() != 2 or tuple(img.shape) != tuple(P.shape) or norms.dim() != 1 or int(norms.shape[0]) != int(P.shape[0]) \
+            or not norms.is_contiguous():
+        raise ValueError("rows_bf16_norm: P [N, K], img [N, K] and a contiguous norms [N], got %s, %s, %s"
+                         % (tuple(P.shape), tuple(img.shape), tuple(norms.shape)))
+    call("arx_rows_bf16_norm", _p(P), _ld(P), int(P.shape[0]), int(P.shape[1]), _p(img), _ld(img), _p(norms), _stream())
+
+
+def gemm_nt_topk_filter_bf16(A, Bimg, coln, col_bias, thr, col_base, cand_v, cand_i, capp, overflow, coeff, tags=None,
+                             ex=None):
+    """gemm_nt_topk_filter_tags on the bf16 matrix pipe (arx_topk_bf16.h): Bimg [N, K] bfloat16 and coln [N] come from
+    rows_bf16_norm, a logit passes when fmaf(coeff * |A[r]|, coln[c], v~) > thr[r]; cand_v receives the APPROXIMATE v~
+    (cand_rescore overwrites it).  coeff: a float32 >= topk.bf16_margin_coeff(K).  tags: (col_tags, want_any, want_all,
+    want_rows) with col_tags ALREADY sliced to this launch's columns, or None; ex: exclusion lists or None."""
+    _chk(Bimg, torch.bfloat16, 'Bimg')
+    _chk(coln, torch.float32, 'coln')
+    if int(coln.shape[0]) < int(Bimg.shape[0]):
+        raise ValueError("gemm_nt_topk_filter_bf16: %d column norms for %d columns"
+                         % (int(coln.shape[0]), int(Bimg.shape[0])))
+    col_tags, want_any, want_all, want_rows = tags if tags is not None else (None, None, None, 0)
+    if col_tags is not None and int(col_tags.shape[0]) < int(Bimg.shape[0]):
+        raise ValueError("gemm_nt_topk_filter_bf16: %d tag words for %d columns"
+                         % (int(col_tags.shape[0]), int(Bimg.shape[0])))
+    keys, key_rows, ptr, cols = ex if ex is not None else (None, 0, None, None)
+    call("arx_gemm_nt_topk_filter_bf16", _p(A), _ld(A), int(A.shape[0]), _p(Bimg), _ld(Bimg), _p(coln),
+         int(Bimg.shape[0]), int(A.shape[1]), float(coeff), _p(col_bias), _p(thr), int(thr.stride(0)), int(col_base),
+         _p(cand_v), _p(cand_i), int(cand_v.stride(0)), int(capp), _p(overflow), _p(keys), int(key_rows), _p(ptr),
+         _p(cols), _p(col_tags), _p(want_any), _p(want_all), int(want_rows), _stream())
+
+
+def cand_rescore(U, P, pbias, cand_v, cand_i):
+    """cand_v[r, j] = U[r] . P[cand_i[r, j]] + pbias[cand_i[r, j]] in slate_scores' arithmetic for every occupied slot
+    (cand_v != -inf) of the candidate rows, in place (arx_topk_bf16.h); P: the WHOLE pool."""
+    _chk(cand_v, torch.float32, 'cand_v')
+    _chk(cand_i, torch.int32, 'cand_i')
+    if cand_v.dim() != 2 or tuple(cand_i.shape) != tuple(cand_v.shape) or cand_i.stride(0) != cand_v.stride(0):
+        raise ValueError("cand_rescore: cand_v and cand_i are [B, ncand] of one row stride")
+    call("arx_cand_rescore", _p(U), _ld(U), int(U.shape[0]), _p(P), _ld(P), _p(pbias), int(P.shape[0]),
+         int(U.shape[1]), _p(cand_v), _p(cand_i), int(cand_v.stride(0)), int(cand_v.shape[1]), _stream())
+
+
 def sample_keyed(sample):
     """A sample tuple's noise key: (tau, tau_rows, seed_words) is the plain convention of arx_sample.h -- None; three
     more entries (col_mul, col_add, noise_rows int32 [tau_rows] or None) are the keyed one of arx_sample_shard.h --

@@ -13,6 +13,9 @@ the chunked and the fused path draw the same sample.  The values are the winners
 not monotone along a row.  What a temperature and a seed may be: sample_params.
 The propensity of a GIVEN ordered list under that policy (arx_list_logp.h): TopKScan.list_logp / dense_list_logp, the
 node ListLogp and the body of the models' list_logprob (check_lists, list_taus, list_logp_key, list_logprob).
+scan_dtype='bf16' (arx_topk_bf16.h): the fused scan's FILTER multiplies on the bf16 matrix pipe, widened by a proven
+bound of the rounding error (bf16_margin_coeff), and what passes is re-scored in f32 -- ids and values stay those of the
+f32 scores (TopKScan.run(scan_bf16=True); check_scan_dtype, no_scan_dtype: where the option may stand).
 """
 from __future__ import annotations
 
@@ -184,6 +187,16 @@ class TopKScan(object):
         self.overflow = torch.zeros(1, dtype=i32, device=dev)
         self.slack, self.min_capp = 4.0, 32          # candidate segment = slack x the expected survivors, >= min_capp
         self._cand = None
+        self._bf16 = None
+
+    def _bf16_bufs(self, n, d):
+        """The scratch of the bf16 scan, owned by this scan and made at the first call that asks for it: the bf16 image
+        [n, d] of the pool rows past the first chunk (rows of 2 d bytes, 16-byte aligned) and their norms [n] --
+        256 MB + 4 MB at 1 M x 128.  Rewritten by every run: never stale."""
+        if self._bf16 is None or tuple(self._bf16[0].shape) != (n, d):
+            self._bf16 = (torch.empty((n, d), dtype=torch.bfloat16, device=self._dev),
+                          torch.empty(n, dtype=torch.float32, device=self._dev))
+        return self._bf16
 
     def _cand_bufs(self, n0, V):
         """Candidate rows [B, parts * capp]: a column range's expected survivors are k (V - n0) / n0 / parts (scores in
@@ -225,7 +238,7 @@ class TopKScan(object):
             self.fused = was
 
     def run(self, latent, pool, bias, ws, values, indices, ex=None, col_scale=None, self_col=None, tags=None,
-            sample=None, logp=None, strip=True):
+            sample=None, logp=None, strip=True, scan_bf16=False):
         """values / indices [B, k] = the top-k of latent . pool^T + bias (bias may be None) over all V >= k pool rows;
         ex: exclusion lists (row_keys, key_rows, ex_ptr, ex_cols) or None.  ws: the GEMM workspace.
         col_scale [V] (None: every launch is the one above): the scores are (latent . pool^T) * col_scale[column] --
@@ -246,7 +259,17 @@ class TopKScan(object):
         the selection); `values` are then the picks' exact scores.
         A keyed sample -- three more entries (col_mul, col_add, noise_rows), ops.sample_keyed -- feeds the noise other
         rows and columns (arx_sample_shard.h: shard s of W passes (W, s, the rows' user ids)); strip=False returns the
-        winners' KEYS (what a merge across shards compares); not with logp."""
+        winners' KEYS (what a merge across shards compares); not with logp.
+        scan_bf16 (arx_topk_bf16.h): inside the fused form the pool rows past the first chunk are rounded to bf16
+        (rows_bf16_norm, at every run: the pool may be a graph node recomputed per call), the filter runs on the bf16
+        matrix pipe with its test widened by bf16_margin_coeff(d) |latent[r]| |pool[c]| -- no column whose f32 score
+        beats the threshold is lost -- and cand_rescore overwrites every survivor's value with its exact f32 score in
+        slate_scores' arithmetic; select, merge and mark_empty run unchanged.  indices / values: the top-k by (score
+        desc, column asc) of the f32 scores -- the first chunk's from the f32 GEMM, the others' from the re-score.
+        Composes with ex and tags; not with sample, col_scale or want_lse.  Outside the fused form (a width the
+        kernels do not take, misaligned rows, chunked()) the run is the f32 one."""
+        if scan_bf16 and (sample is not None or col_scale is not None or self.want_lse):
+            raise ValueError("TopKScan.run: scan_bf16 goes with no sample, no col_scale and no log-sum-exp")
         if logp is not None and not strip:
             raise ValueError("TopKScan.run: strip=False (the keys) does not go with logp")
         V, k = pool.shape[0], self.k
@@ -289,7 +312,15 @@ class TopKScan(object):
             ops.topk_chunk(lg, k, 0, run_v, run_i)
             ops.fill_f32(cand_v.view(-1), float('-inf'))
             ops.fill_i32(self.overflow, 0)
-            if cos:
+            if scan_bf16:
+                img, coln = self._bf16_bufs(V - n0, int(pool.shape[1]))
+                ops.rows_bf16_norm(pool[n0:], img, coln)
+                ops.gemm_nt_topk_filter_bf16(latent, img, coln, bias[n0:] if bias is not None else None,
+                                             run_v[:, k - 1], n0, cand_v, cand_i, capp, self.overflow,
+                                             bf16_margin_coeff_f32(int(pool.shape[1])),
+                                             tags=(tags[0][n0:],) + tuple(tags[1:]) if tags is not None else None, ex=ex)
+                ops.cand_rescore(latent, pool, bias, cand_v, cand_i)
+            elif cos:
                 ops.gemm_nt_topk_filter_cos(latent, pool[n0:], col_scale[n0:], self_col, run_v[:, k - 1], n0, cand_v,
                                             cand_i, capp, self.overflow)
             elif sample is not None:
@@ -442,16 +473,20 @@ class StreamTopK(G.Node, TopKScan):
     result either (the same two places: -inf fills and the fused GEMM's survivor test).  share: another StreamTopK over the same shapes whose logits chunk buffer
     this one re-uses (plans run one after the other on one stream).  sample (optional): a callable giving (tau,
     tau_rows, seed_words) (EmbeddingAttribute.sample_args), or that tuple: the sampled recommend (TopKScan.run).
-    The algorithm and its buffers: TopKScan."""
+    scan_bf16: the fused scan filters on the bf16 matrix pipe and re-scores in f32 (TopKScan.run(scan_bf16=True)); not
+    with sample or want_lse.  The algorithm and its buffers: TopKScan."""
 
     def __init__(self, rt, latent, pool, k, chunk=65536, want_lse=False, exclude=None, share=None, tags=None,
-                 sample=None, logp=False):
+                 sample=None, logp=False, scan_bf16=False):
         G.Node.__init__(self, rt, (latent.shape[0], k), (latent, pool))
         TopKScan.__init__(self, latent.shape[0], pool.shape[0], latent.shape[1], k, rt.device, chunk=chunk,
                           want_lse=want_lse, share=share)
         self.exclude = exclude
         self.tags = tags
         self.sample = sample
+        if scan_bf16 and (sample is not None or want_lse):
+            raise ValueError("StreamTopK: scan_bf16 goes with no sample and no log-sum-exp")
+        self.scan_bf16 = bool(scan_bf16)
         self.fused = self.fused and pool.shape[1] == latent.shape[1]
         # logp (with sample): self.logp [rows, k], the log-probability of every draw (TopKScan.run(logp=))
         if logp and sample is None:
@@ -464,7 +499,7 @@ class StreamTopK(G.Node, TopKScan):
         tags = self.tags() if callable(self.tags) else self.tags
         sample = self.sample() if callable(self.sample) else self.sample
         self.run(latent.value, pool.value, pool.bias_value, self.rt.ws, self.alloc_value(), self.indices, ex, tags=tags,
-                 sample=sample, logp=self.logp)
+                 sample=sample, logp=self.logp, scan_bf16=self.scan_bf16)
 
 
 def recommend_node(rt, logits, k, rows):
@@ -476,12 +511,15 @@ def recommend_node(rt, logits, k, rows):
     return TopK(rt, logits, k)
 
 
-def excluding_twin(rt, node, exclusion_args=None, tag_args=None, sample_args=None, logp=False):
+def excluding_twin(rt, node, exclusion_args=None, tag_args=None, sample_args=None, logp=False, scan_bf16=False):
     """The twin of a recommend node that leaves columns out -- by the exclusion lists, by the item tags, or by both
     (the plain node and its plan stay as they are); a streaming twin shares the plain node's chunk buffer.
     sample_args: the SAMPLED twin (alone, or on top of either filter); logp: that twin also gives node.logp, the
-    log-probability of every draw."""
-    if exclusion_args is None and tag_args is None and sample_args is None:
+    log-probability of every draw.  scan_bf16: the twin of a STREAMING node whose fused scan filters in bf16 (alone --
+    the plain recommend on the bf16 pipe -- or on top of either filter; not with sample_args)."""
+    if scan_bf16 and (sample_args is not None or not isinstance(node, StreamTopK)):
+        raise ValueError("excluding_twin: scan_bf16 goes with a streaming node and no sample_args")
+    if exclusion_args is None and tag_args is None and sample_args is None and not scan_bf16:
         raise ValueError("excluding_twin: exclusion lists, item tags or both")
     if logp and sample_args is None:
         raise ValueError("excluding_twin: logp goes with sample_args")
@@ -491,6 +529,8 @@ def excluding_twin(rt, node, exclusion_args=None, tag_args=None, sample_args=Non
         more = {} if sample_args is None else {'sample': sample_args}
         if logp:
             more['logp'] = True
+        if scan_bf16:
+            more['scan_bf16'] = True
         return StreamTopK(rt, node.inputs[0], node.inputs[1], node.k, chunk=node.chunk, want_lse=node.want_lse,
                           exclude=exclusion_args, share=node, tags=tag_args, **more)
     if logp:
@@ -502,13 +542,16 @@ def excluding_twin(rt, node, exclusion_args=None, tag_args=None, sample_args=Non
     return type(node)(rt, node.inputs[0], node.k, exclude=exclusion_args, tags=tag_args)
 
 
-def recommend_key(exclude_seen, tagged, sampled=False, logp=False):
+def recommend_key(exclude_seen, tagged, sampled=False, logp=False, bf16=False):
     """The plan of a recommend call: 'recommend', 'recommend_ex', 'recommend_tags' or 'recommend_ex_tags'; the sampled
-    twins end in '_sample', those that also give the draws' log-probabilities in '_sample_logp'."""
+    twins end in '_sample', those that also give the draws' log-probabilities in '_sample_logp'; the twins whose scan
+    filters in bf16 (scan_dtype='bf16') end in '_bf16' -- a plan of their own beside the f32 plan of the same filters."""
     if logp and not sampled:
         raise ValueError("recommend_key: log-probabilities belong to the sampled recommend")
+    if bf16 and sampled:
+        raise ValueError("recommend_key: the bf16 scan does not go with the sampled recommend")
     return 'recommend' + ('_ex' if exclude_seen else '') + ('_tags' if tagged else '') + \
-        ('_sample' if sampled else '') + ('_logp' if logp else '')
+        ('_sample' if sampled else '') + ('_logp' if logp else '') + ('_bf16' if bf16 else '')
 
 
 def list_logp_key(exclude_seen, tagged):
@@ -678,6 +721,59 @@ def no_return_logprob(what, return_logprob):
     if return_logprob:
         raise NotImplementedError("%s: return_logprob is not implemented (LatentProductModel.step and LinearSeq.step "
                                   "give the propensities of recommend(sample_temperature=))" % what)
+
+
+def bf16_margin_coeff(K):
+    """c(K) of the bf16 filter scan (arx_topk_bf16.h; proved in DESIGN.md section 4 item 20): for finite u, p of width
+    K well inside float32's range, with u~, p~ their round-to-nearest-even bf16 images,
+        |(u~ . p~ accumulated in float32) - (u . p computed in float32, slate_scores' order)| <= c(K) |u|_2 |p|_2
+    -- 2^-7 + 2^-16 for the two roundings of every product, (K + 8) 2^-22 for the float32 accumulation of both sums
+    (twice what round-to-nearest needs: an accumulator that truncates is covered) and the slack the norms' and the
+    comparison's own roundings are paid from.  The ONE definition: the device takes it as an argument."""
+    return 2.0 ** -7 * (1.0 + 2.0 ** -9) + (int(K) + 8) * 2.0 ** -22
+
+
+def bf16_margin_coeff_f32(K):
+    """bf16_margin_coeff(K) as the float32 the kernel takes, rounded UP."""
+    c = bf16_margin_coeff(K)
+    f = np.float32(c)
+    if float(f) < c:
+        f = np.nextafter(f, np.float32(np.inf))
+    return float(f)
+
+
+SCAN_DTYPES = (None, 'f32', 'bf16')
+
+
+def check_scan_dtype(scan_dtype, recommend, sample_temperature, return_logprob):
+    """The one rule of scan_dtype on the models -> True for the bf16 scan.  None / 'f32': the scan as it always was.
+    'bf16' (with recommend=True) filters the vocabulary past the first chunk on the bf16 matrix pipe and re-scores
+    what passes in f32 -- the same ids, f32 values.  ValueError (before any feed) for another word or without
+    recommend; NotImplementedError naming the option it does not go with: the Gumbel keys of sample_temperature and
+    the rest-mass pass of return_logprob stay f32."""
+    if scan_dtype not in SCAN_DTYPES:
+        raise ValueError("scan_dtype must be None, 'f32' or 'bf16', got %r" % (scan_dtype,))
+    if scan_dtype != 'bf16':
+        return False
+    if not recommend:
+        raise ValueError("scan_dtype='bf16' goes with recommend=True")
+    if return_logprob:
+        raise NotImplementedError("scan_dtype='bf16' is not implemented with return_logprob: the rest-mass pass of the "
+                                  "propensities stays f32")
+    if sample_temperature is not None:
+        raise NotImplementedError("scan_dtype='bf16' is not implemented with sample_temperature: the Gumbel keys of "
+                                  "the sampled recommend stay f32")
+    return True
+
+
+def no_scan_dtype(what, scan_dtype):
+    """The entries without the bf16 scan (SeqModel.step_recommend: its log-sum-exp must stay exact over ALL the columns;
+    every similar_items: the cosine form): NotImplementedError where it is asked."""
+    if scan_dtype not in SCAN_DTYPES:
+        raise ValueError("scan_dtype must be None, 'f32' or 'bf16', got %r" % (scan_dtype,))
+    if scan_dtype == 'bf16':
+        raise NotImplementedError("%s: scan_dtype='bf16' is not implemented (LatentProductModel.step and "
+                                  "LinearSeq.step take it with recommend=True)" % what)
 
 
 def sample_params(temperature, seed, rows):

@@ -27,7 +27,8 @@ from .. import topk as _topk
 from ..attributes import embed_attribute
 from ..attributes.embed_attribute import Dropout
 from ..hmf.hmf_model import _Op, _Var
-from ..topk import check_return_logprob, excluding_twin, recommend_key, recommend_node, run_complete
+from ..topk import (StreamTopK, check_return_logprob, check_scan_dtype, excluding_twin, recommend_key, recommend_node,
+                    run_complete)
 from ..utils.checkpoint import Saver
 
 
@@ -177,7 +178,7 @@ class LinearSeq(object):
         """The items step(recommend=True, exclude_seen=True) leaves out per user: {user_index: items} or a (ptr, items)
         CSR pair in item-index space (EmbeddingAttribute.prepare_recommend_exclusions).  A second call replaces them."""
         for key in ('recommend_ex', 'recommend_ex_sample', 'recommend_ex_tags_sample', 'recommend_ex_sample_logp',
-                    'recommend_ex_tags_sample_logp'):
+                    'recommend_ex_tags_sample_logp', 'recommend_ex_bf16', 'recommend_ex_tags_bf16'):
             self._plans.pop(key, None)
         _topk.drop_list_logp_plans(self, '_ex')
         self.att_emb.prepare_recommend_exclusions(item_sets)
@@ -186,17 +187,18 @@ class LinearSeq(object):
         """The items' 32-bit tag words for step(recommend=True, tags_any=, tags_all=): an integer array [n_items] or
         {item_index: bit numbers 0..31} (EmbeddingAttribute.prepare_item_tags).  A second call replaces them."""
         for key in ('recommend_tags', 'recommend_ex_tags', 'recommend_tags_sample', 'recommend_ex_tags_sample',
-                    'recommend_tags_sample_logp', 'recommend_ex_tags_sample_logp'):
+                    'recommend_tags_sample_logp', 'recommend_ex_tags_sample_logp', 'recommend_tags_bf16',
+                    'recommend_ex_tags_bf16'):
             self._plans.pop(key, None)
         _topk.drop_list_logp_plans(self, '_tags')
         self.att_emb.prepare_item_tags(tags)
 
     def similar_items(self, logit_ids, k, include_self=False, return_values=False, chunk=65536,
-                      return_logprob=False):
+                      return_logprob=False, scan_dtype=None):
         """Cosine nearest neighbours of items (logit indices) over the full vocabulary, in the OUTPUT item latents the
         model scores against (EmbeddingAttribute.similar_items); output_feat 2 / 3: NotImplementedError."""
         return self.att_emb.similar_items(logit_ids, k, include_self=include_self, return_values=return_values,
-                                          return_logprob=return_logprob,
+                                          return_logprob=return_logprob, scan_dtype=scan_dtype,
                                           chunk=chunk, output_feat=self.output_feat)
 
     def prepare_item_groups(self, groups):
@@ -264,6 +266,12 @@ class LinearSeq(object):
                 if getattr(self, 'topk_ex_tags', None) is None:
                     self.topk_ex_tags = excluding_twin(rt, self.topk, m.exclusion_args, m.tag_args)
                 self._plans[key] = G.Plan(rt, [self.topk_ex_tags], False, [])
+            elif key.endswith('_bf16'):        # the twins whose fused scan filters in bf16 (topk.recommend_key)
+                nodes = self.__dict__.setdefault('_bf16_nodes', {})
+                if key not in nodes:
+                    nodes[key] = excluding_twin(rt, self.topk, m.exclusion_args if '_ex' in key else None,
+                                                m.tag_args if '_tags' in key else None, scan_bf16=True)
+                self._plans[key] = G.Plan(rt, [nodes[key]], False, [])
             elif key.endswith('_sample') or key.endswith('_sample_logp'):   # the sampled twins (topk.recommend_key)
                 nodes = self.__dict__.setdefault('_sample_nodes', {})
                 if key not in nodes:
@@ -279,7 +287,8 @@ class LinearSeq(object):
         """Run the 'recommend' / 'recommend_ex' / 'recommend_tags' / 'recommend_ex_tags' plan; a streaming top-k whose fused candidate lists overflowed runs
         once more on the chunked path (as LatentProductModel.step)."""
         self._plan(key)
-        node = self._sample_nodes[key] if key.endswith('_sample') or key.endswith('_sample_logp') else \
+        node = self._bf16_nodes[key] if key.endswith('_bf16') else \
+               self._sample_nodes[key] if key.endswith('_sample') or key.endswith('_sample_logp') else \
                {'recommend': self.topk, 'recommend_ex': getattr(self, 'topk_ex', None),
                 'recommend_tags': getattr(self, 'topk_tags', None),
                 'recommend_ex_tags': getattr(self, 'topk_ex_tags', None)}[key]
@@ -292,7 +301,7 @@ class LinearSeq(object):
     def step(self, session, user_input, item_input=None, item_output=None, item_sampled=None,
              item_sampled_id2idx=None, forward_only=False, recommend=False, recommend_new=False,
              loss=None, run_op=None, run_meta=None, exclude_seen=False, tags_any=None, tags_all=None,
-             sample_temperature=None, sample_seed=None, return_logprob=False):
+             sample_temperature=None, sample_seed=None, return_logprob=False, scan_dtype=None):
         """linear_seq.py:67-121.  item_input: [n_input][mb] context items (time-major);
         item_output: [mb] target items.  Returns the mean loss (train / forward_only) or the
         top-N logit indices [mb, top_N] (recommend; exclude_seen=True: without each user's items of
@@ -301,7 +310,8 @@ class LinearSeq(object):
         sample_temperature / sample_seed: top_N distinct items DRAWN with probability proportional to
         exp(score / temperature), in selection order; return_logprob=True with it: (ids, logprob float32 [mb, top_N]), the
         log-probability of every draw -- LatentProductModel.step states the rules; ValueError without
-        sample_temperature or without recommend).
+        sample_temperature or without recommend; scan_dtype='bf16': the streaming scan filters on the bf16 matrix
+        pipe and re-scores in f32 -- the same ids; not with sample_temperature / return_logprob).
         'mw' / 'mce': item_sampled (n_sampled item ids) stages a new pool -- the first training step needs one,
         later steps keep it until the next is given (run_w2v.py:315-317); item_sampled_id2idx is the host twin of
         the pool's item -> slot map.  forward_only evaluates 'mw' with the full-vocabulary 'warp' loss and 'mce'
@@ -311,6 +321,8 @@ class LinearSeq(object):
         if recommend_new:
             raise NotImplementedError("indices_test is never built by the reference (linear_seq.py:98)")
         check_return_logprob(return_logprob, recommend, sample_temperature)
+        bf16 = check_scan_dtype(scan_dtype, recommend, sample_temperature, return_logprob) and \
+            isinstance(self.topk, StreamTopK)
         if recommend and exclude_seen:
             m.exclusion_args()                 # ValueError before any feed when nothing was prepared
         tagged = recommend and (tags_any is not None or tags_all is not None)
@@ -337,7 +349,7 @@ class LinearSeq(object):
         for op in update_sampled:              # stage the pool (embed_attribute.py:320-348)
             op()
         if recommend:
-            return self._recommend(recommend_key(exclude_seen, tagged, drawn, bool(return_logprob)))
+            return self._recommend(recommend_key(exclude_seen, tagged, drawn, bool(return_logprob), bf16))
         if forward_only:
             self._plan('eval').run()
             return float(self.loss_test.read().item())

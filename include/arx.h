@@ -1177,4 +1177,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_sample_shard.h"
 #include "arx_list_logp.h"
 #include "arx_list_logp_shard.h"
+#include "arx_topk_bf16.h"
 #endif /* ARX_H_ */

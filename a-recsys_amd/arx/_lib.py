@@ -1,7 +1,7 @@
 """ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
 include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h, include/arx_slate_sample.h,
-include/arx_sample_logp.h, include/arx_sample_shard.h, include/arx_list_logp.h, include/arx_list_logp_shard.h and
-include/arx_topk_bf16.h).
+include/arx_sample_logp.h, include/arx_sample_shard.h, include/arx_list_logp.h, include/arx_list_logp_shard.h,
+include/arx_topk_bf16.h and include/arx_neg_hard.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -319,6 +319,13 @@ TOPK_BF16_PROTOTYPES = {
     "arx_cand_rescore": (cint, [f32p, i64, i64, f32p, i64, f32p, i64, cint, f32p, i32p, i64, i64, vp]),
 }
 
+# include/arx_neg_hard.h (pair losses: the hardest of C drawn negatives, one launch), one-to-one as above
+NEG_HARD_PROTOTYPES = {
+    "arx_neg_draw_hardest": (cint, [i32p, i64, i64, i32p, i32p, vp, vp, i64, i32p, u64, vp, u64, cint,
+                                    f32p, i64, i64, i32p, i64, f32p, i64, i64, f32p, i32p, cint,
+                                    i32p, i32p, i32p, i32p, i64, f32p, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -335,7 +342,7 @@ def _load():
                               + list(SAMPLE_PROTOTYPES.items()) + list(SLATE_SAMPLE_PROTOTYPES.items())
                               + list(SAMPLE_LOGP_PROTOTYPES.items()) + list(SAMPLE_SHARD_PROTOTYPES.items())
                               + list(LIST_LOGP_PROTOTYPES.items()) + list(LIST_LOGP_SHARD_PROTOTYPES.items())
-                              + list(TOPK_BF16_PROTOTYPES.items())):
+                              + list(TOPK_BF16_PROTOTYPES.items()) + list(NEG_HARD_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -799,7 +799,23 @@ class EmbeddingAttribute(object):
         similar_scan(scan, table, rows, vals, idx, self._similar_ws, include_self)
         return (idx.clone(), vals.clone()) if return_values else idx.clone()
 
-    def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
+    def check_hardest_of(self, hardest_of):
+        """The refusals of prepare_pair_negatives(hardest_of=), raised before anything is uploaded or dropped:
+        ValueError unless None or an int in [2, 64]; NotImplementedError where the candidates cannot be scored from
+        one table row per side (arx_neg_draw_hardest)."""
+        if hardest_of is None:
+            return
+        if isinstance(hardest_of, bool) or not isinstance(hardest_of, (int, np.integer)) \
+                or not 2 <= int(hardest_of) <= 64:
+            raise ValueError("prepare_pair_negatives: hardest_of is None or an int in [2, 64], got %r" % (hardest_of,))
+        for side, feats in (('user', self.user_feats), ('item', self.item_feats)):
+            if len(feats) != 1 or feats[0].kind != 'cat':
+                raise NotImplementedError(
+                    "prepare_pair_negatives(hardest_of=): the %s side must be exactly one one-hot feature (it has %s); "
+                    "multi-hot and multi-feature %ss have no single table row to score a candidate against"
+                    % (side, ', '.join(f.kind for f in feats) or 'none', side))
+
+    def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None, hardest_of=None):
         """The items a drawn negative of the pair losses must not hit, per user -- typically the training history:
         {user_index: items} or a (ptr, items) CSR pair in item-index space (the forms of
         prepare_recommend_exclusions).  Uploaded as sorted logit columns together with logit_ind2item_ind; steps
@@ -809,7 +825,17 @@ class EmbeddingAttribute(object):
         (counts + smooth) ** power (arx_neg_draw_weighted; 0.75 is the unigram rule of word2vec) -- counts per ITEM
         index, by default the number of users whose list holds the item; an item with counts + smooth == 0 is never
         drawn.  The two int64 tables of that draw (prepare_train.pair_draw_tables) are built here, once.
-        A second call replaces the lists, the tables and the seed."""
+        hardest_of None: one draw per row.  An int C in [2, 64]: dynamic negative sampling -- a TRAINING step draws C
+        candidates by the rule above (the plain draws at C consecutive counters), scores each against the row's user
+        with the current tables and trains against the one the model ranks highest, all in one launch inside the
+        captured step (arx_neg_draw_hardest; ties go to the earlier candidate, a NaN score never wins).  A
+        forward_only step keeps the plain single draw: dev loss and auc stay comparable with a run without hard
+        negatives.  The scores use the user's table row as it is, WITHOUT dropout, whatever the model's dropout.
+        Needs exactly one one-hot feature on the user side and on the item side (NotImplementedError otherwise;
+        ValueError for any other hardest_of) -- both are raised before anything is uploaded, and an earlier prepare
+        stays in force.  col2row, the table row of every logit column, is built here, once.
+        A second call replaces the lists, the tables, the seed and the hard mode."""
+        self.check_hardest_of(hardest_of)
         if self._item2logit_np is None or self.logit_ind2item_ind is None:
             raise ValueError("pair negatives need item_ind2logit_ind and logit_ind2item_ind")
         ptr, cols = exclusion_csr(hist, self.n_users + 1, self._item2logit_np)      # users 0..n_users (_pos_csr)
@@ -833,6 +859,13 @@ class EmbeddingAttribute(object):
             self.neg_draw = G.NegPairDraw(rt, self.u_indices['input'], self.i_indices['neg'],
                                           lambda: self._pair_lists, self.logit_size, seed)
         self.neg_draw.seed = int(seed)
+        self.neg_draw.hard = None
+        if hardest_of is not None:
+            C = int(hardest_of)
+            ut, it = self.user_feats[0].table, self.item_feats[0].table
+            umap = self.user_feats[0].maps[0]
+            col2row = rt.upload(_np_i32(self.item_attributes.features_cat[0])[l2i[:self.logit_size]], torch.int32)
+            self.neg_draw.hard = lambda: (C, ut.E, umap, it.E, it.bias, col2row)
 
     def set_pos_mode(self, forward_only):
         self._pos_mode = 'eval' if forward_only else 'train'      # :727

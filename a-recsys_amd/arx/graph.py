@@ -863,18 +863,30 @@ class NegPairDraw(Node):
     the placeholder.
     lists() -> (ptr, cols, col2item, ex_cum, cum): with the two int64 weight tables set the draw is the weighted one
     (arx_neg_draw_weighted: in proportion to the column weights, -1 for a user whose list covers every column that
-    has weight); with None for both it is the uniform one."""
+    has weight); with None for both it is the uniform one.
+    hard: None, or a callable -> (C, U, umap, P, pbias, col2row).  A TRAIN plan then draws C candidates by the rule
+    above, scores them against the row's user and keeps the best (arx_neg_draw_hardest), and the counter goes up by
+    C: candidate j of the step that starts at counter s is the plain draw at s + j.  A forward-only plan keeps the
+    plain draw and its bump by 1, so dev loss and auc stay comparable with a run without hard negatives."""
 
     pre_step = True
 
     def __init__(self, rt, users, target, lists, V, seed):
         super().__init__(rt, target.shape, (users,))
         self.target, self.lists, self.V, self.seed = target, lists, int(V), int(seed)
+        self.hard = None
         self.value = torch.zeros(target.shape[0], dtype=torch.int32, device=rt.device)
         self.counter = torch.zeros(1, dtype=torch.int64, device=rt.device)
 
     def forward(self, train):
         ptr, cols, col2item, ex_cum, cum = self.lists()
+        if train and self.hard is not None:
+            C, U, umap, P, pbias, col2row = self.hard()
+            ops.neg_draw_hard(self.inputs[0].value, ptr, cols, ex_cum, cum, self.V, col2item, self.seed,
+                              self.counter, 0, C, U, umap, P, pbias, col2row, self.value,
+                              lookup_items=self.target.value)
+            ops.counter_add(self.counter, C)
+            return
         if cum is None:
             ops.neg_draw_uniform(self.inputs[0].value, ptr, cols, self.V, col2item, self.seed, self.counter, 0,
                                  self.value, lookup_items=self.target.value)

@@ -370,18 +370,31 @@ class LatentProductModel(object):
                                   lists, sample_temperature, exclude_seen, tags_any, tags_all, return_values,
                                   return_why)
 
-    def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None):
+    def prepare_pair_negatives(self, hist, seed=0, power=None, smooth=1.0, counts=None, hardest_of=None):
         """'bpr' / 'bpr-hinge': the items a DRAWN negative must not hit, per user -- typically the training history:
         {user_index: items} or a (ptr, items) CSR pair in item-index space.  After this call a step without
         neg_item_input draws one negative per row on the device: uniform over the user's other items (power None),
         or in proportion to (counts + smooth) ** power -- counts per item index, by default the number of users
         whose list holds the item; 0.75 is the usual unigram rule (EmbeddingAttribute.prepare_pair_negatives).
-        A second call replaces the lists, the weights and the seed (the drawing plans are dropped)."""
+        hardest_of = C, an int in [2, 64]: dynamic negative sampling -- a training step draws C candidates by that
+        rule, scores them with the current tables and trains against the one the model ranks highest, inside the
+        same captured step (EmbeddingAttribute.prepare_pair_negatives, arx_neg_draw_hardest); forward_only steps keep
+        the plain single draw.  With dropout < 1 the candidate scores use the UNDROPPED user row.  ValueError for any
+        other hardest_of; NotImplementedError, naming what is unsupported, for nonlinear 'relu' / 'tanh' (the latent is
+        not a table row) and for users or items that are not exactly one one-hot feature -- all raised before anything
+        is uploaded or dropped, so an earlier prepare stays in force.
+        A second call replaces the lists, the weights, the seed and the hard mode (the drawing plans are dropped)."""
         if self.loss_function not in ('bpr', 'bpr-hinge'):
             raise ValueError("prepare_pair_negatives: a model of the 'bpr' / 'bpr-hinge' losses")
+        self.att_emb.check_hardest_of(hardest_of)
+        if hardest_of is not None and self.nonlinear in ('relu', 'tanh'):
+            raise NotImplementedError("prepare_pair_negatives(hardest_of=): nonlinear=%r -- the user latent is an MLP "
+                                      "output, not a table row the candidates could be scored against"
+                                      % (self.nonlinear,))
         for key in ('train_draw', 'eval_draw'):
             self._plans.pop(key, None)
-        self.att_emb.prepare_pair_negatives(hist, seed=seed, power=power, smooth=smooth, counts=counts)
+        self.att_emb.prepare_pair_negatives(hist, seed=seed, power=power, smooth=smooth, counts=counts,
+                                            hardest_of=hardest_of)
 
     def _plan(self, key):
         if key in self._plans:

@@ -448,6 +448,46 @@ def neg_draw_weighted(users, ex_ptr, ex_cols, ex_cum, cum, V, col2item, seed, st
     return neg_items
 
 
+def neg_draw_hard(users, ex_ptr, ex_cols, ex_cum, cum, V, col2item, seed, step_dev, counter, C, U, umap, P, pbias,
+                  col2row, neg_items, lookup_items=None, out_pick=None, out_cand=None, out_score=None):
+    """The hardest of C drawn negatives per row, one launch (arx_neg_hard.h arx_neg_draw_hardest): candidate j is the
+    column neg_draw_uniform (ex_cum and cum None) / neg_draw_weighted gives at counter + j; it scores
+    U[umap[user]] . P[col2row[col]] + pbias[col2row[col]] in slate_scores' arithmetic; the first arg-max wins (a NaN
+    counts as -inf).  -1 for a row the plain draw leaves void and for a user without a row of U.  umap, col2row (one
+    entry per column), col2item, pbias may be None.  out_pick int32 [B], out_cand int32 [B, >= C], out_score float32
+    [B, >= C]: the pick, the columns and the score bits."""
+    _chk(users, torch.int32, "users")
+    _chk(neg_items, torch.int32, "neg_items")
+    _chk(ex_cols, torch.int32, "ex_cols")
+    _chk(ex_cum, torch.int64, "ex_cum")
+    _chk(cum, torch.int64, "cum")
+    if (cum is None) != (ex_cum is None):
+        raise ValueError("neg_draw_hard: cum and ex_cum come together (weighted) or not at all (uniform)")
+    if cum is not None and (int(cum.shape[0]) != int(V) + 1 or int(ex_cum.shape[0]) != int(ex_cols.shape[0])):
+        raise ValueError("neg_draw_hard: cum holds V + 1 entries and ex_cum one per entry of ex_cols")
+    _chk(U, torch.float32, "U"); _chk(P, torch.float32, "P"); _chk(pbias, torch.float32, "pbias")
+    _chk(umap, torch.int32, "umap"); _chk(col2row, torch.int32, "col2row")
+    _chk(out_pick, torch.int32, "out_pick"); _chk(out_cand, torch.int32, "out_cand")
+    _chk(out_score, torch.float32, "out_score")
+    if U.dim() != 2 or P.dim() != 2 or U.shape[1] != P.shape[1]:
+        raise ValueError("neg_draw_hard: U [n_urows, d] and P [n_prows, d]")
+    if pbias is not None and (pbias.dim() != 1 or int(pbias.shape[0]) < int(P.shape[0])):
+        raise ValueError("neg_draw_hard: pbias needs one entry per row of P")
+    if col2row is not None and int(col2row.shape[0]) < int(V):
+        raise ValueError("neg_draw_hard: col2row needs one entry per column")
+    B = int(users.shape[0])
+    for t, name in ((out_cand, "out_cand"), (out_score, "out_score")):
+        if t is not None and (t.dim() != 2 or int(t.shape[0]) != B or int(t.shape[1]) < int(C)):
+            raise ValueError("neg_draw_hard: %s is [B, >= C]" % name)
+    call("arx_neg_draw_hardest", _p(users), B, int(ex_ptr.shape[0]) - 1, _p(ex_ptr), _p(ex_cols), _p(ex_cum), _p(cum),
+         int(V), _p(col2item), int(seed) & (2 ** 64 - 1), _p(step_dev), int(counter) & (2 ** 64 - 1), int(C),
+         _p(U), _ld(U), int(U.shape[0]), _p(umap), int(umap.shape[0]) if umap is not None else 0,
+         _p(P), _ld(P), int(P.shape[0]), _p(pbias), _p(col2row), int(U.shape[1]),
+         _p(neg_items), _p(lookup_items), _p(out_pick), _p(out_cand), _ld(out_cand) if out_cand is not None else 0,
+         _p(out_score), _ld(out_score) if out_score is not None else 0, _stream())
+    return neg_items
+
+
 # ---- a8 -----------------------------------------------------------------------
 # The scorer products run on the bf16 matrix pipe, f32-exact (three exact bf16 pieces per operand, six MFMA terms,
 # f32 accumulation: csrc/gemm_bx6.hip) -- the default since round 4; ARX_SCORER_F32=1 selects the f32-input MFMA

@@ -1178,4 +1178,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_list_logp.h"
 #include "arx_list_logp_shard.h"
 #include "arx_topk_bf16.h"
+#include "arx_neg_hard.h"
 #endif /* ARX_H_ */

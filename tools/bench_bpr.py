@@ -7,6 +7,9 @@ usage: python tools/bench_bpr.py [--workloads c2,c3] [--steps 100] [--warmup 20]
        python tools/bench_bpr.py --sharded            # the world-1 ShardedHMF 'bpr' step at the C2 shape, fed and drawn
        python tools/bench_bpr.py --weighted [--sharded]   # also: the drawn step with the popularity^0.75 draw, and the
                                                           # two draw kernels alone on the workload's lists
+       python tools/bench_bpr.py --workloads c2 --hard 4,16,64    # also: the drawn 'bpr' step training against the
+                                                          # hardest of C candidates (arx_neg_draw_hardest) beside the plain
+                                                          # drawn step of the same run, and that kernel alone
 """
 import argparse
 import gc
@@ -38,6 +41,14 @@ def region_ms(fn, steps, warmup, repeats):
         torch.cuda.synchronize()
         out.append(e0.elapsed_time(e1) / steps)
     return sorted(out)[len(out) // 2]
+
+
+def region_spread_ms(fn, steps, warmup, repeats):
+    """{median, min, max} of `repeats` regions (region_ms keeps the median only)."""
+    for k in range(warmup):
+        fn(k)
+    out = sorted(region_ms(fn, steps, 0, 1) for _ in range(repeats))
+    return {'median': out[len(out) // 2], 'min': out[0], 'max': out[-1]}
 
 
 def pair_kernel_us(B, d, dev, iters=200):
@@ -72,6 +83,24 @@ def draw_kernels_us(users, ptr, cols, ex_cum, cum, V, col2item, dev, iters=200):
         for name, fn in (('uniform_us', uni), ('weighted_us', wtd)):
             res.setdefault(name, []).append(region_ms(fn, iters, 10, 3) * 1e3)
     return {k: min(v) for k, v in res.items()}
+
+
+def hard_kernel_us(users, ptr, cols, V, col2item, hard, Cs, dev, iters=200, repeats=5):
+    """arx_neg_draw_hardest alone: one batch of users on the model's own lists and tables (the uniform rule), a new
+    counter per launch.  The effective rate counts the gathered candidate rows and biases only, B C (d + 1) 4 bytes."""
+    from arx import ops
+    _, U, umap, P, pbias, col2row = hard()
+    B, d = int(users.shape[0]), int(U.shape[1])
+    out, look = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(2))
+    res = {}
+    for C in Cs:
+        fn = lambda k: ops.neg_draw_hard(users, ptr, cols, None, None, V, col2item, 1, None, k * C, C, U, umap, P,
+                                         pbias, col2row, out, lookup_items=look)
+        ms = region_spread_ms(fn, iters, 10, repeats)
+        nbytes = B * C * (d + 1) * 4
+        res[str(C)] = {'us': ms['median'] * 1e3, 'us_min': ms['min'] * 1e3, 'us_max': ms['max'] * 1e3,
+                       'gathered_bytes': nbytes, 'effective_gbs': nbytes / ms['median'] / 1e6}
+    return res
 
 
 def run_workload(name, args, dev):
@@ -141,6 +170,23 @@ def run_workload(name, args, dev):
                 res['draw_kernels'] = draw_kernels_us(batches[0][0], ptr, cols, ex_cum, cum, m.logit_size, c2i, dev)
                 model.prepare_pair_negatives(syn.positives_csr(), seed=1)        # the uniform step once more: spread
                 res['bpr_drawn_again_ms'] = region_ms(drawn, args.steps, args.warmup, args.repeats)
+            if args.hard and name != 'c2':
+                res['hard'] = 'skipped: hardest_of needs one-hot items (the c2 shape)'
+            elif args.hard:
+                # plain, hardest of C for every C, plain again: one run, one model, one set of lists
+                hard = {'plain_ms': region_spread_ms(drawn, args.steps, args.warmup, args.repeats)}
+                for C in args.hard:
+                    model.prepare_pair_negatives(syn.positives_csr(), seed=1, hardest_of=C)
+                    hard['hardest_of_%d_ms' % C] = region_spread_ms(drawn, args.steps, args.warmup, args.repeats)
+                    hard['hardest_of_%d_loss' % C] = float(model.loss.read().item())
+                    hard['hardest_of_%d_auc_last_step' % C] = float(model.auc.read().item())
+                m = model.att_emb
+                ptr, cols, c2i = m._pair_lists[:3]
+                hard['kernel'] = hard_kernel_us(batches[0][0], ptr, cols, m.logit_size, c2i, m.neg_draw.hard,
+                                                args.hard, dev)
+                model.prepare_pair_negatives(syn.positives_csr(), seed=1)
+                hard['plain_again_ms'] = region_spread_ms(drawn, args.steps, args.warmup, args.repeats)
+                res['hard'] = hard
         del model
         gc.collect()
         torch.cuda.synchronize()
@@ -251,6 +297,10 @@ def main():
     ap.add_argument('--weighted', action='store_true',
                     help="with 'bpr-drawn': also the step drawing by popularity^0.75 (arx_neg_draw_weighted), and the "
                          "uniform and the weighted draw kernel alone")
+    ap.add_argument('--hard', default=None, type=lambda v: [int(c) for c in v.split(',') if c],
+                    help="with 'bpr-drawn' on c2: C[,C...] -- also the drawn step with hardest_of=C (arx_neg_draw_hardest) "
+                         "beside the plain drawn step of the same run, {median, min, max} of the repeats, and the kernel "
+                         "alone (us, effective GB/s over B C (d + 1) 4 gathered bytes)")
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     dev = torch.device('cuda:0')

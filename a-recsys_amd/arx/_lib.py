@@ -1,7 +1,7 @@
 """ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
 include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h, include/arx_slate_sample.h,
 include/arx_sample_logp.h, include/arx_sample_shard.h, include/arx_list_logp.h, include/arx_list_logp_shard.h,
-include/arx_topk_bf16.h and include/arx_neg_hard.h).
+include/arx_topk_bf16.h, include/arx_neg_hard.h and include/arx_explain.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -326,6 +326,14 @@ NEG_HARD_PROTOTYPES = {
                                     i32p, i32p, i32p, i32p, i64, f32p, i64, vp]),
 }
 
+# include/arx_explain.h (explain_items: per-feature and per-token contributions to a score), one-to-one as above; the
+# feature descriptors are host arrays (of device pointers, row strides and kinds)
+EXPLAIN_PROTOTYPES = {
+    "arx_explain_slate": (cint, [f32p, i64, i64, cint, i32p, i64, i64, i64, cint, C.POINTER(cint), C.POINTER(vp),
+                                 C.POINTER(i64), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp),
+                                 C.POINTER(vp), cint, f32p, i64, f32p, i64, f32p, i32p, i32p, i64, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -342,7 +350,8 @@ def _load():
                               + list(SAMPLE_PROTOTYPES.items()) + list(SLATE_SAMPLE_PROTOTYPES.items())
                               + list(SAMPLE_LOGP_PROTOTYPES.items()) + list(SAMPLE_SHARD_PROTOTYPES.items())
                               + list(LIST_LOGP_PROTOTYPES.items()) + list(LIST_LOGP_SHARD_PROTOTYPES.items())
-                              + list(TOPK_BF16_PROTOTYPES.items()) + list(NEG_HARD_PROTOTYPES.items())):
+                              + list(TOPK_BF16_PROTOTYPES.items()) + list(NEG_HARD_PROTOTYPES.items())
+                              + list(EXPLAIN_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -13,6 +13,7 @@ import random
 import numpy as np
 import torch
 
+from .. import explain
 from .. import graph as G
 from .. import ops
 from .. import slate
@@ -342,6 +343,26 @@ class LatentProductModel(object):
         return slate.score_items(self, lambda: self._feed(user_input, None, True, self.loss_function, None, None, True),
                                  candidates, k, diversify, max_per_group, sample_temperature, sample_seed,
                                  return_logprob)
+
+    def explain_items(self, user_input, items, top=3):
+        """WHY did these items get these scores for these users: the score score_items gives row r of one full batch
+        of users (the rules of step(recommend=True), dropout off) for each item of its slate items[r] -- [batch_size,
+        C] logit indices, -1 an empty slot -- taken apart on the device (arx_explain.h).  The score is an exact sum
+        over the item's F output features of 1/F * (u . id row + bias) or 1/F * the bag mean of (u . token row +
+        bias); returns arx.explain.Explanation(score, feature, bias, token_value, token_id, token_feature, features):
+        score [mb, C] has score_items' bits; feature [mb, C, F] the part of each output feature (was it the item's
+        own id row or its genre?), summing to the score up to float32 rounding; bias [mb, C] the part that does not
+        depend on the user; token_* [mb, C, top] the `top` largest single-token contributions over all bags of the
+        item (these three words of its title), by (value desc, feature asc, bag position asc), (-inf, -1, -1) past
+        the last position, None with top = 0; features names the columns as (kind, table_name).  Every bag position
+        is an entry of its own: a repeated token appears once per position.  ValueError for a malformed slate or a
+        top that is not an int in [0, 16]; output_feat 2 / 3: NotImplementedError.  One plan per (C, top), at most
+        four kept.  Not offered: SeqModel, the sharded models (their tables are striped), a "most negative" or
+        absolute-value order, merged repeats.
+            ex = model.explain_items(users, cands, top=3)
+            ex.feature[r, j]          # one number per output feature of item cands[r, j]"""
+        return explain.explain_items(self, lambda: self._feed(user_input, None, True, self.loss_function, None, None,
+                                                              True), items, top)
 
     def list_logprob(self, user_input, lists, sample_temperature, exclude_seen=False, tags_any=None, tags_all=None,
                      return_values=False, return_why=False):

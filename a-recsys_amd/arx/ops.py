@@ -1664,6 +1664,85 @@ def slate_merge_shards(parts, out):
          _ld(out), _stream())
 
 
+EXPLAIN_MAX_FEATS, EXPLAIN_MAX_TOP = 8, 16
+
+
+class ExplainSet(object):
+    """Feature descriptors of arx_explain_slate (arx_explain.h) as host arrays, built once per plan.  feats: objects
+    with .kind ('cat' | 'mulhot'), .table (.E [rows, d], .bias [rows] or None) and .maps -- (cat_map | None,) or (vals,
+    starts, lens), indexed by logit column: graph.Feature, the entries of EntityEmbed.feats.  V: the logit columns;
+    every map must hold that many entries.  with_bias False: the biases of the tables are left out (b_f = 0)."""
+
+    def __init__(self, feats, V, with_bias=True):
+        import ctypes as C
+        n = len(feats)
+        if not 1 <= n <= EXPLAIN_MAX_FEATS:
+            raise ValueError("explain_slate: 1 .. %d features, got %d" % (EXPLAIN_MAX_FEATS, n))
+        self.n, self.V, self.d = n, int(V), int(feats[0].table.E.shape[1])
+        for f in feats:
+            if f.kind not in ('cat', 'mulhot'):
+                raise ValueError("explain_slate: feature kind %r" % (f.kind,))
+            _chk(f.table.E, torch.float32, 'E'); _chk(f.table.bias, torch.float32, 'bias')
+            if f.table.E.dim() != 2 or int(f.table.E.shape[1]) != self.d:
+                raise ValueError("explain_slate: tables of equal width [rows, d]")
+            for m in (f.maps[:1] if f.kind == 'cat' else f.maps):
+                _chk(m, torch.int32, 'map')
+            for m in (f.maps[:1] if f.kind == 'cat' else f.maps[1:]):
+                if m is not None and int(m.shape[0]) < self.V:
+                    raise ValueError("explain_slate: a map holds %d entries for %d logit columns" % (m.shape[0], V))
+            if f.kind == 'cat' and f.maps[0] is None and int(f.table.E.shape[0]) < self.V:
+                raise ValueError("explain_slate: an unmapped table of %d rows for %d logit columns"
+                                 % (f.table.E.shape[0], V))
+        vp = lambda xs: (C.c_void_p * n)(*[(_p(x) or None) for x in xs])
+        cat = [f.kind == 'cat' for f in feats]
+        self.kind = (C.c_int * n)(*[0 if c else 1 for c in cat])
+        self.E = vp([f.table.E for f in feats])
+        self.lde = (C.c_int64 * n)(*[_ld(f.table.E) for f in feats])
+        self.bias = vp([f.table.bias if with_bias else None for f in feats])
+        self.cat_map = vp([f.maps[0] if c else None for f, c in zip(feats, cat)])
+        self.vals = vp([None if c else f.maps[0] for f, c in zip(feats, cat)])
+        self.starts = vp([None if c else f.maps[1] for f, c in zip(feats, cat)])
+        self.lens = vp([None if c else f.maps[2] for f, c in zip(feats, cat)])
+        self._keep = list(feats)
+
+
+def explain_slate(U, cand, es, T, feat=None, bias=None, tok_val=None, tok_id=None, tok_feat=None):
+    """The parts of score(r, c) for c = cand[r, j] (arx_explain.h): feat [B, C, F] the per-feature contributions, bias
+    [B, C] the bias part, tok_val / tok_id / tok_feat [B, C, T] the T largest token contributions by (value desc,
+    feature asc, bag position asc), (-inf, -1, -1) past the last; an empty slot (cand < 0 or >= es.V) gives 0, 0 and
+    (-inf, -1, -1).  U [B, d]; cand [B, C] int32; es an ExplainSet.  Every output may be None (tok_* together); U, cand
+    and the outputs may be views whose rows are strided, the inner dimensions contiguous."""
+    _chk(U, torch.float32, 'U'); _chk(cand, torch.int32, 'cand'); _chk(feat, torch.float32, 'feat')
+    _chk(bias, torch.float32, 'bias'); _chk(tok_val, torch.float32, 'tok_val'); _chk(tok_id, torch.int32, 'tok_id')
+    _chk(tok_feat, torch.int32, 'tok_feat')
+    if U.dim() != 2 or cand.dim() != 2 or cand.shape[0] != U.shape[0] or int(U.shape[1]) != es.d:
+        raise ValueError("explain_slate: U [B, %d], cand [B, C]" % es.d)
+    B, C = int(cand.shape[0]), int(cand.shape[1])
+    T = int(T)
+    toks = (tok_val, tok_id, tok_feat)
+    if any(t is None for t in toks) != all(t is None for t in toks):
+        raise ValueError("explain_slate: tok_val, tok_id and tok_feat go together")
+
+    def ld3(t, last, name):
+        """row stride of t [B, C, last] whose rows are contiguous"""
+        if t is None:
+            return 0
+        if tuple(t.shape) != (B, C, last) or (t.numel() and (t.stride(2) != 1 or t.stride(1) != last)):
+            raise ValueError("explain_slate: %s must be [%d, %d, %d] with contiguous rows" % (name, B, C, last))
+        return t.stride(0) if B > 1 else max(t.stride(0), C * last)
+    ldf = ld3(feat, es.n, 'feat')
+    ldt = ld3(tok_val, T, 'tok_val')
+    if tok_val is not None and not (ld3(tok_id, T, 'tok_id') == ldt == ld3(tok_feat, T, 'tok_feat')):
+        raise ValueError("explain_slate: tok_val, tok_id and tok_feat need one row stride")
+    if bias is not None and tuple(bias.shape) != (B, C):
+        raise ValueError("explain_slate: bias must be [%d, %d]" % (B, C))
+    if cand.numel() == 0:
+        return
+    call("arx_explain_slate", _p(U), _ld(U), B, es.d, _p(cand), _ld(cand), C, es.V, es.n, es.kind, es.E, es.lde,
+         es.bias, es.cat_map, es.vals, es.starts, es.lens, T, _p(feat), ldf, _p(bias),
+         _ld(bias) if bias is not None else 0, _p(tok_val), _p(tok_id), _p(tok_feat), ldt, _stream())
+
+
 def slate_mmr_supported(C, d):
     """True iff arx_slate_mmr takes a slate of C slots over rows of d floats (arx_diverse.h: the one owner of the
     rule)."""

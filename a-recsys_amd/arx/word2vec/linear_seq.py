@@ -20,6 +20,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .. import explain
 from .. import graph as G
 from .. import ops
 from .. import slate
@@ -231,6 +232,18 @@ class LinearSeq(object):
             self.att_emb.add_input({}, user_input, item_input, recommend=True, loss=self.loss_function)
         return slate.score_items(self, feed, candidates, k, diversify, max_per_group, sample_temperature, sample_seed,
                                  return_logprob)
+
+    def explain_items(self, user_input, item_input, items, top=3):
+        """The scores score_items gives row r of one full batch (user_input and the [n_input][mb] context item_input)
+        for the items of its slate items[r] ([batch_size, C] logit indices, -1 an empty slot), taken apart into the
+        parts of the OUTPUT item latents' features and the `top` largest single-token contributions of their bags:
+        arx.explain.Explanation(score, feature, bias, token_value, token_id, token_feature, features)
+        (LatentProductModel.explain_items states the fields, the order and the errors; arx_explain.h).  output_feat
+        2 / 3: NotImplementedError.  Not offered: SeqModel, the sharded models, a "most negative" or absolute-value
+        order, merged repeats."""
+        def feed():
+            self.att_emb.add_input({}, user_input, item_input, recommend=True, loss=self.loss_function)
+        return explain.explain_items(self, feed, items, top)
 
     def list_logprob(self, user_input, item_input, lists, sample_temperature, exclude_seen=False, tags_any=None,
                      tags_all=None, return_values=False, return_why=False):

@@ -1179,4 +1179,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_list_logp_shard.h"
 #include "arx_topk_bf16.h"
 #include "arx_neg_hard.h"
+#include "arx_explain.h"
 #endif /* ARX_H_ */

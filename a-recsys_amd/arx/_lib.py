@@ -1,7 +1,7 @@
 """ctypes binding of libarx.so (include/arx.h and the extension headers it includes, include/arx_tags.h,
 include/arx_slate.h, include/arx_diverse.h, include/arx_sample.h, include/arx_slate_sample.h,
 include/arx_sample_logp.h, include/arx_sample_shard.h, include/arx_list_logp.h, include/arx_list_logp_shard.h,
-include/arx_topk_bf16.h, include/arx_neg_hard.h and include/arx_explain.h).
+include/arx_topk_bf16.h, include/arx_neg_hard.h, include/arx_explain.h and include/arx_gru.h).
 
 The library is the product: if it is missing or a symbol is absent this module
 raises -- there is no CPU fallback anywhere in the package.
@@ -334,6 +334,12 @@ EXPLAIN_PROTOTYPES = {
                                  C.POINTER(vp), cint, f32p, i64, f32p, i64, f32p, i32p, i32p, i64, vp]),
 }
 
+# include/arx_gru.h (SeqModel(cell='gru'): the GRU encoder's forward and BPTT), one-to-one as above
+GRU_PROTOTYPES = {
+    "arx_gru_fwd": (cint, [f32p, f32p, f32p, f32p, f32p, i64, i64, cint, cint, f32p, f32p, f32p, vp]),
+    "arx_gru_bwd": (cint, [f32p, f32p, f32p, f32p, f32p, i64, i64, cint, cint, f32p, f32p, vp]),
+}
+
 
 class ArxError(RuntimeError):
     pass
@@ -351,7 +357,7 @@ def _load():
                               + list(SAMPLE_LOGP_PROTOTYPES.items()) + list(SAMPLE_SHARD_PROTOTYPES.items())
                               + list(LIST_LOGP_PROTOTYPES.items()) + list(LIST_LOGP_SHARD_PROTOTYPES.items())
                               + list(TOPK_BF16_PROTOTYPES.items()) + list(NEG_HARD_PROTOTYPES.items())
-                              + list(EXPLAIN_PROTOTYPES.items())):
+                              + list(EXPLAIN_PROTOTYPES.items()) + list(GRU_PROTOTYPES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError as e:

@@ -12,6 +12,8 @@ Same constructor / step / get_batch signatures.  What differs from the TF graph:
     vocabulary, as hmf_model.py:130 does: the reference's own losses_full graph
     for 'mw' (seqModel.py:510) mixes a [mb, n_sampled] mask with [mb, V] logits
     and cannot be built unless n_sampled == V.
+  * cell='gru' (build-defined; the reference has LSTMCell only): TF 1.0's GRUCell in place of the LSTMCell, in
+    persistent kernels of its own (csrc/gru.hip); everything around the cell is the same graph.
 Not implemented (raise): beam search (dead code in the reference).
 """
 from __future__ import annotations
@@ -174,6 +176,66 @@ class LSTM(G.Node):
                 self._dwt[:, din:].zero_()                        # (strided view: torch fill)
             ops.transpose(self._dwt, self.W.grad)                 # both halves flipped by one launch
         self.W.touched = self.b.touched = True
+
+
+def gru_grads(ws, x, hs, rh, dzg, dzc, Wg, Wc, L, B, dWg, dbg, dWc, dbc, scratch, dx=None, dx_beta=0.0):
+    """The GRU cell's gradients from the backward kernel's dzg [L*B, 2h] and dzc [L*B, h], as plain tensors (the GRU
+    node calls this; so can a test).  TN products into the two [., din + h] scratch matrices, one transpose each:
+        dx (optional) = dx_beta * dx + dzg . Wg[:din]^T + dzc . Wc[:din]^T
+        dWg = [x | h_prev]^T . dzg  (h_prev = hs one step, B rows, up; zero h rows at L == 1),  dbg = colsum(dzg)
+        dWc = [x | rh]^T . dzc      (rh's step-0 rows are zero by construction),                dbc = colsum(dzc)"""
+    din = int(x.shape[1])
+    if dx is not None:
+        ops.gemm(dzg, Wg[:din], dx, ws, transB=True, beta=dx_beta)
+        ops.gemm(dzc, Wc[:din], dx, ws, transB=True, beta=1.0)
+    gt, ct = scratch                                              # [2h, din + h], [h, din + h]
+    ops.gemm(dzg, x, gt[:, :din], ws, transA=True, a_rowsum=dbg)
+    if L > 1:
+        ops.gemm(dzg[B:], hs[:(L - 1) * B], gt[:, din:], ws, transA=True)
+    else:
+        gt[:, din:].zero_()                                       # (strided view: torch fill)
+    ops.transpose(gt, dWg)
+    ops.gemm(dzc, x, ct[:, :din], ws, transA=True, a_rowsum=dbc)
+    ops.gemm(dzc, rh, ct[:, din:], ws, transA=True)
+    ops.transpose(ct, dWc)
+
+
+class GRU(G.Node):
+    """tf.contrib.rnn.GRUCell(size) of TF 1.0 under static_rnn from the zero state (build-defined: the reference has
+    the LSTM cell only).  Wg [din + h, 2h] (r, u), bg [2h], Wc [din + h, h], bc [h]; csrc/gru.hip."""
+
+    requires_grad = True
+
+    def __init__(self, rt, x, Wg, bg, Wc, bc, L, B):
+        h = Wc.w.shape[1]
+        super().__init__(rt, (L * B, h), (x,))
+        self.Wg, self.bg, self.Wc, self.bc, self.L, self.B, self.h = Wg, bg, Wc, bc, L, B, h
+        self.din = x.shape[1]
+        dev = rt.device
+        self.gates = torch.empty((L * B, 3 * h), dtype=torch.float32, device=dev)
+        self.rh = torch.empty((L * B, h), dtype=torch.float32, device=dev)
+        self.dzg = self.dzc = self._scratch = None
+
+    def forward(self, train):
+        x = self.inputs[0]
+        ops.gru_fwd(x.value, self.Wg.w, self.bg.w, self.Wc.w, self.bc.w, self.L, self.B, self.din, self.h,
+                    self.alloc_value(), self.gates, self.rh)
+
+    def backward(self):
+        x = self.inputs[0]
+        rt, L, B, din, h = self.rt, self.L, self.B, self.din, self.h
+        if self.dzg is None:
+            dev = rt.device
+            self.dzg = torch.empty((L * B, 2 * h), dtype=torch.float32, device=dev)
+            self.dzc = torch.empty((L * B, h), dtype=torch.float32, device=dev)
+            self._scratch = (torch.empty((2 * h, din + h), dtype=torch.float32, device=dev),    # [dWg_x^T | dWg_h^T]
+                             torch.empty((h, din + h), dtype=torch.float32, device=dev))        # [dWc_x^T | dWc_h^T]
+        ops.gru_bwd(self.Wg.w, self.Wc.w, self.value, self.gates, self.grad, L, B, din, h, self.dzg, self.dzc)
+        dx = x.alloc_grad() if x.requires_grad else None
+        gru_grads(rt.ws, x.value, self.value, self.rh, self.dzg, self.dzc, self.Wg.w, self.Wc.w, L, B,
+                  self.Wg.grad, self.bg.grad, self.Wc.grad, self.bc.grad, self._scratch,
+                  dx=dx, dx_beta=x.grad_beta() if dx is not None else 0.0)
+        self.Wg.touched = self.bg.touched = self.Wc.touched = self.bc.touched = True
 
 
 class SeqPrediction(G.Prediction):
@@ -342,7 +404,9 @@ class SeqModel(SeqBatching):
                  forward_only=False, dropoutRate=1.0, START_ID=0, loss="ce", devices="",
                  run_options=None, run_metadata=None, use_concat=True, output_feat=1,
                  no_input_item_feature=False, no_user_id=True, topk_n=30, dtype='float32',
-                 params=None):
+                 params=None, cell='lstm'):
+        if cell not in ('lstm', 'gru'):
+            raise ValueError("cell must be 'lstm' or 'gru', not %r" % (cell,))
         if num_layers < 1:
             raise ValueError("num_layers must be >= 1")
         if not (0.0 < float(dropoutRate) <= 1.0):
@@ -384,6 +448,7 @@ class SeqModel(SeqBatching):
         self.dropoutAssign_op = _Op(lambda: self.dropoutRate.set(float(dropoutRate)))
         self.dropout10_op = _Op(lambda: self.dropoutRate.set(1.0))
         self.num_layers = num_layers
+        self.cell = cell
 
         # feeds (seqModel.py:118-124): time-major [L*mb]
         self.target_ids_all = G.IdsInput(rt, Lmax * B, 'target_id_all')
@@ -396,7 +461,8 @@ class SeqModel(SeqBatching):
         # MultiRNNCell([cell] * num_layers) (:99-103): every layer maps size -> size with its own
         # weights; initial values under 'lstm_w' / 'lstm_b' (layer 0) and 'lstm_w_<l>' / 'lstm_b_<l>'
         self.Ws, self.bs = [], []
-        for l in range(num_layers):
+        self.gru = []                   # cell='gru': per layer (Wg, bg, Wc, bc)
+        for l in range(num_layers if cell == 'lstm' else 0):
             wname = 'rnn/multi_rnn_cell/cell_%d/lstm_cell/weights' % l
             bname = 'rnn/multi_rnn_cell/cell_%d/lstm_cell/biases' % l
             wk, bk_ = ('lstm_w', 'lstm_b') if l == 0 else ('lstm_w_%d' % l, 'lstm_b_%d' % l)
@@ -412,7 +478,31 @@ class SeqModel(SeqBatching):
             rt.dense[wname], rt.dense[bname] = Wp, bp
             self.Ws.append(Wp)
             self.bs.append(bp)
-        self.W, self.b = self.Ws[0], self.bs[0]
+        # cell='gru': TF's GRUCell variables -- gates/weights [din + size, 2 size] (glorot like the others), gates/biases
+        # initialised to 1.0 as TF does, candidate/weights [din + size, size], candidate/biases 0; initial values under
+        # 'gru_wg' / 'gru_bg' / 'gru_wc' / 'gru_bc' (layer 0) and the same with '_<l>' appended
+        for l in range(num_layers if cell == 'gru' else 0):
+            scope = 'rnn/multi_rnn_cell/cell_%d/gru_cell/' % l
+            sfx = '' if l == 0 else '_%d' % l
+            layer = []
+            for key, name, shape, fill in (('gru_wg', 'gates/weights', (din + size, 2 * size), None),
+                                           ('gru_bg', 'gates/biases', (2 * size,), 1.0),
+                                           ('gru_wc', 'candidate/weights', (din + size, size), None),
+                                           ('gru_bc', 'candidate/biases', (size,), 0.0)):
+                if key + sfx in params:
+                    v = np.asarray(params[key + sfx], dtype=np.float32)
+                    if v.shape != shape:
+                        raise ValueError("params[%r]: shape %r, expected %r" % (key + sfx, v.shape, shape))
+                    t = rt.upload(v, torch.float32)
+                elif fill is None:
+                    t = m._new_var(scope + name, shape, params)
+                else:
+                    t = torch.full(shape, fill, dtype=torch.float32, device=rt.device)
+                p_ = G.DenseParam(scope + name, t.contiguous())
+                rt.dense[scope + name] = p_
+                layer.append(p_)
+            self.gru.append(tuple(layer))
+        self.W, self.b = (self.Ws[0], self.bs[0]) if cell == 'lstm' else (None, None)
 
         rt.clip_coef_dev = torch.ones(1, dtype=torch.float32, device=rt.device)
         self._sq = torch.zeros(1, dtype=torch.float32, device=rt.device)
@@ -473,17 +563,21 @@ class SeqModel(SeqBatching):
         # DropoutWrapper(input_keep_prob) inside every layer, DropoutWrapper(output_keep_prob) on
         # the stack (:100-103); the nodes are the identity while rt.keep_prob == 1
         hs = x
-        bk_drop = []
+        bk_drop, cells = [], []
         for l in range(self.num_layers):
             hs = Dropout(rt, hs)
             bk_drop.append(hs)
-            hs = LSTM(rt, hs, self.Ws[l], self.bs[l], L, B)                                # :477
+            if self.cell == 'gru':
+                hs = GRU(rt, hs, *self.gru[l], L, B)
+            else:
+                hs = LSTM(rt, hs, self.Ws[l], self.bs[l], L, B)                            # :477
+            cells.append(hs)
         hs = Dropout(rt, hs)
         bk_drop.append(hs)
         wn = SeqWeights(rt, self.weights_all if L == Lmax else _FloatView(rt, self.weights_all, n), L, B)
         tid = view(self.target_ids_all, 'target_id_%d' % L)
         tgt = view(self.targets_all, 'target_%d' % L)
-        bk = {'L': L, 'dropouts': bk_drop, 'hs': hs}
+        bk = {'L': L, 'dropouts': bk_drop, 'hs': hs, 'cells': cells}
         seq_pred = lambda lat, pe: SeqPrediction(rt, lat, pe, L, B)     # scorer of all L time steps at once
         if self.loss in ('mw', 'mce'):       # ('mce': build-defined sampled softmax, see arx.h)
             logits = m.get_prediction(hs, 'sampled', output_feat=self.output_feat, pred_cls=seq_pred, steps=(L, B))  # :492

@@ -1981,6 +1981,18 @@ def lstm_bwd(W, hs, cs, gates, dhs, L, B, din, h, dz, wxt=None):
          int(h), _p(dz), _p(wxt), _stream())
 
 
+def gru_fwd(x, Wg, bg, Wc, bc, L, B, din, h, hs, gates, rh):
+    """TF's GRUCell over L steps from the zero state: hs [L*B, h], gates [L*B, 3h] (r, u, c), rh [L*B, h] = r * h_prev."""
+    call("arx_gru_fwd", _p(x), _p(Wg), _p(bg), _p(Wc), _p(bc), int(L), int(B), int(din), int(h), _p(hs), _p(gates),
+         _p(rh), _stream())
+
+
+def gru_bwd(Wg, Wc, hs, gates, dhs, L, B, din, h, dzg, dzc):
+    """dzg [L*B, 2h] (dzr, dzu) and dzc [L*B, h] of the whole unrolled cell."""
+    call("arx_gru_bwd", _p(Wg), _p(Wc), _p(hs), _p(gates), _p(dhs), int(L), int(B), int(din), int(h), _p(dzg),
+         _p(dzc), _stream())
+
+
 def seq_weights(w, L, B, out):
     call("arx_seq_weights", _p(w), int(L), int(B), _p(out), _stream())
 

@@ -1180,4 +1180,5 @@ int arx_graph_feeds_destroy(void* feeds);
 #include "arx_topk_bf16.h"
 #include "arx_neg_hard.h"
 #include "arx_explain.h"
+#include "arx_gru.h"
 #endif /* ARX_H_ */

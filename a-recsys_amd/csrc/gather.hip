@@ -54,10 +54,116 @@ __global__ __launch_bounds__(256) void k_gather_onehot(
 }
 
 // ---------------------------------------------------------------------------
-// K1: multi-hot gather + segment-mean.  One LPR-lane sub-group per bag.  The
-// bag's token ids are fetched coalesced (lane j of the sub-group loads token
-// j), then broadcast with ds_bpermute so every lane issues the row loads of
-// up to 4 tokens back-to-back (4 x 16 B in flight per lane) before summing.
+// The bag sum of K1, of the step's lookup launch and of the serving rows (k_gather_mulhot, k_lookup_multi,
+// k_het_rows_range): one LPR-lane sub-group per bag.  A block of LPR token ids is fetched coalesced (lane j of the
+// sub-group loads token j; `tok0` is the first block, loaded by the caller -- k_het_rows_range has it one row ahead)
+// and broadcast with ds_bpermute -- all NF ids first, one LDS wait -- so that every lane requests the rows of up to
+// NF tokens back to back (NF x 16 B in flight per lane, a bag's tail among them) before the first is waited for.
+//
+// The ORDER of the sums is fixed, and explain.hip restates it: per block of LPR tokens cnt = min(LPR, len - j0) and
+// full = cnt & ~3; token t < full goes to accumulator t % 4, the tokens full <= t < cnt go to accumulator 0 one after
+// the other behind the full groups; the four accumulators carry over the blocks; the result is (a0 + a1) + (a2 + a3).
+// (Before bag_sum, K1 and the lookup launch had four rows in flight and requested the < 4 tokens of a tail one by
+// one, each waited for on its own: at Poisson(20) bags 4.6 batches + 1.5 serial loads per bag against 2.9 batches.)
+// Tokens past cnt are predicated off: no row load, and the cross-lane index is masked, so no token slot outside the
+// bag is read.  BIAS_BEHIND: the tokens' biases are requested in front of the block's rows and added behind them, so
+// their round trip runs beside the rows' instead of in front of them (the same adds in the same order).
+//
+// The three callers (VGPRs / waves per SIMD at LPR >= 16, no scratch in any instance; measurements: DESIGN.md §6):
+//   k_lookup_multi    NF 8, one predicated loop   71 / 7  (was 54 / 8 with four rows and a serial tail; NF 16: 104 / 4
+//                                                          and no faster in the step; whole batches first: 79 / 6, no
+//                                                          faster either; 64 registers: not reached without scratch)
+//   k_gather_mulhot   NF 4, whole batches first   64 / 8  (K1 runs in the throughput regime: NF 8 costs it two waves
+//                                                          and 2-7 us of 31-94 at tables up to 51 MB; at NF 4 only the
+//                                                          tail changes -- requested together, not one by one)
+//   k_het_rows_range  NF 8, one predicated loop   95 / 5  (as before bag_sum; its launch bound of 5 waves leaves no
+//                                                          register for BIAS_BEHIND or the whole-batch loop)
+// ---------------------------------------------------------------------------
+#ifndef ARX_BAG_NF
+#define ARX_BAG_NF 8
+#endif
+constexpr int kBagNF = ARX_BAG_NF;               // rows in flight per lane in k_lookup_multi (A/B: 16 bought nothing)
+
+// returns the bag's sum (this lane's four columns); bacc += the biases of this lane's tokens (bias nullable)
+template <int LPR, int NF, bool WHOLE, bool BIAS_BEHIND>
+__device__ __forceinline__ float4 bag_sum(const float* __restrict__ E, const float* __restrict__ bias,
+                                          const int32_t* __restrict__ vals, int st, int len, int tok0, int lig,
+                                          int col, bool colok, int d, float& bacc) {
+  static_assert(NF % 4 == 0 && NF >= 4, "bag_sum: NF is a multiple of four");
+  const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 a0 = z, a1 = z, a2 = z, a3 = z;
+#pragma unroll 1
+  for (int j0 = 0; j0 < len; j0 += LPR) {
+    const int myj = j0 + lig;
+    int mytok = (j0 == 0) ? tok0 : ((myj < len) ? vals[st + myj] : 0);
+    const bool bok = bias && myj < len;
+    float bv = 0.f;
+    if (BIAS_BEHIND) {
+      // the token is waited for HERE, by every lane: left to the branch below, the wait in front of the cross-lane
+      // reads (which lanes without a bias to fetch reach with the token still in flight) would cover the bias too
+      asm volatile("" : "+v"(mytok));
+      if (bok) bv = bias[mytok];
+    } else if (bok) {
+      bacc += bias[mytok];
+    }
+    const int cnt = min(LPR, len - j0);
+    const int full = cnt & ~3;
+    // WHOLE: batches of NF tokens that the block fills first -- every token of them lies in a full group of four,
+    // there is nothing to predicate -- and the rest of the block (< NF tokens) in the predicated batch behind them
+    int t = 0;
+#pragma unroll 1
+    for (; WHOLE && t + NF <= cnt; t += NF) {
+      int ti[NF];
+#pragma unroll
+      for (int i = 0; i < NF; ++i) ti[i] = __shfl(mytok, t + i, LPR);
+      if (colok) {
+        float4 v[NF];
+#pragma unroll
+        for (int i = 0; i < NF; ++i) v[i] = *reinterpret_cast<const float4*>(E + (int64_t)ti[i] * d + col);
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+          if ((i & 3) == 0) a0 = f4_add(a0, v[i]);
+          if ((i & 3) == 1) a1 = f4_add(a1, v[i]);
+          if ((i & 3) == 2) a2 = f4_add(a2, v[i]);
+          if ((i & 3) == 3) a3 = f4_add(a3, v[i]);
+        }
+      }
+    }
+#pragma unroll 1
+    for (; t < cnt; t += NF) {
+      int ti[NF];
+      float4 v[NF];
+#pragma unroll
+      for (int i = 0; i < NF; ++i) ti[i] = __shfl(mytok, (t + i) & (LPR - 1), LPR);
+#pragma unroll
+      for (int i = 0; i < NF; ++i) {
+        v[i] = z;
+        if (colok && t + i < cnt) v[i] = *reinterpret_cast<const float4*>(E + (int64_t)ti[i] * d + col);
+      }
+      // (every lane waits for its rows here, whichever of the branches below it takes: rows that MAY be in flight at
+      // the loop's back edge would make the next batch's first instruction wait for all loads, the bias among them)
+#pragma unroll
+      for (int i = 0; i < NF; ++i) asm volatile("" : "+v"(v[i].x));
+#pragma unroll
+      for (int i = 0; i < NF; ++i) {
+        const int j = t + i;
+        if (j < full) {
+          if ((i & 3) == 0) a0 = f4_add(a0, v[i]);
+          if ((i & 3) == 1) a1 = f4_add(a1, v[i]);
+          if ((i & 3) == 2) a2 = f4_add(a2, v[i]);
+          if ((i & 3) == 3) a3 = f4_add(a3, v[i]);
+        } else if (j < cnt) {
+          a0 = f4_add(a0, v[i]);
+        }
+      }
+    }
+    if (BIAS_BEHIND && bok) bacc += bv;
+  }
+  return f4_add(f4_add(a0, a1), f4_add(a2, a3));
+}
+
+// ---------------------------------------------------------------------------
+// K1: multi-hot gather + segment-mean, bag_sum per row.
 // ---------------------------------------------------------------------------
 template <int LPR>
 __global__ __launch_bounds__(256) void k_gather_mulhot(
@@ -88,36 +194,9 @@ __global__ __launch_bounds__(256) void k_gather_mulhot(
       if (colok) one = *reinterpret_cast<const float4*>(E1 + (int64_t)row1 * d + col);
       if (bias1 && lig == 0) one_b = bias1[row1];
     }
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
     float bacc = 0.f;
-    for (int j0 = 0; j0 < len; j0 += LPR) {
-      const int myj = j0 + lig;
-      const int mytok = (myj < len) ? vals[st + myj] : 0;
-      if (bias && myj < len) bacc += bias[mytok];
-      const int cnt = min(LPR, len - j0);
-      int t = 0;
-      for (; t + 4 <= cnt; t += 4) {
-        const int t0 = __shfl(mytok, t, LPR);
-        const int t1 = __shfl(mytok, t + 1, LPR);
-        const int t2 = __shfl(mytok, t + 2, LPR);
-        const int t3 = __shfl(mytok, t + 3, LPR);
-        if (colok) {
-          float4 v0 = *reinterpret_cast<const float4*>(E + (int64_t)t0 * d + col);
-          float4 v1 = *reinterpret_cast<const float4*>(E + (int64_t)t1 * d + col);
-          float4 v2 = *reinterpret_cast<const float4*>(E + (int64_t)t2 * d + col);
-          float4 v3 = *reinterpret_cast<const float4*>(E + (int64_t)t3 * d + col);
-          a0 = f4_add(a0, v0);
-          a1 = f4_add(a1, v1);
-          a2 = f4_add(a2, v2);
-          a3 = f4_add(a3, v3);
-        }
-      }
-      for (; t < cnt; ++t) {
-        const int t0 = __shfl(mytok, t, LPR);
-        if (colok) a0 = f4_add(a0, *reinterpret_cast<const float4*>(E + (int64_t)t0 * d + col));
-      }
-    }
-    a0 = f4_add(f4_add(a0, a1), f4_add(a2, a3));
+    const int tok0 = (lig < len) ? vals[st + lig] : 0;
+    const float4 a0 = bag_sum<LPR, 4, true, true>(E, bias, vals, st, len, tok0, lig, col, colok, d, bacc);
     const float flen = (float)len;
     if (colok) {
       float4* op = reinterpret_cast<float4*>(out + r * ldo + col);
@@ -449,6 +528,10 @@ struct LookupSites {
 #ifndef ARX_LOOKUP_ROWS
 #define ARX_LOOKUP_ROWS 1
 #endif
+#ifndef ARX_LOOKUP_BAGS_FIRST
+#define ARX_LOOKUP_BAGS_FIRST 1
+#endif
+constexpr bool kLookupBagsFirst = ARX_LOOKUP_BAGS_FIRST != 0;     // arx_lookup_multi: the sites with bags start first
 constexpr int kLookupRows = ARX_LOOKUP_ROWS;      // rows per sub-group (1: the bag chains are latency-bound, more sub-groups in flight win)
 
 template <int LPR>
@@ -497,48 +580,24 @@ __global__ __launch_bounds__(256) void k_lookup_multi(LookupSites ls, int d) {
       if (bias_out && lig == 0) bias_out[r] = kEmptySlotBias;
       continue;
     }
+    // everything that hangs on the id alone is requested together (the bag's start and length, the id's row number),
+    // and the bag's first tokens before the id row: the id feature's chain runs beside the bag's, not in front of it
+    int st = 0, len = 1, tok0 = 0;
+    if (E) {
+      st = starts[id];
+      len = lens[id];
+    }
+    const int row1 = (E1 && cat_map1) ? cat_map1[id] : id;
+    if (E && lig < len) tok0 = vals[st + lig];
     float4 one = make_float4(0.f, 0.f, 0.f, 0.f);
     float one_b = 0.f;
     if (E1) {
-      const int row1 = cat_map1 ? cat_map1[id] : id;
       if (colok) one = *reinterpret_cast<const float4*>(E1 + (int64_t)row1 * d + col);
       if (bias_out && lig == 0) one_b = bias1[row1];
     }
-    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
+    float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f);
     float bacc = 0.f;
-    int len = 1;
-    if (E) {
-      const int st = starts[id];
-      len = lens[id];
-      for (int j0 = 0; j0 < len; j0 += LPR) {
-        const int myj = j0 + lig;
-        const int mytok = (myj < len) ? vals[st + myj] : 0;
-        if (bias_out && myj < len) bacc += bias[mytok];
-        const int cnt = min(LPR, len - j0);
-        int t = 0;
-        for (; t + 4 <= cnt; t += 4) {
-          const int t0 = __shfl(mytok, t, LPR);
-          const int t1 = __shfl(mytok, t + 1, LPR);
-          const int t2 = __shfl(mytok, t + 2, LPR);
-          const int t3 = __shfl(mytok, t + 3, LPR);
-          if (colok) {
-            float4 v0 = *reinterpret_cast<const float4*>(E + (int64_t)t0 * d + col);
-            float4 v1 = *reinterpret_cast<const float4*>(E + (int64_t)t1 * d + col);
-            float4 v2 = *reinterpret_cast<const float4*>(E + (int64_t)t2 * d + col);
-            float4 v3 = *reinterpret_cast<const float4*>(E + (int64_t)t3 * d + col);
-            a0 = f4_add(a0, v0);
-            a1 = f4_add(a1, v1);
-            a2 = f4_add(a2, v2);
-            a3 = f4_add(a3, v3);
-          }
-        }
-        for (; t < cnt; ++t) {
-          const int t0 = __shfl(mytok, t, LPR);
-          if (colok) a0 = f4_add(a0, *reinterpret_cast<const float4*>(E + (int64_t)t0 * d + col));
-        }
-      }
-      a0 = f4_add(f4_add(a0, a1), f4_add(a2, a3));
-    }
+    if (E) a0 = bag_sum<LPR, kBagNF, false, true>(E, bias, vals, st, len, tok0, lig, col, colok, d, bacc);
     // same arithmetic as k_gather_mulhot / k_gather_onehot: sum / len (a true divide), + id row, * scale
     const float flen = (float)len;
     if (colok) {
@@ -571,8 +630,8 @@ __global__ __launch_bounds__(256) void k_lookup_multi(LookupSites ls, int d) {
 // block ahead), and the sub-groups pick their bag up by a cross-lane read.  Nothing of the per-row chain
 // ids[r] -> starts[id] -> vals[..] -> rows of k_gather_mulhot is left in front of the token rows but vals[..]
 // itself, and that load is issued one row ahead (the next bag's start and length are already in registers).
-// A sub-group of LPR lanes forms a row with the arithmetic of k_gather_mulhot, bit for bit, but with the rows of
-// eight tokens in flight per lane instead of four (and a bag's tail among them): 94 VGPRs at d = 128, 5 waves per
+// A sub-group of LPR lanes forms a row with the arithmetic of k_gather_mulhot, bit for bit (bag_sum), but with the
+// rows of eight tokens in flight per lane instead of four: 95 VGPRs at d = 128, 5 waves per
 // SIMD, no scratch.  (Measured at C3's shape, 1 M bags of ~20 tokens, d = 128: 1.51 ms, the time of k_gather_mulhot
 // on the explicit id vector -- both sit at ~7.5 TB/s of token rows; with four rows in flight and 6 waves this
 // kernel took 1.64 ms.  profiles/r07_het_view_bench.txt)
@@ -645,40 +704,8 @@ __global__ __launch_bounds__(256, 5) void k_het_rows_range(
             if (colok) one = *reinterpret_cast<const float4*>(E_id + c * d + col);
             if (lig == 0) one_b = bias_id[c];
           }
-          float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
           float bacc = 0.f;
-          for (int j0 = 0; j0 < len; j0 += LPR) {
-            const int myj = j0 + lig;
-            const int mytok = (j0 == 0) ? ptok : ((myj < len) ? vals[st + myj] : 0);
-            if (myj < len) bacc += bias[mytok];
-            const int cnt = min(LPR, len - j0);
-            // k_gather_mulhot's sums in k_gather_mulhot's order -- token t of a full group of four goes to
-            // accumulator t % 4, the (< 4) tokens behind the last full group go to a0 one after the other -- with
-            // the rows of EIGHT tokens in flight together, the tail's among them (there: four, then one by one)
-            const int full = cnt & ~3;
-            for (int t = 0; t < cnt; t += 8) {
-              float4 v[8];
-#pragma unroll
-              for (int i = 0; i < 8; ++i) {
-                const int ti = __shfl(mytok, (t + i) & (LPR - 1), LPR);
-                v[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (colok && t + i < cnt) v[i] = *reinterpret_cast<const float4*>(E + (int64_t)ti * d + col);
-              }
-#pragma unroll
-              for (int i = 0; i < 8; ++i) {
-                const int j = t + i;
-                if (j < full) {
-                  if ((i & 3) == 0) a0 = f4_add(a0, v[i]);
-                  if ((i & 3) == 1) a1 = f4_add(a1, v[i]);
-                  if ((i & 3) == 2) a2 = f4_add(a2, v[i]);
-                  if ((i & 3) == 3) a3 = f4_add(a3, v[i]);
-                } else if (j < cnt) {
-                  a0 = f4_add(a0, v[i]);
-                }
-              }
-            }
-          }
-          a0 = f4_add(f4_add(a0, a1), f4_add(a2, a3));
+          const float4 a0 = bag_sum<LPR, 8, false, false>(E, bias, vals, st, len, ptok, lig, col, colok, d, bacc);
           // same arithmetic as k_gather_mulhot: sum / len (a true divide), + id row, * scale
           const float flen = (float)len;
           if (colok) {
@@ -937,7 +964,16 @@ int arx_lookup_multi(int nsites, const float* const* E_id, const float* const* b
   if (rc) return rc;
   LookupSites ls = {};
   int64_t tot = 0;
-  for (int s = 0; s < nsites; ++s) {
+  // slot q of the launch holds the caller's site order[q] (every site writes its own arrays, so the order of the
+  // slots is the order in which the sites' workgroups start and nothing else): ARX_LOOKUP_BAGS_FIRST puts the sites
+  // with a multi-hot table, the long chains, in front of the one-hot-only ones
+  int order[kMaxSites];
+  int nq = 0;
+  for (int pass = 0; pass < 2; ++pass)
+    for (int s = 0; s < nsites; ++s)
+      if (kLookupBagsFirst ? (E_tok[s] != nullptr) == (pass == 0) : pass == 0) order[nq++] = s;
+  for (int q = 0; q < nsites; ++q) {
+    const int s = order[q];
     ARX_CHECK_ARG((E_id[s] || E_tok[s]) && n[s] >= 0 && (n[s] == 0 || (ids[s] && out[s])),
                   "arx_lookup_multi: bad site (a one-hot table, a multi-hot table or both)");
     ARX_CHECK_ARG(!E_tok[s] || (vals && starts && lens && vals[s] && starts[s] && lens[s]),
@@ -948,20 +984,20 @@ int arx_lookup_multi(int nsites, const float* const* E_id, const float* const* b
     const bool wb = bias_out && bias_out[s];
     ARX_CHECK_ARG(!wb || ((!E_id[s] || (bias_id && bias_id[s])) && (!E_tok[s] || (bias_tok && bias_tok[s]))),
                   "arx_lookup_multi: bias_out requires the bias of every feature of the site");
-    ls.E_id[s] = E_id[s];
-    ls.bias_id[s] = (wb && E_id[s]) ? bias_id[s] : nullptr;
-    ls.cat_map[s] = cat_map ? cat_map[s] : nullptr;
-    ls.E_tok[s] = E_tok[s];
-    ls.bias_tok[s] = (wb && E_tok[s]) ? bias_tok[s] : nullptr;
-    ls.vals[s] = E_tok[s] ? vals[s] : nullptr;
-    ls.starts[s] = E_tok[s] ? starts[s] : nullptr;
-    ls.lens[s] = E_tok[s] ? lens[s] : nullptr;
-    ls.ids[s] = ids[s];
-    ls.out[s] = out[s];
-    ls.bias_out[s] = wb ? bias_out[s] : nullptr;
-    ls.ldo[s] = ldo[s];
-    ls.scale[s] = scale[s];
-    ls.n[s] = n[s];
+    ls.E_id[q] = E_id[s];
+    ls.bias_id[q] = (wb && E_id[s]) ? bias_id[s] : nullptr;
+    ls.cat_map[q] = cat_map ? cat_map[s] : nullptr;
+    ls.E_tok[q] = E_tok[s];
+    ls.bias_tok[q] = (wb && E_tok[s]) ? bias_tok[s] : nullptr;
+    ls.vals[q] = E_tok[s] ? vals[s] : nullptr;
+    ls.starts[q] = E_tok[s] ? starts[s] : nullptr;
+    ls.lens[q] = E_tok[s] ? lens[s] : nullptr;
+    ls.ids[q] = ids[s];
+    ls.out[q] = out[s];
+    ls.bias_out[q] = wb ? bias_out[s] : nullptr;
+    ls.ldo[q] = ldo[s];
+    ls.scale[q] = scale[s];
+    ls.n[q] = n[s];
     tot += n[s];
   }
   ls.count = nsites;
@@ -969,10 +1005,10 @@ int arx_lookup_multi(int nsites, const float* const* E_id, const float* const* b
   const int lpr = lanes_per_row(d);
   const int64_t rpb = 4 * (64 / lpr) * kLookupRows;
   int64_t nblk = 0;
-  for (int s = 0; s < nsites; ++s) {
-    nblk += ceil_div(n[s], rpb);
+  for (int q = 0; q < nsites; ++q) {
+    nblk += ceil_div(ls.n[q], rpb);
     ARX_CHECK_ARG(nblk < (int64_t)0x7fffffff, "arx_lookup_multi: too many rows");
-    ls.blk_end[s] = (int32_t)nblk;
+    ls.blk_end[q] = (int32_t)nblk;
   }
   ARX_DISPATCH_LPR(lpr, (k_lookup_multi<LPR><<<(int)nblk, 256, 0, as_stream(stream)>>>(ls, d)));
   ARX_CHECK_LAUNCH();
